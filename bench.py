@@ -198,8 +198,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--passes", type=int, default=0, help="timed passes of K steps each; the median pass is `value` (0: at least 3, and as many as fill --min-seconds)")
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="with --passes 0: keep timing passes until this much wall time is covered")
+    ap.add_argument("--passes", type=int, default=1, help="timed passes of K steps each; the median pass is `value`")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="keep timing further passes of K steps until this much wall time is covered (0: off)")
     ap.add_argument("--neval-per-gpu", type=float, default=1e8)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default): every GPU runs --neval-per-gpu samples and 16 blocks per iteration; strong: ONE problem of "
@@ -211,7 +211,12 @@ def main():
                     help="52 (default): the faithful stream, 52 random mantissa bits per draw like rand(Float64); 32: the opt-in cheaper stream (mci_set_rng_bits)")
     ap.add_argument("--rng-rounds", type=int, default=10, choices=(10, 7),
                     help="10 (default): Philox4x32-10; 7: the opt-in cheaper generator (mci_set_rng_rounds), pinned on the Random123 vectors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): its estimate (iteration_mean, "
+                         "iteration_stdev) and the grid it refined (grid)")
     a = ap.parse_args()
+    if a.dump_outputs and a.min_seconds > 0:
+        ap.error("--dump-outputs needs a fixed number of timed steps: leave --min-seconds at 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -327,13 +332,12 @@ def main():
     grid_after_warmup = eng.grid(0)   # handed to the CPU baseline: it continues from the same trained map
 
     # ---- timed region: `passes` x EXACTLY K iterations, no host synchronisation inside a pass ----
-    # (by default the passes go on for ~5 s: a 40 ms burst is invisible to anything that samples the GPU from outside, and the
-    # median of a hundred passes is a better number than the median of three)
+    # (by default ONE pass: --steps is the number of timed steps; --min-seconds adds passes until that much wall time is covered)
     pass_dt, dry_stats = [], []
     coll0 = eng.comm_collectives()[0] if hasattr(eng, "comm_collectives") else None   # ncclAllReduce calls the library has issued so far
+    npass = max(a.passes, 1)
     if hasattr(eng, "reserve_iterations"):
-        eng.reserve_iterations(a.steps * (a.passes if a.passes > 0 else 400))
-    npass = a.passes if a.passes > 0 else 3
+        eng.reserve_iterations(a.steps * (max(npass, 400) if a.min_seconds > 0 else npass))
     ipass = 0
     while ipass < npass:
         ipass += 1
@@ -354,7 +358,7 @@ def main():
             dt = float(t.item())
         pass_dt.append(dt)
         cfg.iterations_done += a.steps
-        if a.passes <= 0 and not dry and ipass == npass and sum(pass_dt) < a.min_seconds and npass < 400:
+        if not dry and ipass == npass and sum(pass_dt) < a.min_seconds and npass < 400:
             npass += 1   # (dt is already the maximum over the ranks, so every rank takes the same decision)
     if not dry:
         eng.check_status()   # a launch that tripped a device-side error (normalization, histogram) must not print a number
@@ -370,6 +374,7 @@ def main():
     nobs = eng.nobs
     if dry:
         means, stds = [float(m[0]) for m, _ in dry_stats], [float(e[0]) for _, e in dry_stats]
+        last_step = dry_stats[-1]
         neval_reduced = None
     else:
         log = eng.iteration_log(min(ntimed, 4096))   # the estimate pools the last <= 4096 timed iterations
@@ -378,8 +383,15 @@ def main():
             m, e = mci.mean_std(row[:nobs], row[nobs:2 * nobs], block)
             means.append(m[0])
             stds.append(e[0])
+        last_step = (m, e)
         neval_reduced = float(log[-1][2 * nobs + 1])   # config.neval after the all-reduce: the samples of ALL ranks
     mean, err, chi2 = mci.average(means, stds, init=1, max=len(means))
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (integrate: Result.iter_mean / iter_std[-1], the refined config.var);
+        # after the all-reduce every rank holds the same
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in (("iteration_mean", last_step[0]), ("iteration_stdev", last_step[1]), ("grid", eng.grid(0))):
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
 
     # what the communicator itself says about the job: the library's view (mci_comm_rank), every rank's block range
     lib_rank, lib_n = comm.library_ranks() if hasattr(comm, "library_ranks") else (rank, comm.size)

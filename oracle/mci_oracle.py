@@ -11,6 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("MCI_ORACLE_SO") or os.path.join(_HERE, "libmci_oracle.so")   # (MCI_ORACLE_SO: the sanitizer build, oracle/Makefile `sanitize`)
+USER_CODE = os.path.join(_HERE, "user_code")   # gcc builds of user integrand / measure bodies (git-ignored)
 
 CONTINUOUS, DISCRETE, FERMIK = 0, 1, 2
 VEGAS, VEGASMC, MCMC = 0, 1, 2
@@ -538,12 +539,11 @@ def compile_c_measure(body):
     """gcc-compile a measure body (the same text the HIP path JIT-compiles): in scope `x`, `rw`, `ud`, `idx` and
     `obs_add(k, v)` which accumulates v into flat observable k."""
     import hashlib
-    import tempfile
     src = ("#include <math.h>\n#define obs_add(k, v) (obs[(k)] += (v))\n"
            "void mci_user_measure(const double* x, const double* rw, const double* ud, int idx, double* obs) {\n"
            "(void)x; (void)rw; (void)ud; (void)idx;\n%s\n}\n" % body)
     h = hashlib.sha1(src.encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "mci_oracle_user")
+    d = USER_CODE
     os.makedirs(d, exist_ok=True)
     so = os.path.join(d, "m_%s.so" % h)
     if not os.path.exists(so):
@@ -562,11 +562,10 @@ def compile_c_integrand(body, ni=1, name="user"):
     body sees `x`, `w`, `ud` like the device snippet.  Returns a raw function pointer.
     """
     import hashlib
-    import tempfile
     src = ("#include <math.h>\n#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n"
            "void mci_user_integrand(const double* x, double* w, const double* ud) {\n%s\n}\n" % body)
     h = hashlib.sha1(src.encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "mci_oracle_user")
+    d = USER_CODE
     os.makedirs(d, exist_ok=True)
     so = os.path.join(d, "u_%s.so" % h)
     if not os.path.exists(so):

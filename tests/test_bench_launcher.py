@@ -4,14 +4,17 @@ packed buffers every iteration (src/main.jl:177-188) and print ONE JSON line tha
 replaced by the oracle-backed test engine through bench.py's MCI_BENCH_ENGINE seam and the reducer is gloo, so the line is
 a dry run (no throughput claim) -- what is under test is the launcher, the partition and the communicator bookkeeping."""
 import json
+import math
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
+L = math.sqrt(50.0)   # bench.py's domain [-L, L]^16
 
 
 def _run(args, extra_env=None, timeout=300):
@@ -51,6 +54,22 @@ def test_one_rank_line_matches_the_two_rank_estimate_on_the_same_global_blocks(o
     one = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--passes", "1", "--neval-per-gpu", "32000", "--no-cpu-baseline"])
     assert one["n_gpus"] == 1 and one["comm"]["kind"] == "none" and one["comm"]["ranks"] == 1
     assert one["comm"]["per_rank"][0]["blocks"] == [0, 16]
+
+
+def test_steps_is_the_timed_step_count_and_dump_outputs_writes_the_last_step(oracle, tmp_path):
+    """`--steps K` alone times exactly K steps (one pass); `--dump-outputs DIR` writes what the last of them computed, the same arrays
+    from a second run with the same arguments"""
+    dumps = []
+    for run in ("a", "b"):
+        out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--neval-per-gpu", "32000", "--no-cpu-baseline",
+                    "--dump-outputs", str(tmp_path / run)])
+        assert out["steps"] == 3 and out["timing"]["passes"] == 1 and out["estimate"]["iterations"] == 3 and out["ms_per_step"] > 0
+        dumps.append({n: np.load(tmp_path / run / (n + ".npy")) for n in ("iteration_mean", "iteration_stdev", "grid")})
+    a, b = dumps
+    assert a["iteration_mean"].shape == a["iteration_stdev"].shape == (1,) and a["grid"].shape == (1000,)
+    assert np.allclose(a["grid"][[0, -1]], [-L, L], rtol=1e-14, atol=0) and np.all(np.diff(a["grid"]) > 0)
+    for name, x in a.items():
+        assert x.dtype == np.float64 and np.array_equal(x, b[name]), name
 
 
 def test_launched_under_torch_distributed_run_it_does_not_spawn_again(oracle):
@@ -130,18 +149,24 @@ def test_forced_single_rank_communicator_goes_through_the_n_rank_code_path(reduc
 
 
 @pytest.mark.gpu
-def test_strong_scaling_option_splits_one_problem():
+def test_strong_scaling_option_splits_one_problem(tmp_path):
     """--scaling strong: ONE problem (neval, 16 blocks) per iteration whatever the rank count, blocks rounded like main.jl:121-122;
-    with one rank it is the same job as the weak line"""
+    with one rank it is the same job as the weak line.  --dump-outputs: the last timed step's estimate and refined grid"""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCI_BENCH_ENGINE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "3", "--passes", "1",
-                        "--neval-per-gpu", "2e7", "--no-cpu-baseline", "--scaling", "strong"], env=env, capture_output=True, text=True, timeout=600)
+                        "--neval-per-gpu", "2e7", "--no-cpu-baseline", "--scaling", "strong", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert out["scaling"] == "strong" and out["config"]["block"] == 16 and out["config"]["neval_per_iteration"] == 20000000
     assert out["comm"]["kind"] == "none" and out["value"] > 1000.0
+    assert out["steps"] == 3 and out["timing"]["passes"] == 1
+    m, e, grid = (np.load(tmp_path / (n + ".npy")) for n in ("iteration_mean", "iteration_stdev", "grid"))
+    assert m.dtype == e.dtype == grid.dtype == np.float64 and m.shape == e.shape == (1,) and grid.shape == (1000,)
+    assert e[0] > 0 and abs(m[0] - out["estimate"]["exact"]) < 7 * e[0]
+    assert np.allclose(grid[[0, -1]], [-L, L], rtol=1e-14, atol=0) and np.all(np.diff(grid) > 0)
 
 
 def test_strong_scaling_block_partition_on_two_dry_ranks(oracle):

@@ -66,23 +66,14 @@ def test_documents_cite_tests_that_exist():
 
 def test_reference_citations_point_inside_the_cited_files():
     """`src/main.jl:253-264`-style citations all over the repository: the cited file exists in the reference and is at least that long
-    (checked where the reference is at hand; the GPU box has no /root/reference)."""
+    (the reference's files and their line counts: tests/golden/reference_lines.json, made by tests/golden/make_reference_lines.py)."""
     import glob
-    import pytest
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("no reference tree here")
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_lines.json")) as fh:
+        length = json.load(fh)["lines"]
     by_name = {}
-    for root, _, names in os.walk(ref):
-        for n in names:
-            by_name.setdefault(n, []).append(os.path.relpath(os.path.join(root, n), ref))
-    length = {}
-
-    def nlines(rel):
-        if rel not in length:
-            with open(os.path.join(ref, rel), errors="replace") as fh:
-                length[rel] = sum(1 for _ in fh)
-        return length[rel]
+    for rel in length:
+        by_name.setdefault(os.path.basename(rel), []).append(rel)
     files = [os.path.join(ROOT, f) for f in ("bench.py", "__graft_entry__.py")]
     for pat in ("include/*.h", "mcintegration.jl_amd/*.py", "mcintegration.jl_amd/csrc/*", "mcintegration.jl_amd/julia/*.jl", "oracle/*.c", "oracle/*.py",
                 "oracle/*.h", "tests/*.py", "tools/*.py", "*.md", "profiles/README.md"):
@@ -101,6 +92,6 @@ def test_reference_citations_point_inside_the_cited_files():
                         continue                     # (one of our own files)
                     rels = [r for r in rels if r.endswith(name)] or rels
                     checked += 1
-                    if not any(nlines(r) >= last for r in rels):
+                    if not any(length[r] >= last for r in rels):
                         bad.append((os.path.relpath(path, ROOT), ln, m.group(0)))
     assert checked > 1000 and not bad, bad[:20]

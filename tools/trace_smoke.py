@@ -2,7 +2,7 @@
 """Development tool (GPU box): a Python closure traced into device source (integrate(..., trace=True)) next to the same closure on the
 host callback path, and a two-integrand closure with a select under the three solvers."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import mcintegration_jl_amd as mci
 f = lambda x, c: np.exp(-np.sum(x * x, axis=0) / 2) / (2 * np.pi) ** (len(x) / 2)
