@@ -38,6 +38,8 @@ enum { MCI_VEGAS = 0, MCI_VEGASMC = 1, MCI_MCMC = 2 }; /* solver=:vegas main.jl:
 enum { MCI_VEGAS_PERSISTENT = 3 };
 /* ... and the chain solvers' kernels with several lanes per chain (mci_set_chain_speculation), code objects of their own */
 enum { MCI_VEGASMC_LANES = 5, MCI_MCMC_LANES = 6 };
+/* ... and the stratified :vegas sample kernel (mci_set_stratification; the problem must be stratified to compile it) */
+enum { MCI_VEGAS_STRAT = 7 };
 
 typedef struct mci_ctx mci_ctx;
 typedef struct mci_problem mci_problem;
@@ -325,6 +327,26 @@ int mci_set_deterministic(mci_problem *prob, int32_t on);
  * does not expect: mci_integrate reports the block-lineage error for such runs (mci_result.correlated, mci_lineage_sums).
  * Mirrored in the oracle (mcio_set_chain_carry, mcio_resample_chains). */
 int mci_set_chain_carry(mci_problem *prob, int32_t mode);
+/* Stratified :vegas (VEGAS+: Lepage, J. Comput. Phys. 439 (2021) 110386; the default mode of the Python `vegas` package the reference's
+ * example/benchmark/vegas/ files compare against).  The ndim = sum of maxdof draws of a sample cut y-space into prod nstrat[d] hypercubes;
+ * every hypercube gets n_h >= 2 of an iteration's N samples, moved between them after every iteration in proportion to
+ * (sum over the columns of the hypercube's variance)^(beta/2) (beta = 0: even stratification).  An iteration's (mean, std) is the
+ * stratified estimate; `block` plays no part in it.  nstrat = NULL: the default plan for the iteration's N (mci_strat_plan), else
+ * prod nstrat <= N/2 is required (an explicit plan of about two samples per hypercube under-reports the error on heavy tails).  Refused (MCI_ERR_INVALID, naming the reason): Discrete or FermiK variables, a user measure, a host
+ * integrand, several histogram tiles or histograms outside LDS, more than one rank, more than 32 draws or 8 columns; at run time a
+ * solver other than :vegas and measurefreq != 1.  The persistent :vegas launch is never taken.  The allocation starts uniform in
+ * every mci_integrate call and whenever the plan changes; it is not part of mci_save_state. */
+int mci_set_stratification(mci_problem *prob, int32_t ndim, const int32_t *nstrat, double beta, int64_t max_nhcube);
+/* back to plain :vegas (the same kernels and numbers as a problem that was never stratified) */
+int mci_set_stratification_off(mci_problem *prob);
+/* the plan in use: nstrat[ndim] (zeros before the first stratified run of a default plan), ncube (0: off or not planned yet), beta */
+int mci_get_stratification(const mci_problem *prob, int32_t *nstrat, int64_t *ncube, double *beta);
+/* n_h of every hypercube in the allocation the last stratified iteration used (n = ncube).  Synchronises the stream. */
+int mci_get_strat_counts(mci_problem *prob, int64_t *n_h, int64_t n);
+/* host only, touches no device: the default plan for neval samples over ndim draws, eight samples per hypercube on average.
+ * s = floor(min(neval/8, max_nhcube)^(1/ndim)) (at least 1) strata per draw, then the leading draws one at a time s + 1 while
+ * prod nstrat <= min(neval/8, max_nhcube).  (Hypercubes of about two samples report errors far too small on heavy-tailed integrands.) */
+int mci_strat_plan(int64_t neval, int32_t ndim, int64_t max_nhcube, int32_t *nstrat);
 /* chains per block of the last chain-solver launch and whether it continued the launch before it */
 int mci_last_chain_launch(const mci_problem *prob, int64_t *nchain, int32_t *carried);
 /* For a caller that runs the iteration loop itself (mci_iteration_run / _reduce / _finish; mci_integrate does this on its own): does

@@ -110,6 +110,11 @@ SIGNATURES = [
     ("mci_set_persistent", C.c_int, [_VP, C.c_int32]),
     ("mci_last_integrate_persistent", C.c_int, [_VP, C.POINTER(C.c_int32)]),
     ("mci_last_chain_launch", C.c_int, [_VP, C.POINTER(C.c_int64), c_int32_p]),
+    ("mci_set_stratification", C.c_int, [_VP, C.c_int32, c_int32_p, C.c_double, C.c_int64]),
+    ("mci_set_stratification_off", C.c_int, [_VP]),
+    ("mci_get_stratification", C.c_int, [_VP, c_int32_p, C.POINTER(C.c_int64), c_double_p]),
+    ("mci_get_strat_counts", C.c_int, [_VP, C.POINTER(C.c_int64), C.c_int64]),
+    ("mci_strat_plan", C.c_int, [C.c_int64, C.c_int32, C.c_int64, c_int32_p]),
     ("mci_set_chain_speculation", C.c_int, [_VP, C.c_int32, C.c_double, C.c_int32]),
     ("mci_last_chain_speculation", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_chain_speculation_status", C.c_int, [_VP, C.c_int32, c_int32_p]),
@@ -149,6 +154,7 @@ DEBUG_SIGNATURES = [
     ("mci_debug_override", C.c_int, [C.c_char_p, C.c_int64, C.c_int32]),
     ("mci_debug_compiler_id", C.c_int, [C.c_char_p, C.c_char_p, C.c_int32]),
     ("mci_debug_split_chunks", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("mci_debug_strat_dump", C.c_int, [_VP, C.c_int64, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
     ("mci_debug_mcmc_policy", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
 ]
 

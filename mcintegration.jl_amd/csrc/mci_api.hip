@@ -27,6 +27,7 @@
 #include "mci_device.h" // BatchArgs / DumpArgs (the templates themselves are instantiated by the JIT)
 #include "mci_jit.h"
 #include "mci_static_kernels.h"
+#include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
 
 namespace {
 
@@ -57,6 +58,7 @@ extern "C" {
 #include "mci_host_ctx.h"
 #include "mci_host_problem.h"
 #include "mci_host_jit.h"
+#include "mci_host_strat.h"
 #include "mci_host_iteration.h"
 #include "mci_host_integrate.h"
 #include "mci_host_access.h"

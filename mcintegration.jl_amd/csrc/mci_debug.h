@@ -38,6 +38,10 @@ int mci_debug_override(const char *key, int64_t value, int32_t on);
  * -> replay per chunk; override key split_chunk = samples per chunk over all blocks, default min(2^27, 7.5 GB of stream)) and the bytes of
  * parked (weights, bins) stream it held at a time */
 int mci_debug_split_chunks(const mci_problem *prob, int64_t *chunks, int64_t *bytes);
+/* test hook: the NEXT stratified :vegas iteration of the problem (mci_set_stratification) also leaves, for each of its n samples (n must be
+ * that iteration's N), the draws x[n][ndraw], the uniforms y[n][ndraw] after the move into the sample's hypercube, the hypercube h[n],
+ * the Jacobian jac[n] (without r_h) and the weights w[n][ni * ncomp] in these host buffers; the run synchronises.  n = 0 takes it back. */
+int mci_debug_strat_dump(mci_problem *prob, int64_t n, double *x, double *y, int64_t *h, double *jac, double *w);
 /* what mci_jit.h puts into the kernel-cache key for "which compiler made this code object" (hiprtc version, the files of libhiprtc and
  * libamd_comgr, the target): set != NULL overrides it for this process ("" takes the override back); out: the identity in force */
 int mci_debug_compiler_id(const char *set, char *out, int32_t n);

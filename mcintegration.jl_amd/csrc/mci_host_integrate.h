@@ -298,12 +298,18 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     if (a->solver != MCI_VEGAS && a->solver != MCI_VEGASMC && a->solver != MCI_MCMC) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", a->solver); // main.jl:263
     // launch-bound :vegas calls: the whole loop below as one persistent launch (same iterations, same Philox streams)
     int wpb_persist = 0, rc = 0;
-    bool persist = persist_plan(p, a, nevalperblock, hi - lo, &wpb_persist);
+    const bool strat = p->strat.on; // (stratified :vegas: the launch chain, never the persistent launch)
+    if (strat) {
+        if (a->solver != MCI_VEGAS) return fail(MCI_ERR_INVALID, "stratification works with solver = :vegas only (mci_set_stratification_off first)");
+        if (a->measurefreq != 1) return fail(MCI_ERR_INVALID, "stratification: measurefreq = %lld is refused (every sample is measured)", (long long)a->measurefreq);
+        strat_call_start(p); // (the first iteration of a call samples every hypercube alike)
+    }
+    bool persist = !strat && persist_plan(p, a, nevalperblock, hi - lo, &wpb_persist);
     // (automatic mode: a code object that is not in the kernel cache yet is compiled on a thread of its own, and until it is there the
     // calls go through the launch chain -- a new integrand's first call costs what it did, 0.2 s, not the 0.8 s of the larger unit)
     if (persist) (void)compile_persist(p, p->persistent < 0);
     persist = persist && p->persist_compiled;
-    if (!persist && (rc = compile_solver(p, kslot(a->solver, a->measurefreq)))) return rc;
+    if (!persist && !strat && (rc = compile_solver(p, kslot(a->solver, a->measurefreq)))) return rc;
     if ((rc = mci_set_reweight_goal(p, a->reweight_goal, a->reweight_goal ? p->ni + 1 : 0))) return rc;
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
     const size_t nlog = (size_t)a->niter * p->nstat; // the pinned landing place of the statistics (+ the status word), sized outside the timed loop
@@ -391,6 +397,8 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     res->neval = 0;
     for (int it = 0; it < a->niter; ++it) { // main.jl:203
         const double *row = h + (size_t)it * p->nstat;
+        if (strat) strat_mean_std(row, s.nobs, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
+        else
         mci_mean_std(row, row + s.nobs, s.nobs, block, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
         res->neval += (int64_t)row[2 * s.nobs + 1];
         if (res->visited && it == a->niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));

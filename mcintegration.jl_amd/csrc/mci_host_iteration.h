@@ -12,6 +12,10 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     const int64_t nblocks = block_hi - block_lo;
     if (nblocks < 1 || nevalperblock < 1) return fail(MCI_ERR_INVALID, "empty iteration");
     if (p->has_fermik && solver != MCI_MCMC) return fail(MCI_ERR_INVALID, "FermiK variables work with solver=:mcmc only"); // test/bubble_FermiK.jl:2,:133
+    if (p->strat.on) { // stratified :vegas (mci_host_strat.h): its own sample kernel and launch
+        if (solver != MCI_VEGAS) return fail(MCI_ERR_INVALID, "stratification works with solver = :vegas only (mci_set_stratification_off first)");
+        return strat_run(p, nevalperblock, block_lo, block_hi, iteration, seed, measurefreq);
+    }
     const int kern = kslot(solver, measurefreq);
     // (a chain solver's lane-per-chain kernel is compiled once the launch is known to run one lane per chain: a launch of few chains
     // runs the several-lanes-per-chain kernel instead, mci_spec.h, and pays for that code object only)
@@ -914,14 +918,18 @@ int mci_iteration_finish(mci_problem *p, int32_t solver, int64_t block_total, in
     if (int grc = grow_iteration_log(p, (int64_t)p->log_row + 1)) return grc;
     double *row = p->d_iterlog + (size_t)p->log_row * p->nstat;
     // doReweight! runs for the chain solvers whether or not the grid adapts (main.jl:183 is outside the `if adapt`)
+    const bool strat = p->strat.last_run;
     int rc = launch_train(p, adapt ? 1 : 0, (solver == MCI_VEGASMC || solver == MCI_MCMC) ? 1 : 0, gamma, row);
     if (rc) return rc;
+    if (strat && (rc = strat_finish(p, row, adapt))) return rc; // (the row's head: the stratified mean | var)
     p->log_row += 1;
     if (mean || std) {
         std::vector<double> h(p->nstat);
         HIPCHK(hipMemcpyAsync(h.data(), row, (size_t)p->nstat * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
         if ((rc = check_status(p))) return rc; // synchronises
         std::vector<double> m(s.nobs), e(s.nobs);
+        if (strat) strat_mean_std(h.data(), s.nobs, m.data(), e.data());
+        else
         mci_mean_std(h.data(), h.data() + s.nobs, s.nobs, block_total, m.data(), e.data());
         if (mean) memcpy(mean, m.data(), s.nobs * sizeof(double));
         if (std) memcpy(std, e.data(), s.nobs * sizeof(double));

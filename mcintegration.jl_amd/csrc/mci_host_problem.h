@@ -380,6 +380,7 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
     return MCI_OK;
 }
 
+static void strat_free_buffers(mci_problem *p); // (mci_host_strat.h)
 int mci_problem_destroy(mci_problem *p) {
     if (!p) return MCI_OK;
     if (!p->ctx->offline) {
@@ -392,6 +393,8 @@ int mci_problem_destroy(mci_problem *p) {
         for (int k = 0; k < mci_problem::kSlots; ++k)
             if (p->module[k]) (void)hipModuleUnload(p->module[k]);
         if (p->module_persist) (void)hipModuleUnload(p->module_persist);
+        if (p->strat.module) (void)hipModuleUnload(p->strat.module);
+        strat_free_buffers(p);
         if (p->d_persist) (void)hipFree(p->d_persist);
     }
     persist_job_drop(p);

@@ -1,0 +1,455 @@
+// mci_host_strat.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
+// stratified :vegas (VEGAS+ adaptive stratified sampling): the plan, the setters, the sample launch (mci_strat.h) and the iteration's
+// reduce + next allocation (k_strat_reduce, k_strat_alloc).  mci_iteration_run / _finish and mci_integrate call in here when the
+// problem is stratified; nothing here runs otherwise.
+static_assert(mci::kStratMaxCols == mci::kStratReduceCols, "k_strat_reduce keeps the columns the sample kernel writes");
+static int flush_merge(mci_problem *p);
+
+// The default plan leaves kStratSamplesPerCube samples per hypercube on average, not the two every hypercube must have: with two, the
+// per-hypercube variances are two-sample estimates whose sum is far too small on heavy tails (32 seeds of log(x)/sqrt(x) at neval = 1e5:
+// scatter of the means 5.1 x the reported error; the Watson integral 1.3 x), and N - 2 ncube = 0 samples are left to move.  With eight
+// the reported errors match the scatter (1.01, 1.00) and three quarters of the samples follow the variance (profiles/r07_stratified.txt).
+static const int64_t kStratSamplesPerCube = 8;
+
+int mci_strat_plan(int64_t neval, int32_t ndim, int64_t max_nhcube, int32_t *nstrat) {
+    if (!nstrat || ndim < 1) return fail(MCI_ERR_INVALID, "stratification: ndim must be positive");
+    if (max_nhcube < 1) return fail(MCI_ERR_INVALID, "stratification: max_nhcube must be positive");
+    const int64_t per = neval / kStratSamplesPerCube, cap = per < max_nhcube ? per : max_nhcube;
+    if (cap < 1) return fail(MCI_ERR_INVALID, "stratification: neval = %lld is too small for %lld samples per hypercube", (long long)neval,
+                             (long long)kStratSamplesPerCube);
+    // prod of ndim factors v, or cap + 1 once it exceeds cap
+    auto power_le = [cap](int64_t v, int n) {
+        int64_t r = 1;
+        for (int i = 0; i < n; ++i) {
+            if (r > cap / v) return cap + 1;
+            r *= v;
+        }
+        return r;
+    };
+    int64_t s = (int64_t)floor(pow((double)cap, 1.0 / ndim));
+    if (s < 1) s = 1;
+    while (s > 1 && power_le(s, ndim) > cap) --s;
+    while (power_le(s + 1, ndim) <= cap) ++s;
+    int64_t ncube = power_le(s, ndim);
+    for (int d = 0; d < ndim; ++d) nstrat[d] = (int32_t)s;
+    for (int d = 0; d < ndim; ++d) {
+        if (ncube / s * (s + 1) > cap) break;
+        ncube = ncube / s * (s + 1);
+        nstrat[d] = (int32_t)(s + 1);
+    }
+    return MCI_OK;
+}
+
+static void strat_free_buffers(mci_problem *p) {
+    auto &st = p->strat;
+    for (void *q : {(void *)st.d_off, (void *)st.d_d, (void *)st.d_tsum, (void *)st.d_part, (void *)st.d_rec_s, (void *)st.d_stat, (void *)st.d_rec_h})
+        if (q) (void)hipFree(q);
+    st.d_off = nullptr;
+    st.d_d = st.d_tsum = st.d_part = st.d_rec_s = st.d_stat = nullptr;
+    st.d_rec_h = nullptr;
+    st.cap_cube = st.cap_chunk = 0;
+}
+
+namespace {
+// what a stratified problem must not have (the follow-ups of this mode): checked when it is switched on
+int strat_layout_check(const mci_problem *p, int32_t ndim) {
+    const auto &s = p->shape;
+    for (const auto &L : p->leaves)
+        if (L.kind != 0) return fail(MCI_ERR_INVALID, "stratification: only Continuous variables are stratified (a Discrete or FermiK variable is refused)");
+    if (!s.measure_body.empty() || s.host_measure) return fail(MCI_ERR_INVALID, "stratification: a user measure is refused (the default measure only)");
+    if (s.host_integrand) return fail(MCI_ERR_INVALID, "stratification: a host integrand is refused (device source or a traced closure only)");
+    if (p->ctx->nranks != 1) return fail(MCI_ERR_INVALID, "stratification: more than one rank is refused");
+    if (s.ntile > 1 || s.ec_doubles > 0) return fail(MCI_ERR_INVALID, "stratification: a layout with several histogram tiles is refused");
+    if (!(s.table_mode == 0 || s.table_mode == 3)) return fail(MCI_ERR_INVALID, "stratification: histograms outside LDS (table mode %d) are refused", s.table_mode);
+    if (ndim != s.ndraw) return fail(MCI_ERR_INVALID, "stratification: ndim = %d, but a sample has %d draws", (int)ndim, s.ndraw);
+    if (s.ndraw > mci::kStratMaxDraw) return fail(MCI_ERR_INVALID, "stratification: %d draws per sample (at most %d)", s.ndraw, (int)mci::kStratMaxDraw);
+    if (s.ni * s.ncomp > mci::kStratMaxCols) return fail(MCI_ERR_INVALID, "stratification: %d weight columns (at most %d)", s.ni * s.ncomp, (int)mci::kStratMaxCols);
+    return MCI_OK;
+}
+
+int strat_alloc_tiles(int64_t ncube) { return (int)((ncube + 255) / 256 < 1024 ? (ncube + 255) / 256 : 1024); }
+
+// the allocation of the run about to start, over the offsets the last run used: from d_h, or uniform
+int strat_launch_alloc(mci_problem *p, bool uniform) {
+    auto &st = p->strat;
+    mci::StratAllocArgs a{};
+    a.d = st.d_d;
+    a.off = st.d_off;
+    a.tsum = st.d_tsum;
+    a.ncube = st.ncube;
+    a.nsamp = st.nsamp;
+    a.ntile = strat_alloc_tiles(st.ncube);
+    a.uniform = uniform ? 1 : 0;
+    for (int phase = 0; phase < 3; ++phase) {
+        hipLaunchKernelGGL(mci::k_strat_alloc, dim3(phase == 1 ? 1 : (unsigned)a.ntile), dim3(256), 0, p->ctx->stream, a, phase);
+        HIPCHK(hipGetLastError());
+    }
+    st.alloc_valid = true;
+    st.alloc_pending = false;
+    return MCI_OK;
+}
+
+// the plan for N samples per iteration; buffers sized for it; a new plan starts uniform
+int strat_prepare(mci_problem *p, int64_t N) {
+    auto &st = p->strat;
+    const int D = p->shape.ndraw;
+    std::vector<int> ns(D);
+    if (st.want.empty()) {
+        int rc = mci_strat_plan(N, D, st.max_nhcube, ns.data());
+        if (rc) return rc;
+    } else ns = st.want;
+    int64_t ncube = 1;
+    for (int v : ns) {
+        if (ncube > (((int64_t)1 << 31) - 1) / v) return fail(MCI_ERR_INVALID, "stratification: more than 2^31 - 1 hypercubes");
+        ncube *= v;
+    }
+    if (ncube > N / 2) return fail(MCI_ERR_INVALID, "stratification: %lld hypercubes need at least %lld samples per iteration (two each), neval = %lld",
+                                   (long long)ncube, (long long)(2 * ncube), (long long)N);
+    if (ns != st.nstrat || N != st.nsamp) {
+        st.nstrat = ns;
+        st.ncube = ncube;
+        st.nsamp = N;
+        st.alloc_valid = false;
+        st.ran = false;
+        if (ncube > st.cap_cube) {
+            for (void *q : {(void *)st.d_off, (void *)st.d_d, (void *)st.d_tsum})
+                if (q) (void)hipFree(q);
+            st.d_off = nullptr;
+            st.d_d = st.d_tsum = nullptr;
+            st.cap_cube = 0;
+            HIPCHK(hipMalloc((void **)&st.d_off, (size_t)(ncube + 1) * sizeof(long long)));
+            HIPCHK(hipMalloc((void **)&st.d_d, (size_t)ncube * sizeof(double)));
+            HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
+            HIPCHK(hipMemsetAsync(st.d_d, 0, (size_t)ncube * sizeof(double), p->ctx->stream));
+            st.cap_cube = ncube;
+        }
+    }
+    if (!st.alloc_valid) return strat_launch_alloc(p, true);
+    if (st.alloc_pending) return strat_launch_alloc(p, false);
+    return MCI_OK;
+}
+
+} // namespace
+
+static int compile_strat(mci_problem *p) {
+    auto &st = p->strat;
+    const int det = p->deterministic ? 1 : 0;
+    if (st.compiled && st.compiled_det == det) return MCI_OK;
+    if (st.module) {
+        if (!p->ctx->offline) (void)hipModuleUnload(st.module);
+        st.module = nullptr;
+        st.f = nullptr;
+    }
+    Candidate c;
+    mcijit::ProblemShape sh = p->shape;
+    sh.det = det;               // deterministic mode: one histogram copy per wave (mci_device.h hslot)
+    sh.hcopy = det ? 256 / 64 : 1;
+    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitStrat);
+    c.threads = 256;
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrStrat);
+    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (stratified :vegas kernel):\n%s", c.log.c_str());
+    if (mcijit::max_static_lds_bytes(c.code) != 0) return fail(MCI_ERR_COMPILE, "the stratified code object declares static LDS");
+    st.code_object = c.path;
+    if (!p->ctx->offline) {
+        HIPCHK(hipSetDevice(p->ctx->device));
+        HIPCHK(hipModuleLoadData(&st.module, c.code.data()));
+        HIPCHK(hipModuleGetFunction(&st.f, st.module, "mci_vegas_strat"));
+        HIPCHK(hipFuncSetAttribute((const void *)st.f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
+    st.compiled = true;
+    st.compiled_det = det;
+    return MCI_OK;
+}
+
+int mci_set_stratification(mci_problem *p, int32_t ndim, const int32_t *nstrat, double beta, int64_t max_nhcube) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(MCI_ERR_INVALID, "stratification: beta must be finite and >= 0");
+    if (max_nhcube < 1 || max_nhcube > (((int64_t)1 << 31) - 1)) return fail(MCI_ERR_INVALID, "stratification: max_nhcube must lie in [1, 2^31 - 1]");
+    int rc = strat_layout_check(p, ndim);
+    if (rc) return rc;
+    std::vector<int> want;
+    if (nstrat) {
+        int64_t prod = 1;
+        for (int d = 0; d < ndim; ++d) {
+            if (nstrat[d] < 1) return fail(MCI_ERR_INVALID, "stratification: nstrat[%d] = %d, must be >= 1", d, (int)nstrat[d]);
+            prod *= nstrat[d];
+            if (prod > (((int64_t)1 << 31) - 1)) return fail(MCI_ERR_INVALID, "stratification: more than 2^31 - 1 hypercubes");
+            want.push_back(nstrat[d]);
+        }
+    }
+    auto &st = p->strat;
+    st.on = true;
+    st.want = want;
+    st.beta = beta;
+    st.max_nhcube = max_nhcube;
+    st.nstrat.clear(); // (re-planned, and the allocation started uniform, at the next run)
+    st.nsamp = 0;
+    st.ncube = 0;
+    st.alloc_valid = st.alloc_pending = false;
+    st.last_run = false;
+    st.ran = false;
+    return MCI_OK;
+}
+
+int mci_set_stratification_off(mci_problem *p) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    auto &st = p->strat;
+    st.on = false;
+    st.want.clear();
+    st.nstrat.clear();
+    st.ncube = st.nsamp = 0;
+    st.alloc_valid = st.alloc_pending = false;
+    st.last_run = false;
+    st.ran = false;
+    return MCI_OK;
+}
+
+int mci_get_stratification(const mci_problem *p, int32_t *nstrat, int64_t *ncube, double *beta) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    const auto &st = p->strat;
+    if (nstrat)
+        for (int d = 0; d < p->shape.ndraw; ++d) nstrat[d] = !st.on ? 0 : !st.nstrat.empty() ? st.nstrat[d] : !st.want.empty() ? st.want[d] : 0;
+    if (ncube) *ncube = st.on ? st.ncube : 0;
+    if (beta) *beta = st.beta;
+    return MCI_OK;
+}
+
+int mci_get_strat_counts(mci_problem *p, int64_t *n_h, int64_t n) {
+    if (!p || (n > 0 && !n_h)) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    const auto &st = p->strat;
+    if (!st.on || !st.ran) return fail(MCI_ERR_INVALID, "stratification: no stratified iteration has run");
+    if (n != st.ncube) return fail(MCI_ERR_INVALID, "stratification: %lld hypercubes, %lld asked for", (long long)st.ncube, (long long)n);
+    HIPCHK(hipSetDevice(p->ctx->device));
+    std::vector<long long> off((size_t)n + 1);
+    HIPCHK(hipMemcpyAsync(off.data(), st.d_off, off.size() * sizeof(long long), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    for (int64_t h = 0; h < n; ++h) n_h[h] = off[h + 1] - off[h];
+    return MCI_OK;
+}
+
+int mci_debug_strat_dump(mci_problem *p, int64_t n, double *x, double *y, int64_t *h, double *jac, double *w) {
+    if (!p || (n > 0 && (!x || !y || !h || !jac || !w))) return fail(MCI_ERR_INVALID, "NULL argument");
+    auto &st = p->strat;
+    st.hn = n > 0 ? n : 0;
+    st.hx = x;
+    st.hy = y;
+    st.hh = (long long *)h;
+    st.hjac = jac;
+    st.hw = w;
+    return MCI_OK;
+}
+
+// every stratified allocation of a call starts uniform (mci_integrate)
+static void strat_call_start(mci_problem *p) { p->strat.alloc_valid = p->strat.alloc_pending = false; }
+
+// One stratified :vegas iteration's sample launch + the histogram merge (mci_iteration_run's :vegas path for a stratified problem).
+// The nwg partial rows are merged as the call's blocks (or one): the merged statistics head is overwritten with the stratified (mean,
+// var) by mci_iteration_finish (strat_finish).
+static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, int64_t block_hi, int32_t iteration, uint64_t seed, int64_t measurefreq) {
+    auto &st = p->strat;
+    const auto &s = p->shape;
+    if (measurefreq != 1) return fail(MCI_ERR_INVALID, "stratification: measurefreq = %lld is refused (every sample is measured)", (long long)measurefreq);
+    if (p->ctx->nranks != 1) return fail(MCI_ERR_INVALID, "stratification: more than one rank is refused");
+    int rc = flush_merge(p);
+    if (rc) return rc;
+    if ((rc = compile_strat(p))) return rc;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    const int64_t N = (block_hi - block_lo) * nevalperblock;
+    if ((rc = strat_prepare(p, N))) return rc;
+    // chunk size: the largest of 8 | 4 | 2 | 1 trips of 256 samples whose LDS (tables + histograms + the chunk's hypercubes) stays within
+    // 64 KiB -- two workgroups per CU --, else within a CU's 160 KiB
+    const int T = 256, NW = s.ni * s.ncomp;
+    const int64_t base = p->deterministic ? det_lds(p, T) : p->lds_bytes;
+    int trips = 0;
+    int64_t lds = 0;
+    for (int64_t lim : {(int64_t)64 * 1024, (int64_t)159 * 1024}) {
+        for (int k = 8; k >= 1 && !trips; k >>= 1) {
+            const int nloc = k * T / 2 + 1;
+            const int64_t need = base + (int64_t)((nloc + 1) + nloc * 2 * NW + T + T * 2 * NW) * 8;
+            if (need <= lim) {
+                trips = k;
+                lds = need;
+            }
+        }
+        if (trips) break;
+    }
+    if (!trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+    const int64_t S = (int64_t)trips * T, nchunk = (N + S - 1) / S;
+    // (a multiple of the call's block count where there are enough chunks: the merge then groups the rows into the call's blocks, whose
+    // clearStatistics! offsets the histogram carries as classic :vegas's does -- one hypercube gives classic's histogram and map)
+    const int64_t nblocks = block_hi - block_lo;
+    int64_t nwg = nchunk < 2048 ? nchunk : 2048;
+    const int64_t mblocks = nwg >= nblocks ? nblocks : 1;
+    nwg -= nwg % mblocks;
+    if ((rc = ensure_capacity(p, nwg, 1))) return rc;
+    if (nchunk > st.cap_chunk) {
+        for (void *q : {(void *)st.d_part, (void *)st.d_rec_s, (void *)st.d_rec_h})
+            if (q) (void)hipFree(q);
+        st.d_part = st.d_rec_s = nullptr;
+        st.d_rec_h = nullptr;
+        st.cap_chunk = 0;
+        HIPCHK(hipMalloc((void **)&st.d_part, (size_t)nchunk * 2 * NW * sizeof(double)));
+        HIPCHK(hipMalloc((void **)&st.d_rec_s, (size_t)nchunk * 2 * 2 * NW * sizeof(double)));
+        HIPCHK(hipMalloc((void **)&st.d_rec_h, (size_t)nchunk * 2 * sizeof(long long)));
+        st.cap_chunk = nchunk;
+    }
+    if (!st.d_stat) HIPCHK(hipMalloc((void **)&st.d_stat, 2 * mci::kStratMaxCols * sizeof(double)));
+    st.ran = true;
+    st.last_nchunk = nchunk;
+
+    mci::BatchArgs a{};
+    a.edges = p->d_edges;
+    a.dacc = p->d_dacc;
+    a.ddist = p->d_ddist;
+    a.reweight = p->d_reweight;
+    a.ud = p->d_ud;
+    a.part_cols = p->d_part_cols;
+    a.part_hist = p->d_part_hist;
+    a.ghist = p->d_ghist;
+    a.seed = seed;
+    a.iteration = (mci::u32)iteration;
+    a.neval_per_block = nevalperblock;
+    a.block_lo = block_lo;
+    a.wg_per_block = (int)nwg;
+    a.measurefreq = 1;
+    a.nchain = 1;
+    a.status = p->d_status;
+    a.hist_atomic = 0;
+    a.nrows = nwg;
+    mci::StratArgs sa{};
+    sa.off = st.d_off;
+    sa.dnext = st.d_d;
+    sa.part = st.d_part;
+    sa.rec_h = st.d_rec_h;
+    sa.rec_s = st.d_rec_s;
+    sa.ncube = st.ncube;
+    sa.nsamp = N;
+    sa.chunk = S;
+    sa.nchunk = nchunk;
+    sa.first_index = block_lo * nevalperblock;
+    sa.nloc = (int)(S / 2 + 1);
+    sa.beta = st.beta;
+    for (int d = 0; d < s.ndraw; ++d) {
+        const uint32_t n = (uint32_t)st.nstrat[d];
+        int l = 0;
+        while (((uint64_t)1 << l) < n) ++l;
+        // h < 2^31: q = floor(h * m / 2^(32 + l)), m = ceil(2^(32 + l) / n) < 2^33 ... kept in 32 bits by folding one bit into the shift
+        // for l <= 31: m' = ceil(2^(31 + l) / n) <= 2^32 and q = (h * m') >> (31 + l), exact for h < 2^31 (Granlund-Montgomery, N = 31)
+        const uint64_t m = (((uint64_t)1 << (31 + l)) + n - 1) / n;
+        sa.magic[d] = (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m);
+        sa.shift[d] = 31 + l;
+        sa.nstrat[d] = (int)n;
+        sa.inv[d] = 1.0 / (double)n;
+        if (n == 1) { // (h / 1: m' = 2^31, shift 31)
+            sa.magic[d] = 0x80000000u;
+            sa.shift[d] = 31;
+        }
+    }
+    struct Scratch {
+        void *q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Scratch() {
+            for (void *v : q)
+                if (v) (void)hipFree(v);
+        }
+    } dump;
+    const bool dumping = st.hn > 0;
+    if (dumping) {
+        if (st.hn != N) return fail(MCI_ERR_INVALID, "mci_debug_strat_dump: %lld samples asked for, the iteration has %lld", (long long)st.hn, (long long)N);
+        HIPCHK(hipMalloc(&dump.q[0], (size_t)N * s.ndraw * sizeof(double)));
+        HIPCHK(hipMalloc(&dump.q[1], (size_t)N * s.ndraw * sizeof(double)));
+        HIPCHK(hipMalloc(&dump.q[2], (size_t)N * sizeof(long long)));
+        HIPCHK(hipMalloc(&dump.q[3], (size_t)N * sizeof(double)));
+        HIPCHK(hipMalloc(&dump.q[4], (size_t)N * NW * sizeof(double)));
+        sa.dump_x = (double *)dump.q[0];
+        sa.dump_y = (double *)dump.q[1];
+        sa.dump_h = (long long *)dump.q[2];
+        sa.dump_jac = (double *)dump.q[3];
+        sa.dump_w = (double *)dump.q[4];
+    }
+    void *args[] = {&a, &sa};
+    // HIP events around the sample launch under the rule of the classic one (mci_set_kernel_timing, mci_kernel_times_ms)
+    const int slot = (int)(p->launches % mci_problem::kEvRing);
+    p->time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && N >= ((int64_t)1 << 20));
+    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], p->ctx->stream));
+    HIPCHK(hipModuleLaunchKernel(st.f, (unsigned)nwg, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
+    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], p->ctx->stream));
+    p->ev_valid[slot] = p->time_this_launch;
+    p->clock_valid[slot] = false;
+    p->launches += 1;
+    if (dumping) {
+        hipStream_t hs = p->ctx->stream;
+        HIPCHK(hipMemcpyAsync(st.hx, dump.q[0], (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hy, dump.q[1], (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hh, dump.q[2], (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hjac, dump.q[3], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hw, dump.q[4], (size_t)N * NW * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipStreamSynchronize(hs));
+        st.hn = 0;
+    }
+    // merge: the nwg rows as mblocks blocks (the statistics head is replaced by the stratified estimate in strat_finish)
+    const int nb256 = (s.nbin + 255) / 256;
+    if (s.nbin > 0)
+        hipLaunchKernelGGL(mci::k_hist_stage1, dim3(nb256, mci_problem::kGroups), dim3(256), 0, p->ctx->stream, p->d_part_hist, (int)nwg, s.nbin,
+                           (int)mci_problem::kGroups, p->d_stage1);
+    HIPCHK(hipGetLastError());
+    mci::MergeArgs &m = p->merge;
+    m.part_cols = p->d_part_cols;
+    m.ncols = s.ncols;
+    m.nobs = s.nobs;
+    m.ni = s.ni;
+    m.nblocks = (int)mblocks;
+    m.wg_per_block = (int)(nwg / mblocks);
+    m.stage1 = p->d_stage1;
+    m.ngroup = (int)mci_problem::kGroups;
+    m.ghist = p->d_ghist;
+    m.use_ghist = 0;
+    m.nbin = s.nbin;
+    m.packed = p->d_packed;
+    m.status = p->d_status;
+    m.scratch = p->d_scratch;
+    m.part_pa = nullptr;
+    m.npa = p->npa;
+    m.nrows = (int)nwg;
+    m.block_means = nullptr;
+    m.hold = nullptr;
+    p->merge_pending = true;
+    p->last_samples = N;
+    p->last_wg = (int)nwg;
+    p->last_threads = T;
+    p->last_nblocks = (int)mblocks;
+    st.last_run = true;
+    return MCI_OK;
+}
+
+// behind launch_train of a stratified iteration: the stratified (mean, var) into the iteration log row (row[k], row[nobs + k]) and the
+// d_h of the next allocation; when the map adapts, the next run turns them into its offsets first (strat_prepare), so that d_off keeps
+// the allocation this iteration used until then (mci_get_strat_counts) and ONE offset array serves both
+static int strat_finish(mci_problem *p, double *row, int32_t adapt) {
+    auto &st = p->strat;
+    st.last_run = false;
+    mci::StratReduceArgs r{};
+    r.off = st.d_off;
+    r.part = st.d_part;
+    r.rec_h = st.d_rec_h;
+    r.rec_s = st.d_rec_s;
+    r.ncube = st.ncube;
+    r.nchunk = st.last_nchunk;
+    r.nw = p->shape.ni * p->shape.ncomp;
+    r.beta = st.beta;
+    r.dnext = st.d_d;
+    r.out = st.d_stat;
+    r.log_row = row;
+    hipLaunchKernelGGL(mci::k_strat_reduce, dim3(1), dim3(mci::kStratReduceThreads), 0, p->ctx->stream, r);
+    HIPCHK(hipGetLastError());
+    st.alloc_pending = adapt != 0; // (adapt = false: the allocation the call started with stays)
+    return MCI_OK;
+}
+
+// (mean, std) of a stratified iteration log row
+static void strat_mean_std(const double *row, int nobs, double *mean, double *std) {
+    for (int o = 0; o < nobs; ++o) {
+        mean[o] = row[o];
+        std[o] = row[nobs + o] > 0.0 ? sqrt(row[nobs + o]) : 0.0;
+    }
+}

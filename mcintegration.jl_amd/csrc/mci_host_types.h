@@ -296,6 +296,36 @@ struct mci_problem {
     // than the chains that measured the holds a launch's chains may be.  (MCI_MCMC_PILOT / MCI_MCMC_GROW: experiment knobs)
     static int64_t kMcmcPilotSteps, kMcmcGrow;
     static int64_t kMcmcCarryHolds, kMcmcCarryHalfFloors; // carried chains: length in longest holds | minimum length in HALF burn-in floors
+    // Stratified :vegas (VEGAS+, mci_set_stratification; mci_strat.h, mci_host_strat.h).  Not part of `config`: a problem keeps the map
+    // it trained, the allocation starts uniform in every mci_integrate call.
+    struct Strat {
+        bool on = false;
+        std::vector<int> want;        // nstrat the caller asked for, empty = the default plan (mci_strat_plan)
+        double beta = 0.75;
+        int64_t max_nhcube = (int64_t)1 << 24;
+        std::vector<int> nstrat;      // the plan in use (for nsamp samples per iteration), empty = none yet
+        int64_t ncube = 0, nsamp = 0;
+        long long *d_off = nullptr;   // [ncube + 1] offsets of the allocation the last run used; the next run overwrites them first
+        bool ran = false;             // d_off is the allocation a run of this plan used (mci_get_strat_counts)
+        bool alloc_valid = false;     // d_off holds an allocation for this plan (else the next run starts uniform)
+        bool alloc_pending = false;   // the next run first turns the d_h the last iteration measured into d_off (adapt)
+        double *d_d = nullptr;        // [ncube] d_h of the next allocation
+        double *d_tsum = nullptr;     // k_strat_alloc scratch
+        int64_t cap_cube = 0;
+        double *d_part = nullptr, *d_rec_s = nullptr, *d_stat = nullptr;
+        long long *d_rec_h = nullptr;
+        int64_t cap_chunk = 0, last_nchunk = 0;
+        bool last_run = false;        // the last mci_iteration_run was stratified: mci_iteration_finish reduces it
+        bool compiled = false;
+        int compiled_det = -1;
+        hipModule_t module = nullptr;
+        hipFunction_t f = nullptr;
+        std::string code_object;
+        // test hook (mci_debug_strat_dump): host buffers the next stratified run fills
+        double *hx = nullptr, *hy = nullptr, *hjac = nullptr, *hw = nullptr;
+        long long *hh = nullptr;
+        int64_t hn = 0;
+    } strat;
 };
 
 // A repeated iteration (the warm-up of automatic :mcmc chain lengths, mci_integrate) draws from the Philox streams of iteration
@@ -527,6 +557,12 @@ void drop_modules(mci_problem *p) {
     if (p->module_persist) {
         (void)hipModuleUnload(p->module_persist);
         p->module_persist = nullptr;
+    }
+    p->strat.compiled = false;
+    p->strat.f = nullptr;
+    if (p->strat.module) {
+        (void)hipModuleUnload(p->strat.module);
+        p->strat.module = nullptr;
     }
 }
 

@@ -34,6 +34,8 @@ extern const char *const kDeviceHeader;
 extern const char *const kTrainHeader;
 // text of mci_spec.h (the chain solvers with several lanes per chain): the second header of a kUnitSpec unit
 extern const char *const kSpecHeader;
+// text of mci_strat.h (the stratified :vegas sample kernel): the second header of a kUnitStrat unit
+extern const char *const kStratHeader;
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -101,9 +103,10 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // kUnitVegasPersist: the :vegas loop for measurefreq == 1 inside the persistent kernel of mci_train.h (all iterations of a launch-bound
 // integrate() call in one launch): sample loop + block merge + train!
 // kUnitSpec: a chain solver's kernel with several lanes per chain (mci_spec.h: vegasmc_chains_spec / mcmc_chains_spec)
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4 };
+// kUnitStrat: the stratified :vegas sample kernel (mci_strat.h: vegas_strat), measurefreq == 1
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5 };
 // which headers a unit is compiled against next to mci_device.h
-enum { kHdrNone = 0, kHdrTrain = 1, kHdrSpec = 2 };
+enum { kHdrNone = 0, kHdrTrain = 1, kHdrSpec = 2, kHdrStrat = 3 };
 inline std::string generate_source(const ProblemShape &s, int solver, int unit = kUnitSolver, double persist_alpha = 0.0) {
     std::ostringstream o;
     if (unit == kUnitVegasPersist) { // the learning rate and the size of the one leaf the persistent kernel refines (mci_train.h rescale, sum_julia)
@@ -116,6 +119,7 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
     o << "#include \"mci_device.h\"\n";
     if (unit == kUnitVegasPersist) o << "#include \"mci_train.h\"\n";
     if (unit == kUnitSpec) o << "#include \"mci_spec.h\"\n";
+    if (unit == kUnitStrat) o << "#include \"mci_strat.h\"\n";
     o << "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n";
     o << "#ifndef MCI_CHAIN_KERNEL_ATTR\n#define MCI_CHAIN_KERNEL_ATTR\n#endif\n"; // (occupancy experiments on the lane-per-chain kernels: MCI_JIT_FLAGS=-DMCI_CHAIN_KERNEL_ATTR=...)
     o << "namespace {\nstruct Cfg {\n";
@@ -173,7 +177,10 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
          "#define obs_add(k, v) mci::lds_add(&mci_obs_[(k)], (v))\n"
       << s.measure_body << "\n#undef obs_add\n    }\n";
     o << "};\n}\n";
-    if (solver == 0 && unit == kUnitDump) {
+    if (solver == 0 && unit == kUnitStrat) {
+        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_strat(mci::BatchArgs a, mci::StratArgs st) { "
+             "mci::vegas_strat<Cfg>(a, st); }\n";
+    } else if (solver == 0 && unit == kUnitDump) {
         o << "extern \"C\" __global__ void __launch_bounds__(256) mci_sample_dump(mci::DumpArgs a) { "
              "mci::sample_dump<Cfg>(a); }\n";
     } else if (solver == 0 && unit == kUnitVegasPersist) {
@@ -383,6 +390,7 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     std::string key = src + "\n//HDR\n" + kDeviceHeader;
     if (extra_hdr == kHdrTrain) key += std::string("\n//HDR\n") + kTrainHeader;
     if (extra_hdr == kHdrSpec) key += std::string("\n//HDR\n") + kSpecHeader;
+    if (extra_hdr == kHdrStrat) key += std::string("\n//HDR\n") + kStratHeader;
     for (auto &f : opts) key += "\n//" + f;
     key += "\n//COMPILER " + compiler_id();
     char name[64];
@@ -403,7 +411,8 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     if (cache_only) return -1; // (not in the cache: the caller compiles it elsewhere, e.g. on a thread of its own)
     warm_up_join();
     hiprtcProgram prog;
-    const char *hdr[2] = {kDeviceHeader, extra_hdr == kHdrSpec ? kSpecHeader : kTrainHeader}, *hname[2] = {"mci_device.h", extra_hdr == kHdrSpec ? "mci_spec.h" : "mci_train.h"};
+    const char *hdr[2] = {kDeviceHeader, extra_hdr == kHdrSpec ? kSpecHeader : extra_hdr == kHdrStrat ? kStratHeader : kTrainHeader},
+               *hname[2] = {"mci_device.h", extra_hdr == kHdrSpec ? "mci_spec.h" : extra_hdr == kHdrStrat ? "mci_strat.h" : "mci_train.h"};
     if (hiprtcCreateProgram(&prog, src.c_str(), "mci_problem.hip", extra_hdr != kHdrNone ? 2 : 1, hdr, hname) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return 1;

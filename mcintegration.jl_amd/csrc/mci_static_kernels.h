@@ -234,4 +234,148 @@ __global__ void __launch_bounds__(512) k_finish(MergeArgs m, TrainArgs a) {
     train_leaf(L, hl, hp, sm, ps, bad, ssum, a.edges, a.dacc, a.ddist, a.serial_walk, a.status, true, nullptr, false, a.spare ? hl : nullptr); // (hl: free once smoothed)
 }
 
+// =============================================================================================
+// Stratified :vegas (VEGAS+ hypercube redistribution, mci_strat.h): allocation and the iteration's statistics
+// =============================================================================================
+// k_strat_alloc: damped weights d_h -> sample offsets o_h.  C_h = M * P_h / P (M = N - 2 ncube, P_h = sum_{j <= h} d_j, P = P_{ncube-1}),
+// n_h = 2 + floor(C_h) - floor(C_{h-1}), o_h = 2 h + floor(C_{h-1}), C_{ncube-1} := M.  The prefix is formed in a fixed order -- every
+// thread adds its stretch of a tile sequentially, the stretches of a tile and the tiles are chained sequentially -- as
+// P_h = tile base + (stretch base + run), which is monotone in h (the addends are non-negative and every base is the exact sum the
+// stretch or tile before it ends on), so n_h >= 2 holds in floating point.  Three launches: phase 0 (ntile workgroups) tile sums, phase 1
+// (one workgroup) tile bases, total and the decision "uniform" (first iteration of a call, or a total that is 0 or not finite: d_h = 1),
+// phase 2 (ntile workgroups) the offsets.
+struct StratAllocArgs {
+    const double *d;        // [ncube]
+    long long *off;         // [ncube + 1] out
+    double *tsum;           // [2 * ntile + 2] scratch: tile sums | tile bases | total | uniform flag
+    long long ncube, nsamp;
+    int ntile;
+    int uniform;            // 1: d_h = 1 whatever d holds
+};
+__device__ inline void strat_stretch(const StratAllocArgs &a, long long &lo, long long &hi) {
+    const long long tl = (a.ncube + a.ntile - 1) / a.ntile, t0 = (long long)blockIdx.x * tl, t1 = t0 + tl < a.ncube ? t0 + tl : a.ncube;
+    const long long per = (t1 - t0 + 255) / 256;
+    lo = t0 + (long long)threadIdx.x * per;
+    if (lo > t1) lo = t1;
+    hi = lo + per < t1 ? lo + per : t1;
+}
+__global__ void __launch_bounds__(256) k_strat_alloc(StratAllocArgs a, int phase) {
+    __shared__ double part[256];
+    const int tid = threadIdx.x;
+    const long long M = a.nsamp - 2 * a.ncube;
+    if (phase == 1) {
+        if (tid != 0) return;
+        double base = 0.0;
+        for (int g = 0; g < a.ntile; ++g) {
+            a.tsum[a.ntile + g] = base;
+            base += a.tsum[g];
+        }
+        a.tsum[2 * a.ntile] = base;
+        a.tsum[2 * a.ntile + 1] = (a.uniform || !(base > 0.0) || !isfinite(base)) ? 1.0 : 0.0;
+        return;
+    }
+    long long lo, hi;
+    strat_stretch(a, lo, hi);
+    double mine = 0.0;
+    if (!(phase == 2 && a.tsum[2 * a.ntile + 1] != 0.0))
+        for (long long h = lo; h < hi; ++h) mine += a.d[h];
+    part[tid] = mine;
+    __syncthreads();
+    if (phase == 0) {
+        if (tid == 0) {
+            double s = 0.0;
+            for (int t = 0; t < 256; ++t) s += part[t];
+            a.tsum[blockIdx.x] = s;
+        }
+        return;
+    }
+    if (blockIdx.x == 0 && tid == 0) a.off[0] = 0;
+    if (a.tsum[2 * a.ntile + 1] != 0.0) { // uniform: C_h = M (h + 1) / ncube
+        for (long long h = lo; h < hi; ++h) {
+            double C = (double)M * (double)(h + 1) / (double)a.ncube;
+            if (h == a.ncube - 1 || C > (double)M) C = (double)M;
+            a.off[h + 1] = 2 * (h + 1) + (long long)floor(C);
+        }
+        return;
+    }
+    double sbase = 0.0; // this thread's stretch base within the tile: the stretches before it, added in order
+    for (int t = 0; t < tid; ++t) sbase += part[t];
+    const double tbase = a.tsum[a.ntile + blockIdx.x], total = a.tsum[2 * a.ntile];
+    double run = 0.0;
+    for (long long h = lo; h < hi; ++h) {
+        run += a.d[h];
+        double C = (double)M * (tbase + (sbase + run)) / total;
+        if (h == a.ncube - 1 || C > (double)M) C = (double)M;
+        a.off[h + 1] = 2 * (h + 1) + (long long)floor(C);
+    }
+}
+
+// k_strat_reduce: the iteration's (mean, var) per column from the chunks' partial rows (their interior hypercubes) and the boundary
+// records (the hypercubes the chunk boundaries cut: the pieces of one hypercube are the records of consecutive chunks, folded in chunk
+// order), and d_h = (sum_k s^2_{h,k})^(beta/2) of the cut hypercubes.  One workgroup; every thread takes a stretch of chunks, the threads'
+// sums are combined by a fixed tree: bit-identical run to run.  Writes out[2 nw] = mean | var and, when given, the same into the
+// iteration log row (row[k] = mean, row[nobs + k] = var).
+enum { kStratReduceCols = 8, kStratReduceThreads = 1024 };
+struct StratReduceArgs {
+    const long long *off;
+    const double *part;
+    const long long *rec_h;
+    const double *rec_s;
+    long long ncube, nchunk;
+    int nw;
+    double beta;
+    double *dnext;
+    double *out;
+    double *log_row;
+};
+__global__ void __launch_bounds__(kStratReduceThreads) k_strat_reduce(StratReduceArgs a) {
+    __shared__ double red[kStratReduceThreads];
+    const int tid = threadIdx.x, T = blockDim.x, nw = a.nw;
+    double acc[2 * kStratReduceCols];
+    for (int q = 0; q < 2 * kStratReduceCols; ++q) acc[q] = 0.0;
+    const double V = 1.0 / (double)a.ncube;
+    const long long per = (a.nchunk + T - 1) / T;
+    long long c0 = (long long)tid * per;
+    if (c0 > a.nchunk) c0 = a.nchunk;
+    const long long c1 = c0 + per < a.nchunk ? c0 + per : a.nchunk;
+    for (long long c = c0; c < c1; ++c) {
+        for (int q = 0; q < 2 * nw; ++q) acc[q] += a.part[c * 2 * nw + q];
+        for (int rr = 0; rr < 2; ++rr) {
+            const long long h = a.rec_h[2 * c + rr];
+            if (h < 0) continue;
+            if (rr == 0 && c > 0) { // a continuation of the previous chunk's last piece: folded there
+                const long long ph = a.rec_h[2 * c - 1] >= 0 ? a.rec_h[2 * c - 1] : a.rec_h[2 * c - 2];
+                if (ph == h) continue;
+            }
+            double S[2 * kStratReduceCols];
+            for (int q = 0; q < 2 * nw; ++q) S[q] = a.rec_s[(2 * c + rr) * 2 * nw + q];
+            for (long long d = c + 1; d < a.nchunk && a.rec_h[2 * d] == h; ++d)
+                for (int q = 0; q < 2 * nw; ++q) S[q] += a.rec_s[(2 * d) * 2 * nw + q];
+            const double n = (double)(a.off[h + 1] - a.off[h]);
+            double ssum = 0.0;
+            for (int q = 0; q < nw; ++q) {
+                double v2 = (S[nw + q] - S[q] * S[q] / n) / (n - 1.0);
+                v2 = v2 > 0.0 ? v2 : 0.0;
+                acc[q] += V / n * S[q];
+                acc[nw + q] += V * V * v2 / n;
+                ssum += v2;
+            }
+            a.dnext[h] = pow(ssum, 0.5 * a.beta);
+        }
+    }
+    for (int q = 0; q < 2 * nw; ++q) {
+        red[tid] = acc[q];
+        __syncthreads();
+        for (int s = T / 2; s > 0; s >>= 1) {
+            if (tid < s) red[tid] += red[tid + s];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            a.out[q] = red[0];
+            if (a.log_row) a.log_row[q] = red[0]; // (nobs == nw: row[k] = mean, row[nobs + k] = var)
+        }
+        __syncthreads();
+    }
+}
+
 } // namespace mci

@@ -439,11 +439,12 @@ class Engine:
     # ---- kernels -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_code(solver):
-        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6}.get(solver) or _lib.SOLVERS[solver]
+        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
-        "vegasmc_lanes" | "mcmc_lanes" (the chain solvers' kernels with several lanes per chain, csrc/mci_spec.h)"""
+        "vegasmc_lanes" | "mcmc_lanes" (the chain solvers' kernels with several lanes per chain, csrc/mci_spec.h) | "vegas_strat" (the
+        stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -692,6 +693,45 @@ class Engine:
         r, n = C.c_int32(), C.c_int32()
         check(lib().mci_comm_rank(context(self.device), C.byref(r), C.byref(n)))
         return int(n.value)
+
+    # ---- stratified :vegas (VEGAS+; mci_set_stratification) ---------------------------------------------------------------------
+    def set_stratification(self, nstrat=None, beta=0.75, max_nhcube=2 ** 24, on=True):
+        """stratified :vegas from the next iteration on (nstrat None: the default plan for the iteration's neval, mci_strat_plan);
+        on=False: back to plain :vegas"""
+        if not on:
+            check(lib().mci_set_stratification_off(self.p))
+            return
+        ns = None
+        if nstrat is not None:
+            self._nstrat = np.ascontiguousarray(nstrat, dtype=np.int32)
+            ns = self._nstrat.ctypes.data_as(c_int32_p)
+        check(lib().mci_set_stratification(self.p, self.ndraw, ns, float(beta), int(max_nhcube)))
+
+    def stratification(self):
+        """{nstrat, ncube, beta} of the plan in use, None when the problem is not stratified"""
+        ns, nc, b = np.zeros(self.ndraw, dtype=np.int32), C.c_int64(), C.c_double()
+        check(lib().mci_get_stratification(self.p, ns.ctypes.data_as(c_int32_p), C.byref(nc), C.byref(b)))
+        if not ns.any():
+            return None
+        return dict(nstrat=[int(v) for v in ns], ncube=int(nc.value), beta=float(b.value))
+
+    def strat_counts(self):
+        """n_h of every hypercube in the allocation the last stratified iteration used"""
+        info = self.stratification()
+        n = info["ncube"] if info else 0
+        out = np.zeros(n, dtype=np.int64)
+        check(lib().mci_get_strat_counts(self.p, out.ctypes.data_as(C.POINTER(C.c_int64)), n))
+        return out
+
+    def strat_dump_next(self, n):
+        """test hook (mci_debug_strat_dump): buffers the next stratified iteration of n samples fills -- x, y [n, ndraw], h [n], jac [n],
+        w [n, N * ncomp]; read them after that iteration ran"""
+        d = dict(x=np.zeros((n, self.ndraw)), y=np.zeros((n, self.ndraw)), h=np.zeros(n, dtype=np.int64), jac=np.zeros(n),
+                 w=np.zeros((n, self.config.N * self.config.ncomp)))
+        self._strat_dump = d
+        check(lib().mci_debug_strat_dump(self.p, int(n), _dp(d["x"]), _dp(d["y"]), d["h"].ctypes.data_as(C.POINTER(C.c_int64)),
+                                         _dp(d["jac"]), _dp(d["w"])))
+        return d
 
     def sample_dump(self, n, nevalperblock=None, block_index=0, iteration=0, seed=1234):
         nevalperblock = n if nevalperblock is None else nevalperblock

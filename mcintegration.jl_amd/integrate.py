@@ -14,6 +14,49 @@ from .statistics import Result, chain_estimator_bias, report
 from .variables import Continuous, Discrete
 
 
+class Stratify:
+    """integrate(..., solver="vegas", stratify=Stratify(...)): VEGAS+ adaptive stratified sampling (Lepage, J. Comput. Phys. 439
+    (2021) 110386; the default mode of the Python `vegas` package).  y-space is cut into prod(nstrat) hypercubes, every hypercube gets at
+    least two of an iteration's samples, and after every iteration the samples move between hypercubes in proportion to
+    (sum of the hypercube's variances)^(beta/2); beta = 0 keeps the stratification even.  nstrat None: the default plan for neval
+    (mci_strat_plan: about eight samples per hypercube, at most max_nhcube hypercubes).  An iteration's error is the stratified one:
+    `block` plays no part in it.  It is built from every hypercube's sample variance, so it is only as good as those: with an explicit
+    nstrat that leaves about two samples per hypercube, or with beta = 0, a heavy-tailed integrand's error comes out too small
+    (log(x)/sqrt(x): the means scatter 5.1 | 2.4 times the reported error, profiles/r07_stratified.txt); report() says so."""
+
+    def __init__(self, beta=0.75, nstrat=None, max_nhcube=2 ** 24):
+        self.beta, self.max_nhcube = float(beta), int(max_nhcube)
+        self.nstrat = None if nstrat is None else [int(v) for v in nstrat]
+
+    def __repr__(self):
+        return "Stratify(beta=%r, nstrat=%r, max_nhcube=%r)" % (self.beta, self.nstrat, self.max_nhcube)
+
+
+def _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm):
+    """the Stratify an integrate() call asks for (None: plain), refused -- before any engine exists -- where this mode does not reach"""
+    if stratify is None or stratify is False:
+        return None
+    st = Stratify() if stratify is True else stratify
+    if not isinstance(st, Stratify):
+        raise ValueError("stratify = %r: True or mci.Stratify(beta=..., nstrat=..., max_nhcube=...)" % (stratify,))
+    why = None
+    if SOLVERS.get(solver) != VEGAS:   # (the solver by name or by its constant, as integrate() takes it)
+        why = "solver = %r (stratified sampling is a :vegas mode)" % solver
+    elif any(not hasattr(lf, "ninc") for lf in config.leaves):
+        why = "a Discrete or FermiK variable (only Continuous variables are stratified)"
+    elif measure is not None:
+        why = "a user measure (the default measure only)"
+    elif measurefreq != 1:
+        why = "measurefreq = %s (every sample is measured)" % measurefreq
+    elif isinstance(integrand, HostIntegrand) or (trace is False and callable(integrand) and not isinstance(integrand, Integrand)):
+        why = "a host integrand (trace=False): device source or a traced closure only"
+    elif comm.size > 1:
+        why = "%d ranks (one rank only)" % comm.size
+    if why:
+        raise ValueError("stratify: refused for %s" % why)
+    return st
+
+
 def standardize_block(neval, nblock, nworker=1):
     """_standardize_block (main.jl:220-234)"""
     assert neval > nblock, "neval=%s should be larger than nblock = %s" % (neval, nblock)   # :222
@@ -164,7 +207,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
               adapt=True, debug=False, reweight_goal=None, ignore=None, measure=None, measurefreq=1,
               thermal_ratio=0.1, inplace=False, parallel="nothread", print=-1, printio=None, timer=None,
               comm=None, device=None, nchain=0, engine_factory=None, rng_bits=52, rng_rounds=10, deterministic=False, trace=None,
-              integrand_form=None, measure_form=None, **kwargs):
+              integrand_form=None, measure_form=None, stratify=None, **kwargs):
     """Same keywords as the reference (main.jl:71-90; unknown ones go to Configuration, :95-97).
     Extra, engine-specific keywords: `comm` (LocalComm | RcclComm | TorchDistComm), `device`, `nchain`
     (vegasmc chains per block; 0 = auto), `rng_bits` (52 | 32: opt-in cheaper uniform stream of solver="vegas", see
@@ -174,7 +217,8 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     trace_measure -- so that it runs inside the kernels like Julia's inlined closure does in the reference's loop; a closure that
     cannot be written out takes the host batch-callback path, silently with None, with a RuntimeWarning naming the reason with True;
     False: always the host path), `integrand_form` / `measure_form` (callback_form: by default a closure is called in the form the
-    reference's solver calls it in -- `inplace` included -- and one whose parameters do not fit raises TypeError), `engine_factory`
+    reference's solver calls it in -- `inplace` included -- and one whose parameters do not fit raises TypeError), `stratify` (True or
+    Stratify(beta, nstrat, max_nhcube): VEGAS+ adaptive stratified sampling under solver="vegas", see Stratify), `engine_factory`
     (test seam)."""
     if trace is None:
         trace = TRACE_DEFAULT
@@ -190,6 +234,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     if ignore is None:
         ignore = 1 if adapt else 0                                                    # main.jl:82
     comm = comm or LocalComm()
+    strat = _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm)
     if device is None:   # an RcclComm is bound to one device: the engine has to live there (its all_reduce checks it)
         device = getattr(comm, "device", 0)
     neval = int(neval)
@@ -201,6 +246,14 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     eng = _bind(config, integrand, measure, solver, inplace=inplace, trace=trace, print=print, device=device, engine_factory=engine_factory,
                 rng_bits=rng_bits, rng_rounds=rng_rounds, deterministic=deterministic, integrand_form=integrand_form, measure_form=measure_form)
     s = SOLVERS[solver]
+    if strat is not None:
+        if isinstance(eng.integrand, HostIntegrand):
+            raise ValueError("stratify: refused for a host integrand (the closure did not trace): device source or a traced closure only")
+        eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)   # (the allocation starts uniform)
+        eng._strat_on = True
+    elif getattr(eng, "_strat_on", False):   # a plain call on an engine an earlier call stratified: the plain kernels again
+        eng.set_stratification(on=False)
+        eng._strat_on = False
     if hasattr(eng, "set_reweight_goal"):
         eng.set_reweight_goal(reweight_goal)                                          # main.jl:81, :334-337
 
@@ -279,6 +332,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
             res.chain_bias = chain_estimator_bias(solver, nevalperblock, eng.last_chain_launch()[0], block, niter - ignore, pr, ac, eng.ndraw)
         except Exception:
             res.chain_bias = None
+    res.stratification = eng.stratification() if strat is not None else None   # {nstrat, ncube, beta} of a stratified run
     res.warmup = warmup   # launches that were run again instead of being counted (automatic :mcmc chain lengths)
     res.neval_discarded = neval_discarded   # ... and their evaluations: spent (they trained the map), in neither res.neval nor the estimate
     if print >= 0:

@@ -111,6 +111,8 @@ class Result:
         # set by integrate() for a chain solver that ran the reference's one chain per block: chain_estimator_bias (report() prints a
         # note where the expected bias of the blocks' ratio estimator reaches 2 of the final error bars)
         self.chain_bias = None
+        # set by integrate() for a stratified :vegas run (stratify=...): {nstrat, ncube, beta} of the plan it ran, else None
+        self.stratification = None
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
         self.iterations = [(self._shape(self.iter_mean[i]), self._shape(self.iter_std[i]), config) for i in range(niter)]
 
@@ -136,6 +138,7 @@ class Result:
             return self
         r = Result(self.iter_mean, self.iter_std, self.config, ignore, self.neval, self.seconds, self.block_mean, self.correlated, self.block)
         r.chain_bias = self.chain_bias
+        r.stratification = self.stratification
         return r
 
     @property
@@ -283,5 +286,17 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
                     "   (%d warm-up launches run again)" % result.warmup if getattr(result, "warmup", 0) else ""), file=io)
         else:
             print("Integral %s = %s ± %s" % (info, result._flat_mean[col], result._flat_std[col]), file=io)
+    st = getattr(result, "stratification", None)
+    if st:   # (not in the reference: VEGAS+ stratification of the :vegas run)
+        ns = st["nstrat"]
+        print("  stratified sampling: %d hypercubes (nstrat = %s), beta = %g; iteration errors are the stratified ones" % (
+            st["ncube"], ns if len(set(ns)) > 1 else "%d x %d" % (ns[0], len(ns)), st["beta"]), file=io)
+        niter = max(result.iter_mean.shape[0], 1)
+        per = result.neval / niter / max(st["ncube"], 1)
+        if per < 4 or st["beta"] == 0:
+            print("  note: %s -- the errors above can be far too small on heavy-tailed integrands (the default plan keeps about eight "
+                  "samples per hypercube and moves them with beta = 0.75)" % (
+                      "%.1f samples per hypercube" % per if per < 4 else "beta = 0 keeps the samples of a heavy tail's hypercube at the average"),
+                  file=io)
     if getattr(result, "chain_bias_note", None):   # (not in the reference)
         print("  " + result.chain_bias_note, file=io)
