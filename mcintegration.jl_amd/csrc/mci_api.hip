@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "mci_device.h" // BatchArgs / DumpArgs (the templates themselves are instantiated by the JIT)

@@ -272,20 +272,20 @@ int mci_set_kernel_timing(mci_problem *p, int32_t mode) {
 int mci_kernel_times_ms(mci_problem *p, float *ms, int32_t n, int32_t *got, int32_t *wg, int32_t *threads) {
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
     HIPCHK(hipStreamSynchronize(p->ctx->stream));
-    int64_t have = p->launches < mci_problem::kEvRing ? p->launches : mci_problem::kEvRing;
+    int64_t have = p->launch.launches < mci_problem::kEvRing ? p->launch.launches : mci_problem::kEvRing;
     if (have > n) have = n;
     int64_t k = 0;
     for (int64_t i = 0; i < have; ++i) { // oldest first; launches that ran without events (mci_set_kernel_timing) are skipped
-        const int slot = (int)((p->launches - have + i) % mci_problem::kEvRing);
-        if (!p->ev_valid[slot]) continue;
+        const int slot = (int)((p->launch.launches - have + i) % mci_problem::kEvRing);
+        if (!p->launch.ev_valid[slot]) continue;
         float t = 0.f;
         HIPCHK(hipEventElapsedTime(&t, p->evs[2 * slot], p->evs[2 * slot + 1]));
         ms[k++] = t;
     }
     have = k;
     if (got) *got = (int32_t)have;
-    if (wg) *wg = p->last_wg;
-    if (threads) *threads = p->last_threads;
+    if (wg) *wg = p->launch.last_wg;
+    if (threads) *threads = p->launch.last_threads;
     return MCI_OK;
 }
 
@@ -302,12 +302,12 @@ int mci_kernel_clocks(mci_problem *p, double *mhz, int32_t n, int32_t *got) {
     std::vector<unsigned long long> h((size_t)2 * mci_problem::kEvRing);
     HIPCHK(hipMemcpyAsync(h.data(), p->d_clocks, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->ctx->stream));
     HIPCHK(hipStreamSynchronize(p->ctx->stream));
-    int64_t have = p->launches < mci_problem::kEvRing ? p->launches : mci_problem::kEvRing;
+    int64_t have = p->launch.launches < mci_problem::kEvRing ? p->launch.launches : mci_problem::kEvRing;
     if (have > n) have = n;
     int32_t k = 0;
     for (int64_t i = 0; i < have; ++i) {
-        const int slot = (int)((p->launches - have + i) % mci_problem::kEvRing);
-        if (!p->ev_valid[slot] || !p->clock_valid[slot] || !h[(size_t)2 * slot + 1]) continue; // (a slot whose launch did not stamp holds an older launch's words)
+        const int slot = (int)((p->launch.launches - have + i) % mci_problem::kEvRing);
+        if (!p->launch.ev_valid[slot] || !p->launch.clock_valid[slot] || !h[(size_t)2 * slot + 1]) continue; // (a slot whose launch did not stamp holds an older launch's words)
         mhz[k++] = (double)h[(size_t)2 * slot] / (double)h[(size_t)2 * slot + 1] * (double)khz * 1.0e-3;
     }
     *got = k;

@@ -254,14 +254,14 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     HIPCHK(hipModuleLaunchKernel(p->f_persist, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
     p->persist_arrive += (unsigned long long)(ia->niter + 1) * (unsigned long long)nrows; // (+ one "finished reading" per workgroup at the end)
     p->persist_done += (unsigned long long)ia->niter;
-    p->time_this_launch = false;
+    p->launch.time_this_launch = false;
     p->merge_pending = false;
     p->merge = m; // (what `packed` was merged from, for the record)
     p->merge.part_cols = p->d_part_cols + (size_t)((ia->niter - 1) & 1) * (size_t)nrows * s.ncols;
-    p->last_samples = nblocks * nevalperblock;
-    p->last_wg = (int)nrows;
-    p->last_threads = T;
-    p->last_nblocks = (int)nblocks;
+    p->launch.last_samples = nblocks * nevalperblock;
+    p->launch.last_wg = (int)nrows;
+    p->launch.last_threads = T;
+    p->launch.last_nblocks = (int)nblocks;
     p->log_row += ia->niter;
     return MCI_OK;
 }
@@ -325,10 +325,10 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     int64_t blk_row0 = -1; // this call's first row of the block log (chain solvers): the log starts over with every call
     if (a->solver != MCI_VEGAS) {
         if ((rc = flush_merge(p))) return rc; // (a pending merge writes its row of the old log)
-        p->blk_rows = 0;
-        p->blk_carried = 0;
-        p->blk_stride = (hi - lo) * s.nobs;
-        p->blk_lo = lo;
+        p->launch.blk_rows = 0;
+        p->launch.blk_carried = 0;
+        p->launch.blk_stride = (hi - lo) * s.nobs;
+        p->launch.blk_lo = lo;
         blk_row0 = 0;
         if ((rc = grow_block_log(p, a->niter))) return rc;
     }
@@ -357,8 +357,8 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
                 // go on -- and runs again with longer chains (the Philox streams of iteration + kRepeatStride * attempt), until the
                 // first launch that is long enough; from then on nothing is repeated.  The first iteration of a call that ignores it
                 // anyway (main.jl:82) is let through as it is.
-                if (a->solver != MCI_MCMC || a->nchain > 0 || p->mcmc_warm || (it == 0 && ignore >= 1) || attempt >= kMaxRepeats ||
-                    a->first_iteration + it >= kRepeatStride || p->last_nchain <= 1 || !p->hold_inflight)
+                if (a->solver != MCI_MCMC || a->nchain > 0 || p->launch.mcmc_warm || (it == 0 && ignore >= 1) || attempt >= kMaxRepeats ||
+                    a->first_iteration + it >= kRepeatStride || p->launch.last_nchain <= 1 || !p->launch.hold_inflight)
                     break;
                 int32_t valid = 0;
                 if ((rc = mci_mcmc_launch_valid(p, &valid, nullptr, nullptr, nullptr))) return rc;
@@ -410,10 +410,10 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     // (mci_lineage_sums + the reference's own _mean_std over them); same weights, same mean.
     res->correlated = 0;
     res->warmup = res_warmup;
-    if (a->solver != MCI_VEGAS && blk_row0 >= 0 && p->blk_rows - blk_row0 == a->niter && p->blk_carried > 0 && a->niter > ignore + 1) {
+    if (a->solver != MCI_VEGAS && blk_row0 >= 0 && p->launch.blk_rows - blk_row0 == a->niter && p->launch.blk_carried > 0 && a->niter > ignore + 1) {
         const int64_t nb = hi - lo;
         std::vector<double> bm((size_t)a->niter * nb * s.nobs), sums(2 * (size_t)s.nobs);
-        HIPCHK(hipMemcpyAsync(bm.data(), p->d_blocklog + (size_t)blk_row0 * p->blk_stride, bm.size() * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+        HIPCHK(hipMemcpyAsync(bm.data(), p->d_blocklog + (size_t)blk_row0 * p->launch.blk_stride, bm.size() * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
         HIPCHK(hipStreamSynchronize(p->ctx->stream));
         mci_lineage_sums(bm.data(), a->niter, nb, s.nobs, res->iter_std, ignore + 1, a->niter, sums.data(), sums.data() + s.nobs);
         if ((rc = comm_sum_host(p, sums.data(), (int)sums.size()))) return rc;

@@ -46,11 +46,11 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     // target there, and no resampling turns them into a sample of the new one, profiles/r05_bias.txt A4; while the map stays as it is
     // -- adapt = false -- they go on towards the same target)
     const bool carry_on = p->chain_carry != 0;
-    const bool may_carry = solver != MCI_VEGAS && carry_on && p->chain_valid && p->chain_solver == solver &&
-                           p->chain_lo == block_lo && p->chain_hi == block_hi && p->chain_nchain > 1 &&
-                           (solver != MCI_VEGASMC || p->chain_ntrain >= 1 || p->chain_ntrain == p->ntrain) &&
-                           ((p->chain_iteration & (kRepeatStride - 1)) + 1 == (iteration & (kRepeatStride - 1)) ||                        // the next iteration
-                            ((p->chain_iteration & (kRepeatStride - 1)) == (iteration & (kRepeatStride - 1)) && iteration > p->chain_iteration)); // ... or the same one again (mci_integrate, warm-up)
+    const bool may_carry = solver != MCI_VEGAS && carry_on && p->launch.chain_valid && p->launch.chain_solver == solver &&
+                           p->launch.chain_lo == block_lo && p->launch.chain_hi == block_hi && p->launch.chain_nchain > 1 &&
+                           (solver != MCI_VEGASMC || p->launch.chain_ntrain >= 1 || p->launch.chain_ntrain == p->ntrain) &&
+                           ((p->launch.chain_iteration & (kRepeatStride - 1)) + 1 == (iteration & (kRepeatStride - 1)) ||                        // the next iteration
+                            ((p->launch.chain_iteration & (kRepeatStride - 1)) == (iteration & (kRepeatStride - 1)) && iteration > p->launch.chain_iteration)); // ... or the same one again (mci_integrate, warm-up)
     if (solver == MCI_VEGASMC) {
         int nslots = 0; // (pool, slot) pairs changeVariable can pick (updates.jl:50,:58)
         for (int v = 0; v < p->npool; ++v) nslots += p->maxdof[v];
@@ -102,8 +102,8 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             // holds (mci_mcmc_auto_chains).
             if ((rc = hold_consume(p))) return rc;
             // (once warm: the larger of the last two launches' holds, and no growth cap -- both were measured by chains that held them)
-            const int64_t hold_eff = p->mcmc_warm && p->hold_prev > p->hold_max ? p->hold_prev : p->hold_max;
-            nchain = mci_mcmc_auto_chains(nevalperblock, nblocks, nslots, p->ni + 1, p->npool, hold_eff, p->mcmc_warm && p->hold_valid ? 0 : p->hold_len,
+            const int64_t hold_eff = p->launch.mcmc_warm && p->launch.hold_prev > p->launch.hold_max ? p->launch.hold_prev : p->launch.hold_max;
+            nchain = mci_mcmc_auto_chains(nevalperblock, nblocks, nslots, p->ni + 1, p->npool, hold_eff, p->launch.mcmc_warm && p->launch.hold_valid ? 0 : p->launch.hold_len,
                                           may_carry ? 1 : 0);
         }
         if (nchain > nevalperblock) return fail(MCI_ERR_INVALID, "nchain=%lld exceeds the %lld steps of a block", (long long)nchain, (long long)nevalperblock);
@@ -154,8 +154,8 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         T_launch = units >= 256 ? 256 : (int)((units + 63) / 64) * 64;
     }
     if (G == 1 && (rc = compile_solver(p, kern))) return rc;
-    p->last_spec_lanes = G;
-    p->last_spec_maxacc = spec_maxacc;
+    p->launch.last_spec_lanes = G;
+    p->launch.last_spec_maxacc = spec_maxacc;
     int wpb = p->wg_per_block;
     if (G > 1) {
         if (wpb <= 0) wpb = (int)((2048 + nblocks - 1) / nblocks);
@@ -235,8 +235,8 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             p->d_tile_bins = (uint32_t *)((char *)p->d_tile_w + wbytes);
             p->cap_tile = nsamp;
         }
-        p->last_split_chunks = nchunks;
-        p->last_split_bytes = nsamp * bytes;
+        p->launch.last_split_chunks = nchunks;
+        p->launch.last_split_bytes = nsamp * bytes;
     }
     mci::BatchArgs a{};
     a.edges = p->d_edges;
@@ -263,11 +263,12 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     if (solver != MCI_VEGAS) {
         const bool carried = may_carry && nchain > 1;
         const bool keep = carry_on && nchain > 1;
+        if (keep && p->in_self_check) return fail(MCI_ERR_INVALID, "the self-check's launch would overwrite the stored chains");
         if (carried) {
-            a.carry_x = p->d_chain_x[p->chain_cur];
-            a.carry_curr = p->d_chain_curr[p->chain_cur];
-            a.carry_nchain = p->chain_nchain;
-            a.carry_cap = p->chain_cap[p->chain_cur];
+            a.carry_x = p->d_chain_x[p->launch.chain_cur];
+            a.carry_curr = p->d_chain_curr[p->launch.chain_cur];
+            a.carry_nchain = p->launch.chain_nchain;
+            a.carry_cap = p->chain_cap[p->launch.chain_cur];
         }
         if (carried) { // which stored chain each chain continues: the stored ones resampled to the moved target
             if (nblocks * nchain > p->cap_carry_src) {
@@ -277,16 +278,16 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
                 HIPCHK(hipMalloc((void **)&p->d_carry_src, (size_t)(nblocks * nchain) * sizeof(int)));
                 p->cap_carry_src = nblocks * nchain;
             }
-            if (nblocks * p->chain_nchain > p->cap_carry_W) {
+            if (nblocks * p->launch.chain_nchain > p->cap_carry_W) {
                 if (p->d_carry_W) (void)hipFree(p->d_carry_W);
                 p->d_carry_W = nullptr;
                 p->cap_carry_W = 0;
-                HIPCHK(hipMalloc((void **)&p->d_carry_W, (size_t)(nblocks * p->chain_nchain) * sizeof(double)));
-                p->cap_carry_W = nblocks * p->chain_nchain;
+                HIPCHK(hipMalloc((void **)&p->d_carry_W, (size_t)(nblocks * p->launch.chain_nchain) * sizeof(double)));
+                p->cap_carry_W = nblocks * p->launch.chain_nchain;
             }
             mci::ResampleArgs ra{};
-            ra.curr_old = p->d_chain_curr[p->chain_cur];
-            ra.n_old = p->chain_nchain;
+            ra.curr_old = p->d_chain_curr[p->launch.chain_cur];
+            ra.n_old = p->launch.chain_nchain;
             ra.n_new = nchain;
             ra.nd = p->ni + 1;
             ra.rw_now = p->d_reweight;
@@ -296,7 +297,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             if (solver == MCI_VEGASMC) {
                 // :vegasmc: the target itself moved with the map and the reweight factors -- pi_new / pi_old at every stored configuration
                 // (the chain kernel's own code object evaluates it: relocate, integrand, paddings), then the same systematic resampling
-                const int64_t total = nblocks * p->chain_nchain;
+                const int64_t total = nblocks * p->launch.chain_nchain;
                 if (total > p->cap_carry_w) {
                     if (p->d_carry_w) (void)hipFree(p->d_carry_w);
                     p->d_carry_w = nullptr;
@@ -304,7 +305,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
                     HIPCHK(hipMalloc((void **)&p->d_carry_w, (size_t)total * sizeof(double)));
                     p->cap_carry_w = total;
                 }
-                a.carry_P = p->d_chain_P[p->chain_cur];
+                a.carry_P = p->d_chain_P[p->launch.chain_cur];
                 a.carry_w = p->d_carry_w;
                 a.carry_total = total;
                 mci::BatchArgs wa = a; // (edges, tables, reweight, userdata and the carry fields; everything else unused)
@@ -341,7 +342,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             HIPCHK(hipMemcpyAsync(p->d_reweight_used, p->d_reweight, (size_t)(p->ni + 1) * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
         }
         if (keep) {
-            const int wb = p->chain_valid ? 1 - p->chain_cur : p->chain_cur;
+            const int wb = p->launch.chain_valid ? 1 - p->launch.chain_cur : p->launch.chain_cur;
             const int64_t need = nblocks * nchain;
             if (need > p->chain_cap[wb]) {
                 if (p->d_chain_x[wb]) (void)hipFree(p->d_chain_x[wb]);
@@ -360,18 +361,18 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             a.store_curr = p->d_chain_curr[wb];
             a.store_P = solver == MCI_VEGASMC ? p->d_chain_P[wb] : nullptr;
             a.store_cap = p->chain_cap[wb];
-            p->chain_cur = wb;
-            p->chain_valid = true;
-            p->chain_ntrain = p->ntrain;
-            p->chain_solver = solver;
-            p->chain_iteration = iteration;
-            p->chain_lo = block_lo;
-            p->chain_hi = block_hi;
-            p->chain_nchain = nchain;
+            p->launch.chain_cur = wb;
+            p->launch.chain_valid = true;
+            p->launch.chain_ntrain = p->ntrain;
+            p->launch.chain_solver = solver;
+            p->launch.chain_iteration = iteration;
+            p->launch.chain_lo = block_lo;
+            p->launch.chain_hi = block_hi;
+            p->launch.chain_nchain = nchain;
         } else {
-            p->chain_valid = false;
+            p->launch.chain_valid = false;
         }
-        p->last_carried = carried;
+        p->launch.last_carried = carried;
     }
     if (solver == MCI_MCMC && !s.host_integrand && nevalperblock / nchain + nburn < ((int64_t)1 << 31) - 1) {
         if (!p->d_hold) HIPCHK(hipMalloc((void **)&p->d_hold, 64 * sizeof(unsigned long long)));
@@ -526,19 +527,19 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     void *args[] = {&a};
     hipFunction_t f = p->f_solver[G > 1 ? (solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec) : kern];
     hipStream_t st = p->ctx->stream;
-    const int slot = (int)(p->launches % mci_problem::kEvRing);
+    const int slot = (int)(p->launch.launches % mci_problem::kEvRing);
     // HIP events around the sample launch (mci_kernel_times_ms): each record is a barrier packet with a signal, ~5.5 us of idle
     // queue -- a third of a launch-bound iteration (neval = 1e4: 36 -> 25 us), nothing next to a launch of millions of samples.
     // mci_set_kernel_timing: -1 (default) = launches of >= 2^20 samples, 0 = never, 1 = always
-    p->time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && nblocks * nevalperblock >= ((int64_t)1 << 20));
-    if (p->time_this_launch && solver == MCI_VEGAS) { // ... and the clock the sample loop ran at (mci_kernel_clocks)
+    p->launch.time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && nblocks * nevalperblock >= ((int64_t)1 << 20));
+    if (p->launch.time_this_launch && solver == MCI_VEGAS) { // ... and the clock the sample loop ran at (mci_kernel_clocks)
         if (!p->d_clocks) {
             HIPCHK(hipMalloc((void **)&p->d_clocks, (size_t)2 * mci_problem::kEvRing * sizeof(unsigned long long)));
             HIPCHK(hipMemsetAsync(p->d_clocks, 0, (size_t)2 * mci_problem::kEvRing * sizeof(unsigned long long), st));
         }
         a.clock_out = p->d_clocks + 2 * slot;
     }
-    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], st));
+    if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], st));
     if (solver != MCI_VEGAS && s.host_integrand) {
         // The closure sits inside the Markov step (vegas_mc/updates.jl:67-75, mcmc/updates.jl:35-38): the chains of this launch advance
         // in lock step, one kernel launch per step; each hands the host the nc configurations to evaluate and takes their weights back
@@ -627,15 +628,15 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         if (split && c + 1 < nchunks)
             HIPCHK(hipModuleLaunchKernel(p->f_tiles[kern == kSlotVegasAny ? 1 : 0], (unsigned)(((hist_rows + 7) / 8) * 8 * (s.ntile - (s.split_all ? 0 : 1))), 1, 1, (unsigned)T, 1, 1, (unsigned)p->lds_bytes, st, args, nullptr));
     }
-    if (solver == MCI_MCMC) p->hold_measured = a.hold_hist != nullptr;
+    if (solver == MCI_MCMC) p->launch.hold_measured = a.hold_hist != nullptr;
     // (an explicit chain count: nobody sizes a launch from this one's holds, and the host keeps queueing launches back to back)
-    if (a.hold_hist && auto_chains && (rc = hold_publish(p, nevalperblock / nchain, solver != MCI_VEGAS && p->last_carried))) return rc;
+    if (a.hold_hist && auto_chains && (rc = hold_publish(p, nevalperblock / nchain, solver != MCI_VEGAS && p->launch.last_carried))) return rc;
     if (split) // (the replay of the one chunk, or of the last one)
         HIPCHK(hipModuleLaunchKernel(p->f_tiles[kern == kSlotVegasAny ? 1 : 0], (unsigned)(((hist_rows + 7) / 8) * 8 * (s.ntile - (s.split_all ? 0 : 1))), 1, 1, (unsigned)T, 1, 1, (unsigned)p->lds_bytes, st, args, nullptr));
-    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], st));
-    p->ev_valid[slot] = p->time_this_launch;
-    p->clock_valid[slot] = a.clock_out != nullptr && !split && s.ntile == 1; // (what the kernel stamps: mci_device.h vegas_batch `stamp`)
-    p->launches += 1;
+    if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], st));
+    p->launch.ev_valid[slot] = p->launch.time_this_launch;
+    p->launch.clock_valid[slot] = a.clock_out != nullptr && !split && s.ntile == 1; // (what the kernel stamps: mci_device.h vegas_batch `stamp`)
+    p->launch.launches += 1;
     if (s.host_measure) {
         // the closure cannot run on the device: this launch's (measured) configurations and relative weights go to the host
         // (draw-major, like the host integrand path), the callback accumulates block b's observables from block b's records, and
@@ -707,11 +708,11 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st)); // `obs` leaves scope
     }
-    p->last_samples = nblocks * nevalperblock;
-    p->last_wg = (int)nwg;
-    p->last_threads = T_launch;
-    p->last_nblocks = (int)nblocks;
-    if (solver != MCI_VEGAS) p->last_nchain = nchain;
+    p->launch.last_samples = nblocks * nevalperblock;
+    p->launch.last_wg = (int)nwg;
+    p->launch.last_threads = T_launch;
+    p->launch.last_nblocks = (int)nblocks;
+    if (solver != MCI_VEGAS) p->launch.last_nchain = nchain;
     // merge: block sums -> packed
     const int nb256 = (s.nbin + 255) / 256;
     // (reading a few partial rows directly in the second stage instead -- no first-stage launch when an iteration is launch-bound --
@@ -740,18 +741,20 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     m.nrows = (int)nrows;
     m.block_means = nullptr;
     m.hold = a.hold_hist; // (:mcmc: the 64 counts follow the tables in `packed`, so that ONE all-reduce carries them; NULL: zeros)
-    if (solver != MCI_VEGAS) { // the chain solvers keep every block's mean of every iteration (one row of the block log)
+    // the chain solvers keep every block's mean of every iteration (one row of the block log; not the self-check's launches: their rows,
+    // of another stride, would land on the logged ones)
+    if (solver != MCI_VEGAS && !p->in_self_check) {
         const int64_t stride = nblocks * s.nobs;
-        if (stride != p->blk_stride || block_lo != p->blk_lo) {
-            p->blk_rows = 0;
-            p->blk_carried = 0;
-            p->blk_stride = stride;
-            p->blk_lo = block_lo;
+        if (stride != p->launch.blk_stride || block_lo != p->launch.blk_lo) {
+            p->launch.blk_rows = 0;
+            p->launch.blk_carried = 0;
+            p->launch.blk_stride = stride;
+            p->launch.blk_lo = block_lo;
         }
-        if ((rc = grow_block_log(p, p->blk_rows + 1))) return rc;
-        m.block_means = p->d_blocklog + (size_t)p->blk_rows * stride;
-        p->blk_rows += 1;
-        p->blk_carried += p->last_carried ? 1 : 0;
+        if ((rc = grow_block_log(p, p->launch.blk_rows + 1))) return rc;
+        m.block_means = p->d_blocklog + (size_t)p->launch.blk_rows * stride;
+        p->launch.blk_rows += 1;
+        p->launch.blk_carried += p->launch.last_carried ? 1 : 0;
     }
     p->merge_pending = true;
     return MCI_OK;
@@ -775,7 +778,7 @@ int mci_iteration_reduce(mci_problem *p) {
     if (rc) return rc;
     // HIP events around the collective under the sample launch's rule (mci_set_kernel_timing): what a rank waits for here is the
     // slowest rank's sample pass plus the latency of one small all-reduce (mci_comm_times_ms)
-    const bool timed = p->time_this_launch;
+    const bool timed = p->launch.time_this_launch;
     const int slot = (int)(p->reduces % mci_problem::kCevRing);
     if (timed) {
         if (p->cevs.empty()) {
@@ -786,12 +789,12 @@ int mci_iteration_reduce(mci_problem *p) {
     }
     // ONE collective per iteration whatever the solver: [statistics | histograms | propose | accept] and, behind an :mcmc launch that
     // measured its holding times, the 64 counts of their histogram (exact in doubles)
-    const size_t count = (size_t)p->packed_n + (p->hold_deferred ? 64 : 0);
+    const size_t count = (size_t)p->packed_n + (p->launch.hold_deferred ? 64 : 0);
     int r = g_rccl.AllReduce(p->d_packed, p->d_packed, count, kNcclFloat64, kNcclSum, p->ctx->comm, p->ctx->stream);
     if (r) return fail(MCI_ERR_COMM, "ncclAllReduce: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
     p->ctx->collectives += 1;
     p->ctx->last_count = (long long)count;
-    if (p->hold_deferred && (rc = hold_publish_reduced(p))) return rc; // the summed holding-time counts -> pinned host memory
+    if (p->launch.hold_deferred && (rc = hold_publish_reduced(p))) return rc; // the summed holding-time counts -> pinned host memory
     if (timed) HIPCHK(hipEventRecord(p->cevs[2 * slot + 1], p->ctx->stream));
     p->cev_valid[slot] = timed;
     p->reduces += 1;
@@ -810,8 +813,8 @@ int mci_comm_collectives(const mci_ctx *c, int64_t *calls, int64_t *last_count) 
 int mci_external_reduce_done(mci_problem *p) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
-    if (!p->hold_ext_pending) return MCI_OK;
-    p->hold_ext_pending = false;
+    if (!p->launch.hold_ext_pending) return MCI_OK;
+    p->launch.hold_ext_pending = false;
     HIPCHK(hipSetDevice(p->ctx->device));
     return hold_publish_reduced(p);
 }
@@ -860,7 +863,7 @@ static int launch_train(mci_problem *p, int do_train, int do_reweight, double ga
     a.gamma = gamma;
     a.do_train = do_train;
     if (do_train) p->ntrain += 1;
-    a.serial_walk = p->train_serial >= 0 ? p->train_serial : (p->last_samples == 0 || p->last_samples >= mci_problem::kSerialWalkSamples) ? 1 : 0;
+    a.serial_walk = p->train_serial >= 0 ? p->train_serial : (p->launch.last_samples == 0 || p->launch.last_samples >= mci_problem::kSerialWalkSamples) ? 1 : 0;
     if (p->debug_wrong_decision && a.serial_walk == 1) a.serial_walk = 3;
     a.status = p->d_status;
     a.maxn = maxn;

@@ -286,19 +286,16 @@ static int compile_spec(mci_problem *p, int solver) {
 // lane-per-chain kernel, and the two packed buffers are compared: statistics to 1e-9, histogram and propose / accept tables to 1e-8
 // (relative to the larger entry, with the section's largest entry as the floor).  Agreement: a marker file next to the code object,
 // never checked again.  Disagreement: one warning, status -1, and the problem keeps one lane per chain.  The launch that triggered
-// the check then runs as if nothing had happened: everything a launch leaves behind on the host side is put back.
+// the check then runs as if nothing had happened: everything a launch leaves behind on the host side (p->launch) is put back.
 static int spec_self_check(mci_problem *p, int solver, int G, int64_t nevalperblock, int64_t block_lo, int64_t block_hi, int32_t iteration,
                            uint64_t seed, int64_t measurefreq, double thermal_ratio) {
     const int slot = solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec;
     const int64_t nb = block_hi - block_lo < 2 ? block_hi - block_lo : 2, npb = nevalperblock < 512 ? nevalperblock : 512;
     const int64_t mf = measurefreq * 4 <= npb ? measurefreq : 1;
-    struct Saved {
-        int spec_lanes, kernel_timing, chain_cur, chain_solver, chain_iteration, last_wg, last_threads, last_nblocks, last_spec_lanes, last_spec_maxacc, blk_carried;
-        bool chain_valid, last_carried, hold_measured, time_this_launch;
-        int64_t chain_lo, chain_hi, chain_nchain, chain_ntrain, last_samples, last_nchain, launches, blk_rows, blk_stride, blk_lo;
-    } sv = {p->spec_lanes, p->kernel_timing, p->chain_cur, p->chain_solver, p->chain_iteration, p->last_wg, p->last_threads, p->last_nblocks, p->last_spec_lanes,
-            p->last_spec_maxacc, p->blk_carried, p->chain_valid, p->last_carried, p->hold_measured, p->time_this_launch, p->chain_lo, p->chain_hi, p->chain_nchain,
-            p->chain_ntrain, p->last_samples, p->last_nchain, p->launches, p->blk_rows, p->blk_stride, p->blk_lo};
+    // (the stored chains on the device are safe: the check launches run nchain = 1, so they keep none -- mci_iteration_run refuses to
+    // otherwise -- and they log no block means)
+    const mci_problem::LaunchState saved = p->launch; // (everything the two launches leave on the host: put back below)
+    const int spec_lanes = p->spec_lanes, kernel_timing = p->kernel_timing; // (the two settings the check overrides)
     int rc = flush_merge(p);
     if (rc) return rc;
     int h_status[4] = {0, 0, 0, 0};
@@ -314,12 +311,9 @@ static int spec_self_check(mci_problem *p, int solver, int G, int64_t nevalperbl
         if (!rc) rc = mci_get_packed(p, got[pass].data(), p->packed_n); // (merges the launch and waits for it)
     }
     p->in_self_check = false;
-    p->spec_lanes = sv.spec_lanes; p->kernel_timing = sv.kernel_timing; p->chain_cur = sv.chain_cur; p->chain_solver = sv.chain_solver;
-    p->chain_iteration = sv.chain_iteration; p->last_wg = sv.last_wg; p->last_threads = sv.last_threads; p->last_nblocks = sv.last_nblocks;
-    p->last_spec_lanes = sv.last_spec_lanes; p->last_spec_maxacc = sv.last_spec_maxacc; p->blk_carried = sv.blk_carried; p->chain_valid = sv.chain_valid;
-    p->last_carried = sv.last_carried; p->hold_measured = sv.hold_measured; p->time_this_launch = sv.time_this_launch; p->chain_lo = sv.chain_lo;
-    p->chain_hi = sv.chain_hi; p->chain_nchain = sv.chain_nchain; p->chain_ntrain = sv.chain_ntrain; p->last_samples = sv.last_samples;
-    p->last_nchain = sv.last_nchain; p->launches = sv.launches; p->blk_rows = sv.blk_rows; p->blk_stride = sv.blk_stride; p->blk_lo = sv.blk_lo;
+    p->launch = saved;
+    p->spec_lanes = spec_lanes;
+    p->kernel_timing = kernel_timing;
     if (p->d_status) (void)hipMemcpy(p->d_status, h_status, sizeof(h_status), hipMemcpyHostToDevice); // (what the two small launches flagged is theirs)
     if (rc) return rc;
     const size_t nstat = (size_t)(2 * p->shape.nobs + 2 + p->ni + 1);
@@ -344,10 +338,8 @@ static int spec_self_check(mci_problem *p, int solver, int G, int64_t nevalperbl
     p->spec_need_check[solver - 1] = false;
     if (bad == 0) {
         p->spec_state[solver - 1] = 1;
-        if (FILE *f = fopen((p->code_object[slot] + ".ok").c_str(), "w")) { // (the marker: this code object has reproduced the lane-per-chain kernel on a device)
-            fprintf(f, "%s\n", mcijit::compiler_id().c_str());
-            fclose(f);
-        }
+        const std::string id = mcijit::compiler_id() + "\n"; // (the marker: this code object has reproduced the lane-per-chain kernel on a device)
+        mcijit::write_file_atomic(p->code_object[slot] + ".ok", id.data(), id.size());
         return MCI_OK;
     }
     p->spec_state[solver - 1] = -1;
@@ -472,8 +464,8 @@ int mci_chain_speculation_status(const mci_problem *p, int32_t solver, int32_t *
 
 int mci_last_chain_speculation(const mci_problem *p, int32_t *lanes, int32_t *max_accepts) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (lanes) *lanes = p->last_spec_lanes;
-    if (max_accepts) *max_accepts = p->last_spec_maxacc;
+    if (lanes) *lanes = p->launch.last_spec_lanes;
+    if (max_accepts) *max_accepts = p->launch.last_spec_maxacc;
     return MCI_OK;
 }
 
@@ -570,8 +562,8 @@ int mci_debug_override(const char *key, int64_t value, int32_t on) {
 
 int mci_debug_split_chunks(const mci_problem *p, int64_t *chunks, int64_t *bytes) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (chunks) *chunks = p->last_split_chunks;
-    if (bytes) *bytes = p->last_split_bytes;
+    if (chunks) *chunks = p->launch.last_split_chunks;
+    if (bytes) *bytes = p->launch.last_split_bytes;
     return MCI_OK;
 }
 
@@ -610,7 +602,7 @@ int mci_set_chain_carry(mci_problem *p, int32_t mode) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
     if (mode < -1 || mode > 1) return fail(MCI_ERR_INVALID, "chain carry mode must be -1 (automatic) or 1 (many-chain launches of :vegasmc and :mcmc continue the chains of the iteration before) or 0 (every launch starts its chains afresh)");
     p->chain_carry = mode;
-    if (mode == 0) p->chain_valid = false;
+    if (mode == 0) p->launch.chain_valid = false;
     return MCI_OK;
 }
 
@@ -654,8 +646,8 @@ int mci_last_integrate_persistent(const mci_problem *p, int32_t *persistent) {
 
 int mci_last_chain_launch(const mci_problem *p, int64_t *nchain, int32_t *carried) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (nchain) *nchain = p->last_nchain;
-    if (carried) *carried = p->last_carried ? 1 : 0;
+    if (nchain) *nchain = p->launch.last_nchain;
+    if (carried) *carried = p->launch.last_carried ? 1 : 0;
     return MCI_OK;
 }
 

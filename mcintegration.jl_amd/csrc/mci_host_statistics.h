@@ -66,14 +66,14 @@ int64_t mci_mcmc_auto_chains(int64_t nevalperblock, int64_t nblocks, int32_t nsl
 int mci_get_block_means(mci_problem *p, int32_t rows, double *out, int64_t *nblocks, int32_t *carried) {
     if (!p || rows < 0 || (rows > 0 && !out)) return fail(MCI_ERR_INVALID, "bad argument");
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
-    if (rows > p->blk_rows) return fail(MCI_ERR_INVALID, "the block log holds %lld iterations, %d asked for", (long long)p->blk_rows, (int)rows);
+    if (rows > p->launch.blk_rows) return fail(MCI_ERR_INVALID, "the block log holds %lld iterations, %d asked for", (long long)p->launch.blk_rows, (int)rows);
     HIPCHK(hipSetDevice(p->ctx->device));
     int rc = flush_merge(p);
     if (rc) return rc;
-    if (nblocks) *nblocks = p->shape.nobs > 0 ? p->blk_stride / p->shape.nobs : 0;
-    if (carried) *carried = p->blk_carried;
+    if (nblocks) *nblocks = p->shape.nobs > 0 ? p->launch.blk_stride / p->shape.nobs : 0;
+    if (carried) *carried = p->launch.blk_carried;
     if (rows > 0) {
-        HIPCHK(hipMemcpyAsync(out, p->d_blocklog + (size_t)(p->blk_rows - rows) * p->blk_stride, (size_t)rows * p->blk_stride * sizeof(double),
+        HIPCHK(hipMemcpyAsync(out, p->d_blocklog + (size_t)(p->launch.blk_rows - rows) * p->launch.blk_stride, (size_t)rows * p->launch.blk_stride * sizeof(double),
                               hipMemcpyDeviceToHost, p->ctx->stream));
         HIPCHK(hipStreamSynchronize(p->ctx->stream));
     }
@@ -89,8 +89,8 @@ int mci_comm_sum(mci_problem *p, double *v, int32_t n) {
 
 int mci_reset_block_log(mci_problem *p) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
-    p->blk_rows = 0;
-    p->blk_carried = 0;
+    p->launch.blk_rows = 0;
+    p->launch.blk_carried = 0;
     return MCI_OK;
 }
 
@@ -100,10 +100,10 @@ int mci_mcmc_launch_valid(mci_problem *p, int32_t *valid, int32_t *warm, int64_t
     HIPCHK(hipSetDevice(p->ctx->device));
     int rc = hold_consume(p); // (waits for the last :mcmc launch's sample kernel if its histogram is still in flight)
     if (rc) return rc;
-    if (valid) *valid = (p->hold_valid || !p->hold_measured) ? 1 : 0; // (nothing measured: nothing to hold the launch against)
-    if (warm) *warm = p->mcmc_warm ? 1 : 0;
-    if (chain_len) *chain_len = p->hold_len;
-    if (hold_max) *hold_max = p->hold_max;
+    if (valid) *valid = (p->launch.hold_valid || !p->launch.hold_measured) ? 1 : 0; // (nothing measured: nothing to hold the launch against)
+    if (warm) *warm = p->launch.mcmc_warm ? 1 : 0;
+    if (chain_len) *chain_len = p->launch.hold_len;
+    if (hold_max) *hold_max = p->launch.hold_max;
     return MCI_OK;
 }
 
@@ -111,9 +111,9 @@ int mci_iteration_discard(mci_problem *p) {
     if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
     if (p->log_row < 1) return fail(MCI_ERR_INVALID, "no finished iteration to discard");
     p->log_row -= 1;
-    if (p->blk_rows > 0) {
-        p->blk_rows -= 1;
-        p->blk_carried -= (p->last_carried && p->blk_carried > 0) ? 1 : 0;
+    if (p->launch.blk_rows > 0) {
+        p->launch.blk_rows -= 1;
+        p->launch.blk_carried -= (p->launch.last_carried && p->launch.blk_carried > 0) ? 1 : 0;
     }
     return MCI_OK;
 }

@@ -369,14 +369,14 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     }
     void *args[] = {&a, &sa};
     // HIP events around the sample launch under the rule of the classic one (mci_set_kernel_timing, mci_kernel_times_ms)
-    const int slot = (int)(p->launches % mci_problem::kEvRing);
-    p->time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && N >= ((int64_t)1 << 20));
-    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], p->ctx->stream));
+    const int slot = (int)(p->launch.launches % mci_problem::kEvRing);
+    p->launch.time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && N >= ((int64_t)1 << 20));
+    if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], p->ctx->stream));
     HIPCHK(hipModuleLaunchKernel(st.f, (unsigned)nwg, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
-    if (p->time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], p->ctx->stream));
-    p->ev_valid[slot] = p->time_this_launch;
-    p->clock_valid[slot] = false;
-    p->launches += 1;
+    if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], p->ctx->stream));
+    p->launch.ev_valid[slot] = p->launch.time_this_launch;
+    p->launch.clock_valid[slot] = false;
+    p->launch.launches += 1;
     if (dumping) {
         hipStream_t hs = p->ctx->stream;
         HIPCHK(hipMemcpyAsync(st.hx, dump.q[0], (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
@@ -414,10 +414,10 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     m.block_means = nullptr;
     m.hold = nullptr;
     p->merge_pending = true;
-    p->last_samples = N;
-    p->last_wg = (int)nwg;
-    p->last_threads = T;
-    p->last_nblocks = (int)mblocks;
+    p->launch.last_samples = N;
+    p->launch.last_wg = (int)nwg;
+    p->launch.last_threads = T;
+    p->launch.last_nblocks = (int)mblocks;
     st.last_run = true;
     return MCI_OK;
 }

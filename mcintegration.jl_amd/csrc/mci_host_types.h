@@ -115,7 +115,6 @@ struct mci_problem {
     int spec_ntree = 0, spec_first = 0; // trees on the device, the one a group starts on
     float spec_accepts[8] = {};          // the acceptance each of them was built for
     double spec_tab_accept = -1.0;
-    int last_spec_lanes = 1, last_spec_maxacc = 0; // of the last chain launch (1: one lane per chain)
     // A several-lanes-per-chain code object proves itself before it is trusted (mci_host_jit.h spec_self_check): until a code object has
     // reproduced the lane-per-chain kernel's packed sums on THIS device (a marker file next to it in the kernel cache remembers that it did),
     // its first launch is preceded by a two-block, 512-step run through both kernels.  [0] :vegasmc, [1] :mcmc --
@@ -134,13 +133,11 @@ struct mci_problem {
     double *d_part_pa = nullptr;    // [rows][2*npa] per-workgroup propose | accept tables of the chain solvers
     int64_t cap_pa = 0;
     unsigned long long *d_hold = nullptr; // [64] :mcmc holding-time histogram of the last launch (this rank), see mci_get_hold_histogram
-    int64_t hold_max = 0;                 // upper edge of its top occupied bucket; 0: no :mcmc launch seen yet
     // split vegas pass (NTILE > 1): per-sample histogram weights and 16-bit bins of the tiles >= 1
     double *d_tile_w = nullptr;      // (one allocation: the weights, then -- 256-byte aligned -- the packed bins)
     uint32_t *d_tile_bins = nullptr;
     size_t tile_bytes = 0;           // its size
     int64_t cap_tile = 0;
-    int64_t last_split_chunks = 0, last_split_bytes = 0; // chunks of the last many-grid :vegas launch | bytes of parked stream it held at a time
     int ntdraw = 0; // draws whose histogram lives in a tile >= 1
     int tdraw_words = 0; // 32-bit words of packed bins per parked sample (mci_device.h tdraw_words)
     hipFunction_t f_tiles[2] = {nullptr, nullptr}; // replay kernel of the two :vegas variants
@@ -186,9 +183,6 @@ struct mci_problem {
     // compiled kernel uses: the rule's choice, or 1 when that kernel needs more than 128 VGPRs and two 512-thread workgroups
     // would not share a CU)
     int kernel_timing = -1;       // mci_set_kernel_timing
-    bool time_this_launch = true;
-    bool ev_valid[512] = {};      // one per slot of the event ring (kEvRing)
-    bool clock_valid[512] = {};   // ... and: the launch of that slot stamped its shader clock (timed one-tile :vegas launches only, mci_kernel_clocks)
     int hcopy_auto = 1, hcopy_rule = 1; // in force | what the placement rule picked at create
     // deterministic mode (mci_set_deterministic): every solver's kernel keeps one histogram / observable copy per wave; the workgroup
     // size each was compiled for (the largest of 512 / 256 / 128 / 64 threads whose copies fit the CU's LDS)
@@ -200,7 +194,6 @@ struct mci_problem {
     // rank: 1 % of the headline iteration), the prefix-scan form below that; mci_set_train_walk forces one
     int train_serial = -1;
     bool debug_wrong_decision = false; // csrc/mci_debug.h: the serial walk's slots with one planted wrong decision (TrainArgs::serial_walk == 3)
-    int64_t last_samples = 0; // samples (vegas) or chain steps of the last sample launch on this rank
     static const int64_t kSerialWalkSamples = (int64_t)1 << 26;
     bool train_lds_raised = false; // k_train / k_finish allowed more than 64 KiB of dynamic LDS (large grids)
     // HIP events around the per-iteration ncclAllReduce (mci_comm_times_ms), recorded under the same rule as the sample launch's
@@ -214,30 +207,13 @@ struct mci_problem {
     // queued) -- ~10 us of idle queue per iteration, nothing next to a chain launch; the lag is fixed, so a run is reproducible
     unsigned long long *h_hold = nullptr;   // pinned [64]
     double *h_hold_d = nullptr;             // pinned [64]: the histogram summed over the ranks, as it comes out of the packed all-reduce
-    bool hold_from_packed = false;          // the histogram in flight is the summed one (h_hold_d), not this rank's own (h_hold)
-    bool hold_deferred = false;             // a communicator is set: the launch's histogram is published behind its packed all-reduce
-    bool hold_ext_pending = false;          // no communicator: this rank's counts were published; an external reducer may still sum them (mci_external_reduce_done)
-    hipEvent_t hold_ev = nullptr;
-    bool hold_inflight = false;
-    int64_t hold_launches = 0;              // :mcmc launches that recorded a histogram
-    int64_t hold_len = 0;                   // measured steps per chain of the launch `hold_max` comes from
-    int64_t hold_len_inflight = 0;          // ... of the launch whose histogram is in flight
-    bool hold_carried_inflight = false;     // that launch continued the chains of the one before (8 x its holds instead of 16 x)
-    // Warm-up of the automatic :mcmc chain length: until a launch has run chains long enough for the holds IT measured
-    // (mcmc_launch_valid), lengths escalate and mci_integrate repeats an iteration instead of counting it; afterwards a launch is
-    // sized from the larger of the last two launches' holds (the longest hold of a launch is an extreme value: it moves by a bucket
-    // from launch to launch) and nothing is ever repeated or left out again (no selection on what an iteration measured)
-    bool mcmc_warm = false;
-    bool hold_valid = false;                // the launch `hold_max` comes from was long enough for its own holds
-    bool hold_measured = false;             // the last :mcmc launch measured its holding times at all (not with a host integrand)
-    int64_t hold_prev = 0;                  // hold_max of the launch before that, once warm
-    // per-block means of the chain solvers' iterations (MergeArgs::block_means): rows [blk_rows][blk_stride = local blocks * nobs];
+    hipEvent_t hold_ev = nullptr;           // (the values of the hand-over: launch.hold_*)
+    // per-block means of the chain solvers' iterations (MergeArgs::block_means): rows [launch.blk_rows][launch.blk_stride = local blocks * nobs];
     // what the block-lineage error of a run of carried chains is computed from (mci_lineage_sums)
     double *d_blocklog = nullptr;
-    int64_t cap_blocklog = 0, blk_rows = 0, blk_stride = 0, blk_lo = -1;
-    int blk_carried = 0;                    // rows of the log whose launch continued the chains of the one before
+    int64_t cap_blocklog = 0;
     // Carried chains (BatchArgs::carry_x): end configurations of the last chain launch, two buffers (read one, write the other),
-    // and what that launch was -- an iteration continues it when it is the NEXT iteration of the same solver over the same blocks
+    // and what that launch was (launch.chain_*) -- an iteration continues it when it is the NEXT iteration of the same solver over the same blocks
     double *d_chain_x[2] = {nullptr, nullptr};
     double *d_chain_P[2] = {nullptr, nullptr}; // :vegasmc: the target density at every stored configuration (BatchArgs::store_P)
     double *d_carry_w = nullptr;               // :vegasmc: new target / old target of the stored chains (mci_vegasmc_carry_weights)
@@ -245,31 +221,22 @@ struct mci_problem {
     hipFunction_t f_carryw[2] = {nullptr, nullptr}; // that kernel in the lane-per-chain | several-lanes-per-chain code object of :vegasmc
     int *d_chain_curr[2] = {nullptr, nullptr};
     int64_t chain_cap[2] = {0, 0};
-    int chain_cur = 0;           // buffer the last launch wrote
-    bool chain_valid = false;
-    int chain_solver = -1, chain_iteration = -1;
-    int64_t chain_lo = 0, chain_hi = 0, chain_nchain = 0;
     int chain_carry = -1;        // mci_set_chain_carry: -1 automatic / 1 (the rule above), 0 never
     // :vegasmc chains are carried only out of a launch that ran on a map train! had refined at least once: chains of the automatic
     // length have not reached their target on the UNTRAINED map of a heavy-tailed integrand (log(x)/sqrt(x): the first iteration of a cold
     // call is 14 sigma per run off), and a population that is no sample of the old target cannot be resampled into one of the new --
     // carried out of iteration 1 the second iteration was 4 sigma per run-iteration off, started afresh 1.2 (profiles/r05_bias.txt A4)
-    int64_t ntrain = 0, chain_ntrain = 0; // train! steps of this problem so far | ... when the stored chains were launched
+    int64_t ntrain = 0;                   // train! steps of this problem so far (launch.chain_ntrain: ... when the stored chains were launched)
     bool launch_counted = false;          // mci_integrate | mci_set_iteration_counted: the iteration being launched enters the final estimate (it >= ignore)
     // :mcmc: the reweight factors the stored chains ran under, and which stored chain every chain of the launch in flight continues
     // (k_resample_chains: the stored chains resampled to the target doReweight! has moved since)
     double *d_reweight_used = nullptr, *d_carry_W = nullptr;
     int *d_carry_src = nullptr;
     int64_t cap_carry_src = 0, cap_carry_W = 0;
-    bool last_carried = false;   // the last chain launch continued the one before it
-    // last launch
+    // the event ring of the sample launches (launch.launches, launch.ev_valid / clock_valid)
     unsigned long long *d_clocks = nullptr; // [kEvRing][2] shader-clock | reference-clock ticks of the timed :vegas launches' sample loops
     std::vector<hipEvent_t> evs; // ring of (start, stop) pairs around the sampling kernel, one pair per launch
-    int64_t launches = 0;
     static const int kEvRing = 512;
-    static_assert(sizeof(ev_valid) / sizeof(ev_valid[0]) == kEvRing, "one validity flag per event-ring slot");
-    int last_wg = 0, last_threads = 0, last_nblocks = 0;
-    int64_t last_nchain = 0; // chains per block of the last chain-solver launch
     int log_row = 0;
     double *h_log = nullptr;  // pinned: mci_integrate's read-back of the iteration log (+ the status word behind it)
     size_t cap_hlog = 0;
@@ -296,6 +263,58 @@ struct mci_problem {
     // than the chains that measured the holds a launch's chains may be.  (MCI_MCMC_PILOT / MCI_MCMC_GROW: experiment knobs)
     static int64_t kMcmcPilotSteps, kMcmcGrow;
     static int64_t kMcmcCarryHolds, kMcmcCarryHalfFloors; // carried chains: length in longest holds | minimum length in HALF burn-in floors
+    // What a sample launch leaves behind on the host (mci_iteration_run and the functions it calls write it).  VALUES ONLY -- no
+    // pointer, capacity, handle or module: spec_self_check copies the record out before its two small launches and back after them,
+    // and those launches may create or grow buffers (an old pointer or capacity put back would point at freed memory).  Outside it:
+    //   resources the check may create or grow -- d_chain_x / curr / P, chain_cap, d_blocklog, the other d_* / h_* and cap_*, evs,
+    //     the modules and compiled[], the speculation trees on the device (d_spec_tab, spec_tab_*, spec_ntree, spec_first, spec_accepts);
+    //   settings -- spec_lanes, kernel_timing, chain_carry, threads*, ...;
+    //   the check's own result -- spec_state, spec_need_check, in_self_check;
+    //   the merge hand-off -- merge, merge_pending (mci_get_packed flushes it inside the check);
+    //   per-call results of mci_integrate -- last_discarded_*, last_persistent, launch_counted, log_row;
+    //   the reduce's bookkeeping -- reduces, cev_valid[] (mci_iteration_reduce alone writes them; the check does not reduce).
+    struct LaunchState {
+        // the last sample launch on this rank
+        int last_wg = 0, last_threads = 0, last_nblocks = 0;
+        int64_t last_samples = 0;                      // samples (vegas) or chain steps
+        int64_t last_nchain = 0;                       // chains per block of the last chain-solver launch
+        int last_spec_lanes = 1, last_spec_maxacc = 0; // of the last chain launch (1: one lane per chain)
+        bool last_carried = false;                     // the last chain launch continued the one before it
+        int64_t last_split_chunks = 0, last_split_bytes = 0; // chunks of the last many-grid :vegas launch | bytes of parked stream it held at a time
+        // the event ring (evs, d_clocks): sample launches so far, and per slot what its launch left there
+        int64_t launches = 0;
+        bool time_this_launch = true;
+        bool ev_valid[kEvRing] = {};    // the launch of that slot recorded its events
+        bool clock_valid[kEvRing] = {}; // ... and stamped its shader clock (timed one-tile :vegas launches only, mci_kernel_clocks)
+        // the stored chains (d_chain_x / curr / P): what the launch that wrote them was
+        int chain_cur = 0;              // buffer the last launch wrote
+        bool chain_valid = false;
+        int chain_solver = -1, chain_iteration = -1;
+        int64_t chain_lo = 0, chain_hi = 0, chain_nchain = 0;
+        int64_t chain_ntrain = 0;       // ntrain when they were launched
+        // the block log (d_blocklog): rows logged, their stride and first block
+        int64_t blk_rows = 0, blk_stride = 0, blk_lo = -1;
+        int blk_carried = 0;            // rows of the log whose launch continued the chains of the one before
+        // the :mcmc holding-time hand-over (d_hold -> h_hold / h_hold_d, hold_ev)
+        int64_t hold_max = 0;                   // upper edge of the top occupied bucket of the last histogram taken in; 0: none yet
+        int64_t hold_len = 0;                   // measured steps per chain of the launch `hold_max` comes from
+        int64_t hold_prev = 0;                  // hold_max of the launch before that, once warm
+        bool hold_valid = false;                // the launch `hold_max` comes from was long enough for its own holds
+        bool hold_measured = false;             // the last :mcmc launch measured its holding times at all (not with a host integrand)
+        // Warm-up of the automatic :mcmc chain length: until a launch has run chains long enough for the holds IT measured
+        // (mcmc_launch_valid), lengths escalate and mci_integrate repeats an iteration instead of counting it; afterwards a launch is
+        // sized from the larger of the last two launches' holds (the longest hold of a launch is an extreme value: it moves by a bucket
+        // from launch to launch) and nothing is ever repeated or left out again (no selection on what an iteration measured)
+        bool mcmc_warm = false;
+        bool hold_inflight = false;             // a histogram is on its way to the host (hold_ev)
+        bool hold_from_packed = false;          // ... the summed one (h_hold_d), not this rank's own (h_hold)
+        bool hold_deferred = false;             // a communicator is set: the launch's histogram is published behind its packed all-reduce
+        bool hold_ext_pending = false;          // no communicator: this rank's counts were published; an external reducer may still sum them (mci_external_reduce_done)
+        int64_t hold_launches = 0;              // :mcmc launches that recorded a histogram
+        int64_t hold_len_inflight = 0;          // measured steps per chain of the launch whose histogram is in flight
+        bool hold_carried_inflight = false;     // that launch continued the chains of the one before (kMcmcCarryHolds x its holds instead of 16 x)
+    } launch;
+    static_assert(std::is_trivially_copyable<LaunchState>::value, "the launch record holds values only");
     // Stratified :vegas (VEGAS+, mci_set_stratification; mci_strat.h, mci_host_strat.h).  Not part of `config`: a problem keeps the map
     // it trained, the allocation starts uniform in every mci_integrate call.
     struct Strat {
@@ -490,19 +509,19 @@ int hold_publish(mci_problem *p, int64_t chain_len, bool carried) {
         HIPCHK(hipHostMalloc((void **)&p->h_hold_d, 64 * sizeof(double), hipHostMallocDefault));
         HIPCHK(hipEventCreateWithFlags(&p->hold_ev, hipEventDisableTiming));
     }
-    p->hold_len_inflight = chain_len;
-    p->hold_carried_inflight = carried;
-    p->hold_launches += 1;
+    p->launch.hold_len_inflight = chain_len;
+    p->launch.hold_carried_inflight = carried;
+    p->launch.hold_launches += 1;
     if (p->ctx->comm) {
-        p->hold_deferred = true;
+        p->launch.hold_deferred = true;
         return MCI_OK;
     }
-    if (p->hold_inflight) HIPCHK(hipEventSynchronize(p->hold_ev)); // (a histogram nobody looked at)
+    if (p->launch.hold_inflight) HIPCHK(hipEventSynchronize(p->hold_ev)); // (a histogram nobody looked at)
     HIPCHK(hipMemcpyAsync(p->h_hold, p->d_hold, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(p->hold_ev, st));
-    p->hold_inflight = true;
-    p->hold_from_packed = false;
-    p->hold_ext_pending = true;
+    p->launch.hold_inflight = true;
+    p->launch.hold_from_packed = false;
+    p->launch.hold_ext_pending = true;
     return MCI_OK;
 }
 
@@ -513,9 +532,9 @@ int hold_publish_reduced(mci_problem *p) {
     // packed buffer: the summed counts go to ANOTHER pinned buffer, and the event is simply recorded again behind them)
     HIPCHK(hipMemcpyAsync(p->h_hold_d, p->d_packed + p->packed_n, 64 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(p->hold_ev, st));
-    p->hold_inflight = true;
-    p->hold_from_packed = true;
-    p->hold_deferred = false;
+    p->launch.hold_inflight = true;
+    p->launch.hold_from_packed = true;
+    p->launch.hold_deferred = false;
     return MCI_OK;
 }
 
@@ -524,19 +543,19 @@ int hold_publish_reduced(mci_problem *p) {
 // run); what the two-launch lag of the rounds before cost is in profiles/r03_c5_kernel_stats.txt (two more launches sized from the
 // untrained map's holding times: 324 ms of a cold BASELINE configs[4] call).
 int hold_consume(mci_problem *p) {
-    if (!p->hold_inflight) return MCI_OK;
+    if (!p->launch.hold_inflight) return MCI_OK;
     HIPCHK(hipEventSynchronize(p->hold_ev));
-    p->hold_inflight = false;
+    p->launch.hold_inflight = false;
     int top = -1;
     for (int b = 0; b < 64; ++b)
-        if (p->hold_from_packed ? p->h_hold_d[b] > 0.5 : p->h_hold[b] != 0ull) top = b;
+        if (p->launch.hold_from_packed ? p->h_hold_d[b] > 0.5 : p->h_hold[b] != 0ull) top = b;
     if (top >= 0) {
-        p->hold_prev = p->mcmc_warm ? p->hold_max : 0;
-        p->hold_max = (int64_t)1 << top; // bucket b holds bit_width(h) == b, i.e. h < 2^b
-        p->hold_len = p->hold_len_inflight;
+        p->launch.hold_prev = p->launch.mcmc_warm ? p->launch.hold_max : 0;
+        p->launch.hold_max = (int64_t)1 << top; // bucket b holds bit_width(h) == b, i.e. h < 2^b
+        p->launch.hold_len = p->launch.hold_len_inflight;
         // was that launch long enough for what it measured itself?  (the rule its successor is sized by, mci_mcmc_auto_chains)
-        p->hold_valid = p->hold_len >= (p->hold_carried_inflight ? mci_problem::kMcmcCarryHolds : 16) * p->hold_max;
-        if (p->hold_valid) p->mcmc_warm = true;
+        p->launch.hold_valid = p->launch.hold_len >= (p->launch.hold_carried_inflight ? mci_problem::kMcmcCarryHolds : 16) * p->launch.hold_max;
+        if (p->launch.hold_valid) p->launch.mcmc_warm = true;
     }
     return MCI_OK;
 }
@@ -574,7 +593,7 @@ static int comm_sum_host(mci_problem *p, double *v, int n);
 // room for `rows` rows of [blk_stride] doubles in the block log (grows with a copy and a stream synchronisation; mci_integrate reserves
 // its iterations before the loop)
 static int grow_block_log(mci_problem *p, int64_t rows) {
-    const int64_t need = rows * p->blk_stride;
+    const int64_t need = rows * p->launch.blk_stride;
     if (need <= p->cap_blocklog) return MCI_OK;
     int64_t ncap = p->cap_blocklog ? p->cap_blocklog : 4096;
     while (ncap < need) ncap *= 2;

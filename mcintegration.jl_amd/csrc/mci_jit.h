@@ -360,6 +360,18 @@ inline void warm_up_join() {
     if (w.th.joinable()) w.th.join();
 }
 
+// `data` -> `path` in the shared kernel cache: written to a temporary file, then renamed into place, so that no reader ever sees half a
+// file (the temporary name is unique per process AND per call: concurrent host threads writing the same key must not share one)
+inline void write_file_atomic(const std::string &path, const char *data, size_t size) {
+    static std::atomic<unsigned long> seq{0};
+    const std::string tmp = path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(seq.fetch_add(1));
+    std::ofstream f(tmp, std::ios::binary);
+    if (!f) return;
+    f.write(data, (std::streamsize)size);
+    f.close();
+    if (rename(tmp.c_str(), path.c_str()) != 0) unlink(tmp.c_str());
+}
+
 // returns the gfx950 code object for `src`, from the on-disk cache or by compiling with hiprtc
 inline int compile(const std::string &src, int threads, std::vector<char> &code, std::string &log, bool &from_cache, std::string *cache_path = nullptr,
                    int extra_hdr = kHdrNone, bool cache_only = false, bool no_exec_mask_flag = false) {
@@ -437,17 +449,7 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     hiprtcGetCode(prog, code.data());
     hiprtcDestroyProgram(&prog);
     mkdir(dir.c_str(), 0755);
-    // unique per process AND per call: concurrent host threads compiling the same key must not share a temporary file
-    static std::atomic<unsigned long> seq{0};
-    const std::string tmp = path + ".tmp" + std::to_string((long)getpid()) + "." + std::to_string(seq.fetch_add(1));
-    {
-        std::ofstream f(tmp, std::ios::binary);
-        if (f) {
-            f.write(code.data(), (std::streamsize)code.size());
-            f.close();
-            if (rename(tmp.c_str(), path.c_str()) != 0) unlink(tmp.c_str());
-        }
-    }
+    write_file_atomic(path, code.data(), code.size());
     return 0;
 }
 

@@ -105,23 +105,40 @@ def test_whole_runs_of_single_chains_stay_on_the_oracles_trajectory(oracle, solv
 
 
 @pytest.mark.parametrize("solver", ["vegasmc", "mcmc"])
-def test_carried_chains_with_groups_are_the_lane_per_chain_run(solver):
+def test_carried_chains_with_groups_are_the_lane_per_chain_run(solver, tmp_path, monkeypatch):
     """chains carried from one iteration to the next (BatchArgs::carry_x; :mcmc: resampled) under the group kernels: the same numbers
-    as the lane-per-chain kernels give, iteration by iteration, with the group size changing between iterations"""
-    out = []
-    for plan in ([1, 1, 1, 1], [16, 4, 64, 2]):
+    as the lane-per-chain kernels give, iteration by iteration, with the group size changing between iterations.  The third plan starts
+    its group kernel in a cold kernel cache: its self-check (mci_host_jit.h spec_self_check) runs at iteration 1, while stored chains and
+    the block log of iteration 0 wait, and leaves no trace -- same numbers, same chain launches, same block log."""
+    out, chains, blocks = [], [], []
+    for plan in ([1, 1, 1, 1], [16, 4, 64, 2], [1, 16, 4, 64]):
+        cold = plan[1] == 16
+        if cold:
+            monkeypatch.setenv("MCI_KERNEL_CACHE", str(tmp_path))      # nothing in it has a marker
         cfg = mci.Configuration(var=mci.Continuous(0.0, 1.0), dof=[[3], [6], [9], [12]], seed=SEED)
         eng = mci.Engine(cfg, mci.catalog.nested_gauss())
-        rows = []
+        rows, launches = [], []
         for it, lanes in enumerate(plan):
             eng.set_chain_speculation(lanes, 0.4, 2)
+            if cold and it == 1:
+                assert eng.chain_speculation_status(solver) == 0
             got = eng.iteration(solver, 9600, 0, 4, iteration=it, seed=SEED, nchain=12 if it != 2 else 20, thermal_ratio=0.1)
+            if cold and it == 1:
+                assert eng.chain_speculation_status(solver) == 1
             assert eng.last_chain_speculation()[0] == lanes and eng.last_chain_launch()[1] == (it > (1 if solver == "vegasmc" else 0))
             rows.append(got.copy())
+            launches.append(eng.last_chain_launch())
             eng.finish(solver, 4, True, 1.0)
         out.append(rows)
-    for a, b in zip(*out):
+        chains.append(launches)
+        blocks.append(eng.block_means(4))
+        eng.close()
+    for a, b, c in zip(*out):
         np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-300)
+        np.testing.assert_allclose(a, c, rtol=1e-9, atol=1e-300)
+    assert chains[2] == chains[0]
+    np.testing.assert_allclose(blocks[2][0], blocks[0][0], rtol=1e-9, atol=1e-300)
+    assert blocks[2][1] == blocks[0][1]
 
 
 @pytest.mark.parametrize("solver", ["vegasmc", "mcmc"])
