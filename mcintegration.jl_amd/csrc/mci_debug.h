@@ -42,6 +42,9 @@ int mci_debug_split_chunks(const mci_problem *prob, int64_t *chunks, int64_t *by
  * that iteration's N), the draws x[n][ndraw], the uniforms y[n][ndraw] after the move into the sample's hypercube, the hypercube h[n],
  * the Jacobian jac[n] (without r_h) and the weights w[n][ni * ncomp] in these host buffers; the run synchronises.  n = 0 takes it back. */
 int mci_debug_strat_dump(mci_problem *prob, int64_t n, double *x, double *y, int64_t *h, double *jac, double *w);
+/* test hook: d[n] = the damped weights d_h = (sum_k s^2_{h,k})^(beta/2) the last finished stratified iteration wrote (what the next
+ * allocation is made from); n must be the plan's hypercube count, call it after mci_iteration_finish.  Synchronises the stream. */
+int mci_debug_strat_d(mci_problem *prob, double *d, int64_t n);
 /* what mci_jit.h puts into the kernel-cache key for "which compiler made this code object" (hiprtc version, the files of libhiprtc and
  * libamd_comgr, the target): set != NULL overrides it for this process ("" takes the override back); out: the identity in force */
 int mci_debug_compiler_id(const char *set, char *out, int32_t n);

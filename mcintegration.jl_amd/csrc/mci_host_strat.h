@@ -240,6 +240,18 @@ int mci_debug_strat_dump(mci_problem *p, int64_t n, double *x, double *y, int64_
     return MCI_OK;
 }
 
+int mci_debug_strat_d(mci_problem *p, double *d, int64_t n) {
+    if (!p || (n > 0 && !d)) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    const auto &st = p->strat;
+    if (!st.on || !st.ran || st.last_run) return fail(MCI_ERR_INVALID, "stratification: no stratified iteration has been finished");
+    if (n != st.ncube) return fail(MCI_ERR_INVALID, "stratification: %lld hypercubes, %lld asked for", (long long)st.ncube, (long long)n);
+    HIPCHK(hipSetDevice(p->ctx->device));
+    HIPCHK(hipMemcpyAsync(d, st.d_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    return MCI_OK;
+}
+
 // every stratified allocation of a call starts uniform (mci_integrate)
 static void strat_call_start(mci_problem *p) { p->strat.alloc_valid = p->strat.alloc_pending = false; }
 

@@ -723,6 +723,13 @@ class Engine:
         check(lib().mci_get_strat_counts(self.p, out.ctypes.data_as(C.POINTER(C.c_int64)), n))
         return out
 
+    def strat_d(self):
+        """test hook (mci_debug_strat_d): the damped weights d_h the last finished stratified iteration wrote"""
+        info = self.stratification()
+        out = np.zeros(info["ncube"] if info else 0)
+        check(lib().mci_debug_strat_d(self.p, _dp(out), out.size))
+        return out
+
     def strat_dump_next(self, n):
         """test hook (mci_debug_strat_dump): buffers the next stratified iteration of n samples fills -- x, y [n, ndraw], h [n], jac [n],
         w [n, N * ncomp]; read them after that iteration ran"""

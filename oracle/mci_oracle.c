@@ -1839,3 +1839,183 @@ int mcio_integrate(mcio_config *c, int solver, mcio_integrand_fn f, const double
     free(obs_sq);
     return rc;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * VEGAS+ adaptive stratified sampling on top of the map (Lepage, J. Comput. Phys. 439 (2021) 110386, section 3; DESIGN.md section 5
+ * "Stratified :vegas").  Not part of the reference project: written from the paper and the design text as the plain definition -- one
+ * loop over the hypercubes and their samples, the cell of a hypercube by % and /, textbook two-pass statistics in long double.
+ * ---------------------------------------------------------------------------------------- */
+
+/* allocation: C_h = (N - 2 ncube) P_h / P with P_h = d_0 + ... + d_h, n_h = 2 + floor(C_h) - floor(C_{h-1}), C_{ncube-1} = N - 2 ncube;
+   every d_h = 1 when `uniform` is set or P is 0 or not finite.  off[ncube + 1]: first sample of every hypercube. */
+int mcio_strat_alloc(const double *d, long ncube, long N, int uniform, long *off) {
+    if (ncube < 1 || N < 2 * ncube) return -1;
+    const long M = N - 2 * ncube;
+    long double P = 0.0L;
+    if (!uniform)
+        for (long h = 0; h < ncube; ++h) P += (long double)d[h];
+    if (!(P > 0.0L) || !(P <= 1.7976931348623157e308L)) uniform = 1;
+    long double run = 0.0L;
+    long prev = 0;
+    off[0] = 0;
+    for (long h = 0; h < ncube; ++h) {
+        long double C;
+        if (uniform) C = (long double)M * (long double)(h + 1) / (long double)ncube;
+        else {
+            run += (long double)d[h];
+            C = (long double)M * run / P;
+        }
+        long fl = (long)floorl(C);
+        if (fl > M || h == ncube - 1) fl = M;
+        if (fl < prev) fl = prev;
+        off[h + 1] = off[h] + 2 + (fl - prev);
+        prev = fl;
+    }
+    return 0;
+}
+
+typedef struct {
+    double *v;
+    long cap;
+} strat_buf;
+
+int mcio_strat_iteration(mcio_config *c, mcio_integrand_fn f, const double *ud, uint64_t seed, uint32_t iteration, long first_index,
+                         const int *nstrat, const long *off, double beta, mcio_strat_out *out) {
+    const int Ni = c->Ni, npool = c->npool, nc = c->ncomp, NW = Ni * nc, D = c->ndraw;
+    if (D > MCIO_MAXDRAW || Ni > MCIO_MAXNI || D < 1) return -1;
+    for (int l = 0; l < c->nleaf; ++l)
+        if (c->leaf[l].kind != MCIO_CONTINUOUS) return -4; /* y-space is cut along Continuous draws only */
+    long ncube = 1;
+    for (int k = 0; k < D; ++k) {
+        if (nstrat[k] < 1) return -1;
+        ncube *= nstrat[k];
+    }
+    const long N = off[ncube];
+    for (long h = 0; h < ncube; ++h)
+        if (off[h + 1] - off[h] < 2) return -2;
+    const double V = 1.0 / (double)ncube;
+    const uint32_t st = stream_id(iteration, STREAM_VEGAS);
+    int nthreads = 1;
+#ifdef _OPENMP
+    nthreads = omp_get_max_threads();
+    if (nthreads > ncube) nthreads = (int)ncube;
+    if (N < 20000) nthreads = 1;
+#endif
+    mcio_config **work = (mcio_config **)calloc((size_t)nthreads, sizeof(mcio_config *));
+    for (int t = 0; t < nthreads; ++t) {
+        work[t] = mcio_config_clone(c);
+        for (int l = 0; l < c->nleaf; ++l)
+            for (int i = 0; i < c->leaf[l].nbin; ++i) work[t]->leaf[l].hist[i] = 0.0;
+    }
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthreads)
+#endif
+    {
+        int tid = 0;
+#ifdef _OPENMP
+        tid = omp_get_thread_num();
+#endif
+        mcio_config *w = work[tid];
+        strat_buf fb = {NULL, 0};
+        double x[MCIO_MAXDRAW], u[MCIO_MAXDRAW], y[MCIO_MAXDRAW], weights[2 * MCIO_MAXNI], jaci[MCIO_MAXNI];
+        int cell[MCIO_MAXDRAW], diff[MCIO_MAXNI];
+        for (int i = 0; i < Ni; ++i) {
+            diff[i] = 1;
+            for (int v = 0; v < npool; ++v)
+                if (c->dof[i * npool + v] != c->maxdof[v]) diff[i] = 0;
+        }
+        /* contiguous ranges of hypercubes per thread, so that the histogram sums have a fixed order for a given thread count */
+        const long h0 = ncube * tid / nthreads, h1 = ncube * (tid + 1) / nthreads;
+        for (long h = h0; h < h1; ++h) {
+            const long n = off[h + 1] - off[h];
+            const double r = (double)N / ((double)ncube * (double)n); /* r_h: the samples of h stand for N / ncube */
+            long q = h;
+            for (int k = 0; k < D; ++k) { /* draw 0 fastest */
+                cell[k] = (int)(q % nstrat[k]);
+                q /= nstrat[k];
+            }
+            if (n * NW > fb.cap) {
+                free(fb.v);
+                fb.cap = 2 * n * NW;
+                fb.v = (double *)malloc((size_t)fb.cap * sizeof(double));
+            }
+            for (long j = 0; j < n; ++j) {
+                const long s = off[h] + j;
+                const uint64_t gs = (uint64_t)first_index + (uint64_t)s;
+                double jac = 1.0;
+                int k = 0;
+                for (int vi = 0; vi < npool; ++vi) {
+                    const int po = w->pool_offset[vi], nl = w->pool_nleaf[vi];
+                    for (int idx = 1; idx <= w->maxdof[vi]; ++idx) {
+                        for (int l = 0; l < nl; ++l) {
+                            u[k + l] = w->rng_bits == 32 ? mcio_uniform32(seed, st, gs, (uint32_t)(k + l)) : mcio_uniform(seed, st, gs, (uint32_t)(k + l));
+                            y[k + l] = fmin(((double)cell[k + l] + u[k + l]) * (1.0 / (double)nstrat[k + l]), 0x1.fffffffffffffp-1);
+                        }
+                        mcio_pool_create(w, vi, idx + po, y + k);
+                        jac /= w->pool_prob[vi][idx + po];
+                        k += nl;
+                    }
+                }
+                for (int i = 0; i < Ni; ++i) jaci[i] = diff[i] ? jac : mcio_padding_probability(w, i) * jac;
+                gather_x(w, x);
+                f(x, weights, ud);
+                for (int qq = 0; qq < NW; ++qq) fb.v[j * NW + qq] = weights[qq] * jaci[qq / nc];
+                for (int vi = 0; vi < npool; ++vi) {
+                    const int po = w->pool_offset[vi];
+                    for (int i = 0; i < Ni; ++i) {
+                        const double wj = absw(w, weights, i) * jac;
+                        for (int pos = 1; pos <= w->dof[i * npool + vi]; ++pos) pool_accumulate(w, vi, pos + po, (wj * wj) * r);
+                    }
+                }
+                if (out->y) memcpy(out->y + s * D, y, (size_t)D * sizeof(double));
+                if (out->x) memcpy(out->x + s * D, x, (size_t)D * sizeof(double));
+                if (out->jac) out->jac[s] = jac;
+                if (out->jaci) memcpy(out->jaci + s * Ni, jaci, (size_t)Ni * sizeof(double));
+                if (out->w) memcpy(out->w + s * NW, weights, (size_t)NW * sizeof(double));
+            }
+            long double ssum = 0.0L;
+            for (int qq = 0; qq < NW; ++qq) { /* two passes: the mean, then the squared deviations from it */
+                long double s1 = 0.0L, s2 = 0.0L, a1 = 0.0L, dev = 0.0L;
+                for (long j = 0; j < n; ++j) {
+                    const long double v = (long double)fb.v[j * NW + qq];
+                    s1 += v;
+                    s2 += v * v;
+                    a1 += fabsl(v);
+                }
+                const long double m = s1 / (long double)n;
+                for (long j = 0; j < n; ++j) {
+                    const long double e = (long double)fb.v[j * NW + qq] - m;
+                    dev += e * e;
+                }
+                const long double v2 = dev / (long double)(n - 1);
+                out->S1[h * NW + qq] = (double)s1;
+                out->S2[h * NW + qq] = (double)s2;
+                out->A1[h * NW + qq] = (double)a1;
+                out->v2[h * NW + qq] = (double)v2;
+                ssum += v2;
+            }
+            out->d[h] = (double)powl(ssum, 0.5L * (long double)beta);
+        }
+        free(fb.v);
+    }
+    mcio_clear_statistics(c);
+    for (int t = 0; t < nthreads; ++t) {
+        for (int l = 0; l < c->nleaf; ++l)
+            for (int i = 0; i < c->leaf[l].nbin; ++i) c->leaf[l].hist[i] += work[t]->leaf[l].hist[i];
+        mcio_config_destroy(work[t]);
+    }
+    free(work);
+    c->neval = N;
+    c->normalization += (double)N;
+    for (int qq = 0; qq < NW; ++qq) { /* the iteration: mean = sum_h V/n_h S1, var = sum_h V^2 s_h^2 / n_h */
+        long double m = 0.0L, v = 0.0L;
+        for (long h = 0; h < ncube; ++h) {
+            const long double n = (long double)(off[h + 1] - off[h]);
+            m += (long double)V / n * (long double)out->S1[h * NW + qq];
+            v += (long double)V * (long double)V * (long double)out->v2[h * NW + qq] / n;
+        }
+        out->mean[qq] = (double)m;
+        out->var[qq] = (double)v;
+    }
+    return 0;
+}

@@ -252,6 +252,24 @@ long mcio_packed_size(const mcio_config *c);
 mcio_result *mcio_result_create(int niter, int nobs, int Ni);
 void mcio_result_destroy(mcio_result *r);
 
+/* ---- VEGAS+ adaptive stratified sampling (Lepage, J. Comput. Phys. 439 (2021) 110386).  Not in the reference
+   project: the plain definition the stratified :vegas kernels are compared with. ---- */
+/* off[ncube + 1] from the damped weights d[ncube]: C_h = (N - 2 ncube) P_h / P (P_h a long double running sum in index order),
+   n_h = 2 + floor(C_h) - floor(C_{h-1}), C_last = N - 2 ncube; uniform != 0, or P 0 or not finite: every d_h = 1 */
+int mcio_strat_alloc(const double *d, long ncube, long N, int uniform, long *off);
+typedef struct {
+    double *mean, *var;          /* [NW] the iteration's estimate per weight column (NW = Ni * ncomp) and its variance */
+    double *d;                   /* [ncube] (sum_k s^2_{h,k})^(beta/2) */
+    double *S1, *S2, *A1, *v2;   /* [ncube][NW] sum f J | sum (f J)^2 | sum |f J| | two-pass sample variance of f J */
+    double *y, *x, *jac, *jaci, *w; /* per sample, each may be NULL: [N][ndraw] | [N][ndraw] | [N] | [N][Ni] | [N][NW] */
+} mcio_strat_out;
+/* one stratified iteration over the allocation `off` (N = off[ncube]): sample s lies in the hypercube h with off[h] <= s < off[h+1],
+   whose cell along draw k is (h / prod_{k' < k} nstrat[k']) % nstrat[k]; it takes the uniforms mcio_vegas_block takes at counter
+   first_index + s, y = fmin((cell + u) * (1.0 / nstrat), 1 - 2^-53), and the map, the per-integrand Jacobians and the integrand as there.
+   Leaf histograms: clearStatistics! + (|w| jac)^2 r_h per sample, r_h = N / (ncube n_h). */
+int mcio_strat_iteration(mcio_config *c, mcio_integrand_fn f, const double *ud, uint64_t seed, uint32_t iteration, long first_index,
+                         const int *nstrat, const long *off, double beta, mcio_strat_out *out);
+
 /* built-in integrands (independent C restatements of the catalog used by tests/bench) */
 mcio_integrand_fn mcio_builtin(const char *name);
 

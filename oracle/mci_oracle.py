@@ -62,6 +62,10 @@ class _Result(C.Structure):
                 ("neval", C.c_long)]
 
 
+class _StratOut(C.Structure):
+    _fields_ = [(n, c_double_p) for n in ("mean", "var", "d", "S1", "S2", "A1", "v2", "y", "x", "jac", "jaci", "w")]
+
+
 _lib = None
 
 
@@ -149,6 +153,9 @@ def lib():
     L.mcio_result_create.restype = C.POINTER(_Result)
     L.mcio_result_create.argtypes = [C.c_int, C.c_int, C.c_int]
     L.mcio_result_destroy.argtypes = [C.POINTER(_Result)]
+    L.mcio_strat_alloc.argtypes = [c_double_p, C.c_long, C.c_long, C.c_int, c_long_p]
+    L.mcio_strat_iteration.argtypes = [C.POINTER(_Config), C.c_void_p, c_double_p, C.c_uint64, C.c_uint32, C.c_long, c_int_p, c_long_p,
+                                       C.c_double, C.POINTER(_StratOut)]
     L.mcio_builtin.restype = C.c_void_p
     L.mcio_builtin.argtypes = [C.c_char_p]
     _lib = L
@@ -498,6 +505,40 @@ class Config:
         if rc:
             raise RuntimeError("oracle iteration failed (%d)" % rc)
         return out
+
+    def add_hist(self, i, v):
+        """v added to every bin of leaf i's histogram (the clearStatistics! offsets of the blocks a launch is merged as)"""
+        lf = self.leaf(i)
+        np.ctypeslib.as_array(lf.hist, shape=(lf.nbin,))[:] += v
+
+    @staticmethod
+    def strat_alloc(d, N, uniform=False):
+        """VEGAS+ allocation (mcio_strat_alloc): offsets [ncube + 1] of the hypercubes' samples from the damped weights d"""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        off = np.zeros(d.size + 1, dtype=np.int64)
+        rc = lib().mcio_strat_alloc(_dp(d), d.size, int(N), 1 if uniform else 0, off.ctypes.data_as(c_long_p))
+        if rc:
+            raise ValueError("strat_alloc: %d hypercubes need at least %d samples (rc %d)" % (d.size, 2 * d.size, rc))
+        return off
+
+    def strat_iteration(self, f, ud, seed, iteration, first_index, nstrat, off, beta=0.75, samples=False):
+        """one VEGAS+ iteration over the allocation `off` (mcio_strat_iteration): dict of mean, var [NW], d [ncube], S1, S2, A1, v2
+        [ncube, NW] and, with samples=True, y, x [N, ndraw], jac [N], jaci [N, Ni], w [N, NW]; the leaf histograms hold the iteration's"""
+        u = np.ascontiguousarray(ud if ud is not None else [0.0], dtype=np.float64)
+        ns = np.ascontiguousarray(nstrat, dtype=np.int32)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        assert ns.size == self.c.ndraw and off.size == int(np.prod(ns, dtype=np.int64)) + 1
+        nw, nc, N, D = self.c.Ni * self.c.ncomp, off.size - 1, int(off[-1]), self.c.ndraw
+        r = dict(mean=np.zeros(nw), var=np.zeros(nw), d=np.zeros(nc), S1=np.zeros((nc, nw)), S2=np.zeros((nc, nw)), A1=np.zeros((nc, nw)),
+                 v2=np.zeros((nc, nw)))
+        if samples:
+            r.update(y=np.zeros((N, D)), x=np.zeros((N, D)), jac=np.zeros(N), jaci=np.zeros((N, self.c.Ni)), w=np.zeros((N, nw)))
+        so = _StratOut(*[_dp(r[n]) if n in r else None for n, _ in _StratOut._fields_])
+        rc = lib().mcio_strat_iteration(self.p, _fnptr(f), _dp(u), int(seed), int(iteration), int(first_index), _ip(ns),
+                                        off.ctypes.data_as(c_long_p), float(beta), C.byref(so))
+        if rc:
+            raise RuntimeError("oracle stratified iteration failed (%d)" % rc)
+        return r
 
     def integrate(self, solver, f, ud, neval, niter=10, block=16, ignore=None, adapt=True, gamma=1.0,
                   measurefreq=1, seed=1234, nthreads=1, nchain=1):

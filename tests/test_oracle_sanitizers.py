@@ -1,6 +1,6 @@
 """The CPU oracle under AddressSanitizer + UndefinedBehaviorSanitizer (sanitizers).  Every parity claim leans on
-oracle/mci_oracle.c, so its known-answer suite and one whole `mcio_integrate` per solver (carried chains, several chains per block, a
-Discrete and a composite pool, complex weights) run once against an instrumented build: oracle/Makefile `sanitize`, loaded into a
+oracle/mci_oracle.c, so its known-answer suite, one whole `mcio_integrate` per solver (carried chains, several chains per block, a
+Discrete and a composite pool, complex weights) and two stratified iterations on a ragged layout run once against an instrumented build: oracle/Makefile `sanitize`, loaded into a
 Python started with LD_PRELOAD=libasan.so.  GPU AddressSanitizer is not available on this pool; this is the CPU side only."""
 import os
 import subprocess
@@ -26,6 +26,15 @@ for cfg, f in cases:
     for solver, nchain in ((O.VEGAS, 1), (O.VEGASMC, 1), (O.VEGASMC, 4), (O.MCMC, 1), (O.MCMC, 4)):
         r = cfg.integrate(solver, f, None, 8000, niter=4, block=4, seed=7, nchain=nchain)
         assert r["rc"] == 0 and np.all(np.isfinite(r["mean"])) and np.all(np.isfinite(r["stdev"])), (solver, nchain, r)
+# a stratified (VEGAS+) run on the ragged layout: two iterations, the second over the allocation the first one's d_h gives
+cfg = O.Config([dict(kind=0, pool=0, lower=0.0, upper=1.0)], [[2], [3]])
+off = O.Config.strat_alloc(np.ones(15), 3000, True)
+for it in range(2):
+    r = cfg.strat_iteration("sphere2", None, 7, it, 0, [5, 1, 3], off, samples=(it == 1))
+    assert np.all(np.isfinite(r["mean"])) and np.all(r["var"] > 0) and np.all(np.isfinite(r["d"])), r
+    cfg.train()
+    off = O.Config.strat_alloc(r["d"], 3000)
+    assert off[-1] == 3000 and np.diff(off).min() >= 2
 print("sanitized runs ok")
 """
 
