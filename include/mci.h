@@ -388,6 +388,20 @@ int mci_last_integrate_discarded(const mci_problem *prob, int64_t *neval, int32_
  * object; one warning on stderr, and this problem keeps one lane per chain --, -2 the unit did not compile (automatic lanes: one lane per
  * chain; forced lanes: MCI_ERR_COMPILE).  solver: MCI_VEGASMC | MCI_MCMC. */
 int mci_chain_speculation_status(const mci_problem *prob, int32_t solver, int32_t *status);
+/* A :vegas code object proves itself too.  The first mci_iteration_run with solver = MCI_VEGAS through a classic single-tile sample
+ * kernel (either cadence variant, plain or pipelined layout) that has no marker next to it in the kernel cache is preceded by <= 2 blocks
+ * x <= 512 samples through it; the same samples go through mci_sample_dump (map + integrand only) and through a static kernel of the
+ * library that defines the iteration plainly (vegas/montecarlo.jl:117-187), and the two packed buffers are compared (statistics 1e-9,
+ * histogram 1e-8; the static kernel's draws against the dumped ones: x bit for bit, jac 1e-13).  The launch that triggered the check then
+ * runs as if nothing had happened.  status: 0 not looked at (nothing launched yet, or a path the check does not cover: host closures,
+ * several histogram tiles, the stratified and the persistent launch), 1 verified, -1 the check FAILED -- one warning on stderr, the
+ * problem's :vegas units were compiled again in the most conservative layout (plain loop, one histogram copy), that object agreed and is
+ * used from now on --, -2 no layout agreed (a second warning; results of this problem's :vegas runs are not to be trusted).  Advisory:
+ * the triggering call still returns MCI_OK.  flags (NULL: not wanted): bit 0 = the observable sums were not compared (a user measure,
+ * whose body the static kernel cannot run; histogram, neval, normalization and the draws still count), bit 1 = verified from a marker an
+ * earlier process left, not in this one, bit 2 = the check ran but its histogram was empty on both sides (every weight of its 1024
+ * samples underflowed): nothing to compare, status stays 0 and no marker is written. */
+int mci_vegas_check_status(const mci_problem *prob, int32_t *status, int32_t *flags);
 /* lanes per chain of the last chain-solver launch (1: one lane per chain) and the accept levels of its tree */
 int mci_last_chain_speculation(const mci_problem *prob, int32_t *lanes, int32_t *max_accepts);
 /* the tree mci_set_chain_speculation(lanes, accept, max_accepts) stands for, node by node ([lanes] each; NULL: not wanted): the step

@@ -118,6 +118,7 @@ SIGNATURES = [
     ("mci_set_chain_speculation", C.c_int, [_VP, C.c_int32, C.c_double, C.c_int32]),
     ("mci_last_chain_speculation", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_chain_speculation_status", C.c_int, [_VP, C.c_int32, c_int32_p]),
+    ("mci_vegas_check_status", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_last_integrate_discarded", C.c_int, [_VP, C.POINTER(C.c_int64), c_int32_p]),
     ("mci_speculation_tree", C.c_int, [C.c_int32, C.c_double, C.c_int32, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("mci_compile_chain_speculation", C.c_int, [_VP, C.c_int32]),
@@ -157,6 +158,10 @@ DEBUG_SIGNATURES = [
     ("mci_debug_strat_d", C.c_int, [_VP, c_double_p, C.c_int64]),
     ("mci_debug_strat_dump", C.c_int, [_VP, C.c_int64, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
     ("mci_debug_mcmc_policy", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    ("mci_debug_vegas_check", C.c_int, [_VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                        C.POINTER(C.c_int64)]),
+    ("mci_debug_vegas_check_launches", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("mci_debug_vegas_check_layout", C.c_int, [_VP, c_int32_p, c_int32_p, c_double_p, C.POINTER(C.c_uint64), c_int32_p]),
 ]
 
 _lib = None

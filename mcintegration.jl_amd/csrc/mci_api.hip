@@ -1,5 +1,5 @@
 // mci_api.hip -- host core of libmci_hip.so: the C ABI of include/mci.h.  One translation unit; its sections live in the
-// mci_host_*.h files included at the bottom, in this order: types, ctx, problem, jit, iteration, integrate, access, statistics.
+// mci_host_*.h files included at the bottom, in this order: types, ctx, problem, jit, strat, check, iteration, integrate, access, statistics.
 //
 // Owns: the Configuration analogue (src/configuration.jl:105-194), the device-resident state (grids,
 // distributions, histograms, packed statistics), the per-iteration launch chain
@@ -28,6 +28,7 @@
 #include "mci_device.h" // BatchArgs / DumpArgs (the templates themselves are instantiated by the JIT)
 #include "mci_jit.h"
 #include "mci_static_kernels.h"
+#include "mci_check.h" // k_check_vegas: the static yardstick of new :vegas code objects
 #include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
 
 namespace {
@@ -60,6 +61,7 @@ extern "C" {
 #include "mci_host_problem.h"
 #include "mci_host_jit.h"
 #include "mci_host_strat.h"
+#include "mci_host_check.h"
 #include "mci_host_iteration.h"
 #include "mci_host_integrate.h"
 #include "mci_host_access.h"

@@ -31,6 +31,8 @@ int mci_debug_persist_spin_ticks(mci_problem *prob, unsigned long long ticks);
  *   split_chunk      n       (per launch) samples per chunk, over all blocks, of a many-grid :vegas launch (mci_debug_split_chunks)
  *   spec_self_check  0 | 1   (per launch) the self-check of a several-lanes-per-chain code object (mci_chain_speculation_status): never |
  *                            also when the kernel cache holds the marker of an earlier pass (the guard test of tests/test_hip_spec.py)
+ *   vegas_self_check 0 | 1   (per launch) the self-check of a :vegas code object (mci_vegas_check_status): never | also when the kernel
+ *                            cache holds the marker of an earlier pass
  * (The library reads two environment variables and no others: MCI_KERNEL_CACHE -- the directory code objects are cached in -- and
  * MCI_JIT_FLAGS -- extra hiprtc options; INTEGRATION.md.) */
 int mci_debug_override(const char *key, int64_t value, int32_t on);
@@ -52,6 +54,20 @@ int mci_debug_compiler_id(const char *set, char *out, int32_t n);
  * steps of a first launch (4096) | how much longer than the chains that measured the holds a launch's chains may be (2) | length of a
  * carried chain in longest holds (4) | its minimum in half burn-in floors (2); <= 0 keeps a value */
 int mci_debug_mcmc_policy(int64_t pilot_steps, int64_t grow, int64_t carry_holds, int64_t carry_half_floors);
+/* test hook: the library's static :vegas kernel (k_check_vegas, what a new :vegas code object is held against) on its own -- one
+ * iteration of blocks [block_lo, block_lo + nblocks) x nevalperblock samples (at most 1024 in all) into packed[packed size], in the
+ * layout of mci_get_packed.  x[n][ndraw], jac[n], w[n][ni * ncomp]: the samples as mci_sample_dump lays them out, block after block
+ * (all NULL: this problem's own mci_sample_dump); bad[0] / bad[1]: samples whose x (bit for bit) / jac (1e-13) the kernel does not
+ * reproduce.  Problems the check covers only (one histogram tile, device integrand and measure). */
+int mci_debug_vegas_check(mci_problem *prob, int32_t iteration, uint64_t seed, int64_t nevalperblock, int64_t block_lo, int64_t nblocks,
+                          int64_t measurefreq, const double *x, const double *jac, const double *w, double *packed, int64_t *bad);
+/* launches made on behalf of the :vegas self-check of this problem so far (sample kernel under test, sample dump, static kernel) */
+int mci_debug_vegas_check_launches(const mci_problem *prob, int64_t *launches);
+/* the run-time layout table the static :vegas kernel is given (no device needed).  head[8]: ndraw, ni, ncomp, nobs, ncols, nbin, covered
+ * (0 | 1), default or binning measure (0: a user measure); draws[ndraw][6]: kind, table offset, distribution offset, bins, histogram
+ * offset, takes histogram adds; scales[ndraw]: the Jacobian scale; own[ni]: own-draw masks; obs[ni][3]: observable offset, bins,
+ * binning draw.  NULL: not wanted. */
+int mci_debug_vegas_check_layout(const mci_problem *prob, int32_t *head, int32_t *draws, double *scales, uint64_t *own, int32_t *obs);
 #ifdef __cplusplus
 }
 #endif

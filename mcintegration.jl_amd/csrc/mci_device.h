@@ -836,6 +836,17 @@ template <class Cfg> __device__ __forceinline__ double *obs_wave(double *sO) {
     else return sO + (int)(threadIdx.x >> 6) * Cfg::NOBS;
 }
 
+// Stand-in for a miscompiled histogram add, for the tests of the :vegas self-check (tests/test_hip_vegas_check.py): a unit compiled with
+// MCI_JIT_FLAGS=-DMCI_CHECK_PERTURB_HIST=LEVEL adds to the NEXT bin of the draw's leaf, the last bin wrapping to the first -- wrong
+// arithmetic at addresses that are always inside the leaf's histogram.  Level 1: the adds of the pipelined sample loop only (hist_add_draw);
+// level 2: every add that goes through hist_update (all :vegas layouts; the chain solvers' too).  Without the flag -- every build, and the static library always -- the bin passes through.
+template <class Cfg, int LEAF, int LEVEL> __device__ __forceinline__ int perturbed_bin(int bin) {
+#if defined(MCI_CHECK_PERTURB_HIST)
+    if constexpr (MCI_CHECK_PERTURB_HIST >= LEVEL) return bin + 1 >= Cfg::leaf_nbin(LEAF) ? 0 : bin + 1;
+#endif
+    return bin;
+}
+
 // histogram update of one sample: accumulate!(var, pos+offset, weight) for every (integrand i, draw k in own(i))
 // (vegas/montecarlo.jl:170-185).  The per-integrand weights covering the same draw are summed first,
 // so each draw costs one ds_add_f64.
@@ -851,15 +862,16 @@ template <class Cfg, int TILE = -1> __device__ __forceinline__ void hist_update(
                 constexpr int i = decltype(I)::value;
                 if constexpr ((Cfg::own_mask(i) >> k) & 1ull) wk += wh[i];
             });
+            const int hb = perturbed_bin<Cfg, leaf, 2>(s.bin[k]);
             if constexpr (Mode<Cfg>::HIST_LDS) {
                 constexpr int lt = Cfg::leaf_tile(leaf);
                 if constexpr (TILE >= 0) {
-                    if constexpr (Cfg::NTILE == 1 || TILE == lt) lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(lt) + s.bin[k])], wk);
+                    if constexpr (Cfg::NTILE == 1 || TILE == lt) lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(lt) + hb)], wk);
                 } else {
-                    if (Cfg::NTILE == 1 || tile == lt) lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(lt) + s.bin[k])], wk);
+                    if (Cfg::NTILE == 1 || tile == lt) lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(lt) + hb)], wk);
                 }
             } else {
-                global_add(&gH[Cfg::leaf_boff(leaf) + s.bin[k]], wk);
+                global_add(&gH[Cfg::leaf_boff(leaf) + hb], wk);
             }
         }
     });
@@ -874,7 +886,7 @@ template <class Cfg, int K> __device__ __forceinline__ void hist_add_draw(int bi
             constexpr int i = decltype(I)::value;
             if constexpr ((Cfg::own_mask(i) >> K) & 1ull) wk += wh[i];
         });
-        lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(Cfg::leaf_tile(leaf)) + bin)], wk);
+        lds_add(&sH[hslot<Cfg>(Cfg::leaf_boff(leaf) - Cfg::tile_boff(Cfg::leaf_tile(leaf)) + perturbed_bin<Cfg, leaf, 1>(bin))], wk);
     }
 }
 
@@ -889,9 +901,13 @@ template <class Cfg> struct PendingHist {
     int bin[Cfg::NDRAW > 0 ? Cfg::NDRAW : 1];
     double wh[Cfg::NI];
 };
+// MCI_VEGAS_PLAIN_LOOP (set by the host for the conservative layout of a unit that failed its self-check, mci_host_check.h): never
+#ifndef MCI_VEGAS_PLAIN_LOOP
+#define MCI_VEGAS_PLAIN_LOOP 0
+#endif
 template <class Cfg> constexpr bool pipe_eligible() {
     // (the opt-in 32-bit stream too: four draws per Philox block, four reads and four atomics per stage)
-    return Cfg::NDRAW >= 8 && Cfg::NDRAW <= 16 && all_draws_pair_table<Cfg>() && Cfg::NTILE == 1 &&
+    return MCI_VEGAS_PLAIN_LOOP == 0 && Cfg::NDRAW >= 8 && Cfg::NDRAW <= 16 && all_draws_pair_table<Cfg>() && Cfg::NTILE == 1 &&
            Mode<Cfg>::HIST_LDS && Cfg::HOST_INTEGRAND == 0 && Cfg::HOST_MEASURE == 0 && Cfg::EC_DOUBLES == 0;
 }
 template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_sample_pipe(const RoundKeys<KV> &keys, u32 stream, u64 index, Sample<Cfg> &s,

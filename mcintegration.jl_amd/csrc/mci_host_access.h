@@ -226,10 +226,9 @@ int mci_load_state(mci_problem *p, const char *path) {
     return rc;
 }
 
-int mci_sample_dump(mci_problem *p, int32_t iteration, uint64_t seed, int64_t nevalperblock, int64_t block_index, int64_t n,
-                    double *x, double *jac, double *w) {
-    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
-    if (n < 1 || n > nevalperblock) return fail(MCI_ERR_INVALID, "n must be in 1..neval_per_block");
+// n samples from global sample index first_index on through mci_sample_dump, left on the device: x[n][ndraw] | jac[n] | w[n][ni * ncomp]
+// in p->d_dump
+static int sample_dump_device(mci_problem *p, int32_t iteration, uint64_t seed, int64_t first_index, int64_t n) {
     int rc = ensure_dump(p);
     if (rc) return rc;
     HIPCHK(hipSetDevice(p->ctx->device));
@@ -238,6 +237,7 @@ int mci_sample_dump(mci_problem *p, int32_t iteration, uint64_t seed, int64_t ne
     if (n * per > p->cap_dump) {
         if (p->d_dump) (void)hipFree(p->d_dump);
         p->d_dump = nullptr;
+        p->cap_dump = 0;
         HIPCHK(hipMalloc((void **)&p->d_dump, (size_t)(n * per) * sizeof(double)));
         p->cap_dump = n * per;
     }
@@ -251,14 +251,25 @@ int mci_sample_dump(mci_problem *p, int32_t iteration, uint64_t seed, int64_t ne
     a.w = a.jac + n;
     a.seed = seed;
     a.iteration = (mci::u32)iteration;
-    a.first_index = block_index * nevalperblock;
+    a.first_index = first_index;
     a.n = n;
     void *args[] = {&a};
     const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     HIPCHK(hipModuleLaunchKernel(p->f_dump, grid, 1, 1, 256, 1, 1, (unsigned)p->lds_bytes, p->ctx->stream, args, nullptr));
-    if (x) HIPCHK(hipMemcpyAsync(x, a.x, (size_t)n * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
-    if (jac) HIPCHK(hipMemcpyAsync(jac, a.jac, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
-    if (w) HIPCHK(hipMemcpyAsync(w, a.w, (size_t)n * s.ni * s.ncomp * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+    return MCI_OK;
+}
+
+int mci_sample_dump(mci_problem *p, int32_t iteration, uint64_t seed, int64_t nevalperblock, int64_t block_index, int64_t n,
+                    double *x, double *jac, double *w) {
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    if (n < 1 || n > nevalperblock) return fail(MCI_ERR_INVALID, "n must be in 1..neval_per_block");
+    int rc = sample_dump_device(p, iteration, seed, block_index * nevalperblock, n);
+    if (rc) return rc;
+    const auto &s = p->shape;
+    const double *dx = p->d_dump, *djac = dx + n * s.ndraw, *dw = djac + n;
+    if (x) HIPCHK(hipMemcpyAsync(x, dx, (size_t)n * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+    if (jac) HIPCHK(hipMemcpyAsync(jac, djac, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+    if (w) HIPCHK(hipMemcpyAsync(w, dw, (size_t)n * s.ni * s.ncomp * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
     HIPCHK(hipStreamSynchronize(p->ctx->stream));
     return MCI_OK;
 }

@@ -31,7 +31,7 @@ bool persist_layout(const mci_problem *p) {
 // histogram copies and 512-thread workgroups, which this kernel's plain 256-thread layout does not match).
 bool persist_plan(const mci_problem *p, const mci_integrate_args *a, int64_t nevalperblock, int64_t nblocks, int *wpb_out) {
     const auto &s = p->shape;
-    if (p->persistent == 0 || p->persist_failed) return false;
+    if (p->persistent == 0 || p->persist_failed || p->vegas_conservative) return false; // (conservative: the persistent unit is a pipelined one)
     if (a->solver != MCI_VEGAS || a->measurefreq != 1 || a->niter < 1) return false;
     if (p->ctx->nranks != 1) return false; // (a one-rank communicator's all-reduce is the identity)
     if (!persist_layout(p)) return false;

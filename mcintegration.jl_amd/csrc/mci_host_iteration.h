@@ -16,11 +16,20 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         if (solver != MCI_VEGAS) return fail(MCI_ERR_INVALID, "stratification works with solver = :vegas only (mci_set_stratification_off first)");
         return strat_run(p, nevalperblock, block_lo, block_hi, iteration, seed, measurefreq);
     }
-    const int kern = kslot(solver, measurefreq);
+    // (inside vegas_self_check: the code object under test, whatever the cadence of its small launch)
+    const int kern = (p->in_self_check && p->check_slot >= 0 && solver == MCI_VEGAS) ? p->check_slot : kslot(solver, measurefreq);
     // (a chain solver's lane-per-chain kernel is compiled once the launch is known to run one lane per chain: a launch of few chains
     // runs the several-lanes-per-chain kernel instead, mci_spec.h, and pays for that code object only)
     int rc = (solver == MCI_VEGAS || p->deterministic || p->shape.host_integrand || p->spec_lanes == 1) ? compile_solver(p, kern) : MCI_OK;
     if (rc) return rc;
+    // a :vegas code object that has neither a marker nor a passed check yet proves itself first (mci_host_check.h); afterwards this
+    // launch runs as if nothing had happened
+    if (solver == MCI_VEGAS && !p->in_self_check && !p->vegas_check_done[kern == kSlotVegasAny ? 1 : 0] &&
+        (rc = vegas_check_gate(p, kern, nevalperblock, block_lo, block_hi, iteration, seed, measurefreq)))
+        return rc;
+    // (a check that fell back to the conservative layout has unloaded the slot's module; if that unit did not compile the slot is empty:
+    // compiled here again -- a no-op otherwise -- so that the launch below never goes through a handle of an unloaded module)
+    if (solver == MCI_VEGAS && (rc = compile_solver(p, kern))) return rc;
     if (solver == MCI_VEGAS && p->shape.host_integrand && (rc = ensure_dump(p))) return rc;
     if ((rc = flush_merge(p))) return rc; // a previous batch nobody looked at: merge it (resets the global histogram)
     HIPCHK(hipSetDevice(p->ctx->device));
@@ -740,6 +749,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     m.npa = p->npa;
     m.nrows = (int)nrows;
     m.block_means = nullptr;
+    m.hist_no_offset = (p->in_self_check && p->check_slot >= 0) ? 1 : 0; // (vegas_self_check compares the bare sums)
     m.hold = a.hold_hist; // (:mcmc: the 64 counts follow the tables in `packed`, so that ONE all-reduce carries them; NULL: zeros)
     // the chain solvers keep every block's mean of every iteration (one row of the block log; not the self-check's launches: their rows,
     // of another stride, would land on the logged ones)

@@ -79,11 +79,18 @@ static int ensure_dump(mci_problem *p) {
     return MCI_OK;
 }
 
+// prefix of a :vegas unit in the conservative layout: no hand-pipelined sample loop (mci_device.h pipe_eligible)
+static const char *const kVegasPlainLoop = "#define MCI_VEGAS_PLAIN_LOOP 1\n";
 static int compile_solver(mci_problem *p, int slot) {
     if (slot < 0 || slot > kSlotVegasAny) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", slot); // main.jl:263
     if (p->compiled[slot]) return MCI_OK;
     const int solver = slot_solver(slot);
     const int unit = slot == MCI_VEGAS ? mcijit::kUnitVegasMf1 : mcijit::kUnitSolver;
+    // (a problem whose :vegas unit failed its self-check, mci_host_check.h: EVERY :vegas unit it compiles from then on -- either cadence,
+    // planned or planned again after drop_modules -- is the plain loop)
+    auto gen = [&](const mcijit::ProblemShape &sh) {
+        return std::string(p->vegas_conservative && solver == MCI_VEGAS ? kVegasPlainLoop : "") + mcijit::generate_source(sh, solver, unit);
+    };
     if (p->shape.measure_body.empty() && !p->shape.host_measure) // vegas/montecarlo.jl:104, mcmc/montecarlo.jl:84
         for (int i = 0; i < p->ni; ++i)
             if (p->shape.obs_bin_draw[i] < 0 && p->shape.obs_nbin[i] != p->shape.ncomp)
@@ -100,7 +107,7 @@ static int compile_solver(mci_problem *p, int slot) {
         p->shape.det = 1;
         p->shape.hcopy = T / 64;
         Candidate c;
-        c.src = mcijit::generate_source(p->shape, solver, unit);
+        c.src = gen(p->shape);
         c.threads = T;
         c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path);
         if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c.log.c_str());
@@ -112,18 +119,18 @@ static int compile_solver(mci_problem *p, int slot) {
     static const char *const kVgprKeys = "#define MCI_PIPE_VGPR_KEYS 1\n";
     Candidate chosen;
     if (solver != MCI_VEGAS) {
-        chosen.src = mcijit::generate_source(p->shape, solver, unit);
+        chosen.src = gen(p->shape);
         chosen.threads = p->threads;
         chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
         if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
     } else if (p->vegas_planned) {
         // the other measurefreq variant of a kernel whose plan (workgroup size, histogram copies, round keys) stands
-        chosen.src = (p->vegas_keys ? std::string(kVgprKeys) : std::string()) + mcijit::generate_source(p->shape, solver, unit);
+        chosen.src = (p->vegas_keys ? std::string(kVgprKeys) : std::string()) + gen(p->shape);
         chosen.threads = p->threads_vegas ? p->threads_vegas : p->vegas_wide ? 512 : p->threads;
         chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
         if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
         if (p->vegas_keys && (chosen.vgprs() > 128 || chosen.scratch() != 0)) { // (this variant carries a few registers more)
-            chosen.src = mcijit::generate_source(p->shape, solver, unit);
+            chosen.src = gen(p->shape);
             chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
             if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
         }
@@ -136,14 +143,14 @@ static int compile_solver(mci_problem *p, int slot) {
             if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
         }
     } else {
-        const bool hcopy_plan = p->hcopy_plan && !g_over.hist_copies.on;
+        const bool hcopy_plan = p->hcopy_plan && !g_over.hist_copies.on && !p->vegas_conservative;
         int tcopy = 512;
         p->shape.hcopy = planned_hcopy(p, &tcopy);
         if (p->hcopy_plan) p->threads_vegas = tcopy;
         const int T0 = p->threads_vegas ? p->threads_vegas : p->threads;
         // (light integrands: a launch bound of 512 threads costs the plain layout nothing -- see vegas_wide; anything that would need scratch
         // or more than 128 registers under it is compiled for the default size instead)
-        const bool try_wide = p->threads == 256 && !p->threads_explicit && !p->deterministic && p->shape.ndraw <= 8 && !p->shape.host_integrand;
+        const bool try_wide = !p->vegas_conservative && p->threads == 256 && !p->threads_explicit && !p->deterministic && p->shape.ndraw <= 8 && !p->shape.host_integrand;
         if (hcopy_plan) {
             // Histogram copies pay when the kernel runs four or five waves per SIMD either way (81..128 VGPRs: two 512-thread workgroups
             // share a CU).  More registers: two such workgroups no longer fit.  Fewer: the plain layout runs six or more waves per SIMD
@@ -153,13 +160,13 @@ static int compile_solver(mci_problem *p, int slot) {
             // issues faster than the form with an SGPR key: C2 1.358 -> 1.331 ms per 1e8 samples) unless that crosses the line.
             // Candidates, compiled side by side: [copies + VGPR keys], [plain layout]; [copies, SGPR keys] only if the first is too fat.
             Candidate keys, plain, nokeys;
-            const std::string with_copies = mcijit::generate_source(p->shape, solver, unit);
+            const std::string with_copies = gen(p->shape);
             keys.src = kVgprKeys + with_copies;
             keys.threads = nokeys.threads = T0;
             nokeys.src = with_copies;
             mcijit::ProblemShape sh = p->shape;
             sh.hcopy = 1;
-            plain.src = mcijit::generate_source(sh, solver, unit);
+            plain.src = gen(sh);
             plain.threads = try_wide ? 512 : p->threads;
             std::vector<Candidate *> both = {&keys, &plain};
             compile_all(both);
@@ -189,7 +196,7 @@ static int compile_solver(mci_problem *p, int slot) {
             // many-grid plans (one workgroup per CU owns the LDS): the largest of 1024 / 768 / 512 threads at which the sample pass shows
             // no scratch -- the rungs compiled side by side
             Candidate rung[3];
-            const std::string src = mcijit::generate_source(p->shape, solver, unit);
+            const std::string src = gen(p->shape);
             const int ts[3] = {1024, 768, 512};
             std::vector<Candidate *> all;
             for (int i = 0; i < 3; ++i) {
@@ -206,7 +213,7 @@ static int compile_solver(mci_problem *p, int slot) {
             p->threads_vegas = all[pick]->threads;
             chosen = std::move(*all[pick]);
         } else {
-            chosen.src = mcijit::generate_source(p->shape, solver, unit);
+            chosen.src = gen(p->shape);
             chosen.threads = try_wide ? 512 : T0;
             chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
             if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
@@ -278,6 +285,45 @@ static int compile_spec(mci_problem *p, int solver) {
     return MCI_OK;
 }
 
+// The comparison of two packed buffers both self-checks use (spec_self_check below, vegas_self_check in mci_host_check.h): the statistics
+// head [0, nstat) to 1e-9, everything behind it (histogram, propose / accept tables) to 1e-8, relative to the larger entry with 1e-3 of
+// the section's largest entry as the floor.  Entries [0, skip) are left out (the observable sums under a user measure, which the static
+// kernel cannot run).  Non-finite entries agree when they are the same kind of non-finite.  nhist >= 0 (vegas_self_check): the histogram
+// [nstat, nstat + nhist) is a section of its own, measured against ITS OWN largest entry -- next to the propose / accept tables, which a
+// :vegas launch leaves at their clearStatistics! values of ~1e-8, every histogram entry below ~1e-19 would compare equal to anything;
+// hist_top is that largest entry (0: the histogram holds nothing the comparison could have looked at).
+namespace {
+struct PackedDiff {
+    long bad = 0, first_bad = -1;
+    long bad_sec[3] = {0, 0, 0}; // ... in the statistics head | behind it (nhist >= 0: the histogram) | the tables behind the histogram
+    double worst = 0.0;       // largest difference, in units of its section's largest entry
+    double hist_top = 0.0;    // nhist >= 0: largest entry of the histogram section, either side
+};
+void compare_packed(const double *x, const double *y, size_t nstat, size_t n, size_t skip, PackedDiff *out, long nhist = -1) {
+    PackedDiff r;
+    const size_t hend = nhist >= 0 ? nstat + (size_t)nhist : n;
+    for (int sec = 0; sec < (nhist >= 0 ? 3 : 2); ++sec) {
+        const size_t lo = sec == 0 ? skip : sec == 1 ? nstat : hend, hi = sec == 0 ? nstat : sec == 1 ? hend : n;
+        const double tol = sec ? 1e-8 : 1e-9;
+        double top = 0.0;
+        for (size_t i = lo; i < hi; ++i) top = std::fmax(top, std::fmax(std::fabs(x[i]), std::fabs(y[i])));
+        if (sec == 1 && nhist >= 0) r.hist_top = top;
+        for (size_t i = lo; i < hi; ++i) {
+            const double a = x[i], b = y[i];
+            const double d = std::fabs(a - b), lim = tol * (std::fmax(std::fabs(a), std::fabs(b)) + 1e-3 * top);
+            const bool ok = (std::isfinite(a) && std::isfinite(b)) ? d <= lim : (std::isnan(a) == std::isnan(b) && (std::isnan(a) || a == b));
+            if (!ok) {
+                if (r.first_bad < 0) r.first_bad = (long)i;
+                ++r.bad;
+                ++r.bad_sec[sec];
+                if (top > 0.0 && d / top > r.worst) r.worst = d / top;
+            }
+        }
+    }
+    *out = r;
+}
+} // namespace
+
 // A NEW several-lanes-per-chain code object proves itself before it is trusted.  Every user integrand is a new translation unit, and
 // one of ~1000 campaign layouts came out of ROCm 7.2's compiler with the right chains and its histogram adds in the wrong bins
 // (profiles/r05_fuzz.txt: right estimates, a map adapting to noise, no error).  Both chain kernels of a problem are product kernels and
@@ -316,25 +362,10 @@ static int spec_self_check(mci_problem *p, int solver, int G, int64_t nevalperbl
     p->kernel_timing = kernel_timing;
     if (p->d_status) (void)hipMemcpy(p->d_status, h_status, sizeof(h_status), hipMemcpyHostToDevice); // (what the two small launches flagged is theirs)
     if (rc) return rc;
-    const size_t nstat = (size_t)(2 * p->shape.nobs + 2 + p->ni + 1);
-    double worst = 0.0;
-    long bad = 0, first_bad = -1;
-    for (int sec = 0; sec < 2; ++sec) {
-        const size_t lo = sec ? nstat : 0, hi = sec ? (size_t)p->packed_n : nstat;
-        const double tol = sec ? 1e-8 : 1e-9;
-        double top = 0.0;
-        for (size_t i = lo; i < hi; ++i) top = std::fmax(top, std::fmax(std::fabs(got[0][i]), std::fabs(got[1][i])));
-        for (size_t i = lo; i < hi; ++i) {
-            const double a = got[0][i], b = got[1][i];
-            const double d = std::fabs(a - b), lim = tol * (std::fmax(std::fabs(a), std::fabs(b)) + 1e-3 * top);
-            const bool ok = (std::isfinite(a) && std::isfinite(b)) ? d <= lim : (std::isnan(a) == std::isnan(b) && (std::isnan(a) || a == b));
-            if (!ok) {
-                if (first_bad < 0) first_bad = (long)i;
-                ++bad;
-                if (top > 0.0 && d / top > worst) worst = d / top;
-            }
-        }
-    }
+    PackedDiff df;
+    compare_packed(got[0].data(), got[1].data(), (size_t)(2 * p->shape.nobs + 2 + p->ni + 1), (size_t)p->packed_n, 0, &df);
+    const long bad = df.bad, first_bad = df.first_bad;
+    const double worst = df.worst;
     p->spec_need_check[solver - 1] = false;
     if (bad == 0) {
         p->spec_state[solver - 1] = 1;

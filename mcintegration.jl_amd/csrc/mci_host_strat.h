@@ -406,6 +406,7 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
                            (int)mci_problem::kGroups, p->d_stage1);
     HIPCHK(hipGetLastError());
     mci::MergeArgs &m = p->merge;
+    m.hist_no_offset = 0;
     m.part_cols = p->d_part_cols;
     m.ncols = s.ncols;
     m.nobs = s.nobs;

@@ -123,6 +123,16 @@ struct mci_problem {
     int spec_state[2] = {0, 0};
     bool spec_need_check[2] = {false, false}; // the loaded code object has no marker yet
     bool in_self_check = false;
+    // A :vegas code object proves itself too (mci_host_check.h vegas_self_check): the first launch through a classic single-tile sample
+    // kernel without a marker is preceded by <= 2 blocks x <= 512 samples through it, and the packed buffer is compared with what the
+    // static kernel k_check_vegas (mci_check.h) makes of the same samples.  [0] the measurefreq == 1 unit, [1] the any-cadence unit.
+    // vegas_check_state: 0 not looked at, 1 verified, -1 fell back to the conservative layout, -2 no layout agreed
+    int vegas_check_state[2] = {0, 0};
+    bool vegas_check_done[2] = {false, false}; // nothing left to decide for the loaded code object of that unit
+    int vegas_check_flags = 0;                 // bit 0: observables not compared (user measure), bit 1: verified from a marker
+    bool vegas_conservative = false;           // the :vegas units are compiled in the generator's most conservative layout (plain loop, one histogram copy)
+    int check_slot = -1;                       // inside vegas_self_check: the kernel slot its launch goes through, whatever its cadence
+    int64_t check_launches = 0;                // launches made for vegas_self_check so far (mci_debug_vegas_check_launches)
     int64_t last_discarded_neval = 0;              // evaluations of the warm-up launches the last mci_integrate ran again instead of counting
     int32_t last_discarded_launches = 0;
     static const int64_t kSpecFill = 65536;        // lanes a launch of few chains spreads over: one wave on each of the 1024 SIMDs
@@ -269,7 +279,7 @@ struct mci_problem {
     //   resources the check may create or grow -- d_chain_x / curr / P, chain_cap, d_blocklog, the other d_* / h_* and cap_*, evs,
     //     the modules and compiled[], the speculation trees on the device (d_spec_tab, spec_tab_*, spec_ntree, spec_first, spec_accepts);
     //   settings -- spec_lanes, kernel_timing, chain_carry, threads*, ...;
-    //   the check's own result -- spec_state, spec_need_check, in_self_check;
+    //   the check's own result -- spec_state, spec_need_check, in_self_check, vegas_check_*, vegas_conservative, check_*;
     //   the merge hand-off -- merge, merge_pending (mci_get_packed flushes it inside the check);
     //   per-call results of mci_integrate -- last_discarded_*, last_persistent, launch_counted, log_row;
     //   the reduce's bookkeeping -- reduces, cev_valid[] (mci_iteration_reduce alone writes them; the check does not reduce).
@@ -362,7 +372,7 @@ int64_t mci_problem::kMcmcCarryHalfFloors = 2;
 // are cached) and MCI_JIT_FLAGS (extra hiprtc options), mci_jit.h.
 namespace {
 struct Override { bool on = false; int64_t v = 0; };
-struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk; } g_over;
+struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk, vegas_self_check; } g_over;
 Override *override_slot(const char *key) {
     if (!key) return nullptr;
     if (!strcmp(key, "table_mode")) return &g_over.table_mode;
@@ -375,6 +385,7 @@ Override *override_slot(const char *key) {
     if (!strcmp(key, "fresh_burnin_pct")) return &g_over.fresh_burnin_pct;
     if (!strcmp(key, "spec_self_check")) return &g_over.spec_self_check;
     if (!strcmp(key, "split_chunk")) return &g_over.split_chunk;
+    if (!strcmp(key, "vegas_self_check")) return &g_over.vegas_self_check;
     return nullptr;
 }
 } // namespace
@@ -562,6 +573,7 @@ int hold_consume(mci_problem *p) {
 
 void drop_modules(mci_problem *p) {
     p->vegas_planned = p->vegas_keys = p->vegas_wide = false;
+    p->vegas_check_done[0] = p->vegas_check_done[1] = false; // (new code objects: they prove themselves again, or show their markers)
     p->f_dump = nullptr;
     for (int k = 0; k < mci_problem::kSlots; ++k) {
         p->compiled[k] = false;

@@ -44,6 +44,10 @@ struct MergeArgs {
                              // kept per iteration for the block-lineage error of carried chains (mci_lineage_sums)
     const unsigned long long *hold; // [64] or NULL: the :mcmc holding-time histogram of the launch; its counts follow the tables in `packed`
                                     // (exact doubles), so that they ride in the iteration's one all-reduce
+    int hist_no_offset;      // 1: the histogram section WITHOUT the clearStatistics! offsets -- the small launch of the :vegas self-check
+                             // (mci_host_check.h): its comparison is relative to the section's largest entry, and next to offsets of
+                             // 1e-10 per block nothing below ~3e-18 can be seen, while 1024 samples of a peaked integrand on an
+                             // untrained map may put no more than 1e-27 into their fullest bin
 };
 // packed = [ ... | hist(nbin) | propose(npa) | accept(npa) ]: the tables ride in the all-reduce like MPIreduceConfig! reduces them
 // (configuration.jl:297-298).  One wave per entry, lanes stride over the workgroup rows.
@@ -65,7 +69,7 @@ __device__ inline void merge_pa(const MergeArgs &m, int blk) {
 
 // one histogram bin of the merged config: clearStatistics! offsets + the second merge stage
 __device__ inline double merge_hist_bin(const MergeArgs &m, int bin) {
-    double s = (double)(m.nblocks + 1) * 1.0e-10;
+    double s = m.hist_no_offset ? 0.0 : (double)(m.nblocks + 1) * 1.0e-10;
     if (m.use_ghist) { // (use_ghist = the number of buffers the launch spread its atomics over)
         for (int g = 0; g < m.use_ghist; ++g) {
             s += m.ghist[(size_t)g * m.nbin + bin];

@@ -609,6 +609,51 @@ class Engine:
         check(lib().mci_chain_speculation_status(self.p, _lib.SOLVERS[solver], C.byref(st)))
         return int(st.value)
 
+    def vegas_check_status(self):
+        """(status, flags) of the self-check of this problem's :vegas code objects against the library's static :vegas kernel: status 0
+        not looked at (nothing launched yet, or a path the check does not cover), 1 verified, -1 fell back to the conservative layout,
+        -2 no layout agreed; flags bit 0 = observables not compared (a user measure), bit 1 = verified from a marker in the kernel
+        cache, not in this process, bit 2 = the check's histogram was empty on both sides (not compared: status stays 0); see
+        mci_vegas_check_status"""
+        st, fl = C.c_int32(), C.c_int32()
+        check(lib().mci_vegas_check_status(self.p, C.byref(st), C.byref(fl)))
+        return int(st.value), int(fl.value)
+
+    def vegas_check_launches(self):
+        """launches made for the :vegas self-check of this problem so far; see csrc/mci_debug.h mci_debug_vegas_check_launches"""
+        n = C.c_int64()
+        check(lib().mci_debug_vegas_check_launches(self.p, C.byref(n)))
+        return int(n.value)
+
+    def vegas_check_reference(self, nevalperblock, block_lo, nblocks, iteration=0, seed=1234, measurefreq=1, x=None, jac=None, w=None):
+        """(packed, (x mismatches, jac mismatches)): one iteration through the library's static :vegas kernel on its own, fed the samples
+        x[n][ndraw], jac[n], w[n][ni * ncomp] (None: this problem's own sample dump); see csrc/mci_debug.h mci_debug_vegas_check"""
+        packed = np.zeros(self.packed_size)
+        bad = (C.c_int64 * 2)()
+        ptr = [None, None, None]
+        if x is not None:
+            keep = [np.ascontiguousarray(v, dtype=np.float64) for v in (x, jac, w)]
+            ptr = [v.ctypes.data_as(_lib.c_double_p) for v in keep]
+        check(lib().mci_debug_vegas_check(self.p, int(iteration), int(seed), int(nevalperblock), int(block_lo), int(nblocks), int(measurefreq),
+                                          ptr[0], ptr[1], ptr[2], packed.ctypes.data_as(_lib.c_double_p), bad))
+        return packed, (int(bad[0]), int(bad[1]))
+
+    def vegas_check_layout(self):
+        """the run-time layout table the static :vegas kernel is given for this problem (no device needed); see csrc/mci_debug.h
+        mci_debug_vegas_check_layout"""
+        head = (C.c_int32 * 8)()
+        check(lib().mci_debug_vegas_check_layout(self.p, head, None, None, None, None))
+        nd, ni = int(head[0]), int(head[1])
+        draws, scales = (C.c_int32 * (6 * max(nd, 1)))(), (C.c_double * max(nd, 1))()
+        own, obs = (C.c_uint64 * max(ni, 1))(), (C.c_int32 * (3 * max(ni, 1)))()
+        check(lib().mci_debug_vegas_check_layout(self.p, head, draws, scales, own, obs))
+        keys = ("kind", "off", "doff", "nbin", "boff", "hist")
+        return dict(ndraw=nd, ni=ni, ncomp=int(head[2]), nobs=int(head[3]), ncols=int(head[4]), nbin=int(head[5]), covered=bool(head[6]),
+                    with_obs=bool(head[7]),
+                    draws=[dict(zip(keys, [int(draws[6 * k + j]) for j in range(6)]), scale=float(scales[k])) for k in range(nd)],
+                    integrands=[dict(own=int(own[i]), obs_off=int(obs[3 * i]), obs_nbin=int(obs[3 * i + 1]), obs_bin_draw=int(obs[3 * i + 2]))
+                                for i in range(ni)])
+
     def compile_chain_speculation(self, solver):
         """the several-lanes-per-chain kernel of "vegasmc" | "mcmc" (its own code object)"""
         check(lib().mci_compile_chain_speculation(self.p, _lib.SOLVERS[solver]))

@@ -333,6 +333,11 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
         except Exception:
             res.chain_bias = None
     res.stratification = eng.stratification() if strat is not None else None   # {nstrat, ncube, beta} of a stratified run
+    if s == VEGAS and hasattr(eng, "vegas_check_status"):
+        try:   # was the kernel that produced these grids checked?  (status, flags) of mci_vegas_check_status; a note of report() when negative
+            res.vegas_check = eng.vegas_check_status()
+        except Exception:
+            res.vegas_check = None
     res.warmup = warmup   # launches that were run again instead of being counted (automatic :mcmc chain lengths)
     res.neval_discarded = neval_discarded   # ... and their evaluations: spent (they trained the map), in neither res.neval nor the estimate
     if print >= 0:

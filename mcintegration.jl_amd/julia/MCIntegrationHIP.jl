@@ -278,6 +278,13 @@ function acceptance(c::Configuration)        # (propose, accept), each [3, Nd, m
     shape(v) = permutedims(reshape(v, M, Nd, 3), (3, 2, 1))                 # the library is row-major [update][integrand][target]
     shape(pr), shape(ac)
 end
+# (status, flags) of the self-check of the problem's :vegas code objects against the library's static :vegas kernel: 0 not looked at,
+# 1 verified, -1 fell back to the conservative layout, -2 no layout agreed (include/mci.h mci_vegas_check_status)
+function vegas_check_status(c::Configuration)
+    st = Ref{Int32}(0); fl = Ref{Int32}(0)
+    check(ccall((:mci_vegas_check_status, libmci), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c.problem, st, fl))
+    Int(st[]), Int(fl[])
+end
 function visited(c::Configuration)
     n = Ref{Int32}(0); no = Ref{Int32}(0); ps = Ref{Int64}(0); tm = Ref{Int32}(0); lds = Ref{Int64}(0)
     check(ccall((:mci_problem_info, libmci), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}), c.problem, n, no, ps, tm, lds))

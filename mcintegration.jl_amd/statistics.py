@@ -113,6 +113,9 @@ class Result:
         self.chain_bias = None
         # set by integrate() for a stratified :vegas run (stratify=...): {nstrat, ncube, beta} of the plan it ran, else None
         self.stratification = None
+        # set by integrate() after a :vegas run: (status, flags) of the self-check of the problem's :vegas code objects
+        # (Engine.vegas_check_status; report() prints a note when the status is negative), else None
+        self.vegas_check = None
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
         self.iterations = [(self._shape(self.iter_mean[i]), self._shape(self.iter_std[i]), config) for i in range(niter)]
 
@@ -139,7 +142,21 @@ class Result:
         r = Result(self.iter_mean, self.iter_std, self.config, ignore, self.neval, self.seconds, self.block_mean, self.correlated, self.block)
         r.chain_bias = self.chain_bias
         r.stratification = self.stratification
+        r.vegas_check = self.vegas_check
         return r
+
+    @property
+    def vegas_check_note(self):
+        """the sentence report() prints under the tables when the :vegas self-check failed, or None"""
+        st = (self.vegas_check or (0, 0))[0]
+        if st >= 0:
+            return None
+        if st == -1:
+            return ("note: the :vegas sample kernel compiled for this integrand did not reproduce the library's static :vegas kernel on its "
+                    "self-check (a miscompiled code object); the run used the unit compiled again in the conservative layout -- plain loop, one "
+                    "histogram copy --, which agreed (mci_vegas_check_status = -1)")
+        return ("note: NO layout of the :vegas sample kernel compiled for this integrand reproduced the library's static :vegas kernel on its "
+                "self-check (mci_vegas_check_status = -2): the map may have adapted to a wrong histogram, do not trust these numbers")
 
     @property
     def chain_bias_note(self):
@@ -300,3 +317,5 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
                   file=io)
     if getattr(result, "chain_bias_note", None):   # (not in the reference)
         print("  " + result.chain_bias_note, file=io)
+    if getattr(result, "vegas_check_note", None):   # (not in the reference)
+        print("  " + result.vegas_check_note, file=io)

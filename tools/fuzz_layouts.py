@@ -5,7 +5,9 @@ Every case draws a layout (1-5 pools of Continuous / Discrete / CompositeVar, 1-
 2000 increments), a launch shape (blocks, steps per block, chains per block, measure cadence, iteration number) and a generator
 (Philox4x32-10 or -7), JIT-compiles the three sample-batch kernels for it and compares one iteration of each solver with the oracle on
 the same Philox streams: packed sums and histograms to 1e-9 relative, holding-time histogram bucket by bucket, then a three-iteration
-:vegas run with train! in between.  Failures are collected, not fatal.   usage: fuzz_layouts.py [--pipe | --persist | --carry | --walk] [--lanes] [first_case] [ncases]
+:vegas run with train! in between.  Failures are collected, not fatal.   usage: fuzz_layouts.py [--pipe | --persist | --carry | --walk] [--lanes] [--vegas-check] [first_case] [ncases]
+(--vegas-check: the self-check of every :vegas code object forced, marker or not -- override vegas_self_check 1, csrc/mci_debug.h --; the last
+line counts the engines per (status, flags) of mci_vegas_check_status, an alarm also shows on stderr as "does not reproduce")
 (--lanes, with the default and the --carry campaign: a random number of lanes per chain and a random speculation tree per case, csrc/mci_spec.h)
 (--pipe: layouts of the pipelined :vegas loop only; --persist: whole integrate() calls over one Continuous variable type run as ONE
 persistent launch, against the oracle's loop; --carry: four consecutive iterations of :vegasmc and :mcmc with carried chains -- :mcmc:
@@ -97,6 +99,21 @@ if __name__ == "__main__":
     if "--lanes" in sys.argv:     # a random group size and speculation tree per case (the default and the --carry campaign)
         sys.argv.remove("--lanes")
         os.environ["FUZZ_LANES"] = "1"
+    vegas_status = {}
+    if "--vegas-check" in sys.argv:   # the :vegas self-check forced on every case; statuses counted as the engines are closed
+        sys.argv.remove("--vegas-check")
+        from mcintegration_jl_amd._lib import check, lib
+        check(lib().mci_debug_override(b"vegas_self_check", 1, 1))
+        _close = mci.Engine.close
+
+        def _counting_close(self):
+            try:
+                st = self.vegas_check_status()
+                vegas_status[st] = vegas_status.get(st, 0) + 1
+            except Exception:
+                pass
+            return _close(self)
+        mci.Engine.close = _counting_close
     if "--walk" in sys.argv:      # serial walk with given decisions against its general form, deterministic runs, bit for bit
         sys.argv.remove("--walk")
         WALK_MODE = True
@@ -117,5 +134,6 @@ if __name__ == "__main__":
             print("FAIL case %d: %s" % (c, "".join(traceback.format_exception_only(type(e), e))[:3000]), flush=True)
     oracle.set_rng_rounds(10)
     print("%d cases, %d failed %s in %.0f s" % (n, len(bad), bad, time.time() - t0) + (" (%d ran as one persistent launch)" % npersist if PERSIST_MODE else "")
+          + (" (:vegas self-check forced: engines per (status, flags) %s)" % vegas_status if vegas_status else "")
           + (" (serial walks: %d as slots with given decisions, %d through the general form)" % (nslots, ngeneral) if WALK_MODE else ""))
     mci.shutdown()
