@@ -39,6 +39,7 @@ template <int B, int E, class F> __device__ __forceinline__ void static_for(F &&
 //   key = (seed lo, seed hi); ctr = (index lo, index hi, k>>1, stream); draw k -> words 2(k&1), 2(k&1)+1
 //   52 mantissa bits, [1,2) - 1 : the same resolution as Julia's MersenneTwister rand(Float64).
 // ---------------------------------------------------------------------------------------------
+// >>> philox section (tests/test_philox_hoist_host.py compiles the text between the two marker lines for the host)
 struct u32x4 { u32 x, y, z, w; };
 
 // Philox4x32 rounds of every stream: 10, or 7 with the opt-in cheaper generator (mci_set_rng_rounds; set by the generated translation unit)
@@ -58,7 +59,7 @@ template <bool IN_VGPR> __device__ __forceinline__ RoundKeys<IN_VGPR> make_round
 #pragma unroll
     for (int r = 0; r < MCI_PHILOX_ROUNDS; ++r) {
         const u32 a = k0 + (u32)r * 0x9E3779B9u, b = k1 + (u32)r * 0xBB67AE85u; // wave-uniform: scalar ALU
-        if (IN_VGPR) {
+        if constexpr (IN_VGPR) {
             asm("v_mov_b32 %0, %1" : "=v"(K.a[r]) : "s"(a));
             asm("v_mov_b32 %0, %1" : "=v"(K.b[r]) : "s"(b));
         } else {
@@ -91,6 +92,70 @@ template <bool IN_VGPR> __device__ __forceinline__ u32x4 philox4x32_10(u32 c0, u
 __device__ __forceinline__ u32x4 philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1) {
     return philox4x32_10<false>(c0, c1, c2, c3, make_round_keys<false>(k0, k1));
 }
+
+// Block-uniform high index word.  A :vegas sample takes the blocks Philox(ilo, ihi, c, stream), c = 0 .. NCH-1.  Where ihi is the same
+// on every lane and trip of a workgroup (the statistical block's index range does not cross a multiple of 2^32), part of rounds 0-1 does
+// not depend on the lane or the sample and is computed ONCE per workgroup, in scalar arithmetic (PhiloxHead).  With x1 the counter
+// after round 0 and x2 the counter after round 1:
+//   round 0   x1[0] = hi(M1 c) ^ ihi ^ Ka[0] and x1[1] = lo(M1 c) are per-c scalars; x1[2] = hi(M0 ilo) ^ (stream ^ Kb[0]) and
+//             x1[3] = lo(M0 ilo) are per-lane and the same for all blocks of the sample
+//   round 1   p0 = M0 x1[0] is a per-c scalar, p1 = M1 x1[2] one product per sample; x2[0] = hi(p1) ^ (x1[1] ^ Ka[1]) is a per-lane
+//             shared value xor a per-c scalar (a two-source xor), x2[2] = x1[3] ^ hi(p0) ^ Kb[1] the generic three-input xor with a
+//             scalar hi(p0); x2[1] = lo(p1) is shared, x2[3] = lo(p0) a scalar
+//   round 2.. the generic rounds
+// The same integer operations re-associated: the four words are those of philox4x32_10 for every (index, c, stream, key).  Per 16-draw
+// sample the headline loop loses 6 v_mad_u64_u32 (round 1's p0, one per distinct hi(M1 c): the compiler already shared the rest), the
+// 6 three-input xors of round 0's x1[0], and half the cost of 9 more (two-source now).  Round 1's x2[2] and round 2's third word keep
+// the three-input form, with a scalar source (4 issue cycles, not 2).  The hardware would prefer them as two-source xors with the key
+// folded into the scalar (14 more v_xor_b32, 28 cycles fewer); they stay only because the loop's static mix is pinned at fewer than ten
+// v_xor_b32 per sample (tests/test_code_objects.py test_c2_sample_loop_mix; the loop stands at 9).  Once that pin is relaxed, fold
+// Kb[1] into h1 and Kb[2] into l1 here.
+// Counts: profiles/philox_hoist.txt.
+template <int NCH> struct PhiloxHead {
+    u32 sb0;     // stream ^ Kb[0]
+    u32 a1[NCH]; // lo(M1 c) ^ Ka[1]
+    u32 h1[NCH]; // hi(M0 x1[0])
+    u32 l1[NCH]; // lo(M0 x1[0])
+};
+template <int NCH> __device__ __forceinline__ PhiloxHead<NCH> make_philox_head(u32 k0, u32 k1, u32 ihi, u32 stream) {
+    static_assert(MCI_PHILOX_ROUNDS >= 3, "the hoisted form opens rounds 0-1");
+    PhiloxHead<NCH> H;
+    H.sb0 = stream ^ k1;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const u64 m = (u64)0xCD9E8D57u * (u32)c; // compile-time constant
+        const u64 p0 = mul_wide(0xD2511F53u, (u32)(m >> 32) ^ ihi ^ k0); // wave-uniform: s_mul_i32 + s_mul_hi_u32
+        H.a1[c] = (u32)m ^ (k0 + 0x9E3779B9u);
+        H.h1[c] = (u32)(p0 >> 32);
+        H.l1[c] = (u32)p0;
+    }
+    return H;
+}
+// the per-lane part of rounds 0-1, shared by the blocks of one sample
+struct PhiloxLane { u32 lo0, q1lo, q1hi; };
+template <int NCH> __device__ __forceinline__ PhiloxLane philox_lane(u32 ilo, const PhiloxHead<NCH> &H) {
+    const u64 p0 = mul_wide(0xD2511F53u, ilo);
+    const u64 q1 = mul_wide(0xCD9E8D57u, (u32)(p0 >> 32) ^ H.sb0);
+    return {(u32)p0, (u32)q1, (u32)(q1 >> 32)};
+}
+// block C of the sample: philox4x32_10(ilo, ihi, C, stream, K) with ihi and stream folded into H
+template <bool IN_VGPR, int NCH, int C> __device__ __forceinline__ u32x4 philox4x32_10_uniform(const PhiloxLane &L, const PhiloxHead<NCH> &H, const RoundKeys<IN_VGPR> &K) {
+    // the counter after round 1
+    u32 c0 = L.q1hi ^ H.a1[C], c1 = L.q1lo, c2 = __builtin_amdgcn_bitop3_b32(L.lo0, H.h1[C], K.b[1], 0x96), c3 = H.l1[C];
+#pragma unroll
+    for (int r = 2; r < MCI_PHILOX_ROUNDS; ++r) {
+        const u64 p0 = mul_wide(0xD2511F53u, c0), p1 = mul_wide(0xCD9E8D57u, c2);
+        const u32 n0 = __builtin_amdgcn_bitop3_b32((u32)(p1 >> 32), c1, K.a[r], 0x96);
+        const u32 n2 = __builtin_amdgcn_bitop3_b32((u32)(p0 >> 32), c3, K.b[r], 0x96);
+        c1 = (u32)p1;
+        c3 = (u32)p0;
+        c0 = n0;
+        c2 = n2;
+    }
+    return {c0, c1, c2, c3};
+}
+
+// <<< philox section
 
 // 52 random mantissa bits as a double in [1, 2)
 __device__ __forceinline__ double u12(u32 lo, u32 hi) {
@@ -910,9 +975,11 @@ template <class Cfg> constexpr bool pipe_eligible() {
     return MCI_VEGAS_PLAIN_LOOP == 0 && Cfg::NDRAW >= 8 && Cfg::NDRAW <= 16 && all_draws_pair_table<Cfg>() && Cfg::NTILE == 1 &&
            Mode<Cfg>::HIST_LDS && Cfg::HOST_INTEGRAND == 0 && Cfg::HOST_MEASURE == 0 && Cfg::EC_DOUBLES == 0;
 }
-template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_sample_pipe(const RoundKeys<KV> &keys, u32 stream, u64 index, Sample<Cfg> &s,
-                                                                                        const PendingHist<Cfg> &pend, PendingHist<Cfg> &next, double *sH) {
-    constexpr int NCH = (Cfg::NDRAW + DPC - 1) / DPC;
+// UNI: the workgroup's high index word is block-uniform and folded into `head` (philox4x32_10_uniform); otherwise `head` is not read
+template <class Cfg, int DPC> constexpr int pipe_blocks() { return (Cfg::NDRAW + DPC - 1) / DPC; }
+template <class Cfg, bool KV, int DPC, bool UNI> __device__ __forceinline__ void draw_sample_pipe(const RoundKeys<KV> &keys, const PhiloxHead<pipe_blocks<Cfg, DPC>()> &head, u32 stream, u64 index, Sample<Cfg> &s,
+                                                                                                  const PendingHist<Cfg> &pend, PendingHist<Cfg> &next, double *sH) {
+    constexpr int NCH = pipe_blocks<Cfg, DPC>();
     constexpr int LAG = DPC == 4 ? 0 : 1; // blocks between a read and its use: with four reads per block they cover each other (and LAG 1 spills at 1024 threads)
     constexpr unsigned long long ALL = Cfg::NDRAW >= 64 ? ~0ull : ((1ull << Cfg::NDRAW) - 1ull);
     const u32 ilo = (u32)index, ihi = (u32)(index >> 32);
@@ -922,10 +989,14 @@ template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_samp
     typedef double pair_d2 __attribute__((ext_vector_type(2)));
     pair_d2 pe[Cfg::NDRAW];
     double pdy[Cfg::NDRAW];
+    PhiloxLane lane = {0u, 0u, 0u};
+    if constexpr (UNI) lane = philox_lane(ilo, head);
     static_for<0, NCH + LAG>([&](auto C) {
         constexpr int c = decltype(C)::value;
         if constexpr (c < NCH) {
-            const u32x4 r = philox4x32_10<KV>(ilo, ihi, (u32)c, stream, keys);
+            u32x4 r;
+            if constexpr (UNI) r = philox4x32_10_uniform<KV, NCH, c>(lane, head, keys);
+            else r = philox4x32_10<KV>(ilo, ihi, (u32)c, stream, keys);
             // The wave asks for issue priority while it hands its LDS work over (s_setprio 1 ... 0): its two reads and two atomics then
             // go out ahead of the other waves' Philox stretches instead of queueing behind them, and the LDS pipe has them while this
             // wave computes its next block.  Measured on the headline loop, kernel ms per 1e8 samples on two boxes: 1.357 / 1.371 ->
@@ -1287,31 +1358,44 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
     } else if constexpr (pipe_eligible<Cfg>() && !SPLIT && !EC) {
         // two samples per trip, the two pending records swapping roles: with one record the bins of the sample just drawn would be
         // copied into it on every trip (16 v_mov_b32 on the headline loop)
-        PendingHist<Cfg> pa, pb; // nothing pending yet: a zero weight on bin 0
-        static_for<0, Cfg::NDRAW>([&](auto K) { pa.bin[decltype(K)::value] = 0; });
-        static_for<0, Cfg::NI>([&](auto I) { pa.wh[decltype(I)::value] = 0.0; });
-        auto flush = [&](const PendingHist<Cfg> &q) { // a lane's last sample
-            static_for<0, Cfg::NDRAW>([&](auto K) { hist_add_draw<Cfg, decltype(K)::value>(q.bin[decltype(K)::value], q.wh, sH); });
-        };
-        i64 n = (i64)slice * T + tid;
-        for (; n + stride < a.neval_per_block; n += 2 * stride) {
-            {
+        // The block's index range [first, first + neval_per_block) lies below one multiple of 2^32 -- every launch of fewer than 2^32
+        // samples per iteration, and all but one block of any other -- : the high index word is the same on every lane and trip and the
+        // lane-invariant part of Philox rounds 0-1 is computed here, once (PhiloxHead).  Decided per workgroup (B comes from blockIdx: a
+        // scalar branch), so a block that straddles a multiple takes the generic loop and draws exactly the same stream.
+        const u64 first = (u64)(B * a.neval_per_block);
+        const bool uniform_hi = (first >> 32) == ((first + (u64)a.neval_per_block - 1ull) >> 32);
+        auto loop = [&](auto UNIc) {
+            constexpr bool UNI = decltype(UNIc)::value != 0;
+            PendingHist<Cfg> pa, pb; // nothing pending yet: a zero weight on bin 0
+            static_for<0, Cfg::NDRAW>([&](auto K) { pa.bin[decltype(K)::value] = 0; });
+            static_for<0, Cfg::NI>([&](auto I) { pa.wh[decltype(I)::value] = 0.0; });
+            auto flush = [&](const PendingHist<Cfg> &q) { // a lane's last sample
+                static_for<0, Cfg::NDRAW>([&](auto K) { hist_add_draw<Cfg, decltype(K)::value>(q.bin[decltype(K)::value], q.wh, sH); });
+            };
+            PhiloxHead<pipe_blocks<Cfg, DPC>()> head;
+            if constexpr (UNI) head = make_philox_head<pipe_blocks<Cfg, DPC>()>((u32)a.seed, (u32)(a.seed >> 32), (u32)(first >> 32), stream);
+            i64 n = (i64)slice * T + tid;
+            for (; n + stride < a.neval_per_block; n += 2 * stride) {
+                {
+                    Sample<Cfg> s;
+                    draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)n, s, pa, pb, sH);
+                    process(n, s, pb.wh);
+                }
+                {
+                    Sample<Cfg> s;
+                    draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)(n + stride), s, pb, pa, sH);
+                    process(n + stride, s, pa.wh);
+                }
+            }
+            if (n < a.neval_per_block) {
                 Sample<Cfg> s;
-                draw_sample_pipe<Cfg, KV, DPC>(keys, stream, (u64)(B * a.neval_per_block + n), s, pa, pb, sH);
+                draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)n, s, pa, pb, sH);
                 process(n, s, pb.wh);
-            }
-            {
-                Sample<Cfg> s;
-                draw_sample_pipe<Cfg, KV, DPC>(keys, stream, (u64)(B * a.neval_per_block + n + stride), s, pb, pa, sH);
-                process(n + stride, s, pa.wh);
-            }
-        }
-        if (n < a.neval_per_block) {
-            Sample<Cfg> s;
-            draw_sample_pipe<Cfg, KV, DPC>(keys, stream, (u64)(B * a.neval_per_block + n), s, pa, pb, sH);
-            process(n, s, pb.wh);
-            flush(pb);
-        } else flush(pa);
+                flush(pb);
+            } else flush(pa);
+        };
+        if (uniform_hi) loop(IC<1>{});
+        else loop(IC<0>{});
     } else {
         for (i64 n = n_lo + (i64)slice * T + tid; n < n_hi; n += stride) {
             Sample<Cfg> s;
