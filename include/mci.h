@@ -276,7 +276,10 @@ int mci_set_reweight_goal(mci_problem *prob, const double *goal, int32_t n); /* 
 int mci_get_acceptance(mci_problem *prob, double *propose, double *accept, int32_t n);
 /* resume across processes: what train!/doReweight! have learned -- grids, distributions, reweight --
  * as a small self-describing binary file ("MCISTATE", version 1).  The reference keeps this state only in memory
- * (`config = res.config`, docs/src/index.md:129). */
+ * (`config = res.config`, docs/src/index.md:129).  A stratified problem that carries its allocation (mci_set_stratification_carry)
+ * and holds a d_h writes version 2: the version-1 body, then the plan, beta and one double per hypercube -- up to 128 MB at the default
+ * cap of 2^24 hypercubes.  Loading accepts both versions; the d_h of a version-2 file is kept for the next stratified run of a carrying
+ * problem (a file whose plan has another number of draws than the problem is refused), a version-1 file leaves none. */
 int mci_save_state(mci_problem *prob, const char *path);
 int mci_load_state(mci_problem *prob, const char *path);
 /* Opt-in cheaper uniform stream of solver = :vegas: bits = 52 (default) draws every uniform with 52 random mantissa bits, the resolution
@@ -335,8 +338,22 @@ int mci_set_chain_carry(mci_problem *prob, int32_t mode);
  * prod nstrat <= N/2 is required (an explicit plan of about two samples per hypercube under-reports the error on heavy tails).  Refused (MCI_ERR_INVALID, naming the reason): Discrete or FermiK variables, a user measure, a host
  * integrand, several histogram tiles or histograms outside LDS, more than one rank, more than 32 draws or 8 columns; at run time a
  * solver other than :vegas and measurefreq != 1.  The persistent :vegas launch is never taken.  The allocation starts uniform in
- * every mci_integrate call and whenever the plan changes; it is not part of mci_save_state. */
+ * every mci_integrate call and whenever the plan changes, and is not part of mci_save_state, unless the problem carries it
+ * (mci_set_stratification_carry). */
 int mci_set_stratification(mci_problem *prob, int32_t ndim, const int32_t *nstrat, double beta, int64_t max_nhcube);
+/* Carry the allocation (default 0: every call starts uniform).  With on = 1 the d_h = (sum of the hypercube's variances)^(beta/2) of
+ * the last finished stratified iteration -- or of a loaded version-2 state file -- stays with the problem, together with the plan and
+ * the beta it was measured under, and the first allocation of the next call (or of the next mci_iteration_run after the plan, N or a
+ * setting changed) is made from it: as it is when plan and beta are the same (any N >= 2 prod nstrat), else moved onto the new plan --
+ * every new hypercube takes the value of the old hypercube that holds its centre, cell by cell i = floor((2 j + 1) n / (2 n')) in
+ * integers -- and raised to beta_new / beta_old.  A beta of 0 on either side starts uniform.  mci_set_stratification keeps a carried
+ * d_h (call this setter first), mci_set_stratification_off drops it.  With adapt = 0 a call keeps the allocation it started with, which
+ * is then the carried one: train with a small neval, then measure with adapt = 0 and a large one.  Any allocation with n_h >= 2 gives an
+ * unbiased estimate: a carried start changes the error, never what is estimated. */
+int mci_set_stratification_carry(mci_problem *prob, int32_t on);
+/* on: the setting; how: where the last first-allocation came from -- 0 uniform, 1 the carried d_h on its own plan, 2 remapped from
+ * another plan or beta */
+int mci_get_strat_carry(const mci_problem *prob, int32_t *on, int32_t *how);
 /* back to plain :vegas (the same kernels and numbers as a problem that was never stratified) */
 int mci_set_stratification_off(mci_problem *prob);
 /* the plan in use: nstrat[ndim] (zeros before the first stratified run of a default plan), ncube (0: off or not planned yet), beta */

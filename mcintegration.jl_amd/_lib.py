@@ -112,6 +112,8 @@ SIGNATURES = [
     ("mci_last_chain_launch", C.c_int, [_VP, C.POINTER(C.c_int64), c_int32_p]),
     ("mci_set_stratification", C.c_int, [_VP, C.c_int32, c_int32_p, C.c_double, C.c_int64]),
     ("mci_set_stratification_off", C.c_int, [_VP]),
+    ("mci_set_stratification_carry", C.c_int, [_VP, C.c_int32]),
+    ("mci_get_strat_carry", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_get_stratification", C.c_int, [_VP, c_int32_p, C.POINTER(C.c_int64), c_double_p]),
     ("mci_get_strat_counts", C.c_int, [_VP, C.POINTER(C.c_int64), C.c_int64]),
     ("mci_strat_plan", C.c_int, [C.c_int64, C.c_int32, C.c_int64, c_int32_p]),
@@ -156,6 +158,7 @@ DEBUG_SIGNATURES = [
     ("mci_debug_compiler_id", C.c_int, [C.c_char_p, C.c_char_p, C.c_int32]),
     ("mci_debug_split_chunks", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("mci_debug_strat_d", C.c_int, [_VP, c_double_p, C.c_int64]),
+    ("mci_debug_strat_start_d", C.c_int, [_VP, c_double_p, C.c_int64]),
     ("mci_debug_strat_dump", C.c_int, [_VP, C.c_int64, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
     ("mci_debug_mcmc_policy", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     ("mci_debug_vegas_check", C.c_int, [_VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -47,6 +47,10 @@ int mci_debug_strat_dump(mci_problem *prob, int64_t n, double *x, double *y, int
 /* test hook: d[n] = the damped weights d_h = (sum_k s^2_{h,k})^(beta/2) the last finished stratified iteration wrote (what the next
  * allocation is made from); n must be the plan's hypercube count, call it after mci_iteration_finish.  Synchronises the stream. */
 int mci_debug_strat_d(mci_problem *prob, double *d, int64_t n);
+/* test hook: the NEXT first allocation of a stratified run (a call's first iteration, a new plan or N) also leaves the d_h it is made
+ * from -- the carried values as they are, remapped or raised to the new beta (mci_set_stratification_carry); ones for a uniform start --
+ * in d[n]; n must be that plan's hypercube count.  The run synchronises.  n = 0 takes it back. */
+int mci_debug_strat_start_d(mci_problem *prob, double *d, int64_t n);
 /* what mci_jit.h puts into the kernel-cache key for "which compiler made this code object" (hiprtc version, the files of libhiprtc and
  * libamd_comgr, the target): set != NULL overrides it for this process ("" takes the override back); out: the identity in force */
 int mci_debug_compiler_id(const char *set, char *out, int32_t n);

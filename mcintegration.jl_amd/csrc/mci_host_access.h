@@ -157,15 +157,30 @@ int mci_set_reweight_goal(mci_problem *p, const double *goal, int32_t n) {
 // `train!` and `doReweight!` have learned: grids, distributions, reweight.
 //   "MCISTATE" | u32 version | u32 nleaf | u32 ni | per leaf: u32 kind, u32 n | f64 reweight[ni+1] |
 //   per leaf: f64 grid[n]  (Continuous)  or  f64 distribution[n]  (Discrete)
+// Version 2 -- written by a stratified problem that carries its allocation and holds a d_h (mci_set_stratification_carry), and by no
+// other -- is the version-1 body followed by the carried allocation:
+//   u32 ndim | u32 nstrat[ndim] | u64 ncube | f64 beta | f64 d_h[ncube]
 // ---------------------------------------------------------------------------------------------------
 int mci_save_state(mci_problem *p, const char *path) {
     if (!p || !path) return fail(MCI_ERR_INVALID, "NULL argument");
     std::vector<double> rw(p->ni + 1);
     int rc = mci_get_reweight(p, rw.data(), p->ni + 1);
     if (rc) return rc;
+    auto &st = p->strat;
+    const bool carried = st.on && st.carry && st.c_valid && !st.last_run;
+    std::vector<double> dh;
+    if (carried) {
+        if (!st.c_host.empty()) dh = st.c_host; // (loaded, not run since)
+        else {
+            dh.resize((size_t)st.c_ncube);
+            HIPCHK(hipSetDevice(p->ctx->device));
+            HIPCHK(hipMemcpyAsync(dh.data(), st.d_d, dh.size() * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+            HIPCHK(hipStreamSynchronize(p->ctx->stream));
+        }
+    }
     FILE *f = fopen(path, "wb");
     if (!f) return fail(MCI_ERR_INVALID, "cannot open %s for writing", path);
-    const uint32_t hdr[3] = {1u, (uint32_t)p->leaves.size(), (uint32_t)p->ni};
+    const uint32_t hdr[3] = {carried ? 2u : 1u, (uint32_t)p->leaves.size(), (uint32_t)p->ni};
     bool ok = fwrite("MCISTATE", 1, 8, f) == 8 && fwrite(hdr, sizeof(uint32_t), 3, f) == 3;
     for (auto &L : p->leaves) { // (a FermiK leaf has nothing trained: header entry only, n = 0)
         const uint32_t kn[2] = {(uint32_t)L.kind, (uint32_t)(L.kind == MCI_CONTINUOUS ? L.npts : L.kind == MCI_DISCRETE ? L.nbin : 0)};
@@ -181,6 +196,14 @@ int mci_save_state(mci_problem *p, const char *path) {
         if (rc) { fclose(f); return rc; }
         ok = fwrite(v.data(), sizeof(double), (size_t)n, f) == (size_t)n;
     }
+    if (carried && ok) {
+        std::vector<uint32_t> plan(1 + st.c_nstrat.size());
+        plan[0] = (uint32_t)st.c_nstrat.size();
+        for (size_t d = 0; d < st.c_nstrat.size(); ++d) plan[1 + d] = (uint32_t)st.c_nstrat[d];
+        const uint64_t nc = (uint64_t)st.c_ncube;
+        ok = fwrite(plan.data(), sizeof(uint32_t), plan.size(), f) == plan.size() && fwrite(&nc, sizeof(nc), 1, f) == 1 &&
+             fwrite(&st.c_beta, sizeof(double), 1, f) == 1 && fwrite(dh.data(), sizeof(double), dh.size(), f) == dh.size();
+    }
     ok = (fclose(f) == 0) && ok;
     return ok ? MCI_OK : fail(MCI_ERR_INVALID, "short write to %s", path);
 }
@@ -191,9 +214,9 @@ int mci_load_state(mci_problem *p, const char *path) {
     if (!f) return fail(MCI_ERR_INVALID, "cannot open %s", path);
     char magic[8];
     uint32_t hdr[3];
-    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "MCISTATE", 8) || fread(hdr, sizeof(uint32_t), 3, f) != 3 || hdr[0] != 1u) {
+    if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "MCISTATE", 8) || fread(hdr, sizeof(uint32_t), 3, f) != 3 || (hdr[0] != 1u && hdr[0] != 2u)) {
         fclose(f);
-        return fail(MCI_ERR_INVALID, "%s is not a version-1 MCISTATE file", path);
+        return fail(MCI_ERR_INVALID, "%s is not a version-1 or version-2 MCISTATE file", path);
     }
     if (hdr[1] != p->leaves.size() || hdr[2] != (uint32_t)p->ni) {
         fclose(f);
@@ -216,8 +239,51 @@ int mci_load_state(mci_problem *p, const char *path) {
         tabs[l].resize(L.kind == MCI_CONTINUOUS ? L.npts : L.kind == MCI_DISCRETE ? L.nbin : 0);
         ok = fread(tabs[l].data(), sizeof(double), tabs[l].size(), f) == tabs[l].size();
     }
+    // version 2: the carried allocation of a stratified problem
+    std::vector<int> c_nstrat;
+    std::vector<double> c_d;
+    double c_beta = 0.0;
+    if (ok && hdr[0] == 2u) {
+        uint32_t ndim = 0;
+        ok = fread(&ndim, sizeof(uint32_t), 1, f) == 1;
+        if (ok && ndim != (uint32_t)p->shape.ndraw) {
+            fclose(f);
+            return fail(MCI_ERR_INVALID, "%s: the carried allocation has ndim = %u, a sample of the problem has %d draws", path, ndim, p->shape.ndraw);
+        }
+        std::vector<uint32_t> ns(ndim);
+        uint64_t nc = 0, prod = 1;
+        ok = ok && fread(ns.data(), sizeof(uint32_t), ndim, f) == ndim && fread(&nc, sizeof(nc), 1, f) == 1 && fread(&c_beta, sizeof(double), 1, f) == 1;
+        for (uint32_t d = 0; ok && d < ndim; ++d) {
+            prod = ns[d] >= 1 && prod <= (((uint64_t)1 << 31) - 1) / ns[d] ? prod * ns[d] : 0; // (0: no plan of this library)
+            c_nstrat.push_back((int)ns[d]);
+        }
+        if (ok && (prod == 0 || prod != nc || !(c_beta >= 0.0) || !std::isfinite(c_beta))) {
+            fclose(f);
+            return fail(MCI_ERR_INVALID, "%s: the carried allocation's plan does not match its ncube = %llu (prod nstrat = %llu, beta = %g)", path,
+                        (unsigned long long)nc, (unsigned long long)prod, c_beta);
+        }
+        if (ok) {
+            c_d.resize((size_t)nc);
+            ok = fread(c_d.data(), sizeof(double), c_d.size(), f) == c_d.size();
+        }
+        // (k_strat_alloc's n_h >= 2 -- which the sample kernel's LDS carve relies on -- needs non-negative addends)
+        for (size_t h = 0; ok && h < c_d.size(); ++h)
+            if (!(c_d[h] >= 0.0) || !std::isfinite(c_d[h])) {
+                fclose(f);
+                return fail(MCI_ERR_INVALID, "%s: d_h[%zu] = %g of the carried allocation is negative or not finite", path, h, c_d[h]);
+            }
+    }
     fclose(f);
     if (!ok) return fail(MCI_ERR_INVALID, "%s is truncated", path);
+    {   // the file's d_h, or none (version 1), replaces what the problem carried
+        auto &st = p->strat;
+        st.c_valid = !c_d.empty();
+        st.c_host = std::move(c_d);
+        st.c_nstrat = c_nstrat;
+        st.c_ncube = (int64_t)st.c_host.size();
+        st.c_beta = c_beta;
+        if (st.carry) st.alloc_valid = st.alloc_pending = false; // (the next run starts its allocation again, from the file's d_h)
+    }
     int rc = mci_set_reweight(p, rw.data(), p->ni + 1);
     for (size_t l = 0; l < p->leaves.size() && !rc; ++l)
         if (p->leaves[l].kind != MCI_FERMIK)

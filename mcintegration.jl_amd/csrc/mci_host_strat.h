@@ -89,7 +89,134 @@ int strat_launch_alloc(mci_problem *p, bool uniform) {
     return MCI_OK;
 }
 
-// the plan for N samples per iteration; buffers sized for it; a new plan starts uniform
+// h / n = (h * magic) >> shift, exact for h < 2^31 (Granlund-Montgomery, N = 31): the reciprocals the sample kernel decodes a hypercube
+// into its cells with (StratArgs) and k_strat_remap a new hypercube into its
+void strat_magic(uint32_t n, uint32_t *magic, int *shift) {
+    int l = 0;
+    while (((uint64_t)1 << l) < n) ++l;
+    // h < 2^31: q = floor(h * m / 2^(32 + l)), m = ceil(2^(32 + l) / n) < 2^33 ... kept in 32 bits by folding one bit into the shift
+    // for l <= 31: m' = ceil(2^(31 + l) / n) <= 2^32 and q = (h * m') >> (31 + l), exact for h < 2^31
+    const uint64_t m = (((uint64_t)1 << (31 + l)) + n - 1) / n;
+    *magic = (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m);
+    *shift = 31 + l;
+    if (n == 1) { // (h / 1: m' = 2^31, shift 31)
+        *magic = 0x80000000u;
+        *shift = 31;
+    }
+}
+
+// d_off / d_d with room for ncube hypercubes (what they held is gone when they grow)
+int strat_reserve(mci_problem *p, int64_t ncube) {
+    auto &st = p->strat;
+    if (!st.d_tsum) HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
+    if (ncube <= st.cap_cube) return MCI_OK;
+    for (void *q : {(void *)st.d_off, (void *)st.d_d})
+        if (q) (void)hipFree(q);
+    st.d_off = nullptr;
+    st.d_d = nullptr;
+    st.cap_cube = 0;
+    HIPCHK(hipMalloc((void **)&st.d_off, (size_t)(ncube + 1) * sizeof(long long)));
+    HIPCHK(hipMalloc((void **)&st.d_d, (size_t)ncube * sizeof(double)));
+    HIPCHK(hipMemsetAsync(st.d_d, 0, (size_t)ncube * sizeof(double), p->ctx->stream));
+    st.cap_cube = ncube;
+    return MCI_OK;
+}
+
+// The first allocation of plan ns for N samples (a call starts, the plan or N changed, a setter was called): uniform -- or, on a problem
+// that carries its allocation (mci_set_stratification_carry) and holds a d_h, from that d_h: as it is on the plan and under the beta it
+// was measured with, else moved onto this plan and this beta by k_strat_remap.  beta = 0 on either side (nothing learned | an even
+// allocation is asked for) starts uniform.
+int strat_start_alloc(mci_problem *p, const std::vector<int> &ns, int64_t ncube, int64_t N) {
+    auto &st = p->strat;
+    const int D = (int)ns.size();
+    const bool have = st.carry && st.c_valid && (int)st.c_nstrat.size() == D && st.c_beta > 0.0 && st.beta > 0.0;
+    const bool same = have && st.c_nstrat == ns && st.c_beta == st.beta;
+    const bool waiting = !st.c_host.empty(); // (the values of a state file, not on the device yet)
+    int rc;
+    if (!have) {
+        if (st.c_host.empty() && st.c_nstrat != ns) st.c_valid = false; // (d_d is about to hold another plan's values)
+        if ((rc = strat_reserve(p, ncube))) return rc;
+        st.carry_how = 0;
+    } else if (same) {
+        if (waiting) {
+            if ((rc = strat_reserve(p, ncube))) return rc;
+            HIPCHK(hipMemcpyAsync(st.d_d, st.c_host.data(), (size_t)ncube * sizeof(double), hipMemcpyHostToDevice, p->ctx->stream));
+            HIPCHK(hipStreamSynchronize(p->ctx->stream));
+        }
+        st.carry_how = 1;
+    } else {
+        // new buffers first, old -> new, then the old ones go (hipFree waits for the kernel)
+        double *src = st.d_d, *upload = nullptr, *d_new = nullptr;
+        long long *off_new = nullptr;
+        if (!st.d_tsum) HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
+        if (waiting) {
+            HIPCHK(hipMalloc((void **)&upload, (size_t)st.c_ncube * sizeof(double)));
+            if (hipMemcpyAsync(upload, st.c_host.data(), (size_t)st.c_ncube * sizeof(double), hipMemcpyHostToDevice, p->ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(p->ctx->stream) != hipSuccess) {
+                (void)hipFree(upload);
+                return fail(MCI_ERR_HIP, "stratification: the carried d_h could not be copied to the device");
+            }
+            src = upload;
+        }
+        if (hipMalloc((void **)&off_new, (size_t)(ncube + 1) * sizeof(long long)) != hipSuccess ||
+            hipMalloc((void **)&d_new, (size_t)ncube * sizeof(double)) != hipSuccess) {
+            for (void *q : {(void *)upload, (void *)off_new, (void *)d_new})
+                if (q) (void)hipFree(q);
+            return fail(MCI_ERR_HIP, "stratification: no device memory for %lld hypercubes", (long long)ncube);
+        }
+        mci::StratRemapArgs a{};
+        a.d_old = src;
+        a.d_new = d_new;
+        a.ncube = ncube;
+        a.ndim = D;
+        a.e = st.beta / st.c_beta;
+        for (int d = 0; d < D; ++d) {
+            strat_magic((uint32_t)ns[d], &a.magic[d], &a.shift[d]);
+            a.n_new[d] = ns[d];
+            a.n_old[d] = st.c_nstrat[d];
+        }
+        const unsigned grid = (unsigned)((ncube + 255) / 256 < 4096 ? (ncube + 255) / 256 : 4096);
+        hipLaunchKernelGGL(mci::k_strat_remap, dim3(grid), dim3(256), 0, p->ctx->stream, a);
+        const hipError_t launched = hipGetLastError();
+        for (void *q : {(void *)upload, (void *)st.d_off, (void *)st.d_d})
+            if (q) (void)hipFree(q);
+        st.d_off = off_new;
+        st.d_d = d_new;
+        st.cap_cube = ncube;
+        if (launched != hipSuccess) {
+            st.c_valid = false;
+            st.c_host.clear();
+            st.nstrat.clear(); // (re-planned, uniform, at the next run)
+            return fail(MCI_ERR_HIP, "stratification: k_strat_remap: %s", hipGetErrorString(launched));
+        }
+        st.carry_how = 2;
+    }
+    st.nstrat = ns;
+    st.ncube = ncube;
+    st.nsamp = N;
+    if (have) { // d_d now holds the carried values on THIS plan, under this beta
+        st.c_host.clear();
+        st.c_host.shrink_to_fit();
+        st.c_nstrat = ns;
+        st.c_ncube = ncube;
+        st.c_beta = st.beta;
+    }
+    if (st.hstart) { // test hook (mci_debug_strat_start_d)
+        double *out = st.hstart;
+        const int64_t n = st.hstart_n;
+        st.hstart = nullptr;
+        st.hstart_n = 0;
+        if (n != ncube) return fail(MCI_ERR_INVALID, "mci_debug_strat_start_d: %lld values asked for, the plan has %lld hypercubes", (long long)n, (long long)ncube);
+        if (have) {
+            HIPCHK(hipMemcpyAsync(out, st.d_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+            HIPCHK(hipStreamSynchronize(p->ctx->stream));
+        } else
+            for (int64_t h = 0; h < n; ++h) out[h] = 1.0;
+    }
+    return strat_launch_alloc(p, !have);
+}
+
+// the plan for N samples per iteration; buffers sized for it; a new plan starts uniform, or from the carried d_h (strat_start_alloc)
 int strat_prepare(mci_problem *p, int64_t N) {
     auto &st = p->strat;
     const int D = p->shape.ndraw;
@@ -105,26 +232,9 @@ int strat_prepare(mci_problem *p, int64_t N) {
     }
     if (ncube > N / 2) return fail(MCI_ERR_INVALID, "stratification: %lld hypercubes need at least %lld samples per iteration (two each), neval = %lld",
                                    (long long)ncube, (long long)(2 * ncube), (long long)N);
-    if (ns != st.nstrat || N != st.nsamp) {
-        st.nstrat = ns;
-        st.ncube = ncube;
-        st.nsamp = N;
-        st.alloc_valid = false;
-        st.ran = false;
-        if (ncube > st.cap_cube) {
-            for (void *q : {(void *)st.d_off, (void *)st.d_d, (void *)st.d_tsum})
-                if (q) (void)hipFree(q);
-            st.d_off = nullptr;
-            st.d_d = st.d_tsum = nullptr;
-            st.cap_cube = 0;
-            HIPCHK(hipMalloc((void **)&st.d_off, (size_t)(ncube + 1) * sizeof(long long)));
-            HIPCHK(hipMalloc((void **)&st.d_d, (size_t)ncube * sizeof(double)));
-            HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
-            HIPCHK(hipMemsetAsync(st.d_d, 0, (size_t)ncube * sizeof(double), p->ctx->stream));
-            st.cap_cube = ncube;
-        }
-    }
-    if (!st.alloc_valid) return strat_launch_alloc(p, true);
+    const bool replan = ns != st.nstrat || N != st.nsamp;
+    if (replan) st.ran = false;
+    if (replan || !st.alloc_valid) return strat_start_alloc(p, ns, ncube, N);
     if (st.alloc_pending) return strat_launch_alloc(p, false);
     return MCI_OK;
 }
@@ -178,10 +288,17 @@ int mci_set_stratification(mci_problem *p, int32_t ndim, const int32_t *nstrat, 
         }
     }
     auto &st = p->strat;
+    const bool keep = st.carry && st.c_valid && !st.last_run; // a carrying problem keeps its d_h, with the plan and beta it belongs to
     st.on = true;
     st.want = want;
     st.beta = beta;
     st.max_nhcube = max_nhcube;
+    if (keep) { // (the next run starts its allocation from it: strat_start_alloc)
+        st.alloc_valid = st.alloc_pending = false;
+        return MCI_OK;
+    }
+    st.c_valid = false;
+    st.c_host.clear();
     st.nstrat.clear(); // (re-planned, and the allocation started uniform, at the next run)
     st.nsamp = 0;
     st.ncube = 0;
@@ -197,10 +314,27 @@ int mci_set_stratification_off(mci_problem *p) {
     st.on = false;
     st.want.clear();
     st.nstrat.clear();
+    st.c_valid = false; // (the carried d_h goes too)
+    st.c_host.clear();
+    st.carry_how = 0;
     st.ncube = st.nsamp = 0;
     st.alloc_valid = st.alloc_pending = false;
     st.last_run = false;
     st.ran = false;
+    return MCI_OK;
+}
+
+int mci_set_stratification_carry(mci_problem *p, int32_t on) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (on != 0 && on != 1) return fail(MCI_ERR_INVALID, "stratification: carry must be 0 or 1");
+    p->strat.carry = on != 0;
+    return MCI_OK;
+}
+
+int mci_get_strat_carry(const mci_problem *p, int32_t *on, int32_t *how) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (on) *on = p->strat.carry ? 1 : 0;
+    if (how) *how = p->strat.on ? p->strat.carry_how : 0;
     return MCI_OK;
 }
 
@@ -252,7 +386,14 @@ int mci_debug_strat_d(mci_problem *p, double *d, int64_t n) {
     return MCI_OK;
 }
 
-// every stratified allocation of a call starts uniform (mci_integrate)
+int mci_debug_strat_start_d(mci_problem *p, double *d, int64_t n) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    p->strat.hstart = n > 0 ? d : nullptr;
+    p->strat.hstart_n = n > 0 && d ? n : 0;
+    return MCI_OK;
+}
+
+// every stratified allocation of a call starts afresh (mci_integrate): uniform, or from the carried d_h (strat_start_alloc)
 static void strat_call_start(mci_problem *p) { p->strat.alloc_valid = p->strat.alloc_pending = false; }
 
 // One stratified :vegas iteration's sample launch + the histogram merge (mci_iteration_run's :vegas path for a stratified problem).
@@ -344,19 +485,9 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     sa.beta = st.beta;
     for (int d = 0; d < s.ndraw; ++d) {
         const uint32_t n = (uint32_t)st.nstrat[d];
-        int l = 0;
-        while (((uint64_t)1 << l) < n) ++l;
-        // h < 2^31: q = floor(h * m / 2^(32 + l)), m = ceil(2^(32 + l) / n) < 2^33 ... kept in 32 bits by folding one bit into the shift
-        // for l <= 31: m' = ceil(2^(31 + l) / n) <= 2^32 and q = (h * m') >> (31 + l), exact for h < 2^31 (Granlund-Montgomery, N = 31)
-        const uint64_t m = (((uint64_t)1 << (31 + l)) + n - 1) / n;
-        sa.magic[d] = (uint32_t)(m > 0xFFFFFFFFull ? 0xFFFFFFFFull : m);
-        sa.shift[d] = 31 + l;
+        strat_magic(n, &sa.magic[d], &sa.shift[d]);
         sa.nstrat[d] = (int)n;
         sa.inv[d] = 1.0 / (double)n;
-        if (n == 1) { // (h / 1: m' = 2^31, shift 31)
-            sa.magic[d] = 0x80000000u;
-            sa.shift[d] = 31;
-        }
     }
     struct Scratch {
         void *q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -456,6 +587,12 @@ static int strat_finish(mci_problem *p, double *row, int32_t adapt) {
     hipLaunchKernelGGL(mci::k_strat_reduce, dim3(1), dim3(mci::kStratReduceThreads), 0, p->ctx->stream, r);
     HIPCHK(hipGetLastError());
     st.alloc_pending = adapt != 0; // (adapt = false: the allocation the call started with stays)
+    // d_d is now the d_h of a finished iteration of this plan: what a carrying problem starts its next call from
+    st.c_valid = true;
+    st.c_host.clear();
+    if (st.c_nstrat != st.nstrat) st.c_nstrat = st.nstrat;
+    st.c_ncube = st.ncube;
+    st.c_beta = st.beta;
     return MCI_OK;
 }
 

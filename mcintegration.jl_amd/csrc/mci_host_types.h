@@ -326,7 +326,7 @@ struct mci_problem {
     } launch;
     static_assert(std::is_trivially_copyable<LaunchState>::value, "the launch record holds values only");
     // Stratified :vegas (VEGAS+, mci_set_stratification; mci_strat.h, mci_host_strat.h).  Not part of `config`: a problem keeps the map
-    // it trained, the allocation starts uniform in every mci_integrate call.
+    // it trained; the allocation starts uniform in every mci_integrate call unless the problem carries it (mci_set_stratification_carry).
     struct Strat {
         bool on = false;
         std::vector<int> want;        // nstrat the caller asked for, empty = the default plan (mci_strat_plan)
@@ -339,6 +339,16 @@ struct mci_problem {
         bool alloc_valid = false;     // d_off holds an allocation for this plan (else the next run starts uniform)
         bool alloc_pending = false;   // the next run first turns the d_h the last iteration measured into d_off (adapt)
         double *d_d = nullptr;        // [ncube] d_h of the next allocation
+        // Carry (mci_set_stratification_carry): the d_h of the last finished iteration, or of a state file, with the plan and the beta it
+        // was measured under.  c_host empty: the values are d_d's (c_nstrat is then the plan d_d is laid out for); else they wait here
+        // for the next run (mci_load_state).  Kept up to date whether or not `carry` is on; consulted only when it is.
+        bool carry = false;
+        bool c_valid = false;
+        std::vector<int> c_nstrat;
+        int64_t c_ncube = 0;
+        double c_beta = 0.0;
+        std::vector<double> c_host;
+        int carry_how = 0;            // the last start of an allocation: 0 uniform | 1 from the carried d_h on its own plan | 2 remapped
         double *d_tsum = nullptr;     // k_strat_alloc scratch
         int64_t cap_cube = 0;
         double *d_part = nullptr, *d_rec_s = nullptr, *d_stat = nullptr;
@@ -354,6 +364,9 @@ struct mci_problem {
         double *hx = nullptr, *hy = nullptr, *hjac = nullptr, *hw = nullptr;
         long long *hh = nullptr;
         int64_t hn = 0;
+        // test hook (mci_debug_strat_start_d): host buffer the next start of an allocation copies the d_h it allocates from into
+        double *hstart = nullptr;
+        int64_t hstart_n = 0;
     } strat;
 };
 

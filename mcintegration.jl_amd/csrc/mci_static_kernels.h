@@ -310,6 +310,57 @@ __global__ void __launch_bounds__(256) k_strat_alloc(StratAllocArgs a, int phase
     }
 }
 
+// k_strat_remap: a carried d_h (mci_set_stratification_carry) moved from the plan it was measured on to another plan of the same
+// draws, and from the beta it was measured under to another: d'[h'] = d[h]^e, e = beta_new / beta_old, h = the old hypercube that holds
+// the CENTRE of new hypercube h'.  Per draw, new cell j of n' sits in old cell i = floor((2 j + 1) n / (2 n')) of n -- integers only, so
+// a centre that falls on an old cell's edge (n = 2, n' = 3, j = 1: 6 / 6 -> 1, the upper cell) is decided the same way on every machine.  The values
+// are NOT rescaled by the refinement factor: the allocation is proportional to d_h / sum d, and copying a parent's value to each of its
+// m children keeps every family's share of the samples (m d / (m sum) = d / sum); where the plans do not nest the shares move by the
+// cells' overlap, which is what a warm start may do -- any allocation with n_h >= 2 gives an unbiased estimate.  e == 1 copies the bits.
+// One thread per NEW hypercube on a grid-stride loop, the mixed-radix decode (draw 0 fastest) by the magic reciprocals the sample kernel
+// divides with (strat_magic, mci_host_strat.h); plain loads and stores, no LDS.
+// >>> strat remap cell rule (compiled for the host by tests/test_strat_carry_host.py)
+__host__ __device__ inline int strat_remap_cell(int j, int n_old, int n_new) {
+    return (int)(((2ull * (unsigned long long)j + 1ull) * (unsigned long long)n_old) / (2ull * (unsigned long long)n_new));
+}
+// old hypercube of the new hypercube whose cells are j[ndim]
+__host__ __device__ inline long long strat_remap_index(const int *j, const int *n_old, const int *n_new, int ndim) {
+    long long h = 0, stride = 1;
+    for (int d = 0; d < ndim; ++d) {
+        h += (long long)strat_remap_cell(j[d], n_old[d], n_new[d]) * stride;
+        stride *= n_old[d];
+    }
+    return h;
+}
+// <<< strat remap cell rule
+enum { kStratRemapMaxDraw = 32 };
+struct StratRemapArgs {
+    const double *d_old; // [prod n_old]
+    double *d_new;       // [ncube] out
+    long long ncube;     // prod n_new
+    int ndim;
+    double e;            // beta_new / beta_old
+    unsigned magic[kStratRemapMaxDraw]; // h' / n_new[d] = (h' * magic[d]) >> shift[d], exact for h' < 2^31
+    int shift[kStratRemapMaxDraw];
+    int n_new[kStratRemapMaxDraw], n_old[kStratRemapMaxDraw];
+};
+__global__ void __launch_bounds__(256) k_strat_remap(StratRemapArgs a) {
+    const long long step = (long long)gridDim.x * 256;
+    for (long long hn = (long long)blockIdx.x * 256 + threadIdx.x; hn < a.ncube; hn += step) {
+        unsigned q = (unsigned)hn;
+        long long h = 0, stride = 1;
+        for (int d = 0; d < a.ndim; ++d) {
+            const unsigned qn = (unsigned)(((unsigned long long)q * a.magic[d]) >> a.shift[d]);
+            const int j = (int)(q - qn * (unsigned)a.n_new[d]);
+            q = qn;
+            h += (long long)strat_remap_cell(j, a.n_old[d], a.n_new[d]) * stride;
+            stride *= a.n_old[d];
+        }
+        const double v = a.d_old[h];
+        a.d_new[hn] = a.e == 1.0 ? v : pow(v, a.e);
+    }
+}
+
 // k_strat_reduce: the iteration's (mean, var) per column from the chunks' partial rows (their interior hypercubes) and the boundary
 // records (the hypercubes the chunk boundaries cut: the pieces of one hypercube are the records of consecutive chunks, folded in chunk
 // order), and d_h = (sum_k s^2_{h,k})^(beta/2) of the cut hypercubes.  One workgroup; every thread takes a stretch of chunks, the threads'

@@ -540,7 +540,8 @@ class Engine:
         return lib().mci_ctx_stream(context(self.device)) or 0
 
     def save_state(self, path):
-        """grids, distributions and reweight -> MCISTATE file (resume across processes)"""
+        """grids, distributions and reweight -> MCISTATE file (resume across processes); an engine that carries its stratified
+        allocation (set_stratification(carry=True)) adds it: one double per hypercube, up to 128 MB at the default cap"""
         check(lib().mci_save_state(self.p, str(path).encode()))
 
     def load_state(self, path):
@@ -740,12 +741,16 @@ class Engine:
         return int(n.value)
 
     # ---- stratified :vegas (VEGAS+; mci_set_stratification) ---------------------------------------------------------------------
-    def set_stratification(self, nstrat=None, beta=0.75, max_nhcube=2 ** 24, on=True):
+    CARRIED = ("uniform", "same plan", "remapped")   # mci_get_strat_carry: where the last first-allocation of a run came from
+
+    def set_stratification(self, nstrat=None, beta=0.75, max_nhcube=2 ** 24, on=True, carry=False):
         """stratified :vegas from the next iteration on (nstrat None: the default plan for the iteration's neval, mci_strat_plan);
-        on=False: back to plain :vegas"""
+        on=False: back to plain :vegas.  carry=True (mci_set_stratification_carry): the d_h of the last finished iteration, or of a
+        loaded state file, stays with the engine -- through this setter too -- and the next call's first allocation is made from it"""
         if not on:
             check(lib().mci_set_stratification_off(self.p))
             return
+        check(lib().mci_set_stratification_carry(self.p, 1 if carry else 0))   # (first: the setter below keeps a carried d_h only then)
         ns = None
         if nstrat is not None:
             self._nstrat = np.ascontiguousarray(nstrat, dtype=np.int32)
@@ -753,12 +758,30 @@ class Engine:
         check(lib().mci_set_stratification(self.p, self.ndraw, ns, float(beta), int(max_nhcube)))
 
     def stratification(self):
-        """{nstrat, ncube, beta} of the plan in use, None when the problem is not stratified"""
+        """{nstrat, ncube, beta} of the plan in use, None when the problem is not stratified; an engine that carries its allocation
+        (set_stratification(carry=True)) adds carry = True and carried = "uniform" | "same plan" | "remapped": where the first
+        allocation of its last run came from"""
         ns, nc, b = np.zeros(self.ndraw, dtype=np.int32), C.c_int64(), C.c_double()
         check(lib().mci_get_stratification(self.p, ns.ctypes.data_as(c_int32_p), C.byref(nc), C.byref(b)))
         if not ns.any():
             return None
-        return dict(nstrat=[int(v) for v in ns], ncube=int(nc.value), beta=float(b.value))
+        info = dict(nstrat=[int(v) for v in ns], ncube=int(nc.value), beta=float(b.value))
+        on, how = self.strat_carry()
+        if on:
+            info.update(carry=True, carried=self.CARRIED[how])
+        return info
+
+    def strat_carry(self):
+        """(carry on?, how the last first-allocation started: 0 uniform | 1 the carried d_h on its own plan | 2 remapped)"""
+        on, how = C.c_int32(), C.c_int32()
+        check(lib().mci_get_strat_carry(self.p, C.byref(on), C.byref(how)))
+        return bool(on.value), int(how.value)
+
+    def strat_start_d_next(self, n):
+        """test hook (mci_debug_strat_start_d): buffer the next first-allocation of a run fills with the n = ncube d_h it is made from"""
+        self._strat_start_d = np.zeros(int(n))
+        check(lib().mci_debug_strat_start_d(self.p, _dp(self._strat_start_d), int(n)))
+        return self._strat_start_d
 
     def strat_counts(self):
         """n_h of every hypercube in the allocation the last stratified iteration used"""

@@ -22,14 +22,19 @@ class Stratify:
     (mci_strat_plan: about eight samples per hypercube, at most max_nhcube hypercubes).  An iteration's error is the stratified one:
     `block` plays no part in it.  It is built from every hypercube's sample variance, so it is only as good as those: with an explicit
     nstrat that leaves about two samples per hypercube, or with beta = 0, a heavy-tailed integrand's error comes out too small
-    (log(x)/sqrt(x): the means scatter 5.1 | 2.4 times the reported error, profiles/r07_stratified.txt); report() says so."""
+    (log(x)/sqrt(x): the means scatter 5.1 | 2.4 times the reported error, profiles/r07_stratified.txt); report() says so.
+    carry=True (mci_set_stratification_carry): the call starts from the allocation the engine of `config=res.config` learned in its last
+    call -- or loaded from a state file -- instead of a uniform one, moved onto this call's plan and beta where they differ; with
+    adapt=False the whole call keeps it (train at a small neval, then measure at a large one).  The default, False, starts uniform."""
 
-    def __init__(self, beta=0.75, nstrat=None, max_nhcube=2 ** 24):
-        self.beta, self.max_nhcube = float(beta), int(max_nhcube)
+    def __init__(self, beta=0.75, nstrat=None, max_nhcube=2 ** 24, carry=False):
+        if not isinstance(carry, (bool, np.bool_)):
+            raise ValueError("Stratify: carry = %r, must be True or False" % (carry,))
+        self.beta, self.max_nhcube, self.carry = float(beta), int(max_nhcube), bool(carry)
         self.nstrat = None if nstrat is None else [int(v) for v in nstrat]
 
     def __repr__(self):
-        return "Stratify(beta=%r, nstrat=%r, max_nhcube=%r)" % (self.beta, self.nstrat, self.max_nhcube)
+        return "Stratify(beta=%r, nstrat=%r, max_nhcube=%r, carry=%r)" % (self.beta, self.nstrat, self.max_nhcube, self.carry)
 
 
 def _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm):
@@ -38,7 +43,7 @@ def _stratify_request(stratify, solver, config, integrand, measure, measurefreq,
         return None
     st = Stratify() if stratify is True else stratify
     if not isinstance(st, Stratify):
-        raise ValueError("stratify = %r: True or mci.Stratify(beta=..., nstrat=..., max_nhcube=...)" % (stratify,))
+        raise ValueError("stratify = %r: True or mci.Stratify(beta=..., nstrat=..., max_nhcube=..., carry=...)" % (stratify,))
     why = None
     if SOLVERS.get(solver) != VEGAS:   # (the solver by name or by its constant, as integrate() takes it)
         why = "solver = %r (stratified sampling is a :vegas mode)" % solver
@@ -218,7 +223,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     cannot be written out takes the host batch-callback path, silently with None, with a RuntimeWarning naming the reason with True;
     False: always the host path), `integrand_form` / `measure_form` (callback_form: by default a closure is called in the form the
     reference's solver calls it in -- `inplace` included -- and one whose parameters do not fit raises TypeError), `stratify` (True or
-    Stratify(beta, nstrat, max_nhcube): VEGAS+ adaptive stratified sampling under solver="vegas", see Stratify), `engine_factory`
+    Stratify(beta, nstrat, max_nhcube, carry): VEGAS+ adaptive stratified sampling under solver="vegas", see Stratify), `engine_factory`
     (test seam)."""
     if trace is None:
         trace = TRACE_DEFAULT
@@ -249,7 +254,10 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     if strat is not None:
         if isinstance(eng.integrand, HostIntegrand):
             raise ValueError("stratify: refused for a host integrand (the closure did not trace): device source or a traced closure only")
-        eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)   # (the allocation starts uniform)
+        if strat.carry:   # (the allocation starts from what this engine learned or loaded; a test double may not know the keyword)
+            eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube, carry=True)
+        else:             # (the allocation starts uniform)
+            eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)
         eng._strat_on = True
     elif getattr(eng, "_strat_on", False):   # a plain call on an engine an earlier call stratified: the plain kernels again
         eng.set_stratification(on=False)
@@ -332,7 +340,10 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
             res.chain_bias = chain_estimator_bias(solver, nevalperblock, eng.last_chain_launch()[0], block, niter - ignore, pr, ac, eng.ndraw)
         except Exception:
             res.chain_bias = None
-    res.stratification = eng.stratification() if strat is not None else None   # {nstrat, ncube, beta} of a stratified run
+    res.stratification = eng.stratification() if strat is not None else None   # {nstrat, ncube, beta, carry, carried} of a stratified run
+    if res.stratification is not None:
+        res.stratification.setdefault("carry", False)
+        res.stratification.setdefault("carried", "uniform")
     if s == VEGAS and hasattr(eng, "vegas_check_status"):
         try:   # was the kernel that produced these grids checked?  (status, flags) of mci_vegas_check_status; a note of report() when negative
             res.vegas_check = eng.vegas_check_status()

@@ -111,7 +111,7 @@ class Result:
         # set by integrate() for a chain solver that ran the reference's one chain per block: chain_estimator_bias (report() prints a
         # note where the expected bias of the blocks' ratio estimator reaches 2 of the final error bars)
         self.chain_bias = None
-        # set by integrate() for a stratified :vegas run (stratify=...): {nstrat, ncube, beta} of the plan it ran, else None
+        # set by integrate() for a stratified :vegas run (stratify=...): {nstrat, ncube, beta, carry, carried} of the plan it ran, else None
         self.stratification = None
         # set by integrate() after a :vegas run: (status, flags) of the self-check of the problem's :vegas code objects
         # (Engine.vegas_check_status; report() prints a note when the status is negative), else None
@@ -306,8 +306,10 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
     st = getattr(result, "stratification", None)
     if st:   # (not in the reference: VEGAS+ stratification of the :vegas run)
         ns = st["nstrat"]
-        print("  stratified sampling: %d hypercubes (nstrat = %s), beta = %g; iteration errors are the stratified ones" % (
-            st["ncube"], ns if len(set(ns)) > 1 else "%d x %d" % (ns[0], len(ns)), st["beta"]), file=io)
+        start = {"uniform": "a uniform allocation", "same plan": "the allocation carried over from the last call",
+                 "remapped": "the carried allocation, moved onto this plan"}[st.get("carried", "uniform")]
+        print("  stratified sampling: %d hypercubes (nstrat = %s), beta = %g, started from %s; iteration errors are the stratified ones" % (
+            st["ncube"], ns if len(set(ns)) > 1 else "%d x %d" % (ns[0], len(ns)), st["beta"], start), file=io)
         niter = max(result.iter_mean.shape[0], 1)
         per = result.neval / niter / max(st["ncube"], 1)
         if per < 4 or st["beta"] == 0:
