@@ -40,6 +40,8 @@ enum { MCI_VEGAS_PERSISTENT = 3 };
 enum { MCI_VEGASMC_LANES = 5, MCI_MCMC_LANES = 6 };
 /* ... and the stratified :vegas sample kernel (mci_set_stratification; the problem must be stratified to compile it) */
 enum { MCI_VEGAS_STRAT = 7 };
+/* ... and the sweep kernel of mci_integrate_sweep (layouts mci_sweep_supported accepts) */
+enum { MCI_VEGAS_SWEEP = 8 };
 
 typedef struct mci_ctx mci_ctx;
 typedef struct mci_problem mci_problem;
@@ -229,6 +231,35 @@ int mci_iteration_finish(mci_problem *prob, int32_t solver, int64_t block_total,
 int mci_check_status(mci_problem *prob);
 /* the whole loop (main.jl:142-218) */
 int mci_integrate(mci_problem *prob, const mci_integrate_args *args, mci_result *result);
+/* A parameter sweep: `npoint` independent :vegas integrals that differ in the userdata row (a traced closure's captured floats) in ONE
+ * launch.  Result p is what mci_integrate returns on a fresh copy of the problem whose userdata is row p, under the same neval,
+ * niter, block, seed, first_iteration, adapt, gamma and ignore: every point reproduces the loop of src/main.jl:142-207 -- sample n of
+ * block B of iteration i draws the same Philox indices, the map arithmetic (prefix-scan walk), the clearStatistics! offsets, the block
+ * statistics (main.jl:273-287) and the inverse-variance average (statistics.jl:186-220) are the same; only the association of
+ * floating-point sums may differ, as between the persistent launch and the launch chain.  One workgroup runs a point's whole loop;
+ * workgroups never wait for each other.
+ *   userdata  [npoint][nuserdata], nuserdata as given to mci_set_integrand_source
+ *   seeds     NULL: args->seed for every point (common random numbers: a smooth curve over the scan); else [npoint]
+ *   maps_in   NULL: every point starts from the problem's current map; else [npoint][nbin + 1] grids (mci_get_grid's layout)
+ *   maps_out  NULL or [npoint][nbin + 1]: every point's map after its last iteration (== its maps_in row, bit for bit, with adapt = 0)
+ *   results   [npoint], arrays caller-allocated as for mci_integrate (iter_mean / iter_std / visited may be NULL)
+ *   iter_mean, iter_std   NULL or [npoint][niter][nobs]
+ *   status    NULL or [npoint]: what the device flagged for that point, bits 1 block normalization (main.jl:269-271) | 2 histogram not
+ *             finite | 4 histogram not positive (variable.jl:212-213) | 8 distribution not finite (common.jl:79).  A flagged point does
+ *             not fail the call: its train! refused and its map stayed (what mci_integrate would have raised as MCI_ERR_HISTOGRAM /
+ *             MCI_ERR_NORMALIZATION), its result is made of the log rows it left, the other points are not affected.
+ * The problem's own state -- map, packed buffer, iteration log, block log, what the last_* queries report -- is not touched.
+ * npoint <= 65536, and the launch's device memory (~(2 (nbin + 1) + (niter + 1) nstat + nbin + 2 block ncols) doubles per point) at most
+ * 4 GiB: MCI_ERR_INVALID beyond.  A problem or argument set mci_sweep_supported refuses fails with MCI_ERR_INVALID and that reason;
+ * nothing else is run in its place. */
+int mci_integrate_sweep(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                        const double *maps_in, double *maps_out, mci_result *results, double *iter_mean, double *iter_std,
+                        int32_t *status);
+/* MCI_OK when mci_integrate_sweep takes this problem with these arguments; else MCI_ERR_INVALID with the reason in why[n] (and in
+ * mci_last_error): solver other than :vegas, measurefreq != 1, several ranks, stratification, a host integrand or measure,
+ * deterministic mode, more than one variable leaf, a Discrete or FermiK leaf, tables that do not sit in LDS in one tile, or more than
+ * 64 KiB of LDS with the workgroup's copy of the map.  The number of draws per sample is no reason. */
+int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

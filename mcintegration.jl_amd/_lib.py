@@ -86,6 +86,9 @@ SIGNATURES = [
     ("mci_iteration_reduce", C.c_int, [_VP]),
     ("mci_iteration_finish", C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int32, C.c_double, c_double_p, c_double_p]),
     ("mci_integrate", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(ResultC)]),
+    ("mci_integrate_sweep", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
+                                      C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
+    ("mci_sweep_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
     ("mci_get_iteration_log", C.c_int, [_VP, C.c_int32, c_double_p]),
     ("mci_reserve_iteration_log", C.c_int, [_VP, C.c_int32]),
     ("mci_get_packed", C.c_int, [_VP, c_double_p, C.c_int64]),
@@ -165,6 +168,9 @@ DEBUG_SIGNATURES = [
                                         C.POINTER(C.c_int64)]),
     ("mci_debug_vegas_check_launches", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("mci_debug_vegas_check_layout", C.c_int, [_VP, c_int32_p, c_int32_p, c_double_p, C.POINTER(C.c_uint64), c_int32_p]),
+    ("mci_debug_sweep_workgroups", C.c_int, [_VP, C.c_int32]),
+    ("mci_debug_sweep_threads", C.c_int, [_VP, C.c_int32]),
+    ("mci_debug_sweep_last_launch", C.c_int, [_VP, c_int32_p, c_int32_p]),
 ]
 
 _lib = None

@@ -1,5 +1,5 @@
 // mci_api.hip -- host core of libmci_hip.so: the C ABI of include/mci.h.  One translation unit; its sections live in the
-// mci_host_*.h files included at the bottom, in this order: types, ctx, problem, jit, strat, check, iteration, integrate, access, statistics.
+// mci_host_*.h files included at the bottom, in this order: types, ctx, problem, jit, strat, check, iteration, integrate, sweep, access, statistics.
 //
 // Owns: the Configuration analogue (src/configuration.jl:105-194), the device-resident state (grids,
 // distributions, histograms, packed statistics), the per-iteration launch chain
@@ -30,6 +30,7 @@
 #include "mci_static_kernels.h"
 #include "mci_check.h" // k_check_vegas: the static yardstick of new :vegas code objects
 #include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
+#include "mci_sweep.h" // SweepArgs (likewise)
 
 namespace {
 
@@ -64,6 +65,7 @@ extern "C" {
 #include "mci_host_check.h"
 #include "mci_host_iteration.h"
 #include "mci_host_integrate.h"
+#include "mci_host_sweep.h"
 #include "mci_host_access.h"
 #include "mci_host_statistics.h"
 

@@ -72,6 +72,13 @@ int mci_debug_vegas_check_launches(const mci_problem *prob, int64_t *launches);
  * offset, takes histogram adds; scales[ndraw]: the Jacobian scale; own[ni]: own-draw masks; obs[ni][3]: observable offset, bins,
  * binning draw.  NULL: not wanted. */
 int mci_debug_vegas_check_layout(const mci_problem *prob, int32_t *head, int32_t *draws, double *scales, uint64_t *own, int32_t *obs);
+/* test hook: workgroups of this problem's next sweeps (mci_integrate_sweep; at most one per point is launched), so that a test can
+ * make one workgroup run several points; 0 = the default, two per CU */
+int mci_debug_sweep_workgroups(mci_problem *prob, int32_t g);
+/* A/B hook (tools/sweep_bench.py): threads per workgroup of this problem's next sweeps, 256 | 512 | 1024; 0 = the default */
+int mci_debug_sweep_threads(mci_problem *prob, int32_t threads);
+/* workgroups and threads per workgroup of the problem's last sweep launch */
+int mci_debug_sweep_last_launch(const mci_problem *prob, int32_t *workgroups, int32_t *threads);
 #ifdef __cplusplus
 }
 #endif

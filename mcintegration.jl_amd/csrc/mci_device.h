@@ -1200,8 +1200,13 @@ struct WorkItem {
 };
 template <class Cfg> __device__ __forceinline__ WorkItem work_item(const BatchArgs &a) {
     WorkItem w;
+#ifdef MCI_WORK_ITEM_FROM_CALLER // the sweep unit alone (mci_sweep.h): ONE workgroup runs every (block, slice) of a point in turn, so the
+    w.tile = 0;                  // row comes from its caller -- in BatchArgs::chunk_lo, which only a many-grid launch reads (one tile here)
+    w.rowid = a.chunk_lo;
+#else
     w.tile = Cfg::NTILE == 1 ? 0 : (int)(blockIdx.x % Cfg::NTILE);
     w.rowid = Cfg::NTILE == 1 ? (i64)blockIdx.x : (i64)(blockIdx.x / Cfg::NTILE);
+#endif
     w.lb = w.rowid / a.wg_per_block;
     w.slice = (int)(w.rowid % a.wg_per_block);
     return w;

@@ -1,0 +1,291 @@
+// mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
+// batched :vegas parameter sweeps -- eligibility, the sweep unit's JIT, the one launch and the P results (mci_sweep.h vegas_sweep).
+namespace {
+// Points of one sweep, and the device memory one may take.  Per point the launch holds the userdata row, a seed, two maps, niter log
+// rows, nblocks partial rows and as much merge scratch, a statistics head, a histogram row and a status word: ~25 KB at the
+// reference's sizes (999 increments, 16 blocks, 10 iterations), 1.6 GB at 65536 points.
+const int32_t kSweepMaxPoints = 65536;
+const int64_t kSweepMaxBytes = (int64_t)4 << 30;
+
+// Eligibility: persist_layout exactly (one Continuous leaf, table mode 0, one tile, device-source integrand and measure, not
+// deterministic, within 64 KiB including the map copy), measurefreq == 1, one rank.  NOT the draw count: `ndraw <= 7` is
+// persist_plan's rule for when the persistent launch beats the launch chain, nothing a sweep depends on.
+const char *sweep_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
+    const auto &s = p->shape;
+    if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
+    if (a->measurefreq != 1) {
+        buf = "measurefreq = " + std::to_string((long long)a->measurefreq) + " (a sweep measures every sample)";
+        return buf.c_str();
+    }
+    if (a->niter < 1) return "niter < 1";
+    if (p->ctx->nranks != 1) return "several ranks (one rank only)";
+    if (p->strat.on) return "the problem is stratified (mci_set_stratification_off first)";
+    if (s.host_integrand) return "a host integrand (device source or a traced closure only)";
+    if (s.host_measure) return "a host measure (device source only)";
+    if (p->deterministic) return "deterministic mode";
+    if (s.nleaf != 1 || p->leaves.size() != 1) {
+        buf = std::to_string(s.nleaf) + " variable leaves (a sweep point refines ONE Continuous grid)";
+        return buf.c_str();
+    }
+    if (p->leaves[0].kind != 0) return "a Discrete or FermiK variable (a sweep point refines ONE Continuous grid)";
+    if (s.table_mode != 0 || s.ntile != 1 || s.nbin <= 0 || s.ec_doubles > 0) return "the grid and its histogram do not sit in LDS in one tile";
+    if (persist_lds(p, nullptr) > 64 * 1024) {
+        buf = "the sample tables, the refinement scratch and the map copy take " + std::to_string((long long)persist_lds(p, nullptr)) + " bytes of LDS (64 KiB at most)";
+        return buf.c_str();
+    }
+    return nullptr;
+}
+
+// one device allocation per sweep: the context's spare buffer if it fits (tile_alloc's rule), else hipMalloc; handed back on return
+int sweep_alloc(mci_ctx *c, size_t bytes, void **base, size_t *got) {
+    *base = nullptr;
+    {
+        std::lock_guard<std::mutex> g(c->spare_mu);
+        if (c->spare && c->spare_bytes >= bytes && c->spare_bytes <= 2 * bytes + ((size_t)64 << 20)) {
+            *base = c->spare;
+            *got = c->spare_bytes;
+            c->spare = nullptr;
+            c->spare_bytes = 0;
+        }
+    }
+    if (!*base) {
+        HIPCHK(hipMalloc(base, bytes));
+        *got = bytes;
+    }
+    return MCI_OK;
+}
+// (a sweep's buffer grows with P, up to kSweepMaxBytes: only one of up to kSweepKeepBytes is parked with the context -- what a scan of
+// a few thousand points at the reference's sizes takes, so that repeated sweeps do not allocate --, a larger one is freed at once)
+const size_t kSweepKeepBytes = (size_t)256 << 20;
+void sweep_release(mci_ctx *c, void *base, size_t bytes) {
+    if (!base) return;
+    void *drop = base;
+    {
+        std::lock_guard<std::mutex> g(c->spare_mu);
+        if (bytes <= kSweepKeepBytes && bytes > c->spare_bytes) {
+            drop = c->spare;
+            c->spare = base;
+            c->spare_bytes = bytes;
+        }
+    }
+    if (drop) (void)hipFree(drop);
+}
+// Workgroup size of the sweep kernel.  Measured on the 4-D Genz product peak at niter = 10, block = 16 (tools/sweep_bench.py,
+// profiles/r10_sweep.txt); csrc/mci_debug.h mci_debug_sweep_threads forces another one.
+const int kSweepThreads = 256;
+} // namespace
+
+static int compile_sweep(mci_problem *p) {
+    auto &sw = p->sweep;
+    const int T = sw.want_threads > 0 ? sw.want_threads : kSweepThreads;
+    if (sw.compiled && sw.threads == T) return MCI_OK;
+    if (sw.module) {
+        if (!p->ctx->offline) (void)hipModuleUnload(sw.module);
+        sw.module = nullptr;
+        sw.f = nullptr;
+    }
+    sw.compiled = false;
+    Candidate c;
+    mcijit::ProblemShape sh = p->shape;
+    sh.hcopy = 1;
+    sh.det = 0;
+    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweep, p->leaves[0].alpha);
+    c.threads = T;
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweep);
+    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel):\n%s", c.log.c_str());
+    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep") != 0)
+        return fail(MCI_ERR_COMPILE, "the sweep kernel came out with static LDS or scratch at %d threads per workgroup", T);
+    sw.code_object = c.path;
+    sw.threads = T;
+    if (!p->ctx->offline) {
+        HIPCHK(hipSetDevice(p->ctx->device));
+        if (hipModuleLoadData(&sw.module, c.code.data()) != hipSuccess) {
+            if (c.cached) unlink(c.path.c_str()); // a cached code object that does not load (truncated by a crash, foreign file)
+            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object");
+        }
+        HIPCHK(hipModuleGetFunction(&sw.f, sw.module, "mci_vegas_sweep"));
+    }
+    sw.compiled = true;
+    return MCI_OK;
+}
+
+int mci_sweep_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
+    if (why && n > 0) why[0] = 0;
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    std::string buf;
+    const char *r = sweep_refusal(p, a, buf);
+    if (!r) return MCI_OK;
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
+    return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep: %s", r);
+}
+
+// csrc/mci_debug.h
+int mci_debug_sweep_workgroups(mci_problem *p, int32_t g) {
+    if (!p || g < 0) return fail(MCI_ERR_INVALID, "sweep workgroups: >= 1, or 0 for the default");
+    p->sweep.grid = g;
+    return MCI_OK;
+}
+int mci_debug_sweep_threads(mci_problem *p, int32_t threads) {
+    if (!p || (threads != 0 && threads != 256 && threads != 512 && threads != 1024)) return fail(MCI_ERR_INVALID, "sweep threads: 256, 512, 1024, or 0 for the default");
+    p->sweep.want_threads = threads;
+    return MCI_OK;
+}
+int mci_debug_sweep_last_launch(const mci_problem *p, int32_t *workgroups, int32_t *threads) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (workgroups) *workgroups = p->sweep.last_grid;
+    if (threads) *threads = p->sweep.last_threads;
+    return MCI_OK;
+}
+
+// P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
+int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                        double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
+    if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
+    int rc;
+    if ((rc = mci_sweep_supported(p, a, nullptr, 0))) return rc;
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
+    const auto &s = p->shape;
+    const int nud = (int)p->h_ud.size();
+    if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
+    if (!(a->neval > a->block)) return fail(MCI_ERR_INVALID, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block); // main.jl:222
+    for (int q = 0; q < npoint; ++q)
+        if (results[q].niter < a->niter || results[q].nobs != s.nobs || !results[q].mean || !results[q].stdev || !results[q].chi2)
+            return fail(MCI_ERR_INVALID, "result buffers of point %d too small", q);
+    int64_t nevalperblock, block;
+    mci_standardize_block(a->neval, a->block, 1, &nevalperblock, &block); // main.jl:121
+    if (block > (int64_t)1 << 20) return fail(MCI_ERR_INVALID, "block = %lld: too many blocks for a sweep", (long long)block);
+    const int N = p->leaves[0].nbin, nstat = p->nstat, niter = a->niter;
+    const size_t P = (size_t)npoint, nmap = (size_t)N + 1, rows = (size_t)block * s.ncols;
+    // one buffer (doubles, then the 8-byte seeds, then the status words)
+    const size_t o_ud = 0, o_in = o_ud + P * (size_t)nud, o_out = o_in + (maps_in ? P * nmap : 0), o_log = o_out + P * nmap,
+                 o_part = o_log + P * (size_t)niter * nstat, o_scr = o_part + P * rows, o_pk = o_scr + P * rows, o_gh = o_pk + P * (size_t)nstat,
+                 o_seed = o_gh + P * (size_t)s.nbin, o_st = o_seed + (seeds ? P : 0), ndbl = o_st + (P + 1) / 2;
+    if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
+        return fail(MCI_ERR_INVALID, "a sweep of %d points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it",
+                    (int)npoint, niter, (long long)block, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
+    if ((rc = compile_sweep(p))) return rc;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    void *base = nullptr;
+    size_t got = 0;
+    if ((rc = sweep_alloc(p->ctx, ndbl * sizeof(double), &base, &got))) return rc;
+    double *d = (double *)base;
+    std::vector<double> hlog(P * (size_t)niter * nstat), hmap;
+    std::vector<int> hst(P);
+    auto run = [&]() -> int {
+        auto t0 = std::chrono::steady_clock::now();
+        if (nud > 0) HIPCHK(hipMemcpyAsync(d + o_ud, userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
+        if (maps_in) HIPCHK(hipMemcpyAsync(d + o_in, maps_in, P * nmap * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d + o_gh, 0, (ndbl - o_gh) * sizeof(double), st)); // histogram rows, (the seeds: copied next), status words
+        if (seeds) HIPCHK(hipMemcpyAsync(d + o_seed, seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        mci::BatchArgs b{};
+        b.edges = p->d_edges;
+        b.dacc = p->d_dacc;
+        b.ddist = p->d_ddist;
+        b.reweight = p->d_reweight;
+        b.ud = d + o_ud;
+        b.part_cols = d + o_part;
+        b.part_hist = nullptr;
+        b.ghist = d + o_gh;
+        b.seed = a->seed;
+        b.iteration = (mci::u32)a->first_iteration;
+        b.neval_per_block = nevalperblock;
+        b.block_lo = 0;
+        b.wg_per_block = 1;
+        b.measurefreq = 1;
+        b.nchain = 1;
+        b.hist_atomic = 1;
+        b.status = reinterpret_cast<int *>(d + o_st);
+        b.tile_stride = block * nevalperblock;
+        b.nrows = block;
+        mci::SweepArgs f{};
+        mci::MergeArgs &m = f.m;
+        m.part_cols = d + o_part;
+        m.ncols = s.ncols;
+        m.nobs = s.nobs;
+        m.ni = s.ni;
+        m.nblocks = (int)block;
+        m.wg_per_block = 1;
+        m.stage1 = nullptr;
+        m.ngroup = 0;
+        m.ghist = d + o_gh;
+        m.use_ghist = 1;
+        m.nbin = s.nbin;
+        m.packed = d + o_pk;
+        m.status = b.status;
+        m.scratch = d + o_scr;
+        m.part_pa = nullptr;
+        m.npa = 0;
+        m.nrows = (int)block;
+        mci::TrainArgs &t = f.t;
+        t.leaves = p->d_leaves;
+        t.nleaf = s.nleaf;
+        t.packed = d + o_pk;
+        t.nstat = nstat;
+        t.edges = p->d_edges;
+        t.dacc = p->d_dacc;
+        t.ddist = p->d_ddist;
+        t.iter_log_row = d + o_log;
+        t.reweight = nullptr;
+        t.goal = nullptr;
+        t.nd = s.ni + 1;
+        t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
+        t.gamma = a->gamma;
+        t.do_train = a->adapt ? 1 : 0;
+        t.serial_walk = 0;
+        t.status = b.status;
+        t.maxn = N;
+        f.npoint = npoint;
+        f.niter = niter;
+        f.nuserdata = nud;
+        const int64_t lds = persist_lds(p, &f.map_off);
+        f.ud = d + o_ud;
+        f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
+        f.maps_in = maps_in ? d + o_in : nullptr;
+        f.maps_out = d + o_out;
+        // workgroups: two per CU keep a CU's SIMDs busy while one of them sits in its refinement; any grid runs any npoint
+        int cus = 0;
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
+        int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : 2 * (int64_t)(cus > 0 ? cus : 256);
+        if (grid > npoint) grid = npoint;
+        void *args[] = {&b, &f};
+        HIPCHK(hipModuleLaunchKernel(p->sweep.f, (unsigned)grid, 1, 1, (unsigned)p->sweep.threads, 1, 1, (unsigned)lds, st, args, nullptr));
+        p->sweep.last_grid = (int)grid;
+        p->sweep.last_threads = p->sweep.threads;
+        HIPCHK(hipMemcpyAsync(hlog.data(), d + o_log, hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hst.data(), d + o_st, P * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out, d + o_out, P * nmap * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int q = 0; q < npoint; ++q) results[q].seconds = seconds;
+        return MCI_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st); // (nothing of a failed call is still reading the buffer when it goes back)
+    sweep_release(p->ctx, base, got);
+    if (rc) return rc;
+    // per point what mci_integrate makes of its log rows (main.jl:203, :211)
+    const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
+    std::vector<double> tm((size_t)niter * s.nobs), te((size_t)niter * s.nobs);
+    for (int q = 0; q < npoint; ++q) {
+        mci_result *res = &results[q];
+        double *im = iter_mean ? iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
+        double *ie = iter_std ? iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
+        res->neval = 0;
+        for (int it = 0; it < niter; ++it) {
+            const double *row = hlog.data() + ((size_t)q * niter + it) * nstat;
+            mci_mean_std(row, row + s.nobs, s.nobs, block, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
+            res->neval += (int64_t)row[2 * s.nobs + 1];
+            if (res->visited && it == niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
+        }
+        if (iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
+        if (iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
+        for (int o = 0; o < s.nobs; ++o) // main.jl:211 -> statistics.jl:24-55
+            mci_average(im + o, ie + o, s.nobs, ignore + 1, niter, &res->mean[o], &res->stdev[o], &res->chi2[o]);
+        res->correlated = 0;
+        res->warmup = 0;
+        if (status) status[q] = hst[q];
+    }
+    return MCI_OK;
+}

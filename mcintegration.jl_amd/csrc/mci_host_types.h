@@ -368,6 +368,18 @@ struct mci_problem {
         double *hstart = nullptr;
         int64_t hstart_n = 0;
     } strat;
+    // Batched :vegas parameter sweeps (mci_integrate_sweep; mci_sweep.h, mci_host_sweep.h): the sweep unit's code object.  A sweep keeps
+    // nothing else here: its maps, logs and status words come in and go out through the call's arguments.
+    struct Sweep {
+        bool compiled = false;
+        int threads = 0;              // the workgroup size the loaded code object was compiled for
+        hipModule_t module = nullptr;
+        hipFunction_t f = nullptr;
+        std::string code_object;
+        int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
+        int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default
+        int last_grid = 0, last_threads = 0;
+    } sweep;
 };
 
 // A repeated iteration (the warm-up of automatic :mcmc chain lengths, mci_integrate) draws from the Philox streams of iteration
@@ -607,6 +619,12 @@ void drop_modules(mci_problem *p) {
     if (p->strat.module) {
         (void)hipModuleUnload(p->strat.module);
         p->strat.module = nullptr;
+    }
+    p->sweep.compiled = false;
+    p->sweep.f = nullptr;
+    if (p->sweep.module) {
+        (void)hipModuleUnload(p->sweep.module);
+        p->sweep.module = nullptr;
     }
 }
 

@@ -439,12 +439,13 @@ class Engine:
     # ---- kernels -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_code(solver):
-        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7}.get(solver) or _lib.SOLVERS[solver]
+        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
         "vegasmc_lanes" | "mcmc_lanes" (the chain solvers' kernels with several lanes per chain, csrc/mci_spec.h) | "vegas_strat" (the
-        stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification)"""
+        stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification) | "vegas_sweep" (the kernel of
+        integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -703,6 +704,79 @@ class Engine:
             # spared the flush, the copy and the second synchronisation)
             out["block_mean"] = self.block_means(niter)[0]
         return out
+
+    def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration):
+        return _lib.IntegrateArgs(_lib.SOLVERS[solver], int(neval), int(niter), int(block), int(ignore), 1 if adapt else 0, float(gamma),
+                                  int(measurefreq), int(seed), 0, int(first_iteration), 0.1, None)
+
+    def sweep_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, **kw):
+        """None when integrate_sweep takes this problem with these arguments, else the reason (mci_sweep_supported)"""
+        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, 0)
+        why = C.create_string_buffer(512)
+        if lib().mci_sweep_supported(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
+            return None
+        return why.value.decode() or lib().mci_last_error().decode(errors="replace")
+
+    SWEEP_MAX_POINTS = 65536   # include/mci.h mci_integrate_sweep
+
+    def integrate_sweep(self, solver="vegas", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1,
+                        seed=1234, seeds=None, maps=None, first_iteration=0):
+        """A parameter sweep in one launch (mci_integrate_sweep): userdata [P][nuserdata], one row per point -- what an ordinary call
+        would have been given as the integrand's userdata.  Returns a list of P result dicts with the keys of integrate() plus `maps`
+        (the point's map after its last iteration) and `status` (the bits the device flagged for that point; 0 = none).  seed: the same
+        for every point (common random numbers), or seeds = P of them; maps: None (every point starts from the engine's current map)
+        or [P][grid points] starting maps (the layout of grid()).  The engine's own map, packed buffer and logs are not touched.  Raises MCIError naming the
+        reason when the problem or the arguments cannot run as a sweep (sweep_supported): nothing else runs in its place."""
+        nud = len(self.integrand.userdata) if hasattr(self.integrand, "userdata") else 0
+        ud = np.ascontiguousarray(userdata if userdata is not None else np.zeros((0, nud)), dtype=np.float64)
+        if ud.ndim != 2 or ud.shape[1] != nud:
+            raise ValueError("integrate_sweep: userdata must be a 2-D array [points][%d] (one row of the integrand's userdata per point), got shape %s"
+                             % (nud, ud.shape))
+        P = ud.shape[0]
+        if not 1 <= P <= self.SWEEP_MAX_POINTS:
+            raise ValueError("integrate_sweep: %d points; a sweep takes 1 to %d" % (P, self.SWEEP_MAX_POINTS))
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if sd.shape != (P,):
+                raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got shape %s" % (P, sd.shape))
+        leaves = self.config.leaves
+        nmap = leaves[0].ninc if len(leaves) == 1 and hasattr(leaves[0], "ninc") else 0
+        mi = None
+        if maps is not None:
+            mi = np.ascontiguousarray(maps, dtype=np.float64)
+            if nmap and mi.shape != (P, nmap):
+                raise ValueError("integrate_sweep: maps must be [points = %d][grid points = %d], got shape %s" % (P, nmap, mi.shape))
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
+        n = self.nobs
+        im, ie = np.zeros((P, niter, n)), np.zeros((P, niter, n))
+        m, s, c2 = np.zeros((P, n)), np.zeros((P, n)), np.zeros((P, n))
+        vis = np.zeros((P, self.config.N + 1))
+        mo = np.zeros((P, max(nmap, 1)))
+        st = np.zeros(P, dtype=np.int32)
+        res = (_lib.ResultC * P)()
+        for q in range(P):
+            res[q] = _lib.ResultC(niter, n, None, None, _dp(m[q]), _dp(s[q]), _dp(c2[q]), 0, 0.0, _dp(vis[q]), 0, 0)
+        check(lib().mci_integrate_sweep(self.p, C.byref(a), P, _dp(ud) if ud.size else None,
+                                        sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
+                                        _dp(mi) if mi is not None else None, _dp(mo), res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
+        return [dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
+                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q], status=int(st[q]))
+                for q in range(P)]
+
+    def sweep_workgroups(self, g=0):
+        """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""
+        check(lib().mci_debug_sweep_workgroups(self.p, int(g)))
+
+    def sweep_threads(self, threads=0):
+        """A/B hook of csrc/mci_debug.h: threads per workgroup of the next sweeps (256 | 512 | 1024; 0 = the default)"""
+        check(lib().mci_debug_sweep_threads(self.p, int(threads)))
+
+    def last_sweep_launch(self):
+        """(workgroups, threads per workgroup) of the last sweep launch"""
+        g, t = C.c_int32(), C.c_int32()
+        check(lib().mci_debug_sweep_last_launch(self.p, C.byref(g), C.byref(t)))
+        return int(g.value), int(t.value)
 
     def mcmc_launch_valid(self):
         """(the last automatic :mcmc launch was long enough for the holds it measured, some launch of this problem has been, its chain

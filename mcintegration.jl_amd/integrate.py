@@ -356,6 +356,127 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     return res
 
 
+def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
+                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, **kwargs):
+    """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
+    mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
+    integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
+    map, and by default all points share the seed (common random numbers: a smooth curve over the scan); seeds = one per point.
+
+    params: what the integrand reads its parameters from.  For a Python closure these are the `config.userdata` objects (a struct of
+    floats, a dict, a number: examples/bubble_closure.py) -- the closure is traced ONCE, on params[0], and every point's ud row is
+    evaluated from its object by the trace's parameter evaluation (trace.py "Captured parameters").  Only FLOATS are parameters:
+    ints, bools, strings, non-finite floats and array shapes the closure reads off userdata are written into the body, so points that
+    differ in one of them (`Para(a=2)` next to `Para(a=3)`: write 2.0, 3.0), and a closure whose body depends on the values, are
+    refused with a ValueError naming the field -- never run on the body of point 0.  For a device-source string or an Integrand (mci.catalog) they are the
+    userdata rows.  maps: None or [P][grid points] starting maps; every Result carries `map` (the point's map after its last iteration),
+    `status` (device flags of that point, 0 = none) and `sweep_batched`.
+
+    A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves, a Discrete variable, measurefreq != 1, a
+    host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
+    a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
+    import copy
+    import warnings
+    if trace is None:
+        trace = TRACE_DEFAULT
+    if solver in (":vegas", ":vegasmc", ":mcmc"):
+        solver = solver[1:]
+    if solver not in SOLVERS:
+        raise ValueError("Solver %s is not supported!" % solver)
+    try:
+        P = len(params)
+    except TypeError:
+        raise ValueError("integrate_sweep: params must be a sequence with one entry per point")
+    if not 1 <= P <= Engine.SWEEP_MAX_POINTS:
+        raise ValueError("integrate_sweep: %d points; a sweep takes 1 to %d" % (P, Engine.SWEEP_MAX_POINTS))
+    if seeds is not None and len(seeds) != P:
+        raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
+    if maps is not None and len(maps) != P:
+        raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
+    fresh = config is None
+    pristine = copy.deepcopy(kwargs) if fresh else None
+    if fresh:
+        config = Configuration(**kwargs)
+    if ignore is None:
+        ignore = 1 if adapt else 0
+    closure = callable(integrand) and not isinstance(integrand, (Integrand, HostIntegrand))
+    why = rows = bound = None
+    if closure:
+        from . import trace as tr
+        traced_on = copy.copy(config)      # (the caller's Configuration keeps its userdata)
+        traced_on.userdata = params[0]
+        form = callback_form(integrand, solver, False)
+        try:
+            if trace is False:
+                raise tr.TraceError("trace = False")
+            bound = tr.trace_integrand(integrand, traced_on, indexed=form == "indexed", inplace=form == "inplace")
+            if getattr(bound, "userdata_for", None) is None:
+                raise ValueError("integrate_sweep: the closure's body depends on the values of its parameters (a Python branch on a captured "
+                                 "float, a table indexed with a draw): the points would trace to different bodies")
+            rows = np.array([bound.userdata_for(p) for p in params], dtype=np.float64).reshape(P, len(bound.userdata))
+        except tr.TraceError as e:
+            why = "the closure was not traced (%s): a host integrand" % e
+    else:
+        if isinstance(integrand, str):
+            integrand = Integrand(integrand, None)
+        if isinstance(integrand, HostIntegrand):
+            why = "a host integrand (device source or a traced closure only)"
+        else:
+            rows = np.asarray(params, dtype=np.float64)
+            if rows.ndim != 2 or (len(integrand.userdata) and rows.shape[1] != len(integrand.userdata)):
+                raise ValueError("integrate_sweep: params must be userdata rows [points][%d] for this integrand, got shape %s"
+                                 % (len(integrand.userdata), rows.shape))
+            bound = Integrand(integrand.body, rows[0], integrand.name)
+    if device is None:
+        device = 0
+    nevalperblock, block = standardize_block(int(neval), block, 1)
+    eng = None
+    if why is None:
+        eng = _bind(config, bound, measure, solver, trace=trace, print=print, device=device)
+        why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
+    if why is None:
+        rs = eng.integrate_sweep(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
+                                 gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
+                                 first_iteration=config.iterations_done)
+        out = []
+        for p, r in zip(params, rs):
+            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map and logs alone)
+            c.userdata = p if closure else None
+            c.visited = r["visited"]
+            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block)
+            res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
+            res.stratification, res.vegas_check, res.warmup, res.neval_discarded = None, None, 0, 0
+            if print >= 0:
+                report(res)
+            out.append(res)
+        return out
+    # not a sweep layout: the points one after another, each an ordinary call on a configuration of its own
+    if not fresh:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and the looped form builds one Configuration per "
+                         "point from keywords (var=..., dof=...), not from config=" % why)
+    if maps is not None:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and maps= needs the batched form" % why)
+    warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),
+                  RuntimeWarning, stacklevel=2)
+    if eng is not None and hasattr(eng, "close"):
+        eng.close()
+    out = []
+    for k, p in enumerate(params):
+        kw = copy.deepcopy(pristine)
+        if closure:
+            kw["userdata"], f = p, integrand
+        else:
+            f = integrand if isinstance(integrand, HostIntegrand) else Integrand(integrand.body, rows[k], integrand.name)
+        c = Configuration(**kw)
+        if seeds is not None:
+            c.seed = int(seeds[k])
+        res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
+                        measurefreq=measurefreq, device=device, trace=trace, print=print)
+        res.sweep_batched, res.map, res.status = False, None, 0
+        out.append(res)
+    return out
+
+
 def prefill_kernel_cache():
     """Compile (hiprtc, gfx950, no GPU needed) the sample-batch kernels of the BASELINE configs and of the
     test battery into the in-tree kernel cache, so that the GPU box starts from code objects."""

@@ -57,6 +57,9 @@ class _Trace:
         self.nodes = []
         self.index = {}
         self.params = []      # values of the captured parameters: node ("ud", k) stands for params[k]
+        self.sources = []     # where params[k] was read off config.userdata (a path of ("attr", name) / ("item", key) steps), None: elsewhere
+        self.literals = []    # (path, value) of everything ELSE the closure read off config.userdata: ints, bools, strings, non-finite floats,
+                              # arrays that are no parameter tables, the shapes of those that are -- what the body may have baked in
         # Python branches on sampled values (`1.0 if x[0] ** 2 + x[1] ** 2 < 1 else 0.0`, `if`, `and` / `or`, `while`): the closure is run
         # once per WAY through its branches.  `script` forces the outcome of the k-th truth test of a run, `conds` records what was
         # tested; explore() below enumerates the ways and joins their results with selects.
@@ -71,8 +74,9 @@ class _Trace:
         self.conds.append(cond)
         return out
 
-    def param(self, v):
+    def param(self, v, src=None):
         self.params.append(float(v))
+        self.sources.append(src)
         return self.node("ud", len(self.params) - 1)
 
     def node(self, op, *args):
@@ -659,51 +663,116 @@ class _UserdataView:
     """config.userdata (a struct of parameters: test/bubble.jl:12-27 `para`) during a trace: attribute reads hand arrays out as _Tables
     and floats as PARAMETERS of the trace (module docstring: one body for every value of beta, kF, ...)"""
 
-    def __init__(self, obj, t, floats):
+    def __init__(self, obj, t, floats, path=None):
         object.__setattr__(self, "_obj", obj)
         object.__setattr__(self, "_t", t)
         object.__setattr__(self, "_floats", floats)
+        object.__setattr__(self, "_path", path)
         object.__setattr__(self, "_seen", {})
 
-    def _view(self, key, get):
+    def _view(self, key, get, step):
         seen = object.__getattribute__(self, "_seen")
         if key not in seen:
+            path = object.__getattribute__(self, "_path")
             seen[key] = _userdata_view(get(object.__getattribute__(self, "_obj")), object.__getattribute__(self, "_t"),
-                                       object.__getattribute__(self, "_floats"))
+                                       object.__getattribute__(self, "_floats"), None if path is None else path + (step,))
         return seen[key]
 
     def __getattr__(self, name):
-        return self._view(name, lambda o: getattr(o, name))
+        return self._view(name, lambda o: getattr(o, name), ("attr", name))
 
     def __getitem__(self, k):
-        return self._view(("item", k), lambda o: o[k])
+        return self._view(("item", k), lambda o: o[k], ("item", k))
 
     def __setattr__(self, name, v):
         raise TraceError("the closure writes to config.userdata (hidden state)")
 
 
-def _param_table(v, t):
+def _param_table(v, t, path=None):
     """a float array of up to 64 elements as parameters of the trace (one ud slot each) that is also a table for a sampled index"""
     v = np.asarray(v, dtype=np.float64)
     a = np.empty(v.shape, dtype=object)
     for i in np.ndindex(v.shape):
-        a[i] = t.param(v[i])
+        a[i] = t.param(v[i], None if path is None else path + (("index", i),))
     return _Table(a, t, values=v)
 
 
-def _userdata_view(v, t, floats=False):
+def _userdata_view(v, t, floats=False, path=None):
+    """path: how `v` is reached from config.userdata (None: it is not), kept with every parameter read off it (_Trace.sources)"""
     if floats and isinstance(v, (float, np.floating)) and not isinstance(v, bool) and math.isfinite(v):
-        return t.param(v)
+        return t.param(v, path)
     tb = _as_table(v, t)
     if tb is not None:
         if floats and tb._values.size <= 64 and (not isinstance(v, np.ndarray) or v.dtype.kind == "f") and np.all(np.isfinite(tb._values)):
-            return _param_table(tb._values, t)
+            if path is not None:
+                t.literals.append((path + (("shape", None),), _table_kind(v)))   # (the closure may loop over it)
+            return _param_table(tb._values, t, path)
+        if path is not None:
+            t.literals.append((path, v))
         return tb
     if isinstance(v, (str, bytes, int, float, complex, bool, type(None), np.generic, np.ndarray, list, tuple, types.FunctionType,
                       types.BuiltinFunctionType, types.MethodType, types.ModuleType, type)):
+        if path is not None:
+            t.literals.append((path, v))
         return v
     if isinstance(v, dict) or hasattr(v, "__dict__") or hasattr(v, "__slots__"):
-        return _UserdataView(v, t, floats)
+        return _UserdataView(v, t, floats, path)
+    if path is not None:
+        t.literals.append((path, v))
+    return v
+
+
+def _table_kind(v):
+    """(shape, holds integers) of an array read off config.userdata: what decides whether, and as how many, parameters it is traced"""
+    return np.asarray(v, dtype=np.float64).shape, bool(isinstance(v, np.ndarray) and v.dtype.kind != "f")
+
+
+def _reach(obj, path):
+    """what a path recorded on one config.userdata object leads to in another"""
+    for kind, key in path:
+        if kind == "attr":
+            obj = getattr(obj, key)
+        elif kind == "item":
+            obj = obj[key]
+        elif kind == "shape":
+            obj = _table_kind(obj)
+        else:
+            obj = np.asarray(obj, dtype=np.float64)[key]
+    return obj
+
+
+def _path_name(path):
+    return "userdata" + "".join(".%s" % k if kind == "attr" else ".shape" if kind == "shape" else "[%r]" % (k,) for kind, k in path)
+
+
+def _same_leaf(a, b):
+    """two non-parameter leaves of config.userdata mean the same thing to a trace: same type, same value (arrays element by element)"""
+    if a is b:
+        return True
+    if type(a) is not type(b):
+        return False
+    try:
+        if isinstance(a, (list, tuple)):
+            return len(a) == len(b) and all(_same_leaf(x, y) for x, y in zip(a, b))
+        if isinstance(a, np.ndarray):
+            return a.shape == b.shape and a.dtype == b.dtype and bool(np.all((a == b) | ((a != a) & (b != b))))
+        return bool(a == b) or bool(a != a and b != b)
+    except Exception:
+        return False
+
+
+def _follow(obj, path):
+    """the float a parameter's source path leads to in another userdata object"""
+    for kind, key in path:
+        if kind == "attr":
+            obj = getattr(obj, key)
+        elif kind == "item":
+            obj = obj[key]
+        else:
+            obj = np.asarray(obj, dtype=np.float64)[key]
+    v = float(obj)
+    if not math.isfinite(v):
+        raise ValueError("a parameter that is finite at the traced point is not finite here")
     return v
 
 
@@ -711,7 +780,7 @@ def _trace_config(config, t, floats=False):
     """the Configuration a traced closure is called with: the user's, with `userdata` seen through _userdata_view"""
     import copy
     ud = getattr(config, "userdata", None)
-    view = _userdata_view(ud, t, floats)
+    view = _userdata_view(ud, t, floats, ())
     if view is ud:
         return config
     c = copy.copy(config)
@@ -1161,7 +1230,43 @@ def _trace_integrand(fn, config, indexed, check_points, name, parameters, inplac
                 raise TraceError("the traced expression and the closure disagree on integrand %d: the closure is not a pure "
                                  "function of its draws (hidden state, a branch the trace did not see, numpy arithmetic on "
                                  "comparisons that means something else than the same arithmetic on 0.0 / 1.0)" % (i // nc))
-    return Integrand(body, ud or None, name=name or getattr(fn, "__name__", "traced"))
+    traced = Integrand(body, ud or None, name=name or getattr(fn, "__name__", "traced"))
+    if parameters and not tables:
+        # integrate_sweep: the ud row of ANOTHER config.userdata object from this one trace -- the parameters read off userdata are read
+        # again by their paths, everything else keeps its value, and the hoisted subexpressions are evaluated as hoist() evaluated them
+        order = sorted(slots, key=lambda nid: int(slots[nid][3:-1]))
+        def userdata_for(obj):
+            """ValueError when `obj` would trace to a different body: something the trace read off config.userdata that is NOT a
+            parameter -- an int, a bool, a string, a non-finite float, an array's shape -- differs from the traced object's, or a
+            parameter is not there (another type, missing, not finite)"""
+            for path, was in t.literals:
+                try:
+                    now = _reach(obj, path)
+                except Exception as e:
+                    raise ValueError("the points would trace to different bodies: %s cannot be read (%s: %s)" % (_path_name(path), type(e).__name__, e))
+                if not _same_leaf(was, now):
+                    raise ValueError("the points would trace to different bodies: %s is %r at the traced point and %r here, and is not a "
+                                     "float parameter of the trace (ints, bools, strings and shapes are written into the body)"
+                                     % (_path_name(path), was, now))
+            params = []
+            for v, src in zip(t.params, t.sources):
+                if src is None:
+                    params.append(v)
+                    continue
+                try:
+                    leaf = _reach(obj, src[:-1]) if src and src[-1][0] == "index" else _reach(obj, src)
+                    # (a float at the traced point: an int, a bool or a string here is a literal of ITS trace, not a parameter)
+                    if not (src and src[-1][0] == "index") and (isinstance(leaf, (bool, np.bool_)) or not isinstance(leaf, (float, np.floating))):
+                        raise TypeError("%r is no float" % (leaf,))
+                    params.append(_follow(obj, src))
+                except Exception as e:
+                    raise ValueError("the points would trace to different bodies: parameter %s (%s: %s)" % (_path_name(src), type(e).__name__, e))
+            row = [float(evaluate([t.nodes[nid]], np.zeros((0, 1)), params=params)[0][0]) for nid in order]
+            if not all(math.isfinite(v) for v in row):
+                raise TraceError("a captured parameter evaluates to a non-finite value")
+            return row
+        traced.userdata_for = userdata_for
+    return traced
 
 
 class _Obs(np.ndarray):

@@ -1,0 +1,115 @@
+"""Batched :vegas parameter sweeps against a loop of ordinary calls (profiles/r10_sweep.txt).
+
+    python tools/sweep_bench.py table  [--neval 10000] [--points 1,16,256,1024,4096] [--threads 256]
+    python tools/sweep_bench.py threads [--neval 10000] [--points 256,1024] [--repeat 5]
+    python tools/sweep_bench.py once --points 1024       (one warm sweep and nothing else: the run a kernel trace is taken of)
+
+The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
+and of the same points as a loop of Engine.integrate calls with the persistent launch, in the same process.
+`threads`: the sweep at 256 / 512 / 1024 threads per workgroup (a size whose kernel would spill is refused by the library: reported),
+the sizes interleaved `--repeat` times so that a drift of the box shows as scatter, not as a difference between sizes.
+One GPU process; run each mode under its own time limit."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mcintegration_jl_amd as mci  # noqa: E402
+
+D, NITER, BLOCK, SEED = 4, 10, 16, 20240229
+
+
+def point(k):
+    rng = np.random.default_rng(1000 + k)
+    return [float(D), 2.0 + 6.0 * ((k * 0.37) % 1.0)] + list(0.3 + 0.4 * rng.random(D))
+
+
+def body():
+    return mci.catalog.genz_product_peak(D).body
+
+
+def sweep_engine(threads=0):
+    cfg = mci.Configuration(var=mci.Continuous(0.0, 1.0), dof=[[D]], seed=SEED)
+    eng = mci.Engine(cfg, mci.Integrand(body(), point(0), "genz_product_peak%d" % D))
+    eng.sweep_threads(threads)
+    return eng
+
+
+def time_sweep(eng, P, neval, reps=3):
+    uds = np.array([point(k) for k in range(P)])
+    eng.integrate_sweep("vegas", userdata=uds[:min(P, 4)], neval=neval, niter=NITER, block=BLOCK, seed=SEED)      # (compile, first launch)
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        rs = eng.integrate_sweep("vegas", userdata=uds, neval=neval, niter=NITER, block=BLOCK, seed=SEED)
+        best = min(best, time.perf_counter() - t0)
+    assert all(r["status"] == 0 for r in rs)
+    return best, rs
+
+
+def time_loop(P, neval):
+    """as many ordinary calls, one after another, on ONE engine: a fresh map per call (mci_set_grid), the persistent launch.  The
+    userdata stays that of point 0 -- the library has no way to change it without reloading the code objects, and mci.integrate binds
+    a new engine per userdata: both cost more than what is timed here, so the loop is timed at its cheapest."""
+    cfg = mci.Configuration(var=mci.Continuous(0.0, 1.0), dof=[[D]], seed=SEED)
+    eng = mci.Engine(cfg, mci.Integrand(body(), point(0), "genz_product_peak%d" % D))
+    eng.set_persistent("on")
+    g0 = eng.grid(0).copy()
+    eng.integrate("vegas", neval=neval, niter=NITER, block=BLOCK, seed=SEED)
+    assert eng.last_integrate_persistent()
+    n = min(P, 256)      # (a loop is linear in P: 256 calls are timed, larger P scaled)
+    out = []
+    t0 = time.perf_counter()
+    for k in range(n):
+        eng.set_grid(0, g0)
+        out.append(eng.integrate("vegas", neval=neval, niter=NITER, block=BLOCK, seed=SEED)["mean"][0])
+    dt = time.perf_counter() - t0
+    return dt * P / n, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=["table", "threads", "once"])
+    ap.add_argument("--neval", type=int, default=10000)
+    ap.add_argument("--points", default="1,16,256,1024,4096")
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--repeat", type=int, default=1)
+    a = ap.parse_args()
+    Ps = [int(v) for v in a.points.split(",")]
+    mci.use_rocm_compiler()
+    if a.mode == "once":
+        eng = sweep_engine(a.threads)
+        t, _ = time_sweep(eng, Ps[0], a.neval, reps=1)
+        print("sweep P = %d neval = %d: %.3f ms, grid x threads = %s" % (Ps[0], a.neval, 1e3 * t, eng.last_sweep_launch()))
+        return
+    if a.mode == "threads":
+        print("# sweep, neval = %d, niter = %d, block = %d: ms per call (us per point-iteration) by threads per workgroup" % (a.neval, NITER, BLOCK))
+        engines, refused = {T: sweep_engine(T) for T in (256, 512, 1024)}, set()
+        for rep in range(a.repeat):
+            for T, eng in engines.items():
+                for P in Ps:
+                    if T in refused:
+                        break
+                    try:
+                        t, _ = time_sweep(eng, P, a.neval)
+                        print("pass %d  threads %4d  P %5d  %9.3f ms  (%7.3f us)  grid x threads = %s"
+                              % (rep, T, P, 1e3 * t, 1e6 * t / (P * NITER), eng.last_sweep_launch()))
+                    except mci.MCIError as e:
+                        print("pass %d  threads %4d  P %5d  refused: %s" % (rep, T, P, str(e).splitlines()[0]))
+                        refused.add(T)
+        return
+    print("# neval = %d, niter = %d, block = %d: sweep | loop of persistent calls, ms (us per point-iteration) | loop / sweep" % (a.neval, NITER, BLOCK))
+    eng = sweep_engine(a.threads)
+    for P in Ps:
+        ts, rs = time_sweep(eng, P, a.neval)
+        tl, means = time_loop(P, a.neval)
+        same = abs(rs[0]["mean"][0] - means[0]) / abs(means[0])      # (point 0 is the same integral on both sides)
+        print("P %5d  sweep %10.3f ms (%8.3f us)  loop %10.3f ms (%8.3f us)  loop / sweep %7.2f   point 0: means differ by %.1e%s"
+              % (P, 1e3 * ts, 1e6 * ts / (P * NITER), 1e3 * tl, 1e6 * tl / (P * NITER), tl / ts, same, "  (loop: 256 calls timed, scaled)" if P > 256 else ""))
+
+
+if __name__ == "__main__":
+    main()
