@@ -5,7 +5,13 @@ point's parameters from its object, and runs all points in one launch -- one wor
 Every result is what mci.integrate(peak, userdata=that object, ...) returns on a fresh configuration; all points share the seed, so the
 curve over `a` is smooth (common random numbers).
 
-Reference pattern:  for a in as;  integrate((x, c) -> ...; userdata = Para(a, u), var = Continuous(0, 1), dof = [[4]], solver = :vegas)  end"""
+Reference pattern:  for a in as;  integrate((x, c) -> ...; userdata = Para(a, u), var = Continuous(0, 1), dof = [[4]], solver = :vegas)  end
+
+Then the reference's flagship example, the polarisation bubble (test/bubble.jl:12-133; the closures of examples/bubble_closure.py), scanned
+over the density parameter rs at a fixed dimensionless temperature: kF, the external momenta and the imaginary-time domain (0, beta)
+follow rs.  Four Continuous variable types, a Discrete external-momentum index and a histogram over it: `leaves="all"` lets such a
+problem run as a sweep.  The momenta are a table the integrand looks up by the Discrete draw (every point's row carries its own), and
+every point starts from a map of its own -- its T grid spans its own (0, beta)."""
 import math
 import os
 import sys
@@ -42,5 +48,60 @@ def main(points=64):
     return scan, results
 
 
+PI = math.pi
+
+
+def green(tau, omega, beta):                                                 # test/bubble.jl:40-51
+    if tau >= 0.0:
+        return np.exp(-omega * tau) / (1 + np.exp(-omega * beta)) if omega > 0.0 else np.exp(omega * (beta - tau)) / (1 + np.exp(omega * beta))
+    return -np.exp(-omega * (tau + beta)) / (1 + np.exp(-omega * beta)) if omega > 0.0 else -np.exp(-omega * tau) / (1 + np.exp(omega * beta))
+
+
+def bubble(vars, config):                                                    # test/bubble.jl:53-78
+    R, Theta, Phi, T, Ext = vars
+    para = config.userdata
+    kF, beta, me = para.kF, para.beta, para.me
+    r = R[0] / (1 - R[0])
+    theta, phi = Theta[0], Phi[0]
+    k = np.array([r * np.sin(theta) * np.cos(phi), r * np.sin(theta) * np.sin(phi), r * np.cos(theta)])
+    factor = 1.0 / (2 * PI) ** para.dim
+    factor *= r ** 2 / (1 - R[0]) ** 2 * np.sin(theta)
+    q = para.extQ[Ext[0] - 1]                                                # external momentum: a table looked up by the Discrete draw
+    kq = k + q
+    g1 = green(T[0], (np.dot(k, k) - kF ** 2) / (2 * me), beta)
+    g2 = green(-T[0], (np.dot(kq, kq) - kF ** 2) / (2 * me), beta)
+    return g1 * g2 * para.spin * factor
+
+
+def q_histogram(vars, obs, weight, config):                                  # test/bubble.jl:84-88
+    Ext = vars[-1]
+    obs[0][Ext[0] - 1] += weight[0]
+
+
+def bubble_para(rs, beta=25.0, spin=2, Qsize=4, dim=3, me=0.5):             # test/bubble.jl:12-22
+    kF = (9 * PI / (2 * spin)) ** (1 / 3) / rs
+    return types.SimpleNamespace(rs=rs, kF=kF, beta=beta / (kF ** 2 / 2 / me), me=me, spin=spin, dim=dim, Qsize=Qsize,
+                                 extQ=[np.array([q, 0.0, 0.0]) for q in np.linspace(0.0, 1.5 * kF, Qsize)])
+
+
+def bubble_scan(points=16, ninc=1000):
+    scan = [bubble_para(float(rs)) for rs in np.linspace(1.0, 2.0, points)]
+    Qsize = scan[0].Qsize
+    var = (mci.Continuous(0.0, 1.0, alpha=3.0), mci.Continuous(0.0, PI, alpha=3.0), mci.Continuous(0.0, 2 * PI, alpha=3.0),
+           mci.Continuous(0.0, scan[0].beta, alpha=3.0), mci.Discrete(1, Qsize, adapt=False))
+    # a point's starting map, leaf by leaf (Engine.sweep_map_doubles): four grids, then the Discrete leaf's accumulation and distribution
+    uniform = np.full(Qsize, 1.0 / Qsize)
+    maps = [np.concatenate([np.linspace(0.0, hi, ninc) for hi in (1.0, PI, 2 * PI, p.beta)] + [np.concatenate([[0.0], np.cumsum(uniform)]), uniform])
+            for p in scan]
+    results = mci.integrate_sweep(bubble, params=scan, leaves="all", maps=maps, measure=q_histogram, var=var, dof=[[1, 1, 1, 1, 1]],
+                                  obs=[np.zeros(Qsize)], solver="vegas", neval=1e5, niter=10, seed=7)
+    print("bubble batched:", all(r.sweep_batched for r in results), "| %.2f ms for %d points" % (1e3 * results[0].seconds, len(scan)))
+    print("%6s  %s" % ("rs", "  ".join("q = %.1f kF: avg +- err      " % (q[0] / scan[0].kF) for q in scan[0].extQ)))
+    for p, r in list(zip(scan, results))[::max(1, points // 8)]:
+        print("%6.3f  %s" % (p.rs, "  ".join("%12.6f +- %-10.6f" % (r.mean[0][i], r.stdev[0][i]) for i in range(Qsize))))
+    return scan, results
+
+
 if __name__ == "__main__":
     main()
+    bubble_scan()

@@ -42,6 +42,10 @@ enum { MCI_VEGASMC_LANES = 5, MCI_MCMC_LANES = 6 };
 enum { MCI_VEGAS_STRAT = 7 };
 /* ... and the sweep kernel of mci_integrate_sweep (layouts mci_sweep_supported accepts) */
 enum { MCI_VEGAS_SWEEP = 8 };
+/* ... and the sweep kernel for several variable leaves (problems that opted in with mci_set_sweep_leaves and are no one-grid layout) */
+enum { MCI_VEGAS_SWEEP_LEAVES = 9 };
+/* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
+enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
 typedef struct mci_ctx mci_ctx;
 typedef struct mci_problem mci_problem;
@@ -242,6 +246,9 @@ int mci_integrate(mci_problem *prob, const mci_integrate_args *args, mci_result 
  *   seeds     NULL: args->seed for every point (common random numbers: a smooth curve over the scan); else [npoint]
  *   maps_in   NULL: every point starts from the problem's current map; else [npoint][nbin + 1] grids (mci_get_grid's layout)
  *   maps_out  NULL or [npoint][nbin + 1]: every point's map after its last iteration (== its maps_in row, bit for bit, with adapt = 0)
+ *             A problem of several leaves (mci_set_sweep_leaves) has rows of mci_sweep_map_doubles doubles in both: the leaves in
+ *             order, a Continuous leaf its nbin + 1 grid points, a Discrete leaf its accumulation [nbin + 1] and then its
+ *             distribution [nbin]; for one Continuous leaf that is the nbin + 1 above.
  *   results   [npoint], arrays caller-allocated as for mci_integrate (iter_mean / iter_std / visited may be NULL)
  *   iter_mean, iter_std   NULL or [npoint][niter][nobs]
  *   status    NULL or [npoint]: what the device flagged for that point, bits 1 block normalization (main.jl:269-271) | 2 histogram not
@@ -260,6 +267,16 @@ int mci_integrate_sweep(mci_problem *prob, const mci_integrate_args *args, int32
  * deterministic mode, more than one variable leaf, a Discrete or FermiK leaf, tables that do not sit in LDS in one tile, or more than
  * 64 KiB of LDS with the workgroup's copy of the map.  The number of draws per sample is no reason. */
 int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* Which problems run as a sweep.  MCI_SWEEP_ONE_GRID (default): one Continuous leaf, as described above.  MCI_SWEEP_ALL_LEAVES: also
+ * any :vegas problem whose leaves are all Continuous or Discrete (FermiK: "vegas doesn't work with FermiK"), with the tables and the
+ * histograms in LDS in one tile and at most 159 KiB of LDS for the sample tables or the refinement scratch of the largest leaf plus the
+ * point's whole map (mci_sweep_supported names the byte count beyond); measurefreq = 1, one rank, no stratification, no host
+ * integrand or measure and no deterministic mode as before.  Such a problem runs a kernel of its own (MCI_VEGAS_SWEEP_LEAVES: every
+ * leaf's train! per iteration, Discrete leaves included, each refused on its own histogram); a problem with one Continuous leaf runs the
+ * same kernel and code object under either mode. */
+int mci_set_sweep_leaves(mci_problem *prob, int32_t mode);
+/* doubles of one maps_in / maps_out row of mci_integrate_sweep for this problem (nbin + 1 for one Continuous leaf) */
+int mci_sweep_map_doubles(const mci_problem *prob, int32_t *n);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

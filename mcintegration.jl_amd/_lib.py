@@ -89,6 +89,8 @@ SIGNATURES = [
     ("mci_integrate_sweep", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
                                       C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_sweep_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
+    ("mci_set_sweep_leaves", C.c_int, [_VP, C.c_int32]),
+    ("mci_sweep_map_doubles", C.c_int, [_VP, c_int32_p]),
     ("mci_get_iteration_log", C.c_int, [_VP, C.c_int32, c_double_p]),
     ("mci_reserve_iteration_log", C.c_int, [_VP, C.c_int32]),
     ("mci_get_packed", C.c_int, [_VP, c_double_p, C.c_int64]),
@@ -171,6 +173,7 @@ DEBUG_SIGNATURES = [
     ("mci_debug_sweep_workgroups", C.c_int, [_VP, C.c_int32]),
     ("mci_debug_sweep_threads", C.c_int, [_VP, C.c_int32]),
     ("mci_debug_sweep_last_launch", C.c_int, [_VP, c_int32_p, c_int32_p]),
+    ("mci_debug_sweep_lds_bytes", C.c_int, [_VP, C.POINTER(C.c_int64)]),
 ]
 
 _lib = None

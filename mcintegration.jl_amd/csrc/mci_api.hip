@@ -31,6 +31,7 @@
 #include "mci_check.h" // k_check_vegas: the static yardstick of new :vegas code objects
 #include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
 #include "mci_sweep.h" // SweepArgs (likewise)
+#include "mci_sweep_leaves.h" // SweepLeavesArgs (likewise)
 
 namespace {
 

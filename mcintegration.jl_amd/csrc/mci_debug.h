@@ -79,6 +79,8 @@ int mci_debug_sweep_workgroups(mci_problem *prob, int32_t g);
 int mci_debug_sweep_threads(mci_problem *prob, int32_t threads);
 /* workgroups and threads per workgroup of the problem's last sweep launch */
 int mci_debug_sweep_last_launch(const mci_problem *prob, int32_t *workgroups, int32_t *threads);
+/* (tools/sweep_bench.py) dynamic LDS bytes per workgroup of this problem's sweeps under its present mci_set_sweep_leaves mode */
+int mci_debug_sweep_lds_bytes(const mci_problem *prob, int64_t *bytes);
 #ifdef __cplusplus
 }
 #endif

@@ -547,6 +547,11 @@ int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n)
         snprintf(buf, (size_t)n, "%s", p->sweep.code_object.c_str());
         return MCI_OK;
     }
+    if (solver == MCI_VEGAS_SWEEP_LEAVES) {
+        if (!p->sweep.leaves.compiled) return fail(MCI_ERR_INVALID, "the sweep kernel for several leaves has not been compiled yet");
+        snprintf(buf, (size_t)n, "%s", p->sweep.leaves.code_object.c_str());
+        return MCI_OK;
+    }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
     const int slot = (solver == MCI_VEGAS && !p->compiled[solver] && p->compiled[kSlotVegasAny]) ? kSlotVegasAny : solver;
     if (!p->compiled[slot]) return fail(MCI_ERR_INVALID, "solver %d has not been compiled yet", solver);
@@ -696,6 +701,8 @@ static int compile_persist(mci_problem *p, bool background);
 static bool persist_layout_ok(const mci_problem *p);
 static int compile_strat(mci_problem *p); // (mci_host_strat.h)
 static int compile_sweep(mci_problem *p); // (mci_host_sweep.h)
+static int compile_sweep_leaves(mci_problem *p);
+static bool sweep_leaves_unit(const mci_problem *p);
 int mci_compile_solver(mci_problem *p, int32_t solver) {
     if (solver == MCI_VEGAS_PERSISTENT) { // the persistent :vegas kernel (mci_set_persistent), for layouts that allow it
         if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
@@ -712,7 +719,17 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         a.measurefreq = 1;
         a.niter = 1;
         if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
+        if (sweep_leaves_unit(p)) return fail(MCI_ERR_INVALID, "a sweep of this problem runs the sweep kernel for several leaves (MCI_VEGAS_SWEEP_LEAVES; mci_set_sweep_leaves)");
         return compile_sweep(p);
+    }
+    if (solver == MCI_VEGAS_SWEEP_LEAVES) { // (mci_host_sweep.h: the problem has opted in, mci_set_sweep_leaves, and is no one-grid layout)
+        mci_integrate_args a{};
+        a.solver = MCI_VEGAS;
+        a.measurefreq = 1;
+        a.niter = 1;
+        if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
+        if (!sweep_leaves_unit(p)) return fail(MCI_ERR_INVALID, "a sweep of this problem runs the one-grid sweep kernel (MCI_VEGAS_SWEEP; mci_set_sweep_leaves)");
+        return compile_sweep_leaves(p);
     }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver); // main.jl:263
     return compile_solver(p, solver);

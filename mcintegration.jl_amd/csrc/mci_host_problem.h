@@ -395,6 +395,7 @@ int mci_problem_destroy(mci_problem *p) {
         if (p->module_persist) (void)hipModuleUnload(p->module_persist);
         if (p->strat.module) (void)hipModuleUnload(p->strat.module);
         if (p->sweep.module) (void)hipModuleUnload(p->sweep.module);
+        if (p->sweep.leaves.module) (void)hipModuleUnload(p->sweep.leaves.module);
         strat_free_buffers(p);
         if (p->d_persist) (void)hipFree(p->d_persist);
     }

@@ -1,11 +1,59 @@
 // mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
-// batched :vegas parameter sweeps -- eligibility, the sweep unit's JIT, the one launch and the P results (mci_sweep.h vegas_sweep).
+// batched :vegas parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
+// one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in).
 namespace {
 // Points of one sweep, and the device memory one may take.  Per point the launch holds the userdata row, a seed, two maps, niter log
 // rows, nblocks partial rows and as much merge scratch, a statistics head, a histogram row and a status word: ~25 KB at the
 // reference's sizes (999 increments, 16 blocks, 10 iterations), 1.6 GB at 65536 points.
 const int32_t kSweepMaxPoints = 65536;
 const int64_t kSweepMaxBytes = (int64_t)4 << 30;
+
+// LDS of the sweep kernel for several leaves (mci_sweep_leaves.h), bytes: the sample loop's carve in the plain layout (tables in LDS,
+// one histogram copy -- what that layout WOULD take where the problem was given another one, so that the refusal can name the count) or
+// the refinement's scratch for the largest leaf, whichever is larger, and behind them (map_off, doubles) the point's map block
+// edges | dacc | ddist | flags[4], each part on 16 bytes (SweepBlock)
+int sweep_max_nbin(const mci_problem *p) {
+    int n = 1;
+    for (const Leaf &L : p->leaves) n = L.nbin > n ? L.nbin : n;
+    return n;
+}
+int64_t sweep_leaves_lds(const mci_problem *p, int *map_off) {
+    const auto &s = p->shape;
+    const int maxn = sweep_max_nbin(p);
+    const int64_t plain = (int64_t)s.ndacc + s.nddist + s.nobs + 16 * (int64_t)s.ncols + 2 * (int64_t)p->npa + s.nedge + s.nbin;
+    const int64_t a = s.table_mode == 0 && s.ntile == 1 && s.ec_doubles == 0 ? (p->lds_bytes + 7) / 8 : plain;
+    const int64_t b = (int64_t)mci::train_lds_doubles(maxn) + maxn + 256;
+    const int64_t off = ((a > b ? a : b) + 1) & ~(int64_t)1;
+    if (map_off) *map_off = (int)off;
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    return (off + even(s.nedge) + even(s.ndacc) + even(s.nddist) + 4) * 8;
+}
+// doubles of one maps_in / maps_out row: the leaves in order, a grid's nbin + 1 points, a Discrete leaf's accumulation [nbin + 1] and
+// distribution [nbin] (mci_sweep_leaves.h sweep_row_off)
+int64_t sweep_map_doubles(const mci_problem *p) {
+    int64_t n = 0;
+    for (const Leaf &L : p->leaves) n += L.kind == MCI_CONTINUOUS ? L.nbin + 1 : 2 * L.nbin + 1;
+    return n;
+}
+const int64_t kSweepLeavesMaxLds = 159 * 1024;
+// what is left to check of a problem that opted in to sweeps over all its leaves and is no one-grid layout
+const char *sweep_leaves_refusal(const mci_problem *p, std::string &buf) {
+    const auto &s = p->shape;
+    if (p->has_fermik) return "a FermiK variable (vegas doesn't work with FermiK)";
+    for (const Leaf &L : p->leaves)
+        if (L.kind != MCI_CONTINUOUS && L.kind != MCI_DISCRETE) return "a FermiK variable (vegas doesn't work with FermiK)";
+    if (p->leaves.empty() || s.nleaf != (int)p->leaves.size() || s.nbin <= 0) return "no variable leaves";
+    const int64_t lds = sweep_leaves_lds(p, nullptr);
+    if (lds > kSweepLeavesMaxLds) {
+        buf = "the sample tables, the refinement scratch and the point's map take " + std::to_string((long long)lds) + " bytes of LDS (" +
+              std::to_string((long long)kSweepLeavesMaxLds) + " at most)";
+        return buf.c_str();
+    }
+    if (s.table_mode != 0 || s.ntile != 1 || s.ec_doubles > 0) return "the tables and their histograms do not sit in LDS in one tile";
+    return nullptr;
+}
+// the unit a sweep of this problem runs: the one-grid kernel wherever it applies, opted in or not
+bool sweep_uses_leaves(const mci_problem *p) { return p->sweep.leaves_mode == MCI_SWEEP_ALL_LEAVES && !persist_layout(p); }
 
 // Eligibility: persist_layout exactly (one Continuous leaf, table mode 0, one tile, device-source integrand and measure, not
 // deterministic, within 64 KiB including the map copy), measurefreq == 1, one rank.  NOT the draw count: `ndraw <= 7` is
@@ -23,6 +71,7 @@ const char *sweep_refusal(const mci_problem *p, const mci_integrate_args *a, std
     if (s.host_integrand) return "a host integrand (device source or a traced closure only)";
     if (s.host_measure) return "a host measure (device source only)";
     if (p->deterministic) return "deterministic mode";
+    if (p->sweep.leaves_mode == MCI_SWEEP_ALL_LEAVES && !persist_layout(p)) return sweep_leaves_refusal(p, buf); // (opted in: mci_set_sweep_leaves)
     if (s.nleaf != 1 || p->leaves.size() != 1) {
         buf = std::to_string(s.nleaf) + " variable leaves (a sweep point refines ONE Continuous grid)";
         return buf.c_str();
@@ -109,6 +158,50 @@ static int compile_sweep(mci_problem *p) {
     return MCI_OK;
 }
 
+static bool sweep_leaves_unit(const mci_problem *p) { return sweep_uses_leaves(p); }
+
+// the unit of mci_sweep_leaves.h: 256 threads, one histogram copy, every leaf's learning rate read at run time
+static int compile_sweep_leaves(mci_problem *p) {
+    auto &u = p->sweep.leaves;
+    if (u.compiled) return MCI_OK;
+    Candidate c;
+    mcijit::ProblemShape sh = p->shape;
+    sh.hcopy = 1;
+    sh.det = 0;
+    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweepLeaves);
+    c.threads = kSweepThreads;
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweepLeaves);
+    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel, several leaves):\n%s", c.log.c_str());
+    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep_leaves") != 0)
+        return fail(MCI_ERR_COMPILE, "the sweep kernel for several leaves came out with static LDS or scratch at %d threads per workgroup", kSweepThreads);
+    u.code_object = c.path;
+    u.threads = kSweepThreads;
+    if (!p->ctx->offline) {
+        HIPCHK(hipSetDevice(p->ctx->device));
+        if (hipModuleLoadData(&u.module, c.code.data()) != hipSuccess) {
+            if (c.cached) unlink(c.path.c_str());
+            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object (several leaves)");
+        }
+        HIPCHK(hipModuleGetFunction(&u.f, u.module, "mci_vegas_sweep_leaves"));
+        const int64_t lds = sweep_leaves_lds(p, nullptr);
+        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    u.compiled = true;
+    return MCI_OK;
+}
+
+int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
+    if (!p || (mode != MCI_SWEEP_ONE_GRID && mode != MCI_SWEEP_ALL_LEAVES)) return fail(MCI_ERR_INVALID, "sweep leaves: MCI_SWEEP_ONE_GRID (0) or MCI_SWEEP_ALL_LEAVES (1)");
+    p->sweep.leaves_mode = mode;
+    return MCI_OK;
+}
+
+int mci_sweep_map_doubles(const mci_problem *p, int32_t *n) {
+    if (!p || !n) return fail(MCI_ERR_INVALID, "NULL argument");
+    *n = (int32_t)sweep_map_doubles(p);
+    return MCI_OK;
+}
+
 int mci_sweep_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
     if (why && n > 0) why[0] = 0;
     if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
@@ -137,6 +230,12 @@ int mci_debug_sweep_last_launch(const mci_problem *p, int32_t *workgroups, int32
     return MCI_OK;
 }
 
+int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
+    if (!p || !bytes) return fail(MCI_ERR_INVALID, "NULL argument");
+    *bytes = sweep_uses_leaves(p) ? sweep_leaves_lds(p, nullptr) : persist_lds(p, nullptr);
+    return MCI_OK;
+}
+
 // P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
 int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                         double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
@@ -155,8 +254,9 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
     int64_t nevalperblock, block;
     mci_standardize_block(a->neval, a->block, 1, &nevalperblock, &block); // main.jl:121
     if (block > (int64_t)1 << 20) return fail(MCI_ERR_INVALID, "block = %lld: too many blocks for a sweep", (long long)block);
-    const int N = p->leaves[0].nbin, nstat = p->nstat, niter = a->niter;
-    const size_t P = (size_t)npoint, nmap = (size_t)N + 1, rows = (size_t)block * s.ncols;
+    const bool lv = sweep_uses_leaves(p); // (else one Continuous leaf: a row is its grid)
+    const int N = sweep_max_nbin(p), nstat = p->nstat, niter = a->niter;
+    const size_t P = (size_t)npoint, nmap = (size_t)sweep_map_doubles(p), rows = (size_t)block * s.ncols;
     // one buffer (doubles, then the 8-byte seeds, then the status words)
     const size_t o_ud = 0, o_in = o_ud + P * (size_t)nud, o_out = o_in + (maps_in ? P * nmap : 0), o_log = o_out + P * nmap,
                  o_part = o_log + P * (size_t)niter * nstat, o_scr = o_part + P * rows, o_pk = o_scr + P * rows, o_gh = o_pk + P * (size_t)nstat,
@@ -164,7 +264,7 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
     if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
         return fail(MCI_ERR_INVALID, "a sweep of %d points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it",
                     (int)npoint, niter, (long long)block, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
-    if ((rc = compile_sweep(p))) return rc;
+    if ((rc = lv ? compile_sweep_leaves(p) : compile_sweep(p))) return rc;
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
     void *base = nullptr;
@@ -199,60 +299,69 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
         b.status = reinterpret_cast<int *>(d + o_st);
         b.tile_stride = block * nevalperblock;
         b.nrows = block;
-        mci::SweepArgs f{};
-        mci::MergeArgs &m = f.m;
-        m.part_cols = d + o_part;
-        m.ncols = s.ncols;
-        m.nobs = s.nobs;
-        m.ni = s.ni;
-        m.nblocks = (int)block;
-        m.wg_per_block = 1;
-        m.stage1 = nullptr;
-        m.ngroup = 0;
-        m.ghist = d + o_gh;
-        m.use_ghist = 1;
-        m.nbin = s.nbin;
-        m.packed = d + o_pk;
-        m.status = b.status;
-        m.scratch = d + o_scr;
-        m.part_pa = nullptr;
-        m.npa = 0;
-        m.nrows = (int)block;
-        mci::TrainArgs &t = f.t;
-        t.leaves = p->d_leaves;
-        t.nleaf = s.nleaf;
-        t.packed = d + o_pk;
-        t.nstat = nstat;
-        t.edges = p->d_edges;
-        t.dacc = p->d_dacc;
-        t.ddist = p->d_ddist;
-        t.iter_log_row = d + o_log;
-        t.reweight = nullptr;
-        t.goal = nullptr;
-        t.nd = s.ni + 1;
-        t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
-        t.gamma = a->gamma;
-        t.do_train = a->adapt ? 1 : 0;
-        t.serial_walk = 0;
-        t.status = b.status;
-        t.maxn = N;
-        f.npoint = npoint;
-        f.niter = niter;
-        f.nuserdata = nud;
-        const int64_t lds = persist_lds(p, &f.map_off);
-        f.ud = d + o_ud;
-        f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
-        f.maps_in = maps_in ? d + o_in : nullptr;
-        f.maps_out = d + o_out;
+        mci::SweepArgs f1{};
+        mci::SweepLeavesArgs fl{};
+        int64_t lds = 0;
+        auto fill = [&](auto &f) { // (SweepArgs and SweepLeavesArgs carry the same fields)
+            mci::MergeArgs &m = f.m;
+            m.part_cols = d + o_part;
+            m.ncols = s.ncols;
+            m.nobs = s.nobs;
+            m.ni = s.ni;
+            m.nblocks = (int)block;
+            m.wg_per_block = 1;
+            m.stage1 = nullptr;
+            m.ngroup = 0;
+            m.ghist = d + o_gh;
+            m.use_ghist = 1;
+            m.nbin = s.nbin;
+            m.packed = d + o_pk;
+            m.status = b.status;
+            m.scratch = d + o_scr;
+            m.part_pa = nullptr;
+            m.npa = 0;
+            m.nrows = (int)block;
+            mci::TrainArgs &t = f.t;
+            t.leaves = p->d_leaves;
+            t.nleaf = s.nleaf;
+            t.packed = d + o_pk;
+            t.nstat = nstat;
+            t.edges = p->d_edges;
+            t.dacc = p->d_dacc;
+            t.ddist = p->d_ddist;
+            t.iter_log_row = d + o_log;
+            t.reweight = nullptr;
+            t.goal = nullptr;
+            t.nd = s.ni + 1;
+            t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
+            t.gamma = a->gamma;
+            t.do_train = a->adapt ? 1 : 0;
+            t.serial_walk = 0;
+            t.status = b.status;
+            t.maxn = N;
+            f.npoint = npoint;
+            f.niter = niter;
+            f.nuserdata = nud;
+            lds = lv ? sweep_leaves_lds(p, &f.map_off) : persist_lds(p, &f.map_off);
+            f.ud = d + o_ud;
+            f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
+            f.maps_in = maps_in ? d + o_in : nullptr;
+            f.maps_out = d + o_out;
+        };
+        if (lv) fill(fl);
+        else fill(f1);
         // workgroups: two per CU keep a CU's SIMDs busy while one of them sits in its refinement; any grid runs any npoint
         int cus = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
-        int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : 2 * (int64_t)(cus > 0 ? cus : 256);
+        // (several leaves: a map block that leaves no room for two workgroups in a CU's 160 KiB of LDS gets one)
+        const int per_cu = lv && lds > 80 * 1024 ? 1 : 2;
+        int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
         if (grid > npoint) grid = npoint;
-        void *args[] = {&b, &f};
-        HIPCHK(hipModuleLaunchKernel(p->sweep.f, (unsigned)grid, 1, 1, (unsigned)p->sweep.threads, 1, 1, (unsigned)lds, st, args, nullptr));
+        void *args[] = {&b, lv ? (void *)&fl : (void *)&f1};
+        const int threads = lv ? p->sweep.leaves.threads : p->sweep.threads;
+        HIPCHK(hipModuleLaunchKernel(lv ? p->sweep.leaves.f : p->sweep.f, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, st, args, nullptr));
         p->sweep.last_grid = (int)grid;
-        p->sweep.last_threads = p->sweep.threads;
+        p->sweep.last_threads = threads;
         HIPCHK(hipMemcpyAsync(hlog.data(), d + o_log, hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hst.data(), d + o_st, P * sizeof(int), hipMemcpyDeviceToHost, st));
         if (maps_out) HIPCHK(hipMemcpyAsync(maps_out, d + o_out, P * nmap * sizeof(double), hipMemcpyDeviceToHost, st));

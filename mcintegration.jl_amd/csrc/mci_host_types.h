@@ -379,6 +379,16 @@ struct mci_problem {
         int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
         int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default
         int last_grid = 0, last_threads = 0;
+        // mci_set_sweep_leaves: MCI_SWEEP_ONE_GRID (a sweep point refines ONE Continuous grid, the unit above) or MCI_SWEEP_ALL_LEAVES
+        // (a problem that is no one-grid layout runs the unit of mci_sweep_leaves.h, a code object of its own)
+        int leaves_mode = 0;
+        struct Unit {
+            bool compiled = false;
+            int threads = 0;
+            hipModule_t module = nullptr;
+            hipFunction_t f = nullptr;
+            std::string code_object;
+        } leaves;
     } sweep;
 };
 
@@ -625,6 +635,12 @@ void drop_modules(mci_problem *p) {
     if (p->sweep.module) {
         (void)hipModuleUnload(p->sweep.module);
         p->sweep.module = nullptr;
+    }
+    p->sweep.leaves.compiled = false;
+    p->sweep.leaves.f = nullptr;
+    if (p->sweep.leaves.module) {
+        (void)hipModuleUnload(p->sweep.leaves.module);
+        p->sweep.leaves.module = nullptr;
     }
 }
 

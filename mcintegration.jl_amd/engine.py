@@ -439,13 +439,14 @@ class Engine:
     # ---- kernels -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_code(solver):
-        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8}.get(solver) or _lib.SOLVERS[solver]
+        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
         "vegasmc_lanes" | "mcmc_lanes" (the chain solvers' kernels with several lanes per chain, csrc/mci_spec.h) | "vegas_strat" (the
         stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification) | "vegas_sweep" (the kernel of
-        integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts)"""
+        integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts) | "vegas_sweep_leaves" (the sweep kernel of a problem with
+        several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all"))"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -719,11 +720,40 @@ class Engine:
 
     SWEEP_MAX_POINTS = 65536   # include/mci.h mci_integrate_sweep
 
+    def set_sweep_leaves(self, mode="one"):
+        """which problems integrate_sweep takes (mci_set_sweep_leaves): "one" (default) = one Continuous leaf; "all" = also any mix of
+        Continuous and Discrete leaves whose tables, histograms and map fit a workgroup's LDS -- those run a kernel of their own
+        (compile("vegas_sweep_leaves")); sweep_supported() names what still keeps a problem out"""
+        if mode not in ("one", "all"):
+            raise ValueError('set_sweep_leaves: "one" or "all", got %r' % (mode,))
+        check(lib().mci_set_sweep_leaves(self.p, 1 if mode == "all" else 0))
+
+    def sweep_map_doubles(self):
+        """doubles of one `maps` row of integrate_sweep (mci_sweep_map_doubles): the leaves in order, a Continuous leaf its grid, a
+        Discrete leaf its accumulation and then its distribution"""
+        n = C.c_int32()
+        check(lib().mci_sweep_map_doubles(self.p, C.byref(n)))
+        return int(n.value)
+
+    def _split_sweep_map(self, row):
+        """a flat `maps` row -> per leaf: the grid of a Continuous leaf, the distribution of a Discrete one"""
+        out, o = [], 0
+        for lf in self.config.leaves:
+            if hasattr(lf, "ninc"):
+                out.append(row[o:o + lf.ninc])
+                o += lf.ninc
+            else:   # accumulation [n + 1] | distribution [n]
+                n = lf.upper - lf.lower + 1
+                out.append(row[o + n + 1:o + 2 * n + 1])
+                o += 2 * n + 1
+        return out
+
     def integrate_sweep(self, solver="vegas", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1,
                         seed=1234, seeds=None, maps=None, first_iteration=0):
         """A parameter sweep in one launch (mci_integrate_sweep): userdata [P][nuserdata], one row per point -- what an ordinary call
         would have been given as the integrand's userdata.  Returns a list of P result dicts with the keys of integrate() plus `maps`
-        (the point's map after its last iteration) and `status` (the bits the device flagged for that point; 0 = none).  seed: the same
+        (the point's map after its last iteration: the flat row of sweep_map_doubles() doubles), `maps_by_leaf` (that row leaf by leaf:
+        the grid of a Continuous leaf, the distribution of a Discrete one) and `status` (the bits the device flagged for that point; 0 = none).  seed: the same
         for every point (common random numbers), or seeds = P of them; maps: None (every point starts from the engine's current map)
         or [P][grid points] starting maps (the layout of grid()).  The engine's own map, packed buffer and logs are not touched.  Raises MCIError naming the
         reason when the problem or the arguments cannot run as a sweep (sweep_supported): nothing else runs in its place."""
@@ -740,12 +770,11 @@ class Engine:
             sd = np.ascontiguousarray(seeds, dtype=np.uint64)
             if sd.shape != (P,):
                 raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got shape %s" % (P, sd.shape))
-        leaves = self.config.leaves
-        nmap = leaves[0].ninc if len(leaves) == 1 and hasattr(leaves[0], "ninc") else 0
+        nmap = self.sweep_map_doubles()
         mi = None
         if maps is not None:
             mi = np.ascontiguousarray(maps, dtype=np.float64)
-            if nmap and mi.shape != (P, nmap):
+            if mi.shape != (P, nmap):
                 raise ValueError("integrate_sweep: maps must be [points = %d][grid points = %d], got shape %s" % (P, nmap, mi.shape))
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
         n = self.nobs
@@ -761,7 +790,8 @@ class Engine:
                                         sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
                                         _dp(mi) if mi is not None else None, _dp(mo), res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
         return [dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
-                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q], status=int(st[q]))
+                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
+                     maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]))
                 for q in range(P)]
 
     def sweep_workgroups(self, g=0):
@@ -777,6 +807,12 @@ class Engine:
         g, t = C.c_int32(), C.c_int32()
         check(lib().mci_debug_sweep_last_launch(self.p, C.byref(g), C.byref(t)))
         return int(g.value), int(t.value)
+
+    def sweep_lds_bytes(self):
+        """LDS bytes a workgroup of this problem's sweeps takes (csrc/mci_debug.h; tools/sweep_bench.py)"""
+        n = C.c_int64()
+        check(lib().mci_debug_sweep_lds_bytes(self.p, C.byref(n)))
+        return int(n.value)
 
     def mcmc_launch_valid(self):
         """(the last automatic :mcmc launch was long enough for the holds it measured, some launch of this problem has been, its chain

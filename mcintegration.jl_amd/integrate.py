@@ -356,8 +356,63 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     return res
 
 
+class _MeasureConfig:
+    """the configuration a sweep's measure closure is traced on: point 0's, with every read off config.userdata on record"""
+
+    def __init__(self, config, userdata, rec):
+        from . import trace as tr
+        self._config, self._rec, self._touched = config, rec, False
+        self._plain = userdata
+        self._view = tr._userdata_view(userdata, rec, False, ())
+        self._lazy = isinstance(self._view, tr._UserdataView)   # (anything else -- a number, an array -- is read the moment it is touched)
+        if not self._lazy:
+            del rec.literals[:]
+
+    def __getattr__(self, name):
+        return getattr(self._config, name)
+
+    @property
+    def userdata(self):
+        self._touched = True
+        return self._view if self._lazy else self._plain
+
+    def reads(self):
+        if self._lazy:
+            return list(self._rec.literals)
+        return [((), self._plain)] if self._touched and self._plain is not None else []
+
+
+def _trace_sweep_measure(measure, traced_on, params, solver):
+    """The measure closure of a sweep, traced on the configuration the integrand was traced on (point 0).  A sweep has ONE ud row per
+    point and that row is the integrand's: a measure whose body would hold a value read off config.userdata -- a float, an array -- is
+    refused with a ValueError naming it, and so is one that reads anything else (an int, a string) in which the points differ.
+    Returns the traced Measure, or None when the closure does not trace (it is then bound like any other closure)."""
+    from . import trace as tr
+    rec = tr._Trace()
+    mcfg = _MeasureConfig(traced_on, params[0], rec)
+    mindexed = callback_form(measure, solver, what="measure") == "indexed"
+    try:
+        traced = tr.trace_measure(measure, mcfg, indexed=mindexed)
+    except tr.TraceError:
+        traced = None
+    for path, was in mcfg.reads():
+        name = tr._path_name(path)
+        if isinstance(was, (float, np.floating, np.ndarray, list, tuple)) and not isinstance(was, bool):
+            raise ValueError("integrate_sweep: the measure reads %s off config.userdata, and its value would be written into the measure's "
+                             "body: a sweep has one ud row per point, and that row is the integrand's" % name)
+        for q in params[1:]:
+            try:
+                now = tr._reach(q, path)
+            except Exception as e:
+                raise ValueError("integrate_sweep: the measure reads %s, which cannot be read at every point (%s: %s)" % (name, type(e).__name__, e))
+            if not tr._same_leaf(was, now):
+                raise ValueError("integrate_sweep: the measure reads %s, which is %r at the traced point and %r at another: the points "
+                                 "would trace to different measure bodies" % (name, was, now))
+    return traced
+
+
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
-                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, **kwargs):
+                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -369,11 +424,17 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     ints, bools, strings, non-finite floats and array shapes the closure reads off userdata are written into the body, so points that
     differ in one of them (`Para(a=2)` next to `Para(a=3)`: write 2.0, 3.0), and a closure whose body depends on the values, are
     refused with a ValueError naming the field -- never run on the body of point 0.  For a device-source string or an Integrand (mci.catalog) they are the
-    userdata rows.  maps: None or [P][grid points] starting maps; every Result carries `map` (the point's map after its last iteration),
-    `status` (device flags of that point, 0 = none) and `sweep_batched`.
+    userdata rows.  A float array the closure indexes with a Discrete draw (`para.extQ[Ext[0] - 1]`) is a table of the body: every
+    point's row carries its own values, and its shape must be the same at every point.  maps: None or [P][Engine.sweep_map_doubles()]
+    starting maps; every Result carries `map` (the point's map after its last iteration, the flat row), `maps_by_leaf` (leaf by leaf: a
+    Continuous leaf's grid, a Discrete leaf's distribution), `status` (device flags of that point, 0 = none) and `sweep_batched`.
 
-    A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves, a Discrete variable, measurefreq != 1, a
-    host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
+    leaves: "one" (default) sweeps problems with ONE Continuous variable leaf; "all" opts in to sweeps of any mix of Continuous and
+    Discrete leaves that fits a workgroup's LDS (Engine.set_sweep_leaves) -- composites, histograms over a Discrete draw.  A `measure`
+    closure is traced on the same point as the integrand; one that reads a value off config.userdata is refused (ValueError).
+
+    A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
+    measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
     a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
     import copy
     import warnings
@@ -383,6 +444,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         solver = solver[1:]
     if solver not in SOLVERS:
         raise ValueError("Solver %s is not supported!" % solver)
+    if leaves not in ("one", "all"):
+        raise ValueError('integrate_sweep: leaves must be "one" or "all", got %r' % (leaves,))
     try:
         P = len(params)
     except TypeError:
@@ -416,6 +479,9 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             rows = np.array([bound.userdata_for(p) for p in params], dtype=np.float64).reshape(P, len(bound.userdata))
         except tr.TraceError as e:
             why = "the closure was not traced (%s): a host integrand" % e
+        bound_measure = measure
+        if why is None and trace is not False and callable(measure) and not isinstance(measure, (Measure, HostMeasure)) and not hasattr(measure, "pool"):
+            bound_measure = _trace_sweep_measure(measure, traced_on, params, solver) or measure
     else:
         if isinstance(integrand, str):
             integrand = Integrand(integrand, None)
@@ -432,7 +498,9 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     nevalperblock, block = standardize_block(int(neval), block, 1)
     eng = None
     if why is None:
-        eng = _bind(config, bound, measure, solver, trace=trace, print=print, device=device)
+        eng = _bind(config, bound, bound_measure if closure else measure, solver, trace=trace, print=print, device=device)
+        if hasattr(eng, "set_sweep_leaves"):
+            eng.set_sweep_leaves(leaves)
         why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
     if why is None:
         rs = eng.integrate_sweep(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
@@ -445,6 +513,7 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             c.visited = r["visited"]
             res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block)
             res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
+            res.maps_by_leaf = r.get("maps_by_leaf")
             res.stratification, res.vegas_check, res.warmup, res.neval_discarded = None, None, 0, 0
             if print >= 0:
                 report(res)
@@ -472,7 +541,7 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             c.seed = int(seeds[k])
         res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
                         measurefreq=measurefreq, device=device, trace=trace, print=print)
-        res.sweep_batched, res.map, res.status = False, None, 0
+        res.sweep_batched, res.map, res.maps_by_leaf, res.status = False, None, None, 0
         out.append(res)
     return out
 
@@ -500,6 +569,8 @@ def prefill_kernel_cache():
         if meas is not None:
             eng.compile("vegasmc")  # C3 is a :vegasmc config
             eng.compile("vegasmc_lanes")   # ... whose launches of few chains (the example's neval = 1e6) give every chain a group of lanes
+            eng.set_sweep_leaves("all")    # ... and which is scanned over rs as one launch (integrate_sweep(..., leaves="all"))
+            eng.compile("vegas_sweep_leaves")
         eng.close()
         n += 1
     # C5: 4 integrands on a 12-D pool, :mcmc

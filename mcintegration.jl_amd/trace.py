@@ -65,6 +65,7 @@ class _Trace:
         # tested; explore() below enumerates the ways and joins their results with selects.
         self.script, self.conds, self.decided = [], [], []
         self.tables = []      # float arrays the closure indexes with a sampled value (_Table): node ("table", id, j, stride, rows, index)
+        self.table_paths = [] # where tables[k] was read off config.userdata (a path like those of `sources`), None: an array the closure captured
         self.dynamic = []     # trace_measure: `obs[i][sampled index] += value` met by the current run: (observable, index, value)
 
     def decide(self, cond):
@@ -578,13 +579,14 @@ class _Table(np.ndarray):
     0-based like every index here; an index outside the table is clamped (the check against the closure at random points refuses a
     closure that relies on anything else, e.g. Python's negative indices)."""
 
-    def __new__(cls, content, t, values=None):
+    def __new__(cls, content, t, values=None, path=None):
         obj = np.asarray(content).view(cls)
         obj._t, obj._values, obj._tid = t, np.ascontiguousarray(content if values is None else values, dtype=np.float64), None
+        obj._path = path                                   # how it is reached from config.userdata (_Trace.table_paths), None: it is not
         return obj
 
     def __array_finalize__(self, obj):
-        self._t = self._values = self._tid = None          # (a slice or a copy is a plain array again)
+        self._t = self._values = self._tid = self._path = None   # (a slice or a copy is a plain array again)
 
     def __getitem__(self, i):
         if isinstance(i, Sym):
@@ -618,6 +620,7 @@ class _Table(np.ndarray):
         if self._tid is None:                               # (one block of ud[] for the table, however it is indexed)
             self._tid = view._tid = len(self._t.tables)
             self._t.tables.append(self._values)
+            self._t.table_paths.append(self._path)
         return view._lookup(flat)
 
     def _lookup(self, idx):
@@ -629,6 +632,7 @@ class _Table(np.ndarray):
         if self._tid is None:
             self._tid = len(t.tables)
             t.tables.append(self._values)
+            t.table_paths.append(self._path)
         rows = self._values.shape[0]
         stride = int(self._values.size // rows) if rows else 0
         if rows == 0:
@@ -694,7 +698,7 @@ def _param_table(v, t, path=None):
     a = np.empty(v.shape, dtype=object)
     for i in np.ndindex(v.shape):
         a[i] = t.param(v[i], None if path is None else path + (("index", i),))
-    return _Table(a, t, values=v)
+    return _Table(a, t, values=v, path=path)
 
 
 def _userdata_view(v, t, floats=False, path=None):
@@ -703,6 +707,8 @@ def _userdata_view(v, t, floats=False, path=None):
         return t.param(v, path)
     tb = _as_table(v, t)
     if tb is not None:
+        if tb is not v:
+            tb._path = path
         if floats and tb._values.size <= 64 and (not isinstance(v, np.ndarray) or v.dtype.kind == "f") and np.all(np.isfinite(tb._values)):
             if path is not None:
                 t.literals.append((path + (("shape", None),), _table_kind(v)))   # (the closure may loop over it)
@@ -1231,7 +1237,7 @@ def _trace_integrand(fn, config, indexed, check_points, name, parameters, inplac
                                  "function of its draws (hidden state, a branch the trace did not see, numpy arithmetic on "
                                  "comparisons that means something else than the same arithmetic on 0.0 / 1.0)" % (i // nc))
     traced = Integrand(body, ud or None, name=name or getattr(fn, "__name__", "traced"))
-    if parameters and not tables:
+    if parameters:
         # integrate_sweep: the ud row of ANOTHER config.userdata object from this one trace -- the parameters read off userdata are read
         # again by their paths, everything else keeps its value, and the hoisted subexpressions are evaluated as hoist() evaluated them
         order = sorted(slots, key=lambda nid: int(slots[nid][3:-1]))
@@ -1262,6 +1268,20 @@ def _trace_integrand(fn, config, indexed, check_points, name, parameters, inplac
                 except Exception as e:
                     raise ValueError("the points would trace to different bodies: parameter %s (%s: %s)" % (_path_name(src), type(e).__name__, e))
             row = [float(evaluate([t.nodes[nid]], np.zeros((0, 1)), params=params)[0][0]) for nid in order]
+            # the tables the body looks into, where trace_integrand appended point 0's: read again by their paths (their shape is a
+            # literal of the body: the row count clamps the index, the stride addresses the row); a captured array keeps its values
+            for tid in tables:
+                was, path = t.tables[tid], t.table_paths[tid]
+                now = was
+                if path is not None:
+                    try:
+                        now = np.asarray(_reach(obj, path), dtype=np.float64)
+                    except Exception as e:
+                        raise ValueError("the points would trace to different bodies: table %s cannot be read (%s: %s)" % (_path_name(path), type(e).__name__, e))
+                    if now.shape != was.shape:
+                        raise ValueError("the points would trace to different bodies: table %s has shape %r at the traced point and %r here "
+                                         "(the shape of a table is written into the body)" % (_path_name(path), was.shape, now.shape))
+                row += [float(v) for v in now.reshape(-1)]
             if not all(math.isfinite(v) for v in row):
                 raise TraceError("a captured parameter evaluates to a non-finite value")
             return row

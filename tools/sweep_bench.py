@@ -3,11 +3,15 @@
     python tools/sweep_bench.py table  [--neval 10000] [--points 1,16,256,1024,4096] [--threads 256]
     python tools/sweep_bench.py threads [--neval 10000] [--points 256,1024] [--repeat 5]
     python tools/sweep_bench.py once --points 1024       (one warm sweep and nothing else: the run a kernel trace is taken of)
+    python tools/sweep_bench.py table --layout bubble [--neval 10000] [--points 1,16,256,1024]      (profiles/r11_sweep_leaves.txt)
 
 The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
 and of the same points as a loop of Engine.integrate calls with the persistent launch, in the same process.
 `threads`: the sweep at 256 / 512 / 1024 threads per workgroup (a size whose kernel would spill is refused by the library: reported),
 the sizes interleaved `--repeat` times so that a drift of the box shows as scatter, not as a difference between sizes.
+`--layout bubble`: the polarisation bubble (catalog.bubble: four Continuous leaves, a Discrete one, a histogram over it) scanned over
+rs, swept with set_sweep_leaves("all") against a loop of ordinary Engine.integrate calls -- what such a scan runs without the opt-in;
+the header line gives the sweep kernel's LDS bytes, workgroups per CU, VGPRs and scratch.
 One GPU process; run each mode under its own time limit."""
 import argparse
 import os
@@ -70,6 +74,64 @@ def time_loop(P, neval):
     return dt * P / n, out
 
 
+# ---- --layout bubble: several variable leaves (csrc/mci_sweep_leaves.h)
+def bubble_point(k):
+    """ud row of scan point k: rs from 1 to 2 (kF and the external momenta follow), the T domain -- the dimensionless beta of point 0 -- fixed"""
+    rs = 1.0 + (k * 0.37) % 1.0
+    p = mci.catalog.bubble_parameters(rs=rs)
+    return [p["kF"], mci.catalog.bubble_parameters()["beta"], p["me"], float(p["spin"]), float(p["dim"]), float(p["Qsize"])] + list(p["extQ"])
+
+
+def bubble_engine(ud, leaves="one"):
+    import math
+    beta = mci.catalog.bubble_parameters()["beta"]
+    var = (mci.Continuous(0.0, 1.0, alpha=3.0), mci.Continuous(0.0, math.pi, alpha=3.0), mci.Continuous(0.0, 2 * math.pi, alpha=3.0),
+           mci.Continuous(0.0, beta, alpha=3.0), mci.Discrete(1, 4, adapt=False))
+    cfg = mci.Configuration(var=var, dof=[[1, 1, 1, 1, 1]], obs=[np.zeros(4)], seed=SEED)
+    eng = mci.Engine(cfg, mci.Integrand(mci.catalog.bubble().body, ud, "bubble"), measure=mci.bin_by(4))
+    eng.set_sweep_leaves(leaves)
+    return eng
+
+
+def bubble_table(Ps, neval):
+    from mcintegration_jl_amd import isa_mix
+    eng = bubble_engine(bubble_point(0), "all")
+    assert eng.sweep_supported() is None
+    eng.compile("vegas_sweep_leaves")
+    res = isa_mix.resources(eng.code_object("vegas_sweep_leaves"))["mci_vegas_sweep_leaves"]
+    lds = eng.sweep_lds_bytes()
+    print("# bubble (4 Continuous leaves of 999 increments + Discrete(1, 4), q histogram), neval = %d, niter = %d, block = %d" % (neval, NITER, BLOCK))
+    print("# mci_vegas_sweep_leaves: %d bytes of LDS per workgroup -> %d workgroup(s) per CU, %d VGPRs, %d bytes of scratch"
+          % (lds, 2 if lds <= 80 * 1024 else 1, res["vgpr"], res["scratch"]))
+    print("# sweep | loop of ordinary calls, ms (us per point-iteration) | loop / sweep")
+    loop_eng = bubble_engine(bubble_point(0))
+    g0 = [loop_eng.grid(l).copy() for l in range(4)]
+    kw = dict(neval=neval, niter=NITER, block=BLOCK, seed=SEED)
+    loop_eng.integrate("vegas", **kw)
+    for P in Ps:
+        uds = np.array([bubble_point(k) for k in range(P)])
+        eng.integrate_sweep("vegas", userdata=uds[:min(P, 4)], **kw)
+        ts = float("inf")
+        for _ in range(3):
+            t0 = time.perf_counter()
+            rs = eng.integrate_sweep("vegas", userdata=uds, **kw)
+            ts = min(ts, time.perf_counter() - t0)
+        assert all(r["status"] == 0 for r in rs)
+        n = min(P, 64)       # (a loop is linear in P: up to 64 calls are timed, larger P scaled; ud stays point 0's, as in time_loop)
+        tl = float("inf")
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for k in range(n):
+                for l in range(4):
+                    loop_eng.set_grid(l, g0[l])
+                q = loop_eng.integrate("vegas", **kw)
+            tl = min(tl, (time.perf_counter() - t0) * P / n)
+        same = np.max(np.abs(rs[0]["mean"] - q["mean"]) / np.abs(q["mean"]))
+        print("P %5d  sweep %10.3f ms (%8.3f us)  loop %10.3f ms (%8.3f us)  loop / sweep %7.2f   grid x threads = %s   point 0: means differ by %.1e%s"
+              % (P, 1e3 * ts, 1e6 * ts / (P * NITER), 1e3 * tl, 1e6 * tl / (P * NITER), tl / ts, eng.last_sweep_launch(), same,
+                 "  (loop: %d calls timed, scaled)" % n if P > n else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=["table", "threads", "once"])
@@ -77,9 +139,15 @@ def main():
     ap.add_argument("--points", default="1,16,256,1024,4096")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--layout", choices=["genz", "bubble"], default="genz")
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
+    if a.layout == "bubble":
+        if a.mode != "table":
+            ap.error("--layout bubble goes with the table mode")
+        bubble_table(Ps, a.neval)
+        return
     if a.mode == "once":
         eng = sweep_engine(a.threads)
         t, _ = time_sweep(eng, Ps[0], a.neval, reps=1)
