@@ -162,6 +162,7 @@ DEBUG_SIGNATURES = [
     ("mci_debug_override", C.c_int, [C.c_char_p, C.c_int64, C.c_int32]),
     ("mci_debug_compiler_id", C.c_int, [C.c_char_p, C.c_char_p, C.c_int32]),
     ("mci_debug_split_chunks", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("mci_debug_vegas_cursor", C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("mci_debug_strat_d", C.c_int, [_VP, c_double_p, C.c_int64]),
     ("mci_debug_strat_start_d", C.c_int, [_VP, c_double_p, C.c_int64]),
     ("mci_debug_strat_dump", C.c_int, [_VP, C.c_int64, c_double_p, c_double_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),

@@ -33,6 +33,10 @@ int mci_debug_persist_spin_ticks(mci_problem *prob, unsigned long long ticks);
  *                            also when the kernel cache holds the marker of an earlier pass (the guard test of tests/test_hip_spec.py)
  *   vegas_self_check 0 | 1   (per launch) the self-check of a :vegas code object (mci_vegas_check_status): never | also when the kernel
  *                            cache holds the marker of an earlier pass
+ *   vegas_cursor     0 | 1   (per launch) cursor hand-out of :vegas launches through the pipelined one-tile loop (mci_device.h, the cursor
+ *                            section): never | every such launch, whatever its size and with a forced wg_per_block too
+ *   cursor_log2_big  n       (per launch) log2 of the units in a big range, 1 .. 16 (4)
+ *   cursor_ones      n       (per launch) single-unit ranges per wave at the end of a block, 1 .. 4096 (4)
  * (The library reads two environment variables and no others: MCI_KERNEL_CACHE -- the directory code objects are cached in -- and
  * MCI_JIT_FLAGS -- extra hiprtc options; INTEGRATION.md.) */
 int mci_debug_override(const char *key, int64_t value, int32_t on);
@@ -51,6 +55,9 @@ int mci_debug_strat_d(mci_problem *prob, double *d, int64_t n);
  * from -- the carried values as they are, remapped or raised to the new beta (mci_set_stratification_carry); ones for a uniform start --
  * in d[n]; n must be that plan's hypercube count.  The run synchronises.  n = 0 takes it back. */
 int mci_debug_strat_start_d(mci_problem *prob, double *d, int64_t n);
+/* used: did the problem's last sample launch hand its ranges out by cursor (else: the fixed partition)?  base: what its blocks' cursor
+ * words hold once every launch queued so far is through (tickets + waves per launch; tests/test_hip_vegas_cursor.py) */
+int mci_debug_vegas_cursor(const mci_problem *prob, int32_t *used, uint64_t *base);
 /* what mci_jit.h puts into the kernel-cache key for "which compiler made this code object" (hiprtc version, the files of libhiprtc and
  * libamd_comgr, the target): set != NULL overrides it for this process ("" takes the override back); out: the identity in force */
 int mci_debug_compiler_id(const char *set, char *out, int32_t n);

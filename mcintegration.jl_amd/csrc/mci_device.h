@@ -317,7 +317,14 @@ struct BatchArgs {
     // :vegas, timed launches (mci_kernel_clocks): the first wave of workgroup 0 leaves the shader-clock ticks (s_memtime) and the
     // constant-rate reference ticks (s_memrealtime) its sample loop took -- their ratio is the clock the kernel actually ran at
     u64 *clock_out; // [2] or NULL
+    // :vegas, the pipelined one-tile loop: NULL = every lane walks its fixed share of the block (slice, thread, stride wg_per_block x
+    // threads); else the block's waves take ranges of 128-sample units from the block's cursor word, cursor[local block * kCursorStride]
+    // (the cursor section below).  The words only grow: cursor_base is what they hold when this launch starts.
+    u64 *cursor;
+    u64 cursor_base;
+    u32 cursor_log2_big, cursor_ones;
 };
+constexpr int kCursorStride = 32; // (u64 words: a cursor word per 256 bytes, so that the blocks' atomics do not share a cache line)
 
 struct DumpArgs {
     const double *edges, *dacc, *ddist, *ud;
@@ -1194,6 +1201,50 @@ template <class Cfg, class L = Lds<Cfg>, bool WRITE_HIST = true, bool WRITE_PA =
     }
 }
 
+// >>> cursor section
+// Work hand-out of a big :vegas launch (BatchArgs::cursor): a block's samples are cut into UNITS of 128 (one two-sample trip of one wave:
+// unit u is the samples 128 u + 64 j + lane, j = 0 | 1), the units into RANGES, and the waves of the block's workgroups take the ranges in
+// the order their pulls reach the block's cursor word -- one returning atomic add of 1 per pull, so the word counts pulls (TICKETS) and a
+// ticket names its range by a rule every wave and the host evaluate alike.  The rule is laid out from the block's END, so that it does
+// not depend on how long the block is: the last `ones * waves` units go out one at a time, before them `waves` ranges of 2 units, before
+// those `waves` of 4, ... up to half the big size 2^log2_big, and everything earlier in ranges of the big size (the first one takes what
+// is left over).  Large ranges first keep the pull rate on a word low, single units last let every wave end within a unit of the others.
+// A wave stops at its first ticket beyond the last range, so a launch moves a word on by exactly tickets + waves whatever the order of
+// the pulls: the host knows the value the next launch starts from without reading or clearing anything.
+struct CursorRule {
+    u64 units;   // of the block
+    u32 waves;   // of the block's workgroups
+    u32 log2_big, ones;
+};
+__host__ __device__ inline u64 cursor_ones(const CursorRule &r) { return (u64)r.ones * r.waves; }
+// ranges (= tickets that name one) of a block
+__host__ __device__ inline u64 cursor_tickets(const CursorRule &r) {
+    if (r.units <= cursor_ones(r)) return r.units;
+    u64 rem = r.units - cursor_ones(r), n = cursor_ones(r);
+    for (u32 l = 1; l < r.log2_big; ++l) {
+        const u64 level = (u64)r.waves << l;
+        if (rem <= level) return n + ((rem + (1ull << l) - 1ull) >> l);
+        n += r.waves;
+        rem -= level;
+    }
+    return n + ((rem + (1ull << r.log2_big) - 1ull) >> r.log2_big);
+}
+// the units [u0, u1) of ticket t < tickets (counted from the block's start); ntickets = cursor_tickets(r)
+__host__ __device__ inline void cursor_range(const CursorRule &r, u64 ntickets, u64 t, u64 &u0, u64 &u1) {
+    u64 q = ntickets - 1ull - t, e, z = 1ull; // q: tickets behind this one; e: units behind its range; z: its size
+    if (q < cursor_ones(r)) e = q;
+    else {
+        q -= cursor_ones(r);
+        u32 l = 1;
+        for (; l < r.log2_big && q >= r.waves; ++l) q -= r.waves;
+        z = 1ull << l;
+        e = (u64)r.waves * (r.ones + z - 2ull) + q * z; // ones + 2 + 4 + ... + z / 2 units per wave lie behind this level
+    }
+    u1 = r.units - e;
+    u0 = e + z < r.units ? r.units - e - z : 0ull;
+}
+// <<< cursor section
+
 struct WorkItem {
     i64 rowid, lb;
     int slice, tile;
@@ -1267,7 +1318,9 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
     const int slice = wi.slice, tile = wi.tile;
     const i64 B = a.block_lo + wi.lb; // global statistical block
     const u32 stream = a.iteration * 8u + STREAM_VEGAS;
-    const i64 stride = (i64)a.wg_per_block * T;
+    // (the pipelined one-tile loop under a cursor, BatchArgs::cursor: a wave walks its ranges 64 samples at a time)
+    const bool pulled = pipe_eligible<Cfg>() && !SPLIT && !EC && a.cursor != nullptr;
+    const i64 stride = pulled ? 64 : (i64)a.wg_per_block * T;
 
     double acc[Cfg::NW];
     static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
@@ -1294,7 +1347,10 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
     // sample is measured and the carried remainder with its 64-bit compare / select -- a dozen VALU instructions per sample -- is gone)
     auto run = [&](auto TT, auto MF1c) {
     constexpr bool MF1 = decltype(MF1c)::value != 0;
-    auto process = [&](const i64 n, const Sample<Cfg> &s, double *defer_wh = nullptr) { // everything after the draws of sample n
+    // (a trailing argument, whatever it is: the caller counts its samples itself -- the pipelined loop adds them to the NEVAL column,
+    // and at measurefreq == 1 to NORM, once per lane instead of one v_add_f64 per sample and column; exact integers either way)
+    auto process = [&](const i64 n, const Sample<Cfg> &s, double *defer_wh = nullptr, auto... counted) { // everything after the draws of sample n
+        constexpr bool COUNTED = sizeof...(counted) > 0;
         double w[Cfg::NW];
         if constexpr (Cfg::HOST_INTEGRAND != 0) { // the closure ran on the host over the dumped draws
             const i64 hidx = wi.lb * a.neval_per_block + n;
@@ -1302,7 +1358,7 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
         } else {
             Cfg::integrand(s.x, w, a.ud, -1); // vegas/montecarlo.jl:140-144
         }
-        extra[Cols<Cfg>::NEVAL - Cfg::NOBS] += 1.0; // config.neval += 1   :118
+        if constexpr (!COUNTED) extra[Cols<Cfg>::NEVAL - Cfg::NOBS] += 1.0; // config.neval += 1   :118
         bool domeasure = true; // :148
         if constexpr (!MF1) {
             domeasure = mrem == 0;
@@ -1321,7 +1377,7 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
             double relw[Cfg::NW];
             static_for<0, Cfg::NW>([&](auto Q) { constexpr int q = decltype(Q)::value; relw[q] = w[q] * s.jaci[q / Cfg::NCOMP]; }); // :152
             measure<Cfg>(s.x, s.bin, relw, a.ud, acc, obs_wave<Cfg>(sO));
-            extra[Cols<Cfg>::NORM - Cfg::NOBS] += 1.0; // :164
+            if constexpr (!(COUNTED && MF1)) extra[Cols<Cfg>::NORM - Cfg::NOBS] += 1.0; // :164
         }
         double wh[Cfg::NI];
         static_for<0, Cfg::NI>([&](auto I) {
@@ -1379,25 +1435,79 @@ template <class Cfg, bool SPLIT = false> __device__ __forceinline__ void vegas_b
             };
             PhiloxHead<pipe_blocks<Cfg, DPC>()> head;
             if constexpr (UNI) head = make_philox_head<pipe_blocks<Cfg, DPC>()>((u32)a.seed, (u32)(a.seed >> 32), (u32)(first >> 32), stream);
-            i64 n = (i64)slice * T + tid;
-            for (; n + stride < a.neval_per_block; n += 2 * stride) {
-                {
-                    Sample<Cfg> s;
-                    draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)n, s, pa, pb, sH);
-                    process(n, s, pb.wh);
+            // The lane's samples come as RANGES: n, n + stride, ... below lim.  Without a cursor that is one range, the lane's fixed share of
+            // the block; with one (BatchArgs::cursor) the wave pulls tickets from the block's cursor word until one lies beyond the last
+            // range, each pull issued before the range of the one before it is worked on (its latency is a range's work away from its use).
+            // One lane adds, the wave reads the result as a scalar: no barrier, nobody waits for another wave.  The pending-histogram
+            // records carry across ranges; the ragged end of the block -- the last range of all, so a lane meets it at most once -- is the
+            // guarded single sample behind the loop.
+            CursorRule rule;
+            rule.units = (u64)((a.neval_per_block + 127) >> 7);
+            rule.waves = (u32)a.wg_per_block * (u32)(T >> 6);
+            rule.log2_big = a.cursor_log2_big;
+            rule.ones = a.cursor_ones;
+            const u64 ntickets = pulled ? cursor_tickets(rule) : 0ull;
+            u64 *const word = a.cursor + wi.lb * kCursorStride;
+            // (the value stays in lane 0's registers until `ticket` reads it.  The address goes through an empty asm statement as a
+            // vector register: the compiler's rewrite of atomics on a wave-uniform address broadcasts the result right behind the
+            // instruction, which would wait for the pull where it is issued instead of where it is used)
+            auto pull = [&]() -> u64 {
+                u64 r = 0ull;
+                if ((tid & 63) == 0) {
+                    u64 addr = (u64)word;
+                    asm volatile("" : "+v"(addr));
+                    typedef __attribute__((address_space(1))) u64 global_u64; // (a global_ instruction: vmcnt alone counts it)
+                    r = __hip_atomic_fetch_add((global_u64 *)addr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                {
-                    Sample<Cfg> s;
-                    draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)(n + stride), s, pb, pa, sH);
-                    process(n + stride, s, pa.wh);
-                }
+                return r;
+            };
+            auto ticket = [&](u64 r) -> u64 {
+                const u32 lo = (u32)__builtin_amdgcn_readfirstlane((int)(u32)r), hi = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(r >> 32));
+                return (((u64)hi << 32) | lo) - a.cursor_base;
+            };
+            i64 n = (i64)slice * T + tid, lim = a.neval_per_block;
+            u32 trips = 0u; // two-sample trips of this lane (process(..., counted))
+            u64 next = 0ull;
+            if (pulled) {
+                next = pull();
+                n = lim = 0;
             }
-            if (n < a.neval_per_block) {
+            for (;;) {
+                if (pulled) {
+                    const u64 t = ticket(next);
+                    if (t >= ntickets) break;
+                    next = pull();
+                    u64 u0, u1;
+                    cursor_range(rule, ntickets, t, u0, u1);
+                    n = (i64)(u0 << 7) + (tid & 63);
+                    lim = (i64)(u1 << 7) < a.neval_per_block ? (i64)(u1 << 7) : a.neval_per_block;
+                    if constexpr (!MF1) mrem = (n + 1) % mfreq; // (the cadence follows the sample index: anew for every range)
+                }
+                for (; n + stride < lim; n += 2 * stride) {
+                    {
+                        Sample<Cfg> s;
+                        draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)n, s, pa, pb, sH);
+                        process(n, s, pb.wh, 0);
+                    }
+                    {
+                        Sample<Cfg> s;
+                        draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)(n + stride), s, pb, pa, sH);
+                        process(n + stride, s, pa.wh, 0);
+                    }
+                    trips += 1u;
+                }
+                if (!pulled) break;
+            }
+            double count = 2.0 * (double)trips;
+            if (n < lim) {
                 Sample<Cfg> s;
                 draw_sample_pipe<Cfg, KV, DPC, UNI>(keys, head, stream, first + (u64)n, s, pa, pb, sH);
-                process(n, s, pb.wh);
+                process(n, s, pb.wh, 0);
                 flush(pb);
+                count += 1.0;
             } else flush(pa);
+            extra[Cols<Cfg>::NEVAL - Cfg::NOBS] += count;
+            if constexpr (MF1) extra[Cols<Cfg>::NORM - Cfg::NOBS] += count;
         };
         if (uniform_hi) loop(IC<1>{});
         else loop(IC<0>{});

@@ -173,11 +173,13 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         if (wpb < 1) wpb = 1;
     } else
     if (wpb <= 0) { // 256 CUs x 8..16 workgroups in the grid, never a workgroup without work
-        // measured on C2 (workgroup-count sweep): 16 workgroups per CU even out the tail once a launch is long
-        // enough that the extra partial rows (merged by k_hist_stage1) do not matter
-        // (only while a workgroup's tables are cheap to stage: C3 with 66 KB per workgroup lost 15 % at 4096)
-        // (... counted in 256-thread workgroups: the 512-thread workgroups of the histogram-copy plan take half as many -- warm
-        // tools/ab_c2.py, C2: 1024 / 2048 / 4096 / 8192 workgroups 1.509 / 1.504 / 1.515 / 1.551 ms per iteration)
+        // The fixed partition's grid, measured on C2 (tools/wg_sweep.py, profiles/vegas_cursor.txt; 512-thread workgroups of the
+        // histogram-copy plan, sample kernel per launch): 512 / 1024 / 2048 / 4096 workgroups 1.395 / 1.366 / 1.357 / 1.360 ms.  One
+        // round of resident workgroups leaves the CUs that finish early idle (equal shares, unequal clocks); every further round halves
+        // that and costs 3-4 us of prologues and epilogues that the two workgroups of a CU run in phase, plus its partial rows for
+        // k_hist_stage1.  Four rounds (2048 of 512 threads, 4096 of 256) are the best a fixed partition does -- while a workgroup's
+        // tables are cheap to stage: C3 with 66 KB per workgroup lost 15 % at 4096.  Big launches of the pipelined loop leave this
+        // rule for the cursor below, which has neither cost.
         const int64_t big = T >= 1024 ? 1024 : T >= 512 ? 2048 : 4096;
         int64_t target = (units * nblocks >= (int64_t)1 << 25 && p->lds_bytes <= 32 * 1024) ? big : 2048;
         // :vegas launches of up to a few million samples: a workgroup's prologue and epilogue (tables staged, histogram zeroed and
@@ -194,6 +196,30 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         const int64_t maxw = (units + T - 1) / T;
         if (wpb > maxw) wpb = (int)maxw;
         if (wpb < 1) wpb = 1;
+    }
+    // Big :vegas launches of the pipelined one-tile loop: ranges handed out by cursor (mci_device.h, the cursor section) to a grid that
+    // is resident at once.  Every workgroup stages its tables and zeroes its histogram copies once and writes one partial row, so the
+    // rounds of prologues and epilogues of the fixed partition, its idle CUs behind the last round and three quarters of its partial
+    // rows are gone (profiles/vegas_cursor.txt: C2 1.332 -> 1.309 ms per iteration, k_hist_stage1 7.4 -> 4.2 us).  The grid comes from the runtime's occupancy query -- the headline layout: two
+    // 512-thread workgroups on each of 256 CUs, 32 per block -- and nobody waits for another workgroup, so a grid that is NOT resident
+    // at once (a forced wg_per_block) is as correct.  Not for: a forced grid, the deterministic mode (the partition would follow the
+    // hardware), a self-check's launches, anything below 2^25 samples (its few rounds cost less than the pulls' tail).
+    bool cursor = false;
+    if (solver == MCI_VEGAS && G == 1 && !p->in_self_check && vegas_pipe_unit(p) && !(g_over.vegas_cursor.on && g_over.vegas_cursor.v == 0)) {
+        const bool forced = g_over.vegas_cursor.on && g_over.vegas_cursor.v == 1;
+        if (forced) cursor = true;
+        else if (p->wg_per_block <= 0 && units * nblocks >= ((int64_t)1 << 25)) {
+            int resident = 0;
+            if ((rc = cursor_resident(p, kern, T, &resident))) return rc;
+            // (a resident grid of at most kAtomicRows rows would flush its histograms by atomics, the plan of launch-bound
+            // iterations: such layouts -- one workgroup per CU -- keep the fixed partition and its partial rows)
+            if (resident >= nblocks && (resident / nblocks) * nblocks > kAtomicRows) {
+                cursor = true;
+                wpb = (int)(resident / nblocks);
+                const int64_t maxw = (units + T - 1) / T;
+                if (wpb > maxw) wpb = (int)maxw;
+            }
+        }
     }
     const bool hist_lds = (s.table_mode == 0 || s.table_mode == 3);
     // Few partial rows (launch-bound :vegas iterations): no partial histograms, no first merge launch -- the workgroups add their
@@ -533,6 +559,33 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
             HIPCHK(hipMemsetAsync(p->d_midx, 0xFF, (size_t)n * sizeof(int32_t), p->ctx->stream));
         }
     }
+    if (cursor) {
+        mci::CursorRule r;
+        r.units = (mci::u64)((nevalperblock + 127) >> 7);
+        r.waves = (mci::u32)(wpb * (T / 64));
+        r.log2_big = (mci::u32)(g_over.cursor_log2_big.on && g_over.cursor_log2_big.v >= 1 && g_over.cursor_log2_big.v <= 16 ? g_over.cursor_log2_big.v : mci_problem::kCursorLog2Big);
+        r.ones = (mci::u32)(g_over.cursor_ones.on && g_over.cursor_ones.v >= 1 && g_over.cursor_ones.v <= 4096 ? g_over.cursor_ones.v : mci_problem::kCursorOnes);
+        // the words of this launch's blocks all stand at cursor_base: a launch over another number of blocks starts a new set (the only
+        // time anything is cleared; the words only grow and 64 bits do not wrap)
+        if (nblocks != p->cursor_nblocks) {
+            if (nblocks > p->cap_cursor) {
+                if (p->d_cursor) (void)hipFree(p->d_cursor);
+                p->d_cursor = nullptr;
+                p->cap_cursor = 0;
+                HIPCHK(hipMalloc((void **)&p->d_cursor, (size_t)nblocks * mci::kCursorStride * sizeof(unsigned long long)));
+                p->cap_cursor = nblocks;
+            }
+            HIPCHK(hipMemsetAsync(p->d_cursor, 0, (size_t)nblocks * mci::kCursorStride * sizeof(unsigned long long), p->ctx->stream));
+            p->cursor_nblocks = nblocks;
+            p->cursor_base = 0;
+        }
+        a.cursor = p->d_cursor;
+        a.cursor_base = p->cursor_base;
+        a.cursor_log2_big = r.log2_big;
+        a.cursor_ones = r.ones;
+        p->cursor_base += mci::cursor_tickets(r) + r.waves; // every wave stops at its first ticket beyond the last range
+    }
+    p->launch.last_cursor = cursor;
     void *args[] = {&a};
     hipFunction_t f = p->f_solver[G > 1 ? (solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec) : kern];
     hipStream_t st = p->ctx->stream;

@@ -608,6 +608,13 @@ int mci_debug_split_chunks(const mci_problem *p, int64_t *chunks, int64_t *bytes
     return MCI_OK;
 }
 
+int mci_debug_vegas_cursor(const mci_problem *p, int32_t *used, uint64_t *base) {
+    if (!p) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (used) *used = p->launch.last_cursor ? 1 : 0;
+    if (base) *base = p->cursor_base;
+    return MCI_OK;
+}
+
 int mci_debug_compiler_id(const char *set, char *out, int32_t n) {
     if (set) mcijit::compiler_id_override() = set; // ("" takes the override back)
     if (out && n > 0) snprintf(out, (size_t)n, "%s", mcijit::compiler_id().c_str());

@@ -416,6 +416,7 @@ int mci_problem_destroy(mci_problem *p) {
             if (p->d_chain_P[b]) (void)hipFree(p->d_chain_P[b]);
         if (p->d_carry_w) (void)hipFree(p->d_carry_w);
         if (p->d_clocks) (void)hipFree(p->d_clocks);
+        if (p->d_cursor) (void)hipFree(p->d_cursor);
         if (p->d_edges_backup) (void)hipFree(p->d_edges_backup);
         if (p->h_hold) (void)hipHostFree(p->h_hold);
         if (p->h_hold_d) (void)hipHostFree(p->h_hold_d);
@@ -602,5 +603,34 @@ static int64_t det_lds(const mci_problem *p, int threads) { // deterministic mod
 static int64_t solver_lds(const mci_problem *p, int solver) {
     if (p->deterministic) return det_lds(p, solver_threads(p, solver));
     return solver == MCI_VEGAS ? vegas_lds(p) : p->lds_bytes;
+}
+
+// Does this problem's :vegas unit hold the hand-pipelined one-tile sample loop?  (the host's reading of mci_device.h pipe_eligible;
+// the deterministic mode keeps its fixed partition)
+static bool vegas_pipe_unit(const mci_problem *p) {
+    const auto &s = p->shape;
+    if (p->vegas_conservative || p->deterministic || s.det) return false;
+    if (s.ndraw < 8 || s.ndraw > 16 || !s.pair_table || s.table_mode != 0 || s.ntile != 1) return false;
+    if (s.host_integrand || s.host_measure || s.ec_doubles > 0) return false;
+    for (const auto &l : p->leaves)
+        if (l.kind != 0) return false;
+    return true;
+}
+// workgroups of `threads` threads of the :vegas kernel in slot `kern` that are resident on the device at once: the runtime's occupancy
+// for the kernel's registers and the launch's LDS, times the CUs (asked again only when the kernel or the launch shape changed)
+static int cursor_resident(mci_problem *p, int kern, int threads, int *out) {
+    hipFunction_t f = p->f_solver[kern];
+    const int64_t lds = solver_lds(p, MCI_VEGAS);
+    if (f != p->cursor_occ_f || threads != p->cursor_occ_threads || lds != p->cursor_occ_lds) {
+        int per_cu = 0, cus = 0;
+        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, threads, (size_t)lds));
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
+        p->cursor_occ_f = f;
+        p->cursor_occ_threads = threads;
+        p->cursor_occ_lds = lds;
+        p->cursor_occ_resident = per_cu * cus;
+    }
+    *out = p->cursor_occ_resident;
+    return MCI_OK;
 }
 

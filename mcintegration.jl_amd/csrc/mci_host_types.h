@@ -268,6 +268,15 @@ struct mci_problem {
     int persistent = -1;          // -1 automatic (launch-bound :vegas calls of mci_integrate), 0 never, 1 whenever the layout allows
     bool last_persistent = false; // the last mci_integrate ran as one persistent launch
     static const int kGroups = mci::kMergeGroups;
+    // Cursor hand-out of big :vegas launches (mci_device.h, the cursor section; mci_iteration_run).  NOT in LaunchState: a self-check
+    // never launches through the cursor, and what the device words hold is not rolled back with the host's record.
+    static const int kCursorLog2Big = 4, kCursorOnes = 4; // ranges of 16 units, tapering over 8, 4, 2 to 4 single units per wave
+    unsigned long long *d_cursor = nullptr; // [cap_cursor * kCursorStride]
+    int64_t cap_cursor = 0, cursor_nblocks = 0;
+    unsigned long long cursor_base = 0;     // what the words of blocks 0 .. cursor_nblocks - 1 hold when the queued launches are through
+    hipFunction_t cursor_occ_f = nullptr;   // the occupancy query's last answer, and what it was asked about
+    int cursor_occ_threads = 0, cursor_occ_resident = 0;
+    int64_t cursor_occ_lds = 0;
     static const int64_t kChainFill = 131072; // chains per GPU that keep 2 waves on each of the 1024 SIMDs
     // automatic :mcmc chain lengths (mci_mcmc_auto_chains): measured steps per chain while nothing has been measured | how much longer
     // than the chains that measured the holds a launch's chains may be.  (MCI_MCMC_PILOT / MCI_MCMC_GROW: experiment knobs)
@@ -290,6 +299,7 @@ struct mci_problem {
         int64_t last_nchain = 0;                       // chains per block of the last chain-solver launch
         int last_spec_lanes = 1, last_spec_maxacc = 0; // of the last chain launch (1: one lane per chain)
         bool last_carried = false;                     // the last chain launch continued the one before it
+        bool last_cursor = false;                      // the last sample launch handed its ranges out by cursor (mci_debug_vegas_cursor)
         int64_t last_split_chunks = 0, last_split_bytes = 0; // chunks of the last many-grid :vegas launch | bytes of parked stream it held at a time
         // the event ring (evs, d_clocks): sample launches so far, and per slot what its launch left there
         int64_t launches = 0;
@@ -407,7 +417,7 @@ int64_t mci_problem::kMcmcCarryHalfFloors = 2;
 // are cached) and MCI_JIT_FLAGS (extra hiprtc options), mci_jit.h.
 namespace {
 struct Override { bool on = false; int64_t v = 0; };
-struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk, vegas_self_check; } g_over;
+struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk, vegas_self_check, vegas_cursor, cursor_log2_big, cursor_ones; } g_over;
 Override *override_slot(const char *key) {
     if (!key) return nullptr;
     if (!strcmp(key, "table_mode")) return &g_over.table_mode;
@@ -421,6 +431,9 @@ Override *override_slot(const char *key) {
     if (!strcmp(key, "spec_self_check")) return &g_over.spec_self_check;
     if (!strcmp(key, "split_chunk")) return &g_over.split_chunk;
     if (!strcmp(key, "vegas_self_check")) return &g_over.vegas_self_check;
+    if (!strcmp(key, "vegas_cursor")) return &g_over.vegas_cursor;
+    if (!strcmp(key, "cursor_log2_big")) return &g_over.cursor_log2_big;
+    if (!strcmp(key, "cursor_ones")) return &g_over.cursor_ones;
     return nullptr;
 }
 } // namespace
@@ -610,6 +623,7 @@ void drop_modules(mci_problem *p) {
     p->vegas_planned = p->vegas_keys = p->vegas_wide = false;
     p->vegas_check_done[0] = p->vegas_check_done[1] = false; // (new code objects: they prove themselves again, or show their markers)
     p->f_dump = nullptr;
+    p->cursor_occ_f = nullptr; // (the occupancy answer belonged to a kernel of the modules that go)
     for (int k = 0; k < mci_problem::kSlots; ++k) {
         p->compiled[k] = false;
         if (p->module[k]) {

@@ -674,6 +674,13 @@ class Engine:
         check(lib().mci_debug_walk_counts(self.p, out))
         return int(out[0]), int(out[1])
 
+    def last_launch_cursor(self):
+        """(did the last sample launch hand its ranges out by cursor?, the value its blocks' cursor words hold once every queued launch is
+        through); see csrc/mci_debug.h mci_debug_vegas_cursor"""
+        used, base = C.c_int32(0), C.c_uint64(0)
+        check(lib().mci_debug_vegas_cursor(self.p, C.byref(used), C.byref(base)))
+        return bool(used.value), int(base.value)
+
     def split_chunks(self):
         """(chunks, bytes of parked stream held at a time) of the last many-grid :vegas launch; see csrc/mci_debug.h mci_debug_split_chunks"""
         n, b = C.c_int64(), C.c_int64()
