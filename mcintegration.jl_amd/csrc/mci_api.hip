@@ -64,6 +64,7 @@ extern "C" {
 #include "mci_host_jit.h"
 #include "mci_host_strat.h"
 #include "mci_host_check.h"
+#include "mci_host_plan.h"
 #include "mci_host_iteration.h"
 #include "mci_host_integrate.h"
 #include "mci_host_sweep.h"

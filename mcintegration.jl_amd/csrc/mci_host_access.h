@@ -145,7 +145,7 @@ int mci_set_reweight_goal(mci_problem *p, const double *goal, int32_t n) {
     if (n != p->ni + 1) return fail(MCI_ERR_INVALID, "reweight_goal has %d entries", p->ni + 1);
     p->h_goal.assign(goal, goal + n);
     if (p->ctx->offline) return MCI_OK;
-    if (!p->d_goal) HIPCHK(hipMalloc((void **)&p->d_goal, (size_t)n * sizeof(double)));
+    if (int rc = p->d_goal.reserve(n)) return rc;
     HIPCHK(hipMemcpyAsync(p->d_goal, p->h_goal.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, p->ctx->stream));
     HIPCHK(hipStreamSynchronize(p->ctx->stream));
     return MCI_OK;
@@ -300,17 +300,9 @@ static int sample_dump_device(mci_problem *p, int32_t iteration, uint64_t seed, 
     HIPCHK(hipSetDevice(p->ctx->device));
     const auto &s = p->shape;
     const int64_t per = s.ndraw + 1 + s.ni * s.ncomp;
-    if (n * per > p->cap_dump) {
-        if (p->d_dump) (void)hipFree(p->d_dump);
-        p->d_dump = nullptr;
-        p->cap_dump = 0;
-        HIPCHK(hipMalloc((void **)&p->d_dump, (size_t)(n * per) * sizeof(double)));
-        p->cap_dump = n * per;
-    }
+    if ((rc = p->d_dump.reserve(n * per))) return rc;
     mci::DumpArgs a{};
-    a.edges = p->d_edges;
-    a.dacc = p->d_dacc;
-    a.ddist = p->d_ddist;
+    fill_tables(p, a);
     a.ud = p->d_ud;
     a.x = p->d_dump;
     a.jac = p->d_dump + n * s.ndraw;

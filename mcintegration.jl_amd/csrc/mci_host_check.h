@@ -127,9 +127,7 @@ static int vegas_check_reference(mci_problem *p, int32_t iteration, uint64_t see
     a.rng_bits = s.rng_bits;
     a.rng_rounds = s.rng_rounds;
     a.with_obs = s.measure_body.empty() ? 1 : 0;
-    a.edges = p->d_edges;
-    a.dacc = p->d_dacc;
-    a.ddist = p->d_ddist;
+    fill_tables(p, a);
     a.seed = seed;
     a.iteration = (unsigned)iteration;
     a.neval_per_block = nevalperblock;

@@ -159,7 +159,7 @@ static int compile_persist(mci_problem *p, bool background) {
     }
     HIPCHK(hipModuleGetFunction(&p->f_persist, p->module_persist, "mci_vegas_persist"));
     if (!p->d_persist) {
-        HIPCHK(hipMalloc((void **)&p->d_persist, kPersistWords * sizeof(unsigned long long)));
+        if (int rc = p->d_persist.reserve((int64_t)kPersistWords)) return rc;
         HIPCHK(hipMemsetAsync(p->d_persist, 0, kPersistWords * sizeof(unsigned long long), p->ctx->stream));
         p->persist_arrive = p->persist_done = 0;
     }
@@ -178,14 +178,7 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     if ((rc = grow_iteration_log(p, (int64_t)p->log_row + ia->niter))) return rc;
     const int T = p->persist_threads;
     mci::BatchArgs a{};
-    a.edges = p->d_edges;
-    a.dacc = p->d_dacc;
-    a.ddist = p->d_ddist;
-    a.reweight = p->d_reweight;
-    a.ud = p->d_ud;
-    a.part_cols = p->d_part_cols;
-    a.part_hist = p->d_part_hist;
-    a.ghist = p->d_ghist;
+    fill_batch(p, a);
     a.seed = ia->seed;
     a.iteration = (mci::u32)ia->first_iteration;
     a.neval_per_block = nevalperblock;
@@ -199,40 +192,15 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     a.nrows = nrows;
     mci::PersistArgs f{};
     mci::MergeArgs &m = f.m;
-    m.part_cols = p->d_part_cols;
-    m.ncols = s.ncols;
-    m.nobs = s.nobs;
-    m.ni = s.ni;
-    m.nblocks = (int)nblocks;
-    m.wg_per_block = wpb;
-    m.stage1 = p->d_stage1;
-    m.ngroup = (int)mci_problem::kGroups;
-    m.ghist = p->d_ghist;
+    m = merge_args(p, nblocks, wpb, nrows);
     m.use_ghist = 1;
-    m.nbin = s.nbin;
-    m.packed = p->d_packed;
-    m.status = p->d_status;
-    m.scratch = p->d_scratch;
-    m.part_pa = nullptr;
-    m.npa = p->npa;
-    m.nrows = (int)nrows;
     mci::TrainArgs &t = f.t;
-    t.leaves = p->d_leaves;
-    t.nleaf = s.nleaf;
-    t.packed = p->d_packed;
-    t.nstat = p->nstat;
-    t.edges = p->d_edges;
-    t.dacc = p->d_dacc;
-    t.ddist = p->d_ddist;
+    fill_train(p, t);
     t.iter_log_row = p->d_iterlog + (size_t)p->log_row * p->nstat;
-    t.reweight = p->d_reweight;
-    t.goal = nullptr;
-    t.nd = s.ni + 1;
     t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
     t.gamma = ia->gamma;
     t.do_train = ia->adapt ? 1 : 0;
     t.serial_walk = 0;
-    t.status = p->d_status;
     t.maxn = p->leaves[0].nbin;
     f.niter = ia->niter;
     const int64_t lds = persist_lds(p, &f.map_off);
@@ -248,7 +216,7 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     // The map the call starts from, kept aside: workgroup 0 writes the refined map back as soon as ITS last turn is through, and another
     // workgroup can still run out of time after that -- the fall-back to the launch chain (mci_integrate) restores this copy instead
     // of trusting that `edges` was not touched (8 KB, device to device, behind nothing: ~2 us of a 0.17 ms call)
-    if (!p->d_edges_backup) HIPCHK(hipMalloc((void **)&p->d_edges_backup, (p->h_edges.size() ? p->h_edges.size() : 1) * sizeof(double)));
+    if ((rc = p->d_edges_backup.reserve(p->h_edges.size() ? (int64_t)p->h_edges.size() : 1))) return rc;
     if (p->h_edges.size()) HIPCHK(hipMemcpyAsync(p->d_edges_backup, p->d_edges, p->h_edges.size() * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
     // nrows sampling workgroups + the statistics workgroup
     HIPCHK(hipModuleLaunchKernel(p->f_persist, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
@@ -258,10 +226,7 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     p->merge_pending = false;
     p->merge = m; // (what `packed` was merged from, for the record)
     p->merge.part_cols = p->d_part_cols + (size_t)((ia->niter - 1) & 1) * (size_t)nrows * s.ncols;
-    p->launch.last_samples = nblocks * nevalperblock;
-    p->launch.last_wg = (int)nrows;
-    p->launch.last_threads = T;
-    p->launch.last_nblocks = (int)nblocks;
+    record_launch(p, nblocks * nevalperblock, nrows, T, nblocks);
     p->log_row += ia->niter;
     return MCI_OK;
 }
@@ -313,14 +278,10 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     if ((rc = mci_set_reweight_goal(p, a->reweight_goal, a->reweight_goal ? p->ni + 1 : 0))) return rc;
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
     const size_t nlog = (size_t)a->niter * p->nstat; // the pinned landing place of the statistics (+ the status word), sized outside the timed loop
-    if (nlog + 1 > p->cap_hlog) {
-        size_t ncap = p->cap_hlog ? p->cap_hlog : (size_t)64 * p->nstat + 1;
-        while (ncap < nlog + 1) ncap *= 2;
-        if (p->h_log) (void)hipHostFree(p->h_log);
-        p->h_log = nullptr;
-        p->cap_hlog = 0;
-        HIPCHK(hipHostMalloc((void **)&p->h_log, ncap * sizeof(double), hipHostMallocDefault));
-        p->cap_hlog = ncap;
+    if ((int64_t)nlog + 1 > p->h_log.capacity()) {
+        int64_t ncap = p->h_log.capacity() ? p->h_log.capacity() : (int64_t)64 * p->nstat + 1;
+        while (ncap < (int64_t)nlog + 1) ncap *= 2;
+        if ((rc = p->h_log.reserve(ncap))) return rc;
     }
     int64_t blk_row0 = -1; // this call's first row of the block log (chain solvers): the log starts over with every call
     if (a->solver != MCI_VEGAS) {

@@ -460,7 +460,7 @@ static int spec_upload(mci_problem *p, int solver, int lanes, double accept, int
         for (double acc : fam_mcmc) add(acc, limit >= 0 ? limit : (acc >= 0.5 ? 3 : 2));
         p->spec_first = 3;
     }
-    if (!p->d_spec_tab) HIPCHK(hipMalloc((void **)&p->d_spec_tab, 8 * 64 * sizeof(mci::SpecNode)));
+    if (int rc = p->d_spec_tab.reserve(8 * 64)) return rc;
     // (pageable source: the copy has left `all` when the call returns)
     HIPCHK(hipMemcpyAsync(p->d_spec_tab, all.data(), all.size() * sizeof(mci::SpecNode), hipMemcpyHostToDevice, p->ctx->stream));
     HIPCHK(hipStreamSynchronize(p->ctx->stream));

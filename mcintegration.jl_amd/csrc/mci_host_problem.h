@@ -359,19 +359,19 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
     if (!ctx->offline) {
         HIPCHK(hipSetDevice(ctx->device));
         int rc = upload(p);
-        if (rc) { delete p; return rc; }
         // (+ 64: the :mcmc holding-time histogram rides behind the tables in the all-reduce, hold_publish)
-        HIPCHK(hipMalloc((void **)&p->d_packed, (size_t)(p->packed_n + 64) * sizeof(double)));
-        HIPCHK(hipMemset(p->d_packed, 0, (size_t)(p->packed_n + 64) * sizeof(double)));
+        if (!rc) rc = p->d_packed.reserve(p->packed_n + 64);
         // (three buffers: the persistent :vegas kernel rotates through them, mci_train.h vegas_persist; everything else uses the first)
-        HIPCHK(hipMalloc((void **)&p->d_ghist, 3 * (size_t)(s.nbin ? s.nbin : 1) * sizeof(double)));
-        HIPCHK(hipMemset(p->d_ghist, 0, 3 * (size_t)(s.nbin ? s.nbin : 1) * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&p->d_stage1, (size_t)mci_problem::kGroups * (s.nbin ? s.nbin : 1) * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&p->d_status, 4 * sizeof(int))); // [0] ST_* bits | [1], [2] serial walks of train! as slots, in the general form (mci_debug_walk_counts)
-        HIPCHK(hipMemset(p->d_status, 0, 4 * sizeof(int)));
+        if (!rc) rc = p->d_ghist.reserve(3 * (int64_t)(s.nbin ? s.nbin : 1));
+        if (!rc) rc = p->d_stage1.reserve((int64_t)mci_problem::kGroups * (s.nbin ? s.nbin : 1));
+        if (!rc) rc = p->d_status.reserve(4); // [0] ST_* bits | [1], [2] serial walks of train! as slots, in the general form (mci_debug_walk_counts)
         std::vector<mci::LeafDev> ld;
         for (auto &L : p->leaves) ld.push_back({L.kind, L.nbin, L.eoff, L.doff, L.boff, L.adapt, L.alpha});
-        HIPCHK(hipMalloc((void **)&p->d_leaves, ld.size() * sizeof(mci::LeafDev)));
+        if (!rc) rc = p->d_leaves.reserve((int64_t)ld.size());
+        if (rc) { delete p; return rc; }
+        HIPCHK(hipMemset(p->d_packed, 0, (size_t)(p->packed_n + 64) * sizeof(double)));
+        HIPCHK(hipMemset(p->d_ghist, 0, 3 * (size_t)(s.nbin ? s.nbin : 1) * sizeof(double)));
+        HIPCHK(hipMemset(p->d_status, 0, 4 * sizeof(int)));
         HIPCHK(hipMemcpy(p->d_leaves, ld.data(), ld.size() * sizeof(mci::LeafDev), hipMemcpyHostToDevice));
         p->evs.resize(2 * mci_problem::kEvRing);
         for (auto &e : p->evs) HIPCHK(hipEventCreate(&e));
@@ -380,66 +380,27 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
     return MCI_OK;
 }
 
-static void strat_free_buffers(mci_problem *p); // (mci_host_strat.h)
 int mci_problem_destroy(mci_problem *p) {
     if (!p) return MCI_OK;
     if (!p->ctx->offline) {
         (void)hipStreamSynchronize(p->ctx->stream);
-        for (void *q : {(void *)p->d_edges, (void *)p->d_dacc, (void *)p->d_ddist, (void *)p->d_reweight, (void *)p->d_ud,
-                        (void *)p->d_part_cols, (void *)p->d_part_hist, (void *)p->d_ghist, (void *)p->d_stage1,
-                        (void *)p->d_packed, (void *)p->d_scratch, (void *)p->d_iterlog, (void *)p->d_dump,
-                        (void *)p->d_status, (void *)p->d_leaves})
-            if (q) (void)hipFree(q);
         for (int k = 0; k < mci_problem::kSlots; ++k)
             if (p->module[k]) (void)hipModuleUnload(p->module[k]);
         if (p->module_persist) (void)hipModuleUnload(p->module_persist);
         if (p->strat.module) (void)hipModuleUnload(p->strat.module);
         if (p->sweep.module) (void)hipModuleUnload(p->sweep.module);
         if (p->sweep.leaves.module) (void)hipModuleUnload(p->sweep.leaves.module);
-        strat_free_buffers(p);
-        if (p->d_persist) (void)hipFree(p->d_persist);
     }
     persist_job_drop(p);
     if (!p->ctx->offline) {
-        if (p->d_goal) (void)hipFree(p->d_goal);
-        if (p->d_part_pa) (void)hipFree(p->d_part_pa);
-        if (p->d_hold) (void)hipFree(p->d_hold);
-        for (int b = 0; b < 2; ++b) {
-            if (p->d_chain_x[b]) (void)hipFree(p->d_chain_x[b]);
-            if (p->d_chain_curr[b]) (void)hipFree(p->d_chain_curr[b]);
-        }
-        if (p->d_reweight_used) (void)hipFree(p->d_reweight_used);
-        if (p->d_carry_W) (void)hipFree(p->d_carry_W);
-        if (p->d_carry_src) (void)hipFree(p->d_carry_src);
-        if (p->d_spec_tab) (void)hipFree(p->d_spec_tab);
-        for (int b = 0; b < 2; ++b)
-            if (p->d_chain_P[b]) (void)hipFree(p->d_chain_P[b]);
-        if (p->d_carry_w) (void)hipFree(p->d_carry_w);
-        if (p->d_clocks) (void)hipFree(p->d_clocks);
-        if (p->d_cursor) (void)hipFree(p->d_cursor);
-        if (p->d_edges_backup) (void)hipFree(p->d_edges_backup);
-        if (p->h_hold) (void)hipHostFree(p->h_hold);
-        if (p->h_hold_d) (void)hipHostFree(p->h_hold_d);
-        if (p->h_log) (void)hipHostFree(p->h_log);
         if (p->hold_ev) (void)hipEventDestroy(p->hold_ev);
-        if (p->d_blocklog) (void)hipFree(p->d_blocklog);
         for (auto &e : p->cevs) (void)hipEventDestroy(e);
-        if (p->d_hx) (void)hipFree(p->d_hx);
-        if (p->d_hstep) (void)hipFree(p->d_hstep);
-        if (p->h_hidx) (void)hipHostFree(p->h_hidx);
-        if (p->d_hw) (void)hipFree(p->d_hw);
-        if (p->h_hx) (void)hipHostFree(p->h_hx);
-        if (p->h_hw) (void)hipHostFree(p->h_hw);
         tile_release(p); // (to the context: the next many-grid problem takes it)
-        if (p->d_mx) (void)hipFree(p->d_mx);
-        if (p->d_mrelw) (void)hipFree(p->d_mrelw);
-        if (p->d_mobs) (void)hipFree(p->d_mobs);
-        if (p->h_mx) (void)hipHostFree(p->h_mx);
-        if (p->h_mrelw) (void)hipHostFree(p->h_mrelw);
-        if (p->d_midx) (void)hipFree(p->d_midx);
-        if (p->h_midx) (void)hipHostFree(p->h_midx);
         for (auto &e : p->evs) (void)hipEventDestroy(e);
     }
+    // every d_* / h_* buffer goes here, in its member's destructor (DevBuf / PinBuf): the stream is idle, the compile job has been joined,
+    // and the context is still alive (mci_ctx_destroy is the caller's next step, never an earlier one).  An offline problem's buffers
+    // are all empty: no HIP call.
     delete p;
     return MCI_OK;
 }
@@ -452,9 +413,8 @@ int mci_set_integrand_source(mci_problem *p, const char *body, const double *ud,
     p->h_ud.assign(ud, ud + (nud > 0 ? nud : 0));
     drop_modules(p);
     if (!p->ctx->offline) {
-        if (p->d_ud) (void)hipFree(p->d_ud);
-        p->d_ud = nullptr;
-        HIPCHK(hipMalloc((void **)&p->d_ud, (p->h_ud.size() ? p->h_ud.size() : 1) * sizeof(double)));
+        p->d_ud.reset(); // (sized for this integrand's userdata, smaller or larger)
+        if (int rc = p->d_ud.reserve(p->h_ud.size() ? p->h_ud.size() : 1)) return rc;
         if (p->h_ud.size()) HIPCHK(hipMemcpy(p->d_ud, p->h_ud.data(), p->h_ud.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     return MCI_OK;
@@ -469,8 +429,7 @@ int mci_set_integrand_host(mci_problem *p, mci_host_integrand_fn fn, void *user)
     p->shape.body = "";
     p->h_ud.clear();
     drop_modules(p);
-    if (!p->ctx->offline && !p->d_ud) HIPCHK(hipMalloc((void **)&p->d_ud, sizeof(double)));
-    return MCI_OK;
+    return p->ctx->offline ? MCI_OK : p->d_ud.reserve(1);
 }
 
 int mci_set_integrand_host_indexed(mci_problem *p, mci_host_integrand_idx_fn fn, void *user) {
@@ -482,8 +441,7 @@ int mci_set_integrand_host_indexed(mci_problem *p, mci_host_integrand_idx_fn fn,
     p->shape.body = "";
     p->h_ud.clear();
     drop_modules(p);
-    if (!p->ctx->offline && !p->d_ud) HIPCHK(hipMalloc((void **)&p->d_ud, sizeof(double)));
-    return MCI_OK;
+    return p->ctx->offline ? MCI_OK : p->d_ud.reserve(1);
 }
 
 // The host closure over n configurations x[k*n + i].  idx == NULL: every integrand, w[(j*ncomp + q)*n + i] (vegas, vegasmc);

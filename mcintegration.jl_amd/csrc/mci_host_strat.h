@@ -40,16 +40,6 @@ int mci_strat_plan(int64_t neval, int32_t ndim, int64_t max_nhcube, int32_t *nst
     return MCI_OK;
 }
 
-static void strat_free_buffers(mci_problem *p) {
-    auto &st = p->strat;
-    for (void *q : {(void *)st.d_off, (void *)st.d_d, (void *)st.d_tsum, (void *)st.d_part, (void *)st.d_rec_s, (void *)st.d_stat, (void *)st.d_rec_h})
-        if (q) (void)hipFree(q);
-    st.d_off = nullptr;
-    st.d_d = st.d_tsum = st.d_part = st.d_rec_s = st.d_stat = nullptr;
-    st.d_rec_h = nullptr;
-    st.cap_cube = st.cap_chunk = 0;
-}
-
 namespace {
 // what a stratified problem must not have (the follow-ups of this mode): checked when it is switched on
 int strat_layout_check(const mci_problem *p, int32_t ndim) {
@@ -108,17 +98,10 @@ void strat_magic(uint32_t n, uint32_t *magic, int *shift) {
 // d_off / d_d with room for ncube hypercubes (what they held is gone when they grow)
 int strat_reserve(mci_problem *p, int64_t ncube) {
     auto &st = p->strat;
-    if (!st.d_tsum) HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
-    if (ncube <= st.cap_cube) return MCI_OK;
-    for (void *q : {(void *)st.d_off, (void *)st.d_d})
-        if (q) (void)hipFree(q);
-    st.d_off = nullptr;
-    st.d_d = nullptr;
-    st.cap_cube = 0;
-    HIPCHK(hipMalloc((void **)&st.d_off, (size_t)(ncube + 1) * sizeof(long long)));
-    HIPCHK(hipMalloc((void **)&st.d_d, (size_t)ncube * sizeof(double)));
+    int rc = st.d_tsum.reserve(2 * 1024 + 2);
+    if (rc || ncube <= st.d_d.capacity()) return rc;
+    if ((rc = st.d_off.reserve(ncube + 1)) || (rc = st.d_d.reserve(ncube))) return rc;
     HIPCHK(hipMemsetAsync(st.d_d, 0, (size_t)ncube * sizeof(double), p->ctx->stream));
-    st.cap_cube = ncube;
     return MCI_OK;
 }
 
@@ -148,7 +131,7 @@ int strat_start_alloc(mci_problem *p, const std::vector<int> &ns, int64_t ncube,
         // new buffers first, old -> new, then the old ones go (hipFree waits for the kernel)
         double *src = st.d_d, *upload = nullptr, *d_new = nullptr;
         long long *off_new = nullptr;
-        if (!st.d_tsum) HIPCHK(hipMalloc((void **)&st.d_tsum, (size_t)(2 * 1024 + 2) * sizeof(double)));
+        if ((rc = st.d_tsum.reserve(2 * 1024 + 2))) return rc;
         if (waiting) {
             HIPCHK(hipMalloc((void **)&upload, (size_t)st.c_ncube * sizeof(double)));
             if (hipMemcpyAsync(upload, st.c_host.data(), (size_t)st.c_ncube * sizeof(double), hipMemcpyHostToDevice, p->ctx->stream) != hipSuccess ||
@@ -178,11 +161,9 @@ int strat_start_alloc(mci_problem *p, const std::vector<int> &ns, int64_t ncube,
         const unsigned grid = (unsigned)((ncube + 255) / 256 < 4096 ? (ncube + 255) / 256 : 4096);
         hipLaunchKernelGGL(mci::k_strat_remap, dim3(grid), dim3(256), 0, p->ctx->stream, a);
         const hipError_t launched = hipGetLastError();
-        for (void *q : {(void *)upload, (void *)st.d_off, (void *)st.d_d})
-            if (q) (void)hipFree(q);
-        st.d_off = off_new;
-        st.d_d = d_new;
-        st.cap_cube = ncube;
+        if (upload) (void)hipFree(upload);
+        st.d_off.adopt(off_new, ncube + 1);
+        st.d_d.adopt(d_new, ncube);
         if (launched != hipSuccess) {
             st.c_valid = false;
             st.c_host.clear();
@@ -436,30 +417,14 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     const int64_t mblocks = nwg >= nblocks ? nblocks : 1;
     nwg -= nwg % mblocks;
     if ((rc = ensure_capacity(p, nwg, 1))) return rc;
-    if (nchunk > st.cap_chunk) {
-        for (void *q : {(void *)st.d_part, (void *)st.d_rec_s, (void *)st.d_rec_h})
-            if (q) (void)hipFree(q);
-        st.d_part = st.d_rec_s = nullptr;
-        st.d_rec_h = nullptr;
-        st.cap_chunk = 0;
-        HIPCHK(hipMalloc((void **)&st.d_part, (size_t)nchunk * 2 * NW * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&st.d_rec_s, (size_t)nchunk * 2 * 2 * NW * sizeof(double)));
-        HIPCHK(hipMalloc((void **)&st.d_rec_h, (size_t)nchunk * 2 * sizeof(long long)));
-        st.cap_chunk = nchunk;
-    }
-    if (!st.d_stat) HIPCHK(hipMalloc((void **)&st.d_stat, 2 * mci::kStratMaxCols * sizeof(double)));
+    if ((rc = st.d_part.reserve(nchunk * 2 * NW)) || (rc = st.d_rec_s.reserve(nchunk * 2 * 2 * NW)) || (rc = st.d_rec_h.reserve(nchunk * 2)) ||
+        (rc = st.d_stat.reserve(2 * mci::kStratMaxCols)))
+        return rc;
     st.ran = true;
     st.last_nchunk = nchunk;
 
     mci::BatchArgs a{};
-    a.edges = p->d_edges;
-    a.dacc = p->d_dacc;
-    a.ddist = p->d_ddist;
-    a.reweight = p->d_reweight;
-    a.ud = p->d_ud;
-    a.part_cols = p->d_part_cols;
-    a.part_hist = p->d_part_hist;
-    a.ghist = p->d_ghist;
+    fill_batch(p, a);
     a.seed = seed;
     a.iteration = (mci::u32)iteration;
     a.neval_per_block = nevalperblock;
@@ -489,26 +454,19 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
         sa.nstrat[d] = (int)n;
         sa.inv[d] = 1.0 / (double)n;
     }
-    struct Scratch {
-        void *q[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Scratch() {
-            for (void *v : q)
-                if (v) (void)hipFree(v);
-        }
-    } dump;
+    DevBuf<double> dump_x, dump_y, dump_jac, dump_w; // (test hook; freed on every way out)
+    DevBuf<long long> dump_h;
     const bool dumping = st.hn > 0;
     if (dumping) {
         if (st.hn != N) return fail(MCI_ERR_INVALID, "mci_debug_strat_dump: %lld samples asked for, the iteration has %lld", (long long)st.hn, (long long)N);
-        HIPCHK(hipMalloc(&dump.q[0], (size_t)N * s.ndraw * sizeof(double)));
-        HIPCHK(hipMalloc(&dump.q[1], (size_t)N * s.ndraw * sizeof(double)));
-        HIPCHK(hipMalloc(&dump.q[2], (size_t)N * sizeof(long long)));
-        HIPCHK(hipMalloc(&dump.q[3], (size_t)N * sizeof(double)));
-        HIPCHK(hipMalloc(&dump.q[4], (size_t)N * NW * sizeof(double)));
-        sa.dump_x = (double *)dump.q[0];
-        sa.dump_y = (double *)dump.q[1];
-        sa.dump_h = (long long *)dump.q[2];
-        sa.dump_jac = (double *)dump.q[3];
-        sa.dump_w = (double *)dump.q[4];
+        if ((rc = dump_x.reserve(N * s.ndraw)) || (rc = dump_y.reserve(N * s.ndraw)) || (rc = dump_h.reserve(N)) || (rc = dump_jac.reserve(N)) ||
+            (rc = dump_w.reserve(N * NW)))
+            return rc;
+        sa.dump_x = dump_x;
+        sa.dump_y = dump_y;
+        sa.dump_h = dump_h;
+        sa.dump_jac = dump_jac;
+        sa.dump_w = dump_w;
     }
     void *args[] = {&a, &sa};
     // HIP events around the sample launch under the rule of the classic one (mci_set_kernel_timing, mci_kernel_times_ms)
@@ -522,11 +480,11 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     p->launch.launches += 1;
     if (dumping) {
         hipStream_t hs = p->ctx->stream;
-        HIPCHK(hipMemcpyAsync(st.hx, dump.q[0], (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
-        HIPCHK(hipMemcpyAsync(st.hy, dump.q[1], (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
-        HIPCHK(hipMemcpyAsync(st.hh, dump.q[2], (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, hs));
-        HIPCHK(hipMemcpyAsync(st.hjac, dump.q[3], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, hs));
-        HIPCHK(hipMemcpyAsync(st.hw, dump.q[4], (size_t)N * NW * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hx, dump_x, (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hy, dump_y, (size_t)N * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hh, dump_h, (size_t)N * sizeof(long long), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hjac, dump_jac, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipMemcpyAsync(st.hw, dump_w, (size_t)N * NW * sizeof(double), hipMemcpyDeviceToHost, hs));
         HIPCHK(hipStreamSynchronize(hs));
         st.hn = 0;
     }
@@ -536,32 +494,9 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
         hipLaunchKernelGGL(mci::k_hist_stage1, dim3(nb256, mci_problem::kGroups), dim3(256), 0, p->ctx->stream, p->d_part_hist, (int)nwg, s.nbin,
                            (int)mci_problem::kGroups, p->d_stage1);
     HIPCHK(hipGetLastError());
-    mci::MergeArgs &m = p->merge;
-    m.hist_no_offset = 0;
-    m.part_cols = p->d_part_cols;
-    m.ncols = s.ncols;
-    m.nobs = s.nobs;
-    m.ni = s.ni;
-    m.nblocks = (int)mblocks;
-    m.wg_per_block = (int)(nwg / mblocks);
-    m.stage1 = p->d_stage1;
-    m.ngroup = (int)mci_problem::kGroups;
-    m.ghist = p->d_ghist;
-    m.use_ghist = 0;
-    m.nbin = s.nbin;
-    m.packed = p->d_packed;
-    m.status = p->d_status;
-    m.scratch = p->d_scratch;
-    m.part_pa = nullptr;
-    m.npa = p->npa;
-    m.nrows = (int)nwg;
-    m.block_means = nullptr;
-    m.hold = nullptr;
+    p->merge = merge_args(p, mblocks, (int)(nwg / mblocks), nwg);
     p->merge_pending = true;
-    p->launch.last_samples = N;
-    p->launch.last_wg = (int)nwg;
-    p->launch.last_threads = T;
-    p->launch.last_nblocks = (int)mblocks;
+    record_launch(p, N, nwg, T, mblocks);
     st.last_run = true;
     return MCI_OK;
 }

@@ -280,10 +280,7 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
         HIPCHK(hipMemsetAsync(d + o_gh, 0, (ndbl - o_gh) * sizeof(double), st)); // histogram rows, (the seeds: copied next), status words
         if (seeds) HIPCHK(hipMemcpyAsync(d + o_seed, seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         mci::BatchArgs b{};
-        b.edges = p->d_edges;
-        b.dacc = p->d_dacc;
-        b.ddist = p->d_ddist;
-        b.reweight = p->d_reweight;
+        fill_batch(p, b); // (the map and the reweight factors are the problem's; everything else lives in the sweep's own allocation)
         b.ud = d + o_ud;
         b.part_cols = d + o_part;
         b.part_hist = nullptr;
@@ -304,35 +301,22 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
         int64_t lds = 0;
         auto fill = [&](auto &f) { // (SweepArgs and SweepLeavesArgs carry the same fields)
             mci::MergeArgs &m = f.m;
+            m = merge_args(p, block, 1, block);
             m.part_cols = d + o_part;
-            m.ncols = s.ncols;
-            m.nobs = s.nobs;
-            m.ni = s.ni;
-            m.nblocks = (int)block;
-            m.wg_per_block = 1;
             m.stage1 = nullptr;
             m.ngroup = 0;
             m.ghist = d + o_gh;
             m.use_ghist = 1;
-            m.nbin = s.nbin;
             m.packed = d + o_pk;
             m.status = b.status;
             m.scratch = d + o_scr;
-            m.part_pa = nullptr;
             m.npa = 0;
-            m.nrows = (int)block;
             mci::TrainArgs &t = f.t;
-            t.leaves = p->d_leaves;
-            t.nleaf = s.nleaf;
+            fill_train(p, t);
             t.packed = d + o_pk;
             t.nstat = nstat;
-            t.edges = p->d_edges;
-            t.dacc = p->d_dacc;
-            t.ddist = p->d_ddist;
             t.iter_log_row = d + o_log;
             t.reweight = nullptr;
-            t.goal = nullptr;
-            t.nd = s.ni + 1;
             t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
             t.gamma = a->gamma;
             t.do_train = a->adapt ? 1 : 0;

@@ -74,6 +74,42 @@ struct Leaf {
     double lower, upper, alpha;
     int width = 1; // x entries per slot: D for a FermiK leaf
 };
+
+// An owning, grow-only buffer of device memory (DevBuf) or pinned host memory (PinBuf): a pointer and its capacity in elements.
+// reserve(n) does nothing while n fits; otherwise it frees FIRST and then allocates (the peak is the larger of the two sizes, never
+// their sum), the old contents are gone, and a failed allocation leaves the buffer empty.  The destructor frees; a buffer that never
+// reserved anything (every buffer of an offline problem) makes no HIP call.
+template <class T, bool kPinned> struct Buf {
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { reset(); }
+    T *get() const { return ptr; }
+    operator T *() const { return ptr; }
+    int64_t capacity() const { return cap; }
+    void reset() { adopt(nullptr, 0); }
+    // takes over an allocation of `n` elements made elsewhere (the logs that keep their contents when they grow); frees its own
+    void adopt(T *q, int64_t n) {
+        if (ptr) (void)(kPinned ? hipHostFree(ptr) : hipFree(ptr));
+        ptr = q;
+        cap = n;
+    }
+    int reserve(int64_t n) {
+        if (n <= cap) return MCI_OK;
+        reset();
+        void *q = nullptr;
+        HIPCHK(kPinned ? hipHostMalloc(&q, (size_t)n * sizeof(T), hipHostMallocDefault) : hipMalloc(&q, (size_t)n * sizeof(T)));
+        ptr = (T *)q;
+        cap = n;
+        return MCI_OK;
+    }
+
+  private:
+    T *ptr = nullptr;
+    int64_t cap = 0;
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;
 } // namespace
 
 struct mci_problem {
@@ -89,12 +125,11 @@ struct mci_problem {
     // host mirrors of the tables (uploaded at create / set_*)
     std::vector<double> h_edges, h_dacc, h_ddist, h_reweight, h_ud;
     // device
-    double *d_edges = nullptr, *d_dacc = nullptr, *d_ddist = nullptr, *d_reweight = nullptr, *d_ud = nullptr;
-    double *d_part_cols = nullptr, *d_part_hist = nullptr, *d_ghist = nullptr, *d_stage1 = nullptr, *d_packed = nullptr;
-    double *d_scratch = nullptr, *d_iterlog = nullptr, *d_dump = nullptr;
-    int *d_status = nullptr;
-    mci::LeafDev *d_leaves = nullptr;
-    int64_t cap_wg = 0, cap_blocks = 0, cap_iter = 0, cap_dump = 0;
+    DevBuf<double> d_edges, d_dacc, d_ddist, d_reweight, d_ud;
+    DevBuf<double> d_part_cols, d_part_hist, d_ghist, d_stage1, d_packed;
+    DevBuf<double> d_scratch, d_iterlog, d_dump;
+    DevBuf<int> d_status;
+    DevBuf<mci::LeafDev> d_leaves;
     // kernels
     // one code object per solver, JIT-compiled (or loaded from the kernel cache) the first time the solver runs;
     // the vegas module also holds the sample-dump kernel
@@ -110,7 +145,7 @@ struct mci_problem {
     // on a way through it (-1: the solver's default); the tree of the last such launch on the device
     int spec_lanes = -1, spec_maxacc = -1;
     double spec_accept = 0.0;
-    mci::SpecNode *d_spec_tab = nullptr;
+    DevBuf<mci::SpecNode> d_spec_tab;
     int spec_tab_lanes = 0, spec_tab_limit = -2, spec_tab_maxacc = 0;
     int spec_ntree = 0, spec_first = 0; // trees on the device, the one a group starts on
     float spec_accepts[8] = {};          // the acceptance each of them was built for
@@ -138,11 +173,10 @@ struct mci_problem {
     static const int64_t kSpecFill = 65536;        // lanes a launch of few chains spreads over: one wave on each of the 1024 SIMDs
     bool vegas_planned = false, vegas_keys = false; // the :vegas plan (workgroup size, histogram copies, VGPR round keys) stands for both variants
     std::vector<double> h_goal; // reweight_goal (main.jl:81); empty = none
-    double *d_goal = nullptr;
+    DevBuf<double> d_goal;
     int npa = 0;                    // 3 * (ni+1) * max(ni+1, npool): entries of config.propose (configuration.jl:185)
-    double *d_part_pa = nullptr;    // [rows][2*npa] per-workgroup propose | accept tables of the chain solvers
-    int64_t cap_pa = 0;
-    unsigned long long *d_hold = nullptr; // [64] :mcmc holding-time histogram of the last launch (this rank), see mci_get_hold_histogram
+    DevBuf<double> d_part_pa;       // [rows][2*npa] per-workgroup propose | accept tables of the chain solvers
+    DevBuf<unsigned long long> d_hold; // [64] :mcmc holding-time histogram of the last launch (this rank), see mci_get_hold_histogram
     // split vegas pass (NTILE > 1): per-sample histogram weights and 16-bit bins of the tiles >= 1
     double *d_tile_w = nullptr;      // (one allocation: the weights, then -- 256-byte aligned -- the packed bins)
     uint32_t *d_tile_bins = nullptr;
@@ -159,22 +193,21 @@ struct mci_problem {
     // host integrand ("batch callback"): draws dumped SoA -> callback -> weights uploaded -> accumulate kernel
     mci_host_integrand_fn host_fn = nullptr;
     mci_host_integrand_idx_fn host_idx_fn = nullptr; // the `integrand(idx, var, config)` form (mcmc/montecarlo.jl:34-36)
-    int32_t *h_hidx = nullptr;                       // pinned: which integrand the host evaluates per chain (:mcmc)
-    int64_t cap_hidx = 0;
+    PinBuf<int32_t> h_hidx;                          // pinned: which integrand the host evaluates per chain (:mcmc)
     std::vector<double> h_tmp;                       // all-integrands <-> one-integrand adaptation of the two callback forms
     void *host_user = nullptr;
-    double *d_hx = nullptr, *d_hw = nullptr, *h_hx = nullptr, *h_hw = nullptr; // device / pinned host
-    int64_t cap_host = 0;
+    DevBuf<double> d_hx, d_hw; // device
+    PinBuf<double> h_hx, h_hw; // pinned host
     // chain state between the per-step launches of a chain solver with a host integrand (BatchArgs::HostStep)
-    void *d_hstep = nullptr;
-    int64_t cap_hstep = 0; // chains
+    DevBuf<char> d_hstep; // (bytes)
     // host measure ("batch callback"): draws + relative weights of the launch -> host closure per block -> block observables
     mci_host_measure_fn hmeas_fn = nullptr;
     mci_host_measure_idx_fn hmeas_idx_fn = nullptr; // the `measure(idx, var, obs, relative_weight, config)` form (mcmc/montecarlo.jl:166-169)
     void *hmeas_user = nullptr;
-    double *d_mx = nullptr, *d_mrelw = nullptr, *h_mx = nullptr, *h_mrelw = nullptr, *d_mobs = nullptr;
-    int32_t *d_midx = nullptr, *h_midx = nullptr;   // chain solvers: the integrand index of every record (:mcmc), -1 = no record
-    int64_t cap_hmeas = 0, cap_mobs = 0;
+    DevBuf<double> d_mx, d_mrelw, d_mobs;
+    PinBuf<double> h_mx, h_mrelw;
+    DevBuf<int32_t> d_midx;                         // chain solvers: the integrand index of every record (:mcmc), -1 = no record
+    PinBuf<int32_t> h_midx;
     std::vector<double> h_mtmp;                     // callback form != record form: rows regrouped here
     std::vector<int32_t> h_mitmp;
     int threads = 256, wg_per_block = 0; // 0 = auto
@@ -215,22 +248,21 @@ struct mci_problem {
     // an all-reduce over the ranks, so that every rank sizes its chains from the SAME histogram) and is looked at when launch k + 1
     // is sized: the host waits for the sample kernel of launch k (not for its merge / train!, which run while launch k + 1 is
     // queued) -- ~10 us of idle queue per iteration, nothing next to a chain launch; the lag is fixed, so a run is reproducible
-    unsigned long long *h_hold = nullptr;   // pinned [64]
-    double *h_hold_d = nullptr;             // pinned [64]: the histogram summed over the ranks, as it comes out of the packed all-reduce
+    PinBuf<unsigned long long> h_hold;      // pinned [64]
+    PinBuf<double> h_hold_d;                // pinned [64]: the histogram summed over the ranks, as it comes out of the packed all-reduce
     hipEvent_t hold_ev = nullptr;           // (the values of the hand-over: launch.hold_*)
     // per-block means of the chain solvers' iterations (MergeArgs::block_means): rows [launch.blk_rows][launch.blk_stride = local blocks * nobs];
     // what the block-lineage error of a run of carried chains is computed from (mci_lineage_sums)
-    double *d_blocklog = nullptr;
-    int64_t cap_blocklog = 0;
+    DevBuf<double> d_blocklog;
     // Carried chains (BatchArgs::carry_x): end configurations of the last chain launch, two buffers (read one, write the other),
     // and what that launch was (launch.chain_*) -- an iteration continues it when it is the NEXT iteration of the same solver over the same blocks
-    double *d_chain_x[2] = {nullptr, nullptr};
-    double *d_chain_P[2] = {nullptr, nullptr}; // :vegasmc: the target density at every stored configuration (BatchArgs::store_P)
-    double *d_carry_w = nullptr;               // :vegasmc: new target / old target of the stored chains (mci_vegasmc_carry_weights)
-    int64_t cap_carry_w = 0;
+    DevBuf<double> d_chain_x[2];
+    DevBuf<double> d_chain_P[2];               // :vegasmc: the target density at every stored configuration (BatchArgs::store_P)
+    DevBuf<double> d_carry_w;                  // :vegasmc: new target / old target of the stored chains (mci_vegasmc_carry_weights)
     hipFunction_t f_carryw[2] = {nullptr, nullptr}; // that kernel in the lane-per-chain | several-lanes-per-chain code object of :vegasmc
-    int *d_chain_curr[2] = {nullptr, nullptr};
-    int64_t chain_cap[2] = {0, 0};
+    DevBuf<int> d_chain_curr[2];
+    // chains the buffers of that side are laid out for: the stride of d_chain_x (BatchArgs::carry_cap / store_cap)
+    int64_t chain_stride(int b) const { return d_chain_curr[b].capacity(); }
     int chain_carry = -1;        // mci_set_chain_carry: -1 automatic / 1 (the rule above), 0 never
     // :vegasmc chains are carried only out of a launch that ran on a map train! had refined at least once: chains of the automatic
     // length have not reached their target on the UNTRAINED map of a heavy-tailed integrand (log(x)/sqrt(x): the first iteration of a cold
@@ -240,16 +272,14 @@ struct mci_problem {
     bool launch_counted = false;          // mci_integrate | mci_set_iteration_counted: the iteration being launched enters the final estimate (it >= ignore)
     // :mcmc: the reweight factors the stored chains ran under, and which stored chain every chain of the launch in flight continues
     // (k_resample_chains: the stored chains resampled to the target doReweight! has moved since)
-    double *d_reweight_used = nullptr, *d_carry_W = nullptr;
-    int *d_carry_src = nullptr;
-    int64_t cap_carry_src = 0, cap_carry_W = 0;
+    DevBuf<double> d_reweight_used, d_carry_W;
+    DevBuf<int> d_carry_src;
     // the event ring of the sample launches (launch.launches, launch.ev_valid / clock_valid)
-    unsigned long long *d_clocks = nullptr; // [kEvRing][2] shader-clock | reference-clock ticks of the timed :vegas launches' sample loops
+    DevBuf<unsigned long long> d_clocks;    // [kEvRing][2] shader-clock | reference-clock ticks of the timed :vegas launches' sample loops
     std::vector<hipEvent_t> evs; // ring of (start, stop) pairs around the sampling kernel, one pair per launch
     static const int kEvRing = 512;
     int log_row = 0;
-    double *h_log = nullptr;  // pinned: mci_integrate's read-back of the iteration log (+ the status word behind it)
-    size_t cap_hlog = 0;
+    PinBuf<double> h_log;     // pinned: mci_integrate's read-back of the iteration log (+ the status word behind it)
     // persistent :vegas iterations (mci_train.h vegas_persist; mci_set_persistent): its own code object -- the plain layout at
     // `threads` -- and the two grid-wide counters, which only grow (the host keeps their values)
     hipModule_t module_persist = nullptr;
@@ -261,8 +291,8 @@ struct mci_problem {
     // object that is not in the kernel cache is compiled on a thread of its own while the calls go through the launch chain
     struct PersistJob;
     PersistJob *persist_job = nullptr;
-    unsigned long long *d_persist = nullptr; // [0] arrived | done << 40, [2] gave up
-    double *d_edges_backup = nullptr;        // the map a persistent launch started from (restored when it stalls)
+    DevBuf<unsigned long long> d_persist;    // [0] arrived | done << 40, [2] gave up
+    DevBuf<double> d_edges_backup;           // the map a persistent launch started from (restored when it stalls)
     unsigned long long persist_arrive = 0, persist_done = 0;
     unsigned long long persist_spin_ticks = 200000000ull; // ticks of the 100 MHz wall clock a grid-wide wait may take: 2 s (mci_debug_persist_spin_ticks)
     int persistent = -1;          // -1 automatic (launch-bound :vegas calls of mci_integrate), 0 never, 1 whenever the layout allows
@@ -271,8 +301,8 @@ struct mci_problem {
     // Cursor hand-out of big :vegas launches (mci_device.h, the cursor section; mci_iteration_run).  NOT in LaunchState: a self-check
     // never launches through the cursor, and what the device words hold is not rolled back with the host's record.
     static const int kCursorLog2Big = 4, kCursorOnes = 4; // ranges of 16 units, tapering over 8, 4, 2 to 4 single units per wave
-    unsigned long long *d_cursor = nullptr; // [cap_cursor * kCursorStride]
-    int64_t cap_cursor = 0, cursor_nblocks = 0;
+    DevBuf<unsigned long long> d_cursor;    // [blocks * kCursorStride]
+    int64_t cursor_nblocks = 0;
     unsigned long long cursor_base = 0;     // what the words of blocks 0 .. cursor_nblocks - 1 hold when the queued launches are through
     hipFunction_t cursor_occ_f = nullptr;   // the occupancy query's last answer, and what it was asked about
     int cursor_occ_threads = 0, cursor_occ_resident = 0;
@@ -284,9 +314,9 @@ struct mci_problem {
     static int64_t kMcmcCarryHolds, kMcmcCarryHalfFloors; // carried chains: length in longest holds | minimum length in HALF burn-in floors
     // What a sample launch leaves behind on the host (mci_iteration_run and the functions it calls write it).  VALUES ONLY -- no
     // pointer, capacity, handle or module: spec_self_check copies the record out before its two small launches and back after them,
-    // and those launches may create or grow buffers (an old pointer or capacity put back would point at freed memory).  Outside it:
-    //   resources the check may create or grow -- d_chain_x / curr / P, chain_cap, d_blocklog, the other d_* / h_* and cap_*, evs,
-    //     the modules and compiled[], the speculation trees on the device (d_spec_tab, spec_tab_*, spec_ntree, spec_first, spec_accepts);
+    // and those launches may create or grow buffers (every d_* / h_* is a DevBuf / PinBuf, which cannot be copied).  Outside it:
+    //   resources the check may create -- evs, the modules and compiled[], what describes the speculation trees on the device
+    //     (spec_tab_*, spec_ntree, spec_first, spec_accepts);
     //   settings -- spec_lanes, kernel_timing, chain_carry, threads*, ...;
     //   the check's own result -- spec_state, spec_need_check, in_self_check, vegas_check_*, vegas_conservative, check_*;
     //   the merge hand-off -- merge, merge_pending (mci_get_packed flushes it inside the check);
@@ -344,11 +374,11 @@ struct mci_problem {
         int64_t max_nhcube = (int64_t)1 << 24;
         std::vector<int> nstrat;      // the plan in use (for nsamp samples per iteration), empty = none yet
         int64_t ncube = 0, nsamp = 0;
-        long long *d_off = nullptr;   // [ncube + 1] offsets of the allocation the last run used; the next run overwrites them first
+        DevBuf<long long> d_off;      // [ncube + 1] offsets of the allocation the last run used; the next run overwrites them first
         bool ran = false;             // d_off is the allocation a run of this plan used (mci_get_strat_counts)
         bool alloc_valid = false;     // d_off holds an allocation for this plan (else the next run starts uniform)
         bool alloc_pending = false;   // the next run first turns the d_h the last iteration measured into d_off (adapt)
-        double *d_d = nullptr;        // [ncube] d_h of the next allocation
+        DevBuf<double> d_d;           // [ncube] d_h of the next allocation
         // Carry (mci_set_stratification_carry): the d_h of the last finished iteration, or of a state file, with the plan and the beta it
         // was measured under.  c_host empty: the values are d_d's (c_nstrat is then the plan d_d is laid out for); else they wait here
         // for the next run (mci_load_state).  Kept up to date whether or not `carry` is on; consulted only when it is.
@@ -359,11 +389,10 @@ struct mci_problem {
         double c_beta = 0.0;
         std::vector<double> c_host;
         int carry_how = 0;            // the last start of an allocation: 0 uniform | 1 from the carried d_h on its own plan | 2 remapped
-        double *d_tsum = nullptr;     // k_strat_alloc scratch
-        int64_t cap_cube = 0;
-        double *d_part = nullptr, *d_rec_s = nullptr, *d_stat = nullptr;
-        long long *d_rec_h = nullptr;
-        int64_t cap_chunk = 0, last_nchunk = 0;
+        DevBuf<double> d_tsum;        // k_strat_alloc scratch
+        DevBuf<double> d_part, d_rec_s, d_stat;
+        DevBuf<long long> d_rec_h;
+        int64_t last_nchunk = 0;
         bool last_run = false;        // the last mci_iteration_run was stratified: mci_iteration_finish reduces it
         bool compiled = false;
         int compiled_det = -1;
@@ -488,9 +517,9 @@ void tile_release(mci_problem *p) {
 
 int upload(mci_problem *p) {
     if (p->ctx->offline) return MCI_OK;
-    auto up = [&](double *&d, const std::vector<double> &h) -> int {
-        size_t n = h.size() ? h.size() : 1;
-        if (!d) HIPCHK(hipMalloc((void **)&d, n * sizeof(double)));
+    auto up = [&](DevBuf<double> &d, const std::vector<double> &h) -> int {
+        if (!d) // (sized once: the tables keep their sizes)
+            if (int rc = d.reserve(h.size() ? h.size() : 1)) return rc;
         if (h.size()) HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->ctx->stream));
         return MCI_OK;
     };
@@ -505,21 +534,68 @@ int upload(mci_problem *p) {
 
 int ensure_capacity(mci_problem *p, int64_t nwg, int64_t nblocks) {
     const auto &s = p->shape;
-    if (nwg > p->cap_wg) {
-        if (p->d_part_cols) (void)hipFree(p->d_part_cols);
-        if (p->d_part_hist) (void)hipFree(p->d_part_hist);
-        p->d_part_cols = p->d_part_hist = nullptr;
-        HIPCHK(hipMalloc((void **)&p->d_part_cols, (size_t)nwg * s.ncols * sizeof(double)));
-        if (s.table_mode == 0 || s.table_mode == 3) HIPCHK(hipMalloc((void **)&p->d_part_hist, (size_t)nwg * (s.nbin ? s.nbin : 1) * sizeof(double)));
-        p->cap_wg = nwg;
-    }
-    if (nblocks > p->cap_blocks) {
-        if (p->d_scratch) (void)hipFree(p->d_scratch);
-        p->d_scratch = nullptr;
-        HIPCHK(hipMalloc((void **)&p->d_scratch, (size_t)nblocks * s.ncols * sizeof(double)));
-        p->cap_blocks = nblocks;
-    }
-    return MCI_OK;
+    int rc = p->d_part_cols.reserve(nwg * s.ncols);
+    if (!rc && (s.table_mode == 0 || s.table_mode == 3)) rc = p->d_part_hist.reserve(nwg * (s.nbin ? s.nbin : 1));
+    if (!rc) rc = p->d_scratch.reserve(nblocks * s.ncols);
+    return rc;
+}
+
+// ---- the argument structs of the launches: each filled from the problem in ONE place; a caller then sets only what differs ----------
+// the map and the distributions (BatchArgs, DumpArgs, CheckArgs, TrainArgs)
+template <class Args> void fill_tables(const mci_problem *p, Args &a) {
+    a.edges = p->d_edges;
+    a.dacc = p->d_dacc;
+    a.ddist = p->d_ddist;
+}
+// ... with the reweight factors, the userdata and where a sample launch leaves its sums (where it reports -- BatchArgs::status -- is
+// the caller's: the problem's word, a sweep point's own, none for the carry-weights launch)
+void fill_batch(const mci_problem *p, mci::BatchArgs &a) {
+    fill_tables(p, a);
+    a.reweight = p->d_reweight;
+    a.ud = p->d_ud;
+    a.part_cols = p->d_part_cols;
+    a.part_hist = p->d_part_hist;
+    a.ghist = p->d_ghist;
+}
+// the merge of nrows partial rows, wpb per block, into `packed`: a :vegas launch whose histogram rows went through k_hist_stage1
+// (use_ghist = 0, no propose | accept tables, no block means, no holding times, the clearStatistics! offsets in place)
+mci::MergeArgs merge_args(const mci_problem *p, int64_t nblocks, int wpb, int64_t nrows) {
+    const auto &s = p->shape;
+    mci::MergeArgs m{};
+    m.part_cols = p->d_part_cols;
+    m.ncols = s.ncols;
+    m.nobs = s.nobs;
+    m.ni = s.ni;
+    m.nblocks = (int)nblocks;
+    m.wg_per_block = wpb;
+    m.stage1 = p->d_stage1;
+    m.ngroup = (int)mci_problem::kGroups;
+    m.ghist = p->d_ghist;
+    m.nbin = s.nbin;
+    m.packed = p->d_packed;
+    m.status = p->d_status;
+    m.scratch = p->d_scratch;
+    m.npa = p->npa;
+    m.nrows = (int)nrows;
+    return m;
+}
+// the problem-wide part of train!'s arguments (what to do, the walk, the log row and the LDS plan are the caller's)
+void fill_train(const mci_problem *p, mci::TrainArgs &t) {
+    fill_tables(p, t);
+    t.leaves = p->d_leaves;
+    t.nleaf = p->shape.nleaf;
+    t.packed = p->d_packed;
+    t.nstat = p->nstat;
+    t.reweight = p->d_reweight;
+    t.nd = p->shape.ni + 1;
+    t.status = p->d_status;
+}
+// the geometry of the sample launch just queued (mci_kernel_times_ms; launch_train picks train!'s walk by last_samples)
+void record_launch(mci_problem *p, int64_t samples, int64_t nwg, int threads, int64_t nblocks) {
+    p->launch.last_samples = samples;
+    p->launch.last_wg = (int)nwg;
+    p->launch.last_threads = threads;
+    p->launch.last_nblocks = (int)nblocks;
 }
 
 int check_status(mci_problem *p) {
@@ -564,8 +640,9 @@ int persist_recover(mci_problem *p) {
 int hold_publish(mci_problem *p, int64_t chain_len, bool carried) {
     hipStream_t st = p->ctx->stream;
     if (!p->h_hold) {
-        HIPCHK(hipHostMalloc((void **)&p->h_hold, 64 * sizeof(unsigned long long), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void **)&p->h_hold_d, 64 * sizeof(double), hipHostMallocDefault));
+        int rc = p->h_hold.reserve(64);
+        if (!rc) rc = p->h_hold_d.reserve(64);
+        if (rc) return rc;
         HIPCHK(hipEventCreateWithFlags(&p->hold_ev, hipEventDisableTiming));
     }
     p->launch.hold_len_inflight = chain_len;
@@ -663,22 +740,27 @@ void drop_modules(mci_problem *p) {
 static int flush_merge(mci_problem *p);
 static int comm_sum_host(mci_problem *p, double *v, int n);
 
+// a log that keeps its rows when it grows: room for `need` rows of `width` doubles, doubling from `first` rows; the new buffer
+// first, old -> new, then the old one goes (a copy and a stream synchronisation each time)
+static int grow_keeping(mci_problem *p, DevBuf<double> &log, int64_t need, int64_t first, int64_t width) {
+    const int64_t have = log.capacity() / width;
+    if (need <= have) return MCI_OK;
+    int64_t ncap = have ? have : first;
+    while (ncap < need) ncap *= 2;
+    double *n = nullptr;
+    HIPCHK(hipMalloc((void **)&n, (size_t)ncap * width * sizeof(double)));
+    if (log) {
+        HIPCHK(hipMemcpyAsync(n, log, (size_t)have * width * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
+        HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    }
+    log.adopt(n, ncap * width);
+    return MCI_OK;
+}
+
 // room for `rows` rows of [blk_stride] doubles in the block log (grows with a copy and a stream synchronisation; mci_integrate reserves
 // its iterations before the loop)
 static int grow_block_log(mci_problem *p, int64_t rows) {
     const int64_t need = rows * p->launch.blk_stride;
-    if (need <= p->cap_blocklog) return MCI_OK;
-    int64_t ncap = p->cap_blocklog ? p->cap_blocklog : 4096;
-    while (ncap < need) ncap *= 2;
-    double *n = nullptr;
-    HIPCHK(hipMalloc((void **)&n, (size_t)ncap * sizeof(double)));
-    if (p->d_blocklog) {
-        HIPCHK(hipMemcpyAsync(n, p->d_blocklog, (size_t)p->cap_blocklog * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
-        HIPCHK(hipStreamSynchronize(p->ctx->stream));
-        (void)hipFree(p->d_blocklog);
-    }
-    p->d_blocklog = n;
-    p->cap_blocklog = ncap;
-    return MCI_OK;
+    return grow_keeping(p, p->d_blocklog, need, 4096, 1);
 }
 

@@ -53,6 +53,13 @@ def test_offline_jit_and_problem_info():
     big = mci.Engine(mci.Configuration(var=mci.Continuous([(0.0, 1.0)] * 32), dof=[[1]]), mci.catalog.genz_product_peak(32), device=-1)
     # 32 grids = 256 KB of edges + 256 KB of histograms: histograms in LDS (two tiles), edges from L2
     assert big.table_mode == 3 and big.ndraw == 32 and big.lds_bytes <= 160 * 1024
+    # an offline problem of every solver, compiled and then destroyed: none of its buffers was ever allocated, nothing to free
+    for solver in ("vegas", "vegasmc", "mcmc"):
+        e = mci.Engine(mci.Configuration(var=mci.Continuous(0.0, 1.0), dof=[[2], [3]]), mci.catalog.sphere2(), device=-1)
+        e.compile(solver)
+        assert e.code_object(solver)
+        e.close()
+        assert e.p is None
 
 
 def test_bad_integrand_source_reports_compile_error():
