@@ -3,7 +3,8 @@
 The closure reads its parameters off `config.userdata` (a struct of floats); mci.integrate_sweep traces it once, evaluates every
 point's parameters from its object, and runs all points in one launch -- one workgroup per point runs that point's whole :vegas loop.
 Every result is what mci.integrate(peak, userdata=that object, ...) returns on a fresh configuration; all points share the seed, so the
-curve over `a` is smooth (common random numbers).
+curve over `a` is smooth (common random numbers).  `stratified()` runs the same scan with stratify=True (VEGAS+ at every point, still one
+launch) and then freezes what it learned for a second scan.
 
 Reference pattern:  for a in as;  integrate((x, c) -> ...; userdata = Para(a, u), var = Continuous(0, 1), dof = [[4]], solver = :vegas)  end
 
@@ -46,6 +47,25 @@ def main(points=64):
     for p, r in list(zip(scan, results))[::max(1, points // 8)]:
         print("a = %5.2f   %12.5f +- %-10.5f  exact %12.5f  (%+.1f sigma)" % (p.a, r.mean[0], r.stdev[0], exact(p), (r.mean[0] - exact(p)) / r.stdev[0]))
     return scan, results
+
+
+def stratified(points=64):
+    """the same scan with VEGAS+ adaptive stratified sampling at every point (stratify=True: what mci.integrate(..., stratify=True) runs),
+    still one launch; then train-then-freeze over the whole scan: the maps and hypercube allocations the first scan learned, kept
+    (adapt=False) for a second one under other seeds"""
+    u = np.array([0.3 + 0.4 * d / (D - 1) for d in range(D)])
+    scan = [types.SimpleNamespace(a=float(a), u=u) for a in np.linspace(2.0, 8.0, points)]
+    kw = dict(var=mci.Continuous(0.0, 1.0), dof=[[D]], solver="vegas", neval=1e4, niter=10)
+    trained = mci.integrate_sweep(peak, params=scan, stratify=True, seed=7, **kw)
+    s = trained[0].stratification
+    print("stratified, batched:", all(r.sweep_batched for r in trained), "| nstrat %s (%d hypercubes) | %.2f ms for %d points"
+          % (s["nstrat"], s["ncube"], 1e3 * trained[0].seconds, len(scan)))
+    frozen = mci.integrate_sweep(peak, params=scan, stratify=True, adapt=False, alloc=[r.strat_d for r in trained], maps=[r.map for r in trained],
+                                 seeds=[100 + k for k in range(points)], **kw)
+    for p, r, f in list(zip(scan, trained, frozen))[::max(1, points // 8)]:
+        print("a = %5.2f   adapting %12.5f +- %-10.5f  frozen (%s) %12.5f +- %-10.5f  exact %12.5f" % (p.a, r.mean[0], r.stdev[0], f.stratification["carried"],
+                                                                                                     f.mean[0], f.stdev[0], exact(p)))
+    return scan, trained, frozen
 
 
 PI = math.pi
@@ -104,4 +124,5 @@ def bubble_scan(points=16, ninc=1000):
 
 if __name__ == "__main__":
     main()
+    stratified()
     bubble_scan()

@@ -44,6 +44,8 @@ enum { MCI_VEGAS_STRAT = 7 };
 enum { MCI_VEGAS_SWEEP = 8 };
 /* ... and the sweep kernel for several variable leaves (problems that opted in with mci_set_sweep_leaves and are no one-grid layout) */
 enum { MCI_VEGAS_SWEEP_LEAVES = 9 };
+/* ... and the sweep kernel for stratified points (mci_integrate_sweep_strat; problems mci_sweep_strat_supported accepts) */
+enum { MCI_VEGAS_SWEEP_STRAT = 10 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -277,6 +279,32 @@ int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args,
 int mci_set_sweep_leaves(mci_problem *prob, int32_t mode);
 /* doubles of one maps_in / maps_out row of mci_integrate_sweep for this problem (nbin + 1 for one Continuous leaf) */
 int mci_sweep_map_doubles(const mci_problem *prob, int32_t *n);
+/* A stratified parameter sweep: `npoint` independent VEGAS+ loops -- what mci_integrate runs on a stratified problem
+ * (mci_set_stratification) -- in ONE launch, one workgroup per point.  The opt-in form of mci_integrate_sweep for stratified problems:
+ * mci_integrate_sweep and mci_sweep_supported keep refusing them.  The problem's nstrat / beta / max_nhcube give the plan, through
+ * mci_strat_plan for the call's neval where no nstrat was set.  Per point and iteration: the allocation (k_strat_alloc's arithmetic:
+ * uniform at the start of a point without d_in, from d_h otherwise; with adapt = 0 the allocation the point started with stays), the
+ * samples of mci_integrate's stratified iteration (same Philox indices, hypercubes, Jacobians and histogram weights), the stratified
+ * mean and variance, the histogram with the clearStatistics! offsets of the ordinary call's blocks, train!.  Only the association of
+ * floating-point sums differs from the ordinary call.  userdata, seeds, maps_in, maps_out, results, iter_mean, iter_std and status are
+ * mci_integrate_sweep's (one Continuous leaf: rows of nbin + 1 doubles); results are what mci_integrate makes of stratified log rows.
+ *   d_in        NULL: every point starts uniform; else [npoint][ncube] d_h, taken as measured on exactly this plan and beta (there is
+ *               no remap in a sweep): the first allocation of point p is made from row p
+ *   d_out       NULL or [npoint][ncube]: the d_h every point's last iteration measured (what a later call passes as d_in)
+ *   counts_out  NULL or [npoint][ncube]: n_h of the allocation every point's last iteration used
+ * ncube comes from mci_sweep_strat_doubles.  The problem's own map, packed buffer, logs, allocation, carry state and last_* queries are
+ * not touched.  npoint <= 65536 and at most 4 GiB of device memory (mci_integrate_sweep's buffer plus, per point, ncube + 1 offsets,
+ * ncube d_h and the allocation's tile bases): MCI_ERR_INVALID with the byte count beyond. */
+int mci_integrate_sweep_strat(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                              const double *maps_in, double *maps_out, const double *d_in, double *d_out, int64_t *counts_out,
+                              mci_result *results, double *iter_mean, double *iter_std, int32_t *status);
+/* MCI_OK when mci_integrate_sweep_strat takes this problem with these arguments; else MCI_ERR_INVALID with the reason in why[n] (and in
+ * mci_last_error): the problem is not stratified, solver other than :vegas, measurefreq != 1, several ranks, a host integrand or
+ * measure, a user measure, deterministic mode, more than one variable leaf or a leaf that is not Continuous, tables that do not sit in
+ * LDS in one tile, more than 32 draws or 8 weight columns, more hypercubes than neval / 2, or more than 159 KiB of LDS (named). */
+int mci_sweep_strat_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* hypercubes of the plan mci_integrate_sweep_strat runs these arguments on: the row length of d_in / d_out / counts_out */
+int mci_sweep_strat_doubles(const mci_problem *prob, const mci_integrate_args *args, int64_t *ncube);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

@@ -32,6 +32,7 @@
 #include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
 #include "mci_sweep.h" // SweepArgs (likewise)
 #include "mci_sweep_leaves.h" // SweepLeavesArgs (likewise)
+#include "mci_sweep_strat.h" // SweepStratArgs (likewise)
 
 namespace {
 

@@ -552,6 +552,11 @@ int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n)
         snprintf(buf, (size_t)n, "%s", p->sweep.leaves.code_object.c_str());
         return MCI_OK;
     }
+    if (solver == MCI_VEGAS_SWEEP_STRAT) {
+        if (!p->sweep.strat.compiled) return fail(MCI_ERR_INVALID, "the sweep kernel for stratified points has not been compiled yet");
+        snprintf(buf, (size_t)n, "%s", p->sweep.strat.code_object.c_str());
+        return MCI_OK;
+    }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
     const int slot = (solver == MCI_VEGAS && !p->compiled[solver] && p->compiled[kSlotVegasAny]) ? kSlotVegasAny : solver;
     if (!p->compiled[slot]) return fail(MCI_ERR_INVALID, "solver %d has not been compiled yet", solver);
@@ -710,6 +715,7 @@ static int compile_strat(mci_problem *p); // (mci_host_strat.h)
 static int compile_sweep(mci_problem *p); // (mci_host_sweep.h)
 static int compile_sweep_leaves(mci_problem *p);
 static bool sweep_leaves_unit(const mci_problem *p);
+static int compile_sweep_strat(mci_problem *p);
 int mci_compile_solver(mci_problem *p, int32_t solver) {
     if (solver == MCI_VEGAS_PERSISTENT) { // the persistent :vegas kernel (mci_set_persistent), for layouts that allow it
         if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
@@ -737,6 +743,16 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
         if (!sweep_leaves_unit(p)) return fail(MCI_ERR_INVALID, "a sweep of this problem runs the one-grid sweep kernel (MCI_VEGAS_SWEEP; mci_set_sweep_leaves)");
         return compile_sweep_leaves(p);
+    }
+    if (solver == MCI_VEGAS_SWEEP_STRAT) { // (mci_host_sweep.h: a stratified problem mci_sweep_strat_supported accepts)
+        mci_integrate_args a{};
+        a.solver = MCI_VEGAS;
+        a.measurefreq = 1;
+        a.niter = 1;
+        a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
+        a.block = 1;
+        if (int rc = mci_sweep_strat_supported(p, &a, nullptr, 0)) return rc;
+        return compile_sweep_strat(p);
     }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver); // main.jl:263
     return compile_solver(p, solver);

@@ -390,6 +390,7 @@ int mci_problem_destroy(mci_problem *p) {
         if (p->strat.module) (void)hipModuleUnload(p->strat.module);
         if (p->sweep.module) (void)hipModuleUnload(p->sweep.module);
         if (p->sweep.leaves.module) (void)hipModuleUnload(p->sweep.leaves.module);
+        if (p->sweep.strat.module) (void)hipModuleUnload(p->sweep.strat.module);
     }
     persist_job_drop(p);
     if (!p->ctx->offline) {

@@ -57,7 +57,41 @@ int strat_layout_check(const mci_problem *p, int32_t ndim) {
     return MCI_OK;
 }
 
-int strat_alloc_tiles(int64_t ncube) { return (int)((ncube + 255) / 256 < 1024 ? (ncube + 255) / 256 : 1024); }
+// The geometry of a stratified iteration of N samples in `nblocks` statistical blocks (strat_run; the stratified sweep asks for mblocks, and
+// for the chunk of its own LDS need).  Chunk size: the largest of 8 | 4 | 2 | 1 trips of 256 samples whose LDS -- need[0 .. 3] bytes, with
+// strat_nloc(trips) hypercubes per chunk -- stays within 64 KiB (two workgroups per CU), else within a CU's 159 KiB; trips = 0: neither.
+// Workgroups: one per chunk up to 2048, a multiple of the call's block count where there are enough chunks: the merge then groups the
+// rows into the call's blocks, whose clearStatistics! offsets the histogram carries as classic :vegas's does -- one hypercube gives
+// classic's histogram and map.
+struct StratGeometry {
+    int trips = 0;
+    int64_t lds = 0, S = 0, nchunk = 0, nwg = 0, mblocks = 0;
+};
+// LDS behind the sample kernel's own carve, bytes (mci_strat.h strat_lds_doubles at 256 threads)
+int strat_nloc(int trips) { return trips * 256 / 2 + 1; }
+int64_t strat_chunk_lds_bytes(int nloc, int NW) { return (int64_t)((nloc + 1) + nloc * 2 * NW + 256 + 256 * 2 * NW) * 8; }
+void strat_geometry(int64_t N, int64_t nblocks, const int64_t (&need)[4], StratGeometry &g) {
+    g = StratGeometry();
+    const int T = 256;
+    for (int64_t lim : {(int64_t)64 * 1024, (int64_t)159 * 1024}) {
+        for (int k = 8; k >= 1 && !g.trips; k >>= 1) {
+            const int64_t bytes = need[k == 8 ? 0 : k == 4 ? 1 : k == 2 ? 2 : 3];
+            if (bytes <= lim) {
+                g.trips = k;
+                g.lds = bytes;
+            }
+        }
+        if (g.trips) break;
+    }
+    if (!g.trips) return;
+    g.S = (int64_t)g.trips * T;
+    g.nchunk = (N + g.S - 1) / g.S;
+    g.nwg = g.nchunk < 2048 ? g.nchunk : 2048;
+    g.mblocks = g.nwg >= nblocks ? nblocks : 1;
+    g.nwg -= g.nwg % g.mblocks;
+}
+
+int strat_alloc_tiles(int64_t ncube) { return mci::strat_alloc_ntile(ncube); }
 
 // the allocation of the run about to start, over the offsets the last run used: from d_h, or uniform
 int strat_launch_alloc(mci_problem *p, bool uniform) {
@@ -391,31 +425,14 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     HIPCHK(hipSetDevice(p->ctx->device));
     const int64_t N = (block_hi - block_lo) * nevalperblock;
     if ((rc = strat_prepare(p, N))) return rc;
-    // chunk size: the largest of 8 | 4 | 2 | 1 trips of 256 samples whose LDS (tables + histograms + the chunk's hypercubes) stays within
-    // 64 KiB -- two workgroups per CU --, else within a CU's 160 KiB
     const int T = 256, NW = s.ni * s.ncomp;
     const int64_t base = p->deterministic ? det_lds(p, T) : p->lds_bytes;
-    int trips = 0;
-    int64_t lds = 0;
-    for (int64_t lim : {(int64_t)64 * 1024, (int64_t)159 * 1024}) {
-        for (int k = 8; k >= 1 && !trips; k >>= 1) {
-            const int nloc = k * T / 2 + 1;
-            const int64_t need = base + (int64_t)((nloc + 1) + nloc * 2 * NW + T + T * 2 * NW) * 8;
-            if (need <= lim) {
-                trips = k;
-                lds = need;
-            }
-        }
-        if (trips) break;
-    }
-    if (!trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
-    const int64_t S = (int64_t)trips * T, nchunk = (N + S - 1) / S;
-    // (a multiple of the call's block count where there are enough chunks: the merge then groups the rows into the call's blocks, whose
-    // clearStatistics! offsets the histogram carries as classic :vegas's does -- one hypercube gives classic's histogram and map)
-    const int64_t nblocks = block_hi - block_lo;
-    int64_t nwg = nchunk < 2048 ? nchunk : 2048;
-    const int64_t mblocks = nwg >= nblocks ? nblocks : 1;
-    nwg -= nwg % mblocks;
+    const int64_t need[4] = {base + strat_chunk_lds_bytes(strat_nloc(8), NW), base + strat_chunk_lds_bytes(strat_nloc(4), NW), base + strat_chunk_lds_bytes(strat_nloc(2), NW),
+                             base + strat_chunk_lds_bytes(strat_nloc(1), NW)};
+    StratGeometry g;
+    strat_geometry(N, block_hi - block_lo, need, g);
+    if (!g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+    const int64_t lds = g.lds, S = g.S, nchunk = g.nchunk, nwg = g.nwg, mblocks = g.mblocks;
     if ((rc = ensure_capacity(p, nwg, 1))) return rc;
     if ((rc = st.d_part.reserve(nchunk * 2 * NW)) || (rc = st.d_rec_s.reserve(nchunk * 2 * 2 * NW)) || (rc = st.d_rec_h.reserve(nchunk * 2)) ||
         (rc = st.d_stat.reserve(2 * mci::kStratMaxCols)))

@@ -382,3 +382,319 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
     }
     return MCI_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// stratified (VEGAS+) points in a sweep: mci_sweep_strat.h vegas_sweep_strat, one workgroup runs a point's whole stratified loop
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// the plan of a stratified sweep of N samples per iteration: the problem's own request, or the default plan for N (strat_prepare's rule)
+int sweep_strat_plan(const mci_problem *p, int64_t N, std::vector<int> &ns, int64_t *ncube) {
+    const auto &st = p->strat;
+    const int D = p->shape.ndraw;
+    ns.assign((size_t)D, 1);
+    if (st.want.empty()) {
+        int rc = mci_strat_plan(N, D, st.max_nhcube, ns.data());
+        if (rc) return rc;
+    } else ns = st.want;
+    int64_t nc = 1;
+    for (int v : ns) {
+        if (nc > (((int64_t)1 << 31) - 1) / v) return fail(MCI_ERR_INVALID, "stratification: more than 2^31 - 1 hypercubes");
+        nc *= v;
+    }
+    *ncube = nc;
+    return MCI_OK;
+}
+// LDS of the stratified sweep kernel, bytes, for chunks of nloc hypercubes: the sample carve + the chunk's hypercubes or the refinement's
+// scratch, whichever is larger, and behind them (map_off, doubles) the map [N + 2] | flags [4] | running sums and the cut hypercube's
+// sums [4 kStratMaxCols] (mci_sweep_strat.h SweepStratArgs::map_off)
+int64_t sweep_strat_lds(const mci_problem *p, int nloc, int *map_off) {
+    const int N = p->leaves.empty() ? 1 : p->leaves[0].nbin, NW = p->shape.ni * p->shape.ncomp;
+    const int64_t a = (p->lds_bytes + 7) / 8 + strat_chunk_lds_bytes(nloc, NW) / 8, b = (int64_t)mci::train_lds_doubles(N) + N + 256;
+    const int64_t off = ((a > b ? a : b) + 1) & ~(int64_t)1;
+    if (map_off) *map_off = (int)off;
+    return (off + (N + 2) + 4 + 4 * (int64_t)mci::kStratMaxCols) * 8;
+}
+// samples per iteration of a call (main.jl:121 on one rank)
+int64_t sweep_strat_nsamp(const mci_integrate_args *a, int64_t *nblocks) {
+    int64_t nevalperblock, block;
+    mci_standardize_block(a->neval, a->block, 1, &nevalperblock, &block);
+    if (nblocks) *nblocks = block;
+    return nevalperblock * block;
+}
+const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
+    const auto &s = p->shape;
+    if (!p->strat.on) return "the problem is not stratified (mci_set_stratification first; mci_integrate_sweep runs the others)";
+    if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
+    if (a->measurefreq != 1) {
+        buf = "measurefreq = " + std::to_string((long long)a->measurefreq) + " (a sweep measures every sample)";
+        return buf.c_str();
+    }
+    if (a->niter < 1) return "niter < 1";
+    if (p->ctx->nranks != 1) return "several ranks (one rank only)";
+    if (s.host_integrand) return "a host integrand (device source or a traced closure only)";
+    if (s.host_measure) return "a host measure (the default measure only)";
+    if (!s.measure_body.empty()) return "a user measure (the default measure only)";
+    if (p->deterministic) return "deterministic mode";
+    if (s.nleaf != 1 || p->leaves.size() != 1) {
+        buf = std::to_string(s.nleaf) + " variable leaves (a stratified sweep point refines ONE Continuous grid; several Continuous leaves are a follow-up)";
+        return buf.c_str();
+    }
+    if (p->leaves[0].kind != 0) return "a Discrete or FermiK variable (a stratified sweep point refines ONE Continuous grid)";
+    if (s.table_mode != 0 || s.ntile != 1 || s.nbin <= 0 || s.ec_doubles > 0) return "the grid and its histogram do not sit in LDS in one tile";
+    if (s.ndraw > mci::kStratMaxDraw) {
+        buf = std::to_string(s.ndraw) + " draws per sample (at most " + std::to_string((int)mci::kStratMaxDraw) + ")";
+        return buf.c_str();
+    }
+    if (s.ni * s.ncomp > mci::kStratMaxCols) {
+        buf = std::to_string(s.ni * s.ncomp) + " weight columns (at most " + std::to_string((int)mci::kStratMaxCols) + ")";
+        return buf.c_str();
+    }
+    if (!(a->neval > a->block)) return "neval should be larger than nblock";
+    const int64_t N = sweep_strat_nsamp(a, nullptr);
+    std::vector<int> ns;
+    int64_t ncube = 0;
+    if (sweep_strat_plan(p, N, ns, &ncube)) {
+        buf = g_err;
+        return buf.c_str();
+    }
+    if (ncube > N / 2) {
+        buf = std::to_string((long long)ncube) + " hypercubes need at least " + std::to_string((long long)(2 * ncube)) + " samples per iteration (two each), neval = " +
+              std::to_string((long long)N);
+        return buf.c_str();
+    }
+    const int64_t lds = sweep_strat_lds(p, strat_nloc(1), nullptr); // (the smallest chunk: one trip)
+    if (lds > kSweepLeavesMaxLds) {
+        buf = "the sample tables, one chunk's hypercubes, the refinement scratch and the map copy take " + std::to_string((long long)lds) + " bytes of LDS (" +
+              std::to_string((long long)kSweepLeavesMaxLds) + " at most)";
+        return buf.c_str();
+    }
+    return nullptr;
+}
+} // namespace
+
+// the unit of mci_sweep_strat.h: 256 threads, one histogram copy, compiled like the one-grid sweep unit
+static int compile_sweep_strat(mci_problem *p) {
+    auto &u = p->sweep.strat;
+    if (u.compiled) return MCI_OK;
+    Candidate c;
+    mcijit::ProblemShape sh = p->shape;
+    sh.hcopy = 1;
+    sh.det = 0;
+    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweepStrat, p->leaves[0].alpha);
+    c.threads = kSweepThreads;
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweepStrat);
+    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel, stratified points):\n%s", c.log.c_str());
+    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep_strat") != 0)
+        return fail(MCI_ERR_COMPILE, "the sweep kernel for stratified points came out with static LDS or scratch at %d threads per workgroup", kSweepThreads);
+    u.code_object = c.path;
+    u.threads = kSweepThreads;
+    if (!p->ctx->offline) {
+        HIPCHK(hipSetDevice(p->ctx->device));
+        if (hipModuleLoadData(&u.module, c.code.data()) != hipSuccess) {
+            if (c.cached) unlink(c.path.c_str());
+            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object (stratified points)");
+        }
+        HIPCHK(hipModuleGetFunction(&u.f, u.module, "mci_vegas_sweep_strat"));
+    }
+    u.compiled = true;
+    return MCI_OK;
+}
+
+int mci_sweep_strat_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
+    if (why && n > 0) why[0] = 0;
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    std::string buf;
+    const char *r = sweep_strat_refusal(p, a, buf);
+    if (!r) return MCI_OK;
+    const std::string reason = r; // (may live in g_err, which fail() rewrites)
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", reason.c_str());
+    return fail(MCI_ERR_INVALID, "this problem cannot run as a stratified sweep: %s", reason.c_str());
+}
+
+int mci_sweep_strat_doubles(const mci_problem *p, const mci_integrate_args *a, int64_t *ncube) {
+    if (!p || !a || !ncube) return fail(MCI_ERR_INVALID, "NULL argument");
+    int rc;
+    if ((rc = mci_sweep_strat_supported(p, a, nullptr, 0))) return rc;
+    std::vector<int> ns;
+    return sweep_strat_plan(p, sweep_strat_nsamp(a, nullptr), ns, ncube);
+}
+
+// P independent stratified integrate() loops, one workgroup each, in one launch
+int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                              double *maps_out, const double *d_in, double *d_out, int64_t *counts_out, mci_result *results, double *iter_mean, double *iter_std,
+                              int32_t *status) {
+    if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
+    int rc;
+    if ((rc = mci_sweep_strat_supported(p, a, nullptr, 0))) return rc;
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
+    const auto &s = p->shape;
+    const int nud = (int)p->h_ud.size();
+    if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
+    for (int q = 0; q < npoint; ++q)
+        if (results[q].niter < a->niter || results[q].nobs != s.nobs || !results[q].mean || !results[q].stdev || !results[q].chi2)
+            return fail(MCI_ERR_INVALID, "result buffers of point %d too small", q);
+    int64_t block = 0, ncube = 0;
+    const int64_t nsamp = sweep_strat_nsamp(a, &block);
+    std::vector<int> ns;
+    if ((rc = sweep_strat_plan(p, nsamp, ns, &ncube))) return rc;
+    const int NW = s.ni * s.ncomp, N = p->leaves[0].nbin, nstat = p->nstat, niter = a->niter, ntile = mci::strat_alloc_ntile(ncube);
+    // mblocks: what the ordinary stratified call merges its rows as (strat_run); the chunk: of this kernel's own LDS need
+    int64_t need0[4], need[4];
+    for (int k = 0; k < 4; ++k) {
+        need0[k] = p->lds_bytes + strat_chunk_lds_bytes(strat_nloc(8 >> k), NW);
+        need[k] = sweep_strat_lds(p, strat_nloc(8 >> k), nullptr);
+    }
+    StratGeometry g0, g;
+    strat_geometry(nsamp, block, need0, g0);
+    strat_geometry(nsamp, block, need, g);
+    if (!g0.trips || !g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+    const size_t P = (size_t)npoint, nmap = (size_t)N + 1, nc = (size_t)ncube;
+    // one buffer (doubles; the 8-byte offsets and seeds among them; then the status words)
+    const size_t o_ud = 0, o_in = o_ud + P * (size_t)nud, o_out = o_in + (maps_in ? P * nmap : 0), o_log = o_out + P * nmap,
+                 o_part = o_log + P * (size_t)niter * nstat, o_scr = o_part + P * (size_t)s.ncols, o_pk = o_scr + P * (size_t)s.ncols,
+                 o_off = o_pk + P * (size_t)nstat, o_tb = o_off + P * (nc + 1), o_gh = o_tb + P * (size_t)ntile, o_d = o_gh + P * (size_t)s.nbin,
+                 o_seed = o_d + P * nc, o_st = o_seed + (seeds ? P : 0), ndbl = o_st + (P + 1) / 2;
+    if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
+        return fail(MCI_ERR_INVALID, "a stratified sweep of %d points x %d iterations x %lld hypercubes needs %lld bytes of device memory (limit %lld): split it",
+                    (int)npoint, niter, (long long)ncube, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
+    if ((rc = compile_sweep_strat(p))) return rc;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    void *base = nullptr;
+    size_t got = 0;
+    if ((rc = sweep_alloc(p->ctx, ndbl * sizeof(double), &base, &got))) return rc;
+    double *d = (double *)base;
+    std::vector<double> hlog(P * (size_t)niter * nstat);
+    std::vector<long long> hoff(counts_out ? P * (nc + 1) : 0);
+    std::vector<int> hst(P);
+    auto run = [&]() -> int {
+        auto t0 = std::chrono::steady_clock::now();
+        if (nud > 0) HIPCHK(hipMemcpyAsync(d + o_ud, userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
+        if (maps_in) HIPCHK(hipMemcpyAsync(d + o_in, maps_in, P * nmap * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d + o_gh, 0, (ndbl - o_gh) * sizeof(double), st)); // histogram rows, d rows, (the seeds: copied next), status words
+        if (d_in) HIPCHK(hipMemcpyAsync(d + o_d, d_in, P * nc * sizeof(double), hipMemcpyHostToDevice, st));
+        if (seeds) HIPCHK(hipMemcpyAsync(d + o_seed, seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        mci::BatchArgs b{};
+        fill_batch(p, b); // (the map and the reweight factors are the problem's; everything else lives in the sweep's own allocation)
+        b.ud = d + o_ud;
+        b.part_cols = d + o_part;
+        b.part_hist = nullptr;
+        b.ghist = d + o_gh;
+        b.seed = a->seed;
+        b.iteration = (mci::u32)a->first_iteration;
+        b.neval_per_block = nsamp / block;
+        b.block_lo = 0;
+        b.wg_per_block = 1;
+        b.measurefreq = 1;
+        b.nchain = 1;
+        b.hist_atomic = 1;
+        b.status = reinterpret_cast<int *>(d + o_st);
+        b.tile_stride = nsamp;
+        b.nrows = 1;
+        mci::SweepStratArgs f{};
+        mci::MergeArgs &m = f.m;
+        m = merge_args(p, 1, 1, 1);
+        m.part_cols = d + o_part;
+        m.stage1 = nullptr;
+        m.ngroup = 0;
+        m.ghist = d + o_gh;
+        m.use_ghist = 1;
+        m.packed = d + o_pk;
+        m.status = b.status;
+        m.scratch = d + o_scr;
+        m.npa = 0;
+        m.block_means = nullptr;
+        mci::TrainArgs &t = f.t;
+        fill_train(p, t);
+        t.packed = d + o_pk;
+        t.nstat = nstat;
+        t.iter_log_row = d + o_log;
+        t.reweight = nullptr;
+        t.do_reweight = 0;
+        t.gamma = a->gamma;
+        t.do_train = a->adapt ? 1 : 0;
+        t.serial_walk = 0;
+        t.status = b.status;
+        t.maxn = N;
+        mci::StratArgs &sa = f.st;
+        sa.off = reinterpret_cast<const long long *>(d + o_off);
+        sa.dnext = d + o_d;
+        sa.ncube = ncube;
+        sa.nsamp = nsamp;
+        sa.chunk = g.S;
+        sa.nchunk = g.nchunk;
+        sa.first_index = 0;
+        sa.nloc = (int)(g.S / 2 + 1);
+        sa.beta = p->strat.beta;
+        for (int k = 0; k < s.ndraw; ++k) {
+            const uint32_t n = (uint32_t)ns[k];
+            strat_magic(n, &sa.magic[k], &sa.shift[k]);
+            sa.nstrat[k] = (int)n;
+            sa.inv[k] = 1.0 / (double)n;
+        }
+        f.npoint = npoint;
+        f.niter = niter;
+        f.nuserdata = nud;
+        const int64_t lds = sweep_strat_lds(p, sa.nloc, &f.map_off);
+        f.have_d = d_in ? 1 : 0;
+        f.start_uniform = 1;
+        f.mblocks = (int)g0.mblocks;
+        f.ntile = ntile;
+        f.tbase = d + o_tb;
+        f.ud = d + o_ud;
+        f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
+        f.maps_in = maps_in ? d + o_in : nullptr;
+        f.maps_out = d + o_out;
+        // workgroups: two per CU up to 80 KiB of LDS each, one above; any grid runs any npoint
+        int cus = 0;
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
+        const int per_cu = lds > 80 * 1024 ? 1 : 2;
+        int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
+        if (grid > npoint) grid = npoint;
+        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)p->sweep.strat.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        void *args[] = {&b, &f};
+        HIPCHK(hipModuleLaunchKernel(p->sweep.strat.f, (unsigned)grid, 1, 1, (unsigned)p->sweep.strat.threads, 1, 1, (unsigned)lds, st, args, nullptr));
+        p->sweep.last_grid = (int)grid;
+        p->sweep.last_threads = p->sweep.strat.threads;
+        HIPCHK(hipMemcpyAsync(hlog.data(), d + o_log, hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hst.data(), d + o_st, P * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out, d + o_out, P * nmap * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (d_out) HIPCHK(hipMemcpyAsync(d_out, d + o_d, P * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (counts_out) HIPCHK(hipMemcpyAsync(hoff.data(), d + o_off, hoff.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int q = 0; q < npoint; ++q) results[q].seconds = seconds;
+        return MCI_OK;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st); // (nothing of a failed call is still reading the buffer when it goes back)
+    sweep_release(p->ctx, base, got);
+    if (rc) return rc;
+    if (counts_out)
+        for (size_t q = 0; q < P; ++q)
+            for (size_t h = 0; h < nc; ++h) counts_out[q * nc + h] = hoff[q * (nc + 1) + h + 1] - hoff[q * (nc + 1) + h];
+    // per point what mci_integrate makes of stratified log rows (strat_mean_std, then mci_average)
+    const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
+    std::vector<double> tm((size_t)niter * s.nobs), te((size_t)niter * s.nobs);
+    for (int q = 0; q < npoint; ++q) {
+        mci_result *res = &results[q];
+        double *im = iter_mean ? iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
+        double *ie = iter_std ? iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
+        res->neval = 0;
+        for (int it = 0; it < niter; ++it) {
+            const double *row = hlog.data() + ((size_t)q * niter + it) * nstat;
+            strat_mean_std(row, s.nobs, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
+            res->neval += (int64_t)row[2 * s.nobs + 1];
+            if (res->visited && it == niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
+        }
+        if (iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
+        if (iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
+        for (int o = 0; o < s.nobs; ++o)
+            mci_average(im + o, ie + o, s.nobs, ignore + 1, niter, &res->mean[o], &res->stdev[o], &res->chi2[o]);
+        res->correlated = 0;
+        res->warmup = 0;
+        if (status) status[q] = hst[q];
+    }
+    return MCI_OK;
+}

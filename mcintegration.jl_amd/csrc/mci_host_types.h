@@ -428,6 +428,7 @@ struct mci_problem {
             hipFunction_t f = nullptr;
             std::string code_object;
         } leaves;
+        Unit strat;                   // the unit of mci_sweep_strat.h (mci_integrate_sweep_strat: stratified points)
     } sweep;
 };
 
@@ -732,6 +733,12 @@ void drop_modules(mci_problem *p) {
     if (p->sweep.leaves.module) {
         (void)hipModuleUnload(p->sweep.leaves.module);
         p->sweep.leaves.module = nullptr;
+    }
+    p->sweep.strat.compiled = false;
+    p->sweep.strat.f = nullptr;
+    if (p->sweep.strat.module) {
+        (void)hipModuleUnload(p->sweep.strat.module);
+        p->sweep.strat.module = nullptr;
     }
 }
 

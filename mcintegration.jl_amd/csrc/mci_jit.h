@@ -40,6 +40,8 @@ extern const char *const kStratHeader;
 extern const char *const kSweepHeader;
 // text of mci_sweep_leaves.h (sweeps of problems with several variable leaves): the third header of a kUnitSweepLeaves unit, behind mci_train.h
 extern const char *const kSweepLeavesHeader;
+// text of mci_sweep_strat.h (stratified points in sweeps): the fourth header of a kUnitSweepStrat unit, behind mci_strat.h and mci_train.h
+extern const char *const kSweepStratHeader;
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -112,12 +114,14 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // compiled like the persistent unit (scan walk, one Continuous grid) plus MCI_WORK_ITEM_FROM_CALLER, which no other unit sets
 // kUnitSweepLeaves: the same loop inside the sweep kernel of mci_sweep_leaves.h, for any mix of Continuous and Discrete leaves: the scan
 // walk and MCI_WORK_ITEM_FROM_CALLER like kUnitSweep, but the Discrete form of train! stays in and the learning rate is each leaf's own
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7 };
+// kUnitSweepStrat: the stratified sample trip (mci_strat.h strat_trip) inside the sweep kernel of mci_sweep_strat.h (one workgroup runs a
+// point's whole VEGAS+ loop); compiled like kUnitSweep (scan walk, one Continuous grid, the leaf's learning rate)
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8 };
 // which headers a unit is compiled against next to mci_device.h
-enum { kHdrNone = 0, kHdrTrain = 1, kHdrSpec = 2, kHdrStrat = 3, kHdrSweep = 4, kHdrSweepLeaves = 5 };
+enum { kHdrNone = 0, kHdrTrain = 1, kHdrSpec = 2, kHdrStrat = 3, kHdrSweep = 4, kHdrSweepLeaves = 5, kHdrSweepStrat = 6 };
 inline std::string generate_source(const ProblemShape &s, int solver, int unit = kUnitSolver, double persist_alpha = 0.0) {
     std::ostringstream o;
-    if (unit == kUnitVegasPersist || unit == kUnitSweep) { // the learning rate and the size of the one leaf the persistent kernel refines (mci_train.h rescale, sum_julia)
+    if (unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepStrat) { // the learning rate and the size of the one leaf the persistent kernel refines (mci_train.h rescale, sum_julia)
         o << "#define MCI_TRAIN_POWER " << (persist_alpha == 2.0 ? 2 : persist_alpha == 3.0 ? 3 : persist_alpha == 1.0 ? 1 : 4) << "\n";
         if (!s.leaf_nbin.empty() && s.leaf_nbin[0] <= 1024) o << "#define MCI_TRAIN_SHORT_SUMS 1\n";
     }
@@ -126,8 +130,8 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
         for (int n : s.leaf_nbin) all_short = all_short && n <= 1024;
         if (all_short) o << "#define MCI_TRAIN_SHORT_SUMS 1\n";
     }
-    if (solver == 0 && unit != kUnitDump) o << "#define MCI_MF_ONLY " << (unit == kUnitVegasMf1 || unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepLeaves ? 1 : 0) << "\n";
-    if (unit == kUnitVegasPersist || unit == kUnitSweep) o << "#define MCI_TRAIN_SCAN_ONLY 1\n#define MCI_TRAIN_CONTINUOUS_ONLY 1\n";
+    if (solver == 0 && unit != kUnitDump) o << "#define MCI_MF_ONLY " << (unit == kUnitVegasMf1 || unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepLeaves || unit == kUnitSweepStrat ? 1 : 0) << "\n";
+    if (unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepStrat) o << "#define MCI_TRAIN_SCAN_ONLY 1\n#define MCI_TRAIN_CONTINUOUS_ONLY 1\n";
     if (unit == kUnitSweepLeaves) o << "#define MCI_TRAIN_SCAN_ONLY 1\n"; // (MCI_TRAIN_POWER undefined: alpha is decided per leaf at run time)
     if (unit == kUnitSweep || unit == kUnitSweepLeaves) o << "#define MCI_WORK_ITEM_FROM_CALLER 1\n"; // (mci_device.h work_item: the row comes from vegas_sweep)
     if (s.rng_rounds != 10) o << "#define MCI_PHILOX_ROUNDS " << s.rng_rounds << "\n"; // opt-in cheaper stream (mci_set_rng_rounds)
@@ -137,6 +141,7 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
     if (unit == kUnitStrat) o << "#include \"mci_strat.h\"\n";
     if (unit == kUnitSweep) o << "#include \"mci_sweep.h\"\n"; // (includes mci_train.h)
     if (unit == kUnitSweepLeaves) o << "#include \"mci_sweep_leaves.h\"\n"; // (likewise)
+    if (unit == kUnitSweepStrat) o << "#include \"mci_sweep_strat.h\"\n"; // (includes mci_strat.h and mci_train.h)
     o << "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n";
     o << "#ifndef MCI_CHAIN_KERNEL_ATTR\n#define MCI_CHAIN_KERNEL_ATTR\n#endif\n"; // (occupancy experiments on the lane-per-chain kernels: MCI_JIT_FLAGS=-DMCI_CHAIN_KERNEL_ATTR=...)
     o << "namespace {\nstruct Cfg {\n";
@@ -200,6 +205,9 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
     } else if (solver == 0 && unit == kUnitSweep) {
         o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep(mci::BatchArgs a, mci::SweepArgs f) { "
              "mci::vegas_sweep<Cfg>(a, f); }\n";
+    } else if (solver == 0 && unit == kUnitSweepStrat) {
+        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep_strat(mci::BatchArgs a, mci::SweepStratArgs f) { "
+             "mci::vegas_sweep_strat<Cfg>(a, f); }\n";
     } else if (solver == 0 && unit == kUnitSweepLeaves) {
         o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep_leaves(mci::BatchArgs a, mci::SweepLeavesArgs f) { "
              "mci::vegas_sweep_leaves<Cfg>(a, f); }\n";
@@ -428,6 +436,7 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     if (extra_hdr == kHdrStrat) key += std::string("\n//HDR\n") + kStratHeader;
     if (extra_hdr == kHdrSweep) key += std::string("\n//HDR\n") + kTrainHeader + "\n//HDR\n" + kSweepHeader;
     if (extra_hdr == kHdrSweepLeaves) key += std::string("\n//HDR\n") + kTrainHeader + "\n//HDR\n" + kSweepLeavesHeader;
+    if (extra_hdr == kHdrSweepStrat) key += std::string("\n//HDR\n") + kStratHeader + "\n//HDR\n" + kTrainHeader + "\n//HDR\n" + kSweepStratHeader;
     for (auto &f : opts) key += "\n//" + f;
     key += "\n//COMPILER " + compiler_id();
     char name[64];
@@ -448,10 +457,20 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     if (cache_only) return -1; // (not in the cache: the caller compiles it elsewhere, e.g. on a thread of its own)
     warm_up_join();
     hiprtcProgram prog;
-    const bool leaves = extra_hdr == kHdrSweepLeaves;
-    const char *hdr[3] = {kDeviceHeader, extra_hdr == kHdrSpec ? kSpecHeader : extra_hdr == kHdrStrat ? kStratHeader : kTrainHeader, leaves ? kSweepLeavesHeader : kSweepHeader},
-               *hname[3] = {"mci_device.h", extra_hdr == kHdrSpec ? "mci_spec.h" : extra_hdr == kHdrStrat ? "mci_strat.h" : "mci_train.h", leaves ? "mci_sweep_leaves.h" : "mci_sweep.h"};
-    if (hiprtcCreateProgram(&prog, src.c_str(), "mci_problem.hip", extra_hdr == kHdrSweep || leaves ? 3 : extra_hdr != kHdrNone ? 2 : 1, hdr, hname) != HIPRTC_SUCCESS) {
+    // mci_device.h, then the unit's own headers in the order they include one another (at most four in all: kHdrSweepStrat)
+    const char *hdr[4] = {kDeviceHeader, nullptr, nullptr, nullptr}, *hname[4] = {"mci_device.h", nullptr, nullptr, nullptr};
+    int nhdr = 1;
+    auto add = [&](const char *text, const char *name) {
+        hdr[nhdr] = text;
+        hname[nhdr++] = name;
+    };
+    if (extra_hdr == kHdrSpec) add(kSpecHeader, "mci_spec.h");
+    if (extra_hdr == kHdrStrat || extra_hdr == kHdrSweepStrat) add(kStratHeader, "mci_strat.h");
+    if (extra_hdr == kHdrTrain || extra_hdr == kHdrSweep || extra_hdr == kHdrSweepLeaves || extra_hdr == kHdrSweepStrat) add(kTrainHeader, "mci_train.h");
+    if (extra_hdr == kHdrSweep) add(kSweepHeader, "mci_sweep.h");
+    if (extra_hdr == kHdrSweepLeaves) add(kSweepLeavesHeader, "mci_sweep_leaves.h");
+    if (extra_hdr == kHdrSweepStrat) add(kSweepStratHeader, "mci_sweep_strat.h");
+    if (hiprtcCreateProgram(&prog, src.c_str(), "mci_problem.hip", nhdr, hdr, hname) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return 1;
     }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mci_train.h" // merge / train device functions, ST_* status bits
+#include "mci_strat.h" // the allocation rule k_strat_alloc shares with the stratified sweep (strat_alloc_*)
 
 namespace mci {
 
@@ -252,17 +253,11 @@ struct StratAllocArgs {
     int ntile;
     int uniform;            // 1: d_h = 1 whatever d holds
 };
-__device__ inline void strat_stretch(const StratAllocArgs &a, long long &lo, long long &hi) {
-    const long long tl = (a.ncube + a.ntile - 1) / a.ntile, t0 = (long long)blockIdx.x * tl, t1 = t0 + tl < a.ncube ? t0 + tl : a.ncube;
-    const long long per = (t1 - t0 + 255) / 256;
-    lo = t0 + (long long)threadIdx.x * per;
-    if (lo > t1) lo = t1;
-    hi = lo + per < t1 ? lo + per : t1;
-}
+// The arithmetic per tile and thread is mci_strat.h's allocation rule (strat_alloc_*), which the stratified sweep's one workgroup walks
+// tile by tile (mci_sweep_strat.h); here blockIdx.x selects the tile.
 __global__ void __launch_bounds__(256) k_strat_alloc(StratAllocArgs a, int phase) {
     __shared__ double part[256];
     const int tid = threadIdx.x;
-    const long long M = a.nsamp - 2 * a.ncube;
     if (phase == 1) {
         if (tid != 0) return;
         double base = 0.0;
@@ -271,43 +266,22 @@ __global__ void __launch_bounds__(256) k_strat_alloc(StratAllocArgs a, int phase
             base += a.tsum[g];
         }
         a.tsum[2 * a.ntile] = base;
-        a.tsum[2 * a.ntile + 1] = (a.uniform || !(base > 0.0) || !isfinite(base)) ? 1.0 : 0.0;
+        a.tsum[2 * a.ntile + 1] = strat_alloc_uniform(a.uniform, base) ? 1.0 : 0.0;
         return;
     }
     long long lo, hi;
-    strat_stretch(a, lo, hi);
-    double mine = 0.0;
-    if (!(phase == 2 && a.tsum[2 * a.ntile + 1] != 0.0))
-        for (long long h = lo; h < hi; ++h) mine += a.d[h];
-    part[tid] = mine;
+    strat_alloc_stretch(a.ncube, a.ntile, (int)blockIdx.x, tid, lo, hi);
+    const bool uniform = phase == 2 && a.tsum[2 * a.ntile + 1] != 0.0;
+    part[tid] = uniform ? 0.0 : strat_alloc_stretch_sum(a.d, lo, hi);
     __syncthreads();
     if (phase == 0) {
-        if (tid == 0) {
-            double s = 0.0;
-            for (int t = 0; t < 256; ++t) s += part[t];
-            a.tsum[blockIdx.x] = s;
-        }
+        if (tid == 0) a.tsum[blockIdx.x] = strat_alloc_base(part, 256);
         return;
     }
     if (blockIdx.x == 0 && tid == 0) a.off[0] = 0;
-    if (a.tsum[2 * a.ntile + 1] != 0.0) { // uniform: C_h = M (h + 1) / ncube
-        for (long long h = lo; h < hi; ++h) {
-            double C = (double)M * (double)(h + 1) / (double)a.ncube;
-            if (h == a.ncube - 1 || C > (double)M) C = (double)M;
-            a.off[h + 1] = 2 * (h + 1) + (long long)floor(C);
-        }
-        return;
-    }
-    double sbase = 0.0; // this thread's stretch base within the tile: the stretches before it, added in order
-    for (int t = 0; t < tid; ++t) sbase += part[t];
-    const double tbase = a.tsum[a.ntile + blockIdx.x], total = a.tsum[2 * a.ntile];
-    double run = 0.0;
-    for (long long h = lo; h < hi; ++h) {
-        run += a.d[h];
-        double C = (double)M * (tbase + (sbase + run)) / total;
-        if (h == a.ncube - 1 || C > (double)M) C = (double)M;
-        a.off[h + 1] = 2 * (h + 1) + (long long)floor(C);
-    }
+    // (this thread's stretch base within the tile: the stretches before it, added in order)
+    const double sbase = uniform ? 0.0 : strat_alloc_base(part, tid);
+    strat_alloc_offsets(a.d, a.off, a.ncube, a.nsamp, lo, hi, uniform ? 1 : 0, sbase, a.tsum[a.ntile + blockIdx.x], a.tsum[2 * a.ntile]);
 }
 
 // k_strat_remap: a carried d_h (mci_set_stratification_carry) moved from the plan it was measured on to another plan of the same

@@ -38,6 +38,55 @@ struct StratArgs {
     long long *dump_h;
 };
 
+// The allocation rule of k_strat_alloc (mci_static_kernels.h) and of the stratified sweep (mci_sweep_strat.h), per tile and thread: the
+// hypercubes are cut into ntile tiles, a tile into 256 stretches; P_h = tile base + (stretch base + running sum), every base the
+// sequential sum of what lies before it; C_h = M P_h / P (M = N - 2 ncube), off[h + 1] = 2 (h + 1) + floor(C_h), the last C_h := M.
+// k_strat_alloc takes the tile from blockIdx.x, the sweep's one workgroup walks the tiles in order.
+// >>> strat alloc rule (compiled for the host by tests/test_sweep_strat_host.py)
+__host__ __device__ inline int strat_alloc_ntile(long long ncube) { return (int)((ncube + 255) / 256 < 1024 ? (ncube + 255) / 256 : 1024); }
+// the hypercubes [lo, hi) of thread tid of 256 in tile `tile` of ntile
+__host__ __device__ inline void strat_alloc_stretch(long long ncube, int ntile, int tile, int tid, long long &lo, long long &hi) {
+    const long long tl = (ncube + ntile - 1) / ntile, t0 = (long long)tile * tl, t1 = t0 + tl < ncube ? t0 + tl : ncube;
+    const long long per = (t1 - t0 + 255) / 256;
+    lo = t0 + (long long)tid * per;
+    if (lo > t1) lo = t1;
+    hi = lo + per < t1 ? lo + per : t1;
+}
+__host__ __device__ inline double strat_alloc_stretch_sum(const double *d, long long lo, long long hi) {
+    double mine = 0.0;
+    for (long long h = lo; h < hi; ++h) mine += d[h];
+    return mine;
+}
+// 256 stretch sums of a tile -> the tile's sum | the base of stretch tid: added in stretch order
+__host__ __device__ inline double strat_alloc_base(const double *part, int tid) {
+    double s = 0.0;
+    for (int t = 0; t < tid; ++t) s += part[t];
+    return s;
+}
+// d_h = 1 whatever d holds: asked for, or a total that is 0 or not finite
+__host__ __device__ inline int strat_alloc_uniform(int asked, double total) { return (asked || !(total > 0.0) || !(total - total == 0.0)) ? 1 : 0; }
+// off[h + 1] for the hypercubes [lo, hi) of one stretch; sbase / tbase / total are not read when uniform
+__host__ __device__ inline void strat_alloc_offsets(const double *d, long long *off, long long ncube, long long nsamp, long long lo, long long hi, int uniform,
+                                                    double sbase, double tbase, double total) {
+    const long long M = nsamp - 2 * ncube;
+    if (uniform) { // C_h = M (h + 1) / ncube
+        for (long long h = lo; h < hi; ++h) {
+            double C = (double)M * (double)(h + 1) / (double)ncube;
+            if (h == ncube - 1 || C > (double)M) C = (double)M;
+            off[h + 1] = 2 * (h + 1) + (long long)floor(C);
+        }
+        return;
+    }
+    double run = 0.0;
+    for (long long h = lo; h < hi; ++h) {
+        run += d[h];
+        double C = (double)M * (tbase + (sbase + run)) / total;
+        if (h == ncube - 1 || C > (double)M) C = (double)M;
+        off[h + 1] = 2 * (h + 1) + (long long)floor(C);
+    }
+}
+// <<< strat alloc rule
+
 // largest y below 1: (i + u) / n rounds to 1.0 for some u < 1 (i = 2, n = 3, u = 1 - 2^-52), and draw_leaf would read bin N
 __device__ __forceinline__ double strat_clamp(double y) { return fmin(y, 0x1.fffffffffffffp-1); }
 
@@ -95,6 +144,86 @@ __device__ __forceinline__ double strat_s2(double s1, double s2, double n) {
 // lane values / reduction scratch [T][2 NW]
 template <class Cfg> constexpr int strat_lds_doubles(int nloc, int T) { return (nloc + 1) + nloc * 2 * Cfg::NW + T + T * 2 * Cfg::NW; }
 
+// One trip of the chunk [c0, c1): the T samples base + tid.  The chunk's hypercubes are hfirst .. hfirst + nl - 1, their offsets staged in
+// sOff[nl + 1]; a lane finds its hypercube by bisection there, draws, evaluates, adds to the LDS histogram and to its own acc / extra; then
+// the first lane of every run of one hypercube adds the run up, in lane order, into that hypercube's sums sS.  Ends behind a barrier.
+// Shared by vegas_strat and the stratified sweep (mci_sweep_strat.h).
+template <class Cfg, int DPC> __device__ __forceinline__ void strat_trip(const BatchArgs &a, const StratArgs &st, const Tables<Cfg> &t, const RoundKeys<false> &keys, u32 stream,
+                                                                          long long base, long long c1, long long hfirst, int nl, const long long *sOff, double *sS,
+                                                                          int *sLane, double *sV, double *sH, double *acc /*[NW]*/, double *extra /*[NCOLS - NOBS]*/) {
+    constexpr int NW = Cfg::NW;
+    const int tid = threadIdx.x, T = blockDim.x;
+    const long long sidx = base + tid;
+    const bool valid = sidx < c1;
+    int jl = -1;
+    if (valid) {
+        int l = 0, h = nl - 1; // largest j with sOff[j] <= sidx
+        while (l < h) {
+            const int m = (l + h + 1) >> 1;
+            if (sOff[m] <= sidx) l = m;
+            else h = m - 1;
+        }
+        jl = l;
+        const long long hc = hfirst + l;
+        const long long nh = sOff[l + 1] - sOff[l];
+        const double r = (double)st.nsamp / ((double)st.ncube * (double)nh); // r_h
+        int cell[Cfg::NDRAW];
+        u32 q = (u32)hc;
+        static_for<0, Cfg::NDRAW>([&](auto K) { // mixed radix, draw 0 fastest
+            constexpr int k = decltype(K)::value;
+            const u32 qn = (u32)(((u64)q * st.magic[k]) >> st.shift[k]);
+            cell[k] = (int)(q - qn * (u32)st.nstrat[k]);
+            q = qn;
+        });
+        Sample<Cfg> s;
+        double *yd = st.dump_y ? st.dump_y + sidx * Cfg::NDRAW : nullptr;
+        draw_sample_strat<Cfg, false, DPC>(t, keys, stream, (u64)(st.first_index + sidx), st, cell, s, yd);
+        double w[NW];
+        Cfg::integrand(s.x, w, a.ud, -1); // vegas/montecarlo.jl:140-144
+        extra[Cols<Cfg>::NEVAL - Cfg::NOBS] += 1.0;
+        extra[Cols<Cfg>::NORM - Cfg::NOBS] += 1.0;
+        static_for<0, NW>([&](auto Q) {
+            constexpr int qq = decltype(Q)::value;
+            const double fj = w[qq] * s.jaci[qq / Cfg::NCOMP]; // f J  (vegas/montecarlo.jl:152, J without r_h)
+            acc[qq] += fj * r;                                 // the observable: jac * r_h
+            sV[tid * NW + qq] = fj;
+        });
+        double wh[Cfg::NI];
+        static_for<0, Cfg::NI>([&](auto I) {
+            constexpr int i = decltype(I)::value;
+            const double wj = absw<Cfg, i>(w) * s.jac; // vegas/montecarlo.jl:173-174
+            wh[i] = wj * wj * r;                       // (|w| jac)^2 r_h: each bin estimates what classic :vegas estimates
+        });
+        hist_update<Cfg, 0>(s, wh, sH, a.ghist, 0);
+        if (st.dump_x) {
+            static_for<0, Cfg::NDRAW>([&](auto K) { st.dump_x[sidx * Cfg::NDRAW + decltype(K)::value] = s.x[decltype(K)::value]; });
+            static_for<0, NW>([&](auto Q) { st.dump_w[sidx * NW + decltype(Q)::value] = w[decltype(Q)::value]; });
+            st.dump_jac[sidx] = s.jac;
+            st.dump_h[sidx] = hc;
+        }
+    }
+    sLane[tid] = jl;
+    __syncthreads();
+    // the first lane of every run of one hypercube adds the run up, in lane order, into that hypercube's LDS sums
+    if (valid && (tid == 0 || sLane[tid - 1] != jl)) {
+        double s1[NW], s2[NW];
+        static_for<0, NW>([&](auto Q) { s1[decltype(Q)::value] = 0.0; s2[decltype(Q)::value] = 0.0; });
+        for (int u = tid; u < T && sLane[u] == jl; ++u)
+            static_for<0, NW>([&](auto Q) {
+                constexpr int qq = decltype(Q)::value;
+                const double v = sV[u * NW + qq];
+                s1[qq] += v;
+                s2[qq] += v * v;
+            });
+        static_for<0, NW>([&](auto Q) {
+            constexpr int qq = decltype(Q)::value;
+            sS[jl * 2 * NW + qq] += s1[qq];
+            sS[jl * 2 * NW + NW + qq] += s2[qq];
+        });
+    }
+    __syncthreads();
+}
+
 template <class Cfg> __device__ __forceinline__ void vegas_strat(const BatchArgs &a, const StratArgs &st) {
     static_assert(Cfg::NTILE == 1 && Cfg::CUSTOM_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0 && Cfg::HOST_MEASURE == 0, "stratified :vegas: one tile, device integrand, default measure");
     static_assert(Cfg::NDRAW <= kStratMaxDraw && Cfg::NW <= kStratMaxCols, "stratified :vegas: draws / columns");
@@ -126,7 +255,7 @@ template <class Cfg> __device__ __forceinline__ void vegas_strat(const BatchArgs
     static_for<0, NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
     double extra[Cfg::NCOLS - Cfg::NOBS];
     static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
-    const double V = 1.0 / (double)st.ncube, N = (double)st.nsamp;
+    const double V = 1.0 / (double)st.ncube;
 
     for (long long chunk = blockIdx.x; chunk < st.nchunk; chunk += gridDim.x) {
         const long long c0 = chunk * st.chunk, c1 = c0 + st.chunk < st.nsamp ? c0 + st.chunk : st.nsamp;
@@ -149,77 +278,7 @@ template <class Cfg> __device__ __forceinline__ void vegas_strat(const BatchArgs
         for (int j = tid; j <= nl; j += T) sOff[j] = st.off[hfirst + j];
         for (int j = tid; j < nl * 2 * NW; j += T) sS[j] = 0.0;
         __syncthreads();
-        for (long long base = c0; base < c1; base += T) {
-            const long long sidx = base + tid;
-            const bool valid = sidx < c1;
-            int jl = -1;
-            if (valid) {
-                int l = 0, h = nl - 1; // largest j with sOff[j] <= sidx
-                while (l < h) {
-                    const int m = (l + h + 1) >> 1;
-                    if (sOff[m] <= sidx) l = m;
-                    else h = m - 1;
-                }
-                jl = l;
-                const long long hc = hfirst + l;
-                const long long nh = sOff[l + 1] - sOff[l];
-                const double r = N / ((double)st.ncube * (double)nh); // r_h
-                int cell[Cfg::NDRAW];
-                u32 q = (u32)hc;
-                static_for<0, Cfg::NDRAW>([&](auto K) { // mixed radix, draw 0 fastest
-                    constexpr int k = decltype(K)::value;
-                    const u32 qn = (u32)(((u64)q * st.magic[k]) >> st.shift[k]);
-                    cell[k] = (int)(q - qn * (u32)st.nstrat[k]);
-                    q = qn;
-                });
-                Sample<Cfg> s;
-                double *yd = st.dump_y ? st.dump_y + sidx * Cfg::NDRAW : nullptr;
-                draw_sample_strat<Cfg, false, DPC>(t, keys, stream, (u64)(st.first_index + sidx), st, cell, s, yd);
-                double w[NW];
-                Cfg::integrand(s.x, w, a.ud, -1); // vegas/montecarlo.jl:140-144
-                extra[Cols<Cfg>::NEVAL - Cfg::NOBS] += 1.0;
-                extra[Cols<Cfg>::NORM - Cfg::NOBS] += 1.0;
-                static_for<0, NW>([&](auto Q) {
-                    constexpr int qq = decltype(Q)::value;
-                    const double fj = w[qq] * s.jaci[qq / Cfg::NCOMP]; // f J  (vegas/montecarlo.jl:152, J without r_h)
-                    acc[qq] += fj * r;                                 // the observable: jac * r_h
-                    sV[tid * NW + qq] = fj;
-                });
-                double wh[Cfg::NI];
-                static_for<0, Cfg::NI>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    const double wj = absw<Cfg, i>(w) * s.jac; // vegas/montecarlo.jl:173-174
-                    wh[i] = wj * wj * r;                       // (|w| jac)^2 r_h: each bin estimates what classic :vegas estimates
-                });
-                hist_update<Cfg, 0>(s, wh, sH, a.ghist, 0);
-                if (st.dump_x) {
-                    static_for<0, Cfg::NDRAW>([&](auto K) { st.dump_x[sidx * Cfg::NDRAW + decltype(K)::value] = s.x[decltype(K)::value]; });
-                    static_for<0, NW>([&](auto Q) { st.dump_w[sidx * NW + decltype(Q)::value] = w[decltype(Q)::value]; });
-                    st.dump_jac[sidx] = s.jac;
-                    st.dump_h[sidx] = hc;
-                }
-            }
-            sLane[tid] = jl;
-            __syncthreads();
-            // the first lane of every run of one hypercube adds the run up, in lane order, into that hypercube's LDS sums
-            if (valid && (tid == 0 || sLane[tid - 1] != jl)) {
-                double s1[NW], s2[NW];
-                static_for<0, NW>([&](auto Q) { s1[decltype(Q)::value] = 0.0; s2[decltype(Q)::value] = 0.0; });
-                for (int u = tid; u < T && sLane[u] == jl; ++u)
-                    static_for<0, NW>([&](auto Q) {
-                        constexpr int qq = decltype(Q)::value;
-                        const double v = sV[u * NW + qq];
-                        s1[qq] += v;
-                        s2[qq] += v * v;
-                    });
-                static_for<0, NW>([&](auto Q) {
-                    constexpr int qq = decltype(Q)::value;
-                    sS[jl * 2 * NW + qq] += s1[qq];
-                    sS[jl * 2 * NW + NW + qq] += s2[qq];
-                });
-            }
-            __syncthreads();
-        }
+        for (long long base = c0; base < c1; base += T) strat_trip<Cfg, DPC>(a, st, t, keys, stream, base, c1, hfirst, nl, sOff, sS, sLane, sV, sH, acc, extra);
         // the chunk's hypercubes: interior ones -> partial row + d_h, cut ones -> boundary records
         double pm[2 * NW];
         static_for<0, 2 * NW>([&](auto Q) { pm[decltype(Q)::value] = 0.0; });

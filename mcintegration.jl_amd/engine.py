@@ -439,14 +439,15 @@ class Engine:
     # ---- kernels -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_code(solver):
-        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9}.get(solver) or _lib.SOLVERS[solver]
+        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
         "vegasmc_lanes" | "mcmc_lanes" (the chain solvers' kernels with several lanes per chain, csrc/mci_spec.h) | "vegas_strat" (the
         stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification) | "vegas_sweep" (the kernel of
         integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts) | "vegas_sweep_leaves" (the sweep kernel of a problem with
-        several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all"))"""
+        several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all")) | "vegas_sweep_strat" (the kernel of
+        integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -801,6 +802,89 @@ class Engine:
                      maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]))
                 for q in range(P)]
 
+    def sweep_strat_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, **kw):
+        """None when integrate_sweep_strat takes this (stratified) problem with these arguments, else the reason
+        (mci_sweep_strat_supported)"""
+        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, 0)
+        why = C.create_string_buffer(512)
+        if lib().mci_sweep_strat_supported(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
+            return None
+        return why.value.decode() or lib().mci_last_error().decode(errors="replace")
+
+    def sweep_strat_plan(self, neval=10000, block=16):
+        """{nstrat, ncube, beta} of the plan a stratified sweep of these arguments runs on: the nstrat set_stratification was given, or
+        the default plan for this neval (mci_strat_plan)"""
+        req = getattr(self, "_strat_req", None)
+        if req is None:
+            raise ValueError("sweep_strat_plan: the problem is not stratified (set_stratification)")
+        a = self._integrate_args("vegas", neval, 1, block, -1, True, 1.0, 1, 0, 0)
+        nc = C.c_int64()
+        check(lib().mci_sweep_strat_doubles(self.p, C.byref(a), C.byref(nc)))
+        if req[0] is not None:
+            ns = list(req[0])
+        else:
+            npb, nb = C.c_int64(), C.c_int64()
+            lib().mci_standardize_block(int(neval), int(block), 1, C.byref(npb), C.byref(nb))
+            buf = np.zeros(self.ndraw, dtype=np.int32)
+            check(lib().mci_strat_plan(npb.value * nb.value, self.ndraw, req[2], buf.ctypes.data_as(c_int32_p)))
+            ns = [int(v) for v in buf]
+        return dict(nstrat=ns, ncube=int(nc.value), beta=req[1])
+
+    def integrate_sweep_strat(self, solver="vegas", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1,
+                              seed=1234, seeds=None, maps=None, first_iteration=0, d=None):
+        """A stratified parameter sweep in one launch (mci_integrate_sweep_strat): P independent VEGAS+ loops -- what integrate() runs on
+        this stratified engine -- one workgroup per point.  Arguments and result dicts as integrate_sweep (one Continuous leaf); every
+        dict gains `strat_d` (the d_h the point's last iteration measured, [ncube]) and `strat_counts` (n_h of the allocation that
+        iteration used).  d: None (every point starts from a uniform allocation) or [P][ncube] d_h measured on exactly this plan and
+        beta -- e.g. the strat_d of an earlier sweep; with adapt=False the allocation made from it stays for the whole call.  The
+        engine's own map, logs and allocation are not touched.  Raises MCIError with the reason of sweep_strat_supported()."""
+        nud = len(self.integrand.userdata) if hasattr(self.integrand, "userdata") else 0
+        ud = np.ascontiguousarray(userdata if userdata is not None else np.zeros((0, nud)), dtype=np.float64)
+        if ud.ndim != 2 or ud.shape[1] != nud:
+            raise ValueError("integrate_sweep_strat: userdata must be a 2-D array [points][%d] (one row of the integrand's userdata per point), got shape %s"
+                             % (nud, ud.shape))
+        P = ud.shape[0]
+        if not 1 <= P <= self.SWEEP_MAX_POINTS:
+            raise ValueError("integrate_sweep_strat: %d points; a sweep takes 1 to %d" % (P, self.SWEEP_MAX_POINTS))
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if sd.shape != (P,):
+                raise ValueError("integrate_sweep_strat: seeds must hold one seed per point (%d), got shape %s" % (P, sd.shape))
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
+        nc = C.c_int64()
+        check(lib().mci_sweep_strat_doubles(self.p, C.byref(a), C.byref(nc)))
+        ncube = int(nc.value)
+        nmap = self.sweep_map_doubles()
+        mi = None
+        if maps is not None:
+            mi = np.ascontiguousarray(maps, dtype=np.float64)
+            if mi.shape != (P, nmap):
+                raise ValueError("integrate_sweep_strat: maps must be [points = %d][grid points = %d], got shape %s" % (P, nmap, mi.shape))
+        di = None
+        if d is not None:
+            di = np.ascontiguousarray(d, dtype=np.float64)
+            if di.shape != (P, ncube):
+                raise ValueError("integrate_sweep_strat: d must be [points = %d][hypercubes = %d], got shape %s" % (P, ncube, di.shape))
+        n = self.nobs
+        im, ie = np.zeros((P, niter, n)), np.zeros((P, niter, n))
+        m, s, c2 = np.zeros((P, n)), np.zeros((P, n)), np.zeros((P, n))
+        vis = np.zeros((P, self.config.N + 1))
+        mo = np.zeros((P, max(nmap, 1)))
+        do, co = np.zeros((P, ncube)), np.zeros((P, ncube), dtype=np.int64)
+        st = np.zeros(P, dtype=np.int32)
+        res = (_lib.ResultC * P)()
+        for q in range(P):
+            res[q] = _lib.ResultC(niter, n, None, None, _dp(m[q]), _dp(s[q]), _dp(c2[q]), 0, 0.0, _dp(vis[q]), 0, 0)
+        check(lib().mci_integrate_sweep_strat(self.p, C.byref(a), P, _dp(ud) if ud.size else None,
+                                              sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
+                                              _dp(mi) if mi is not None else None, _dp(mo), _dp(di) if di is not None else None, _dp(do),
+                                              co.ctypes.data_as(C.POINTER(C.c_int64)), res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
+        return [dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
+                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
+                     maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]), strat_d=do[q], strat_counts=co[q])
+                for q in range(P)]
+
     def sweep_workgroups(self, g=0):
         """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""
         check(lib().mci_debug_sweep_workgroups(self.p, int(g)))
@@ -866,7 +950,9 @@ class Engine:
         loaded state file, stays with the engine -- through this setter too -- and the next call's first allocation is made from it"""
         if not on:
             check(lib().mci_set_stratification_off(self.p))
+            self._strat_req = None
             return
+        self._strat_req = (None if nstrat is None else [int(v) for v in np.atleast_1d(nstrat)], float(beta), int(max_nhcube))
         check(lib().mci_set_stratification_carry(self.p, 1 if carry else 0))   # (first: the setter below keeps a carried d_h only then)
         ns = None
         if nstrat is not None:

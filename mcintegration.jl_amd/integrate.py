@@ -37,6 +37,34 @@ class Stratify:
         return "Stratify(beta=%r, nstrat=%r, max_nhcube=%r, carry=%r)" % (self.beta, self.nstrat, self.max_nhcube, self.carry)
 
 
+class StratD(np.ndarray):
+    """Result.strat_d of a stratified sweep: the d_h of a point's last iteration, with the plan (`nstrat`) and `beta` it was measured
+    under, so that integrate_sweep(alloc=...) can refuse it on another plan"""
+
+    def __new__(cls, values, nstrat, beta):
+        obj = np.asarray(values, dtype=np.float64).view(cls)
+        obj.nstrat, obj.beta = [int(v) for v in nstrat], float(beta)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.nstrat, self.beta = getattr(obj, "nstrat", None), getattr(obj, "beta", None)
+
+
+def _sweep_alloc_rows(alloc, P, plan):
+    """alloc= of a stratified sweep -> [P][ncube] d_h, checked against the call's plan {nstrat, ncube, beta}"""
+    rows = np.zeros((P, plan["ncube"]))
+    for k, v in enumerate(alloc):
+        ns, beta = getattr(v, "nstrat", None), getattr(v, "beta", None)
+        if ns is not None and (list(ns) != list(plan["nstrat"]) or beta != plan["beta"]):
+            raise ValueError("integrate_sweep: alloc[%d] was measured on nstrat = %s under beta = %r, this call runs nstrat = %s under beta = %r "
+                             "(there is no remap in a sweep)" % (k, list(ns), beta, list(plan["nstrat"]), plan["beta"]))
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape != (plan["ncube"],):
+            raise ValueError("integrate_sweep: alloc[%d] has shape %s, the plan nstrat = %s has %d hypercubes" % (k, v.shape, list(plan["nstrat"]), plan["ncube"]))
+        rows[k] = v
+    return rows
+
+
 def _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm):
     """the Stratify an integrate() call asks for (None: plain), refused -- before any engine exists -- where this mode does not reach"""
     if stratify is None or stratify is False:
@@ -412,7 +440,8 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
-                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", **kwargs):
+                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
+                    **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -432,6 +461,15 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     leaves: "one" (default) sweeps problems with ONE Continuous variable leaf; "all" opts in to sweeps of any mix of Continuous and
     Discrete leaves that fits a workgroup's LDS (Engine.set_sweep_leaves) -- composites, histograms over a Discrete draw.  A `measure`
     closure is traced on the same point as the integrand; one that reads a value off config.userdata is refused (ValueError).
+
+    stratify: True or Stratify(beta, nstrat, max_nhcube) -- every point runs VEGAS+ adaptive stratified sampling, what
+    integrate(..., stratify=...) runs, still in ONE launch (Engine.integrate_sweep_strat; one Continuous variable leaf).  Every Result
+    then carries `stratification` (nstrat, ncube, beta, carried = "uniform" | "same plan"), `strat_d` (the d_h its last iteration
+    measured) and `strat_counts` (the allocation that iteration used).  alloc: a list of P strat_d arrays, e.g. [r.strat_d for r in
+    trained] -- every point's first allocation is made from its entry, which must have been measured on this call's plan and beta
+    (there is no remap in a sweep: a strat_d remembers the plan and beta it was measured under, and another one raises ValueError);
+    with adapt=False the whole scan keeps it: train, then freeze.  A sweep carries through alloc, never through Stratify(carry=True).
+    Where the stratified sweep is refused the points run as integrate(..., stratify=...) calls, as below; alloc= then raises.
 
     A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
     measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
@@ -456,12 +494,24 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
     if maps is not None and len(maps) != P:
         raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
+    if alloc is not None and (stratify is None or stratify is False):
+        raise ValueError("integrate_sweep: alloc= belongs to a stratified sweep (stratify=True or mci.Stratify(...))")
+    if alloc is not None:
+        try:
+            nalloc = len(alloc)
+        except TypeError:
+            raise ValueError("integrate_sweep: alloc must be a list with one strat_d array per point")
+        if nalloc != P:
+            raise ValueError("integrate_sweep: alloc must hold one strat_d array per point (%d), got %d" % (P, nalloc))
     fresh = config is None
     pristine = copy.deepcopy(kwargs) if fresh else None
     if fresh:
         config = Configuration(**kwargs)
     if ignore is None:
         ignore = 1 if adapt else 0
+    strat = _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, LocalComm())
+    if strat is not None and strat.carry:
+        raise ValueError("integrate_sweep: Stratify(carry=True) is the ordinary call's way to carry an allocation; a sweep takes alloc=")
     closure = callable(integrand) and not isinstance(integrand, (Integrand, HostIntegrand))
     why = rows = bound = None
     if closure:
@@ -501,7 +551,36 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         eng = _bind(config, bound, bound_measure if closure else measure, solver, trace=trace, print=print, device=device)
         if hasattr(eng, "set_sweep_leaves"):
             eng.set_sweep_leaves(leaves)
-        why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
+        if strat is not None:
+            if not hasattr(eng, "integrate_sweep_strat"):
+                why = "this engine has no stratified sweep"
+            else:
+                eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)
+                why = eng.sweep_strat_supported(solver, nevalperblock * block, niter, block, measurefreq)
+        else:
+            why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
+    if why is None and strat is not None:
+        plan = eng.sweep_strat_plan(nevalperblock * block, block)
+        d_rows = _sweep_alloc_rows(alloc, P, plan) if alloc is not None else None
+        rs = eng.integrate_sweep_strat(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
+                                       gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
+                                       first_iteration=config.iterations_done, d=d_rows)
+        out = []
+        for p, r in zip(params, rs):
+            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, logs and allocation alone)
+            c.userdata = p if closure else None
+            c.visited = r["visited"]
+            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block)
+            res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
+            res.maps_by_leaf = r.get("maps_by_leaf")
+            res.stratification = dict(nstrat=list(plan["nstrat"]), ncube=plan["ncube"], beta=plan["beta"], carry=False,
+                                      carried="same plan" if alloc is not None else "uniform")
+            res.strat_d, res.strat_counts = StratD(r["strat_d"], plan["nstrat"], plan["beta"]), r["strat_counts"]
+            res.vegas_check, res.warmup, res.neval_discarded = None, 0, 0
+            if print >= 0:
+                report(res)
+            out.append(res)
+        return out
     if why is None:
         rs = eng.integrate_sweep(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
                                  gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
@@ -525,6 +604,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
                          "point from keywords (var=..., dof=...), not from config=" % why)
     if maps is not None:
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and maps= needs the batched form" % why)
+    if alloc is not None:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and alloc= needs the batched form" % why)
     warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),
                   RuntimeWarning, stacklevel=2)
     if eng is not None and hasattr(eng, "close"):
@@ -540,7 +621,7 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         if seeds is not None:
             c.seed = int(seeds[k])
         res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
-                        measurefreq=measurefreq, device=device, trace=trace, print=print)
+                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}))
         res.sweep_batched, res.map, res.maps_by_leaf, res.status = False, None, None, 0
         out.append(res)
     return out

@@ -4,6 +4,7 @@
     python tools/sweep_bench.py threads [--neval 10000] [--points 256,1024] [--repeat 5]
     python tools/sweep_bench.py once --points 1024       (one warm sweep and nothing else: the run a kernel trace is taken of)
     python tools/sweep_bench.py table --layout bubble [--neval 10000] [--points 1,16,256,1024]      (profiles/r11_sweep_leaves.txt)
+    python tools/sweep_bench.py strat [--neval 10000] [--points 1,16,256,1024]                      (profiles/r12_sweep_strat.txt)
 
 The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
 and of the same points as a loop of Engine.integrate calls with the persistent launch, in the same process.
@@ -12,6 +13,9 @@ the sizes interleaved `--repeat` times so that a drift of the box shows as scatt
 `--layout bubble`: the polarisation bubble (catalog.bubble: four Continuous leaves, a Discrete one, a histogram over it) scanned over
 rs, swept with set_sweep_leaves("all") against a loop of ordinary Engine.integrate calls -- what such a scan runs without the opt-in;
 the header line gives the sweep kernel's LDS bytes, workgroups per CU, VGPRs and scratch.
+`strat`: the stratified sweep (Engine.integrate_sweep_strat, the default plan) against a loop of ordinary stratified calls
+(Engine.integrate on a stratified engine: the launch chain of csrc/mci_host_strat.h) and against the classic sweep, the points under
+seeds of their own at ONE parameter value, so that the scatter of their means is the error: sigma^2 x time can be read off each column.
 One GPU process; run each mode under its own time limit."""
 import argparse
 import os
@@ -132,9 +136,60 @@ def bubble_table(Ps, neval):
                  "  (loop: %d calls timed, scaled)" % n if P > n else ""))
 
 
+# ---- strat: stratified points (csrc/mci_sweep_strat.h)
+def strat_table(Ps, neval):
+    from mcintegration_jl_amd import isa_mix
+    kw = dict(neval=neval, niter=NITER, block=BLOCK)
+    strat = sweep_engine()
+    strat.set_stratification()
+    assert strat.sweep_strat_supported(**kw) is None
+    strat.compile("vegas_sweep_strat")
+    res = isa_mix.resources(strat.code_object("vegas_sweep_strat"))["mci_vegas_sweep_strat"]
+    plan = strat.sweep_strat_plan(neval, BLOCK)
+    print("# 4-D Genz product peak (point 0), neval = %d, niter = %d, block = %d; plan nstrat = %s (%d hypercubes), beta = %g"
+          % (neval, NITER, BLOCK, plan["nstrat"], plan["ncube"], plan["beta"]))
+    print("# mci_vegas_sweep_strat: %d VGPRs, %d bytes of scratch" % (res["vgpr"], res["scratch"]))
+    print("# stratified sweep | loop of ordinary stratified calls | classic sweep: ms (us per point-iteration), scatter of the points' means over their seeds")
+    classic = sweep_engine()
+    loop = sweep_engine()
+    loop.set_stratification()
+    g0 = loop.grid(0).copy()
+    loop.integrate("vegas", seed=SEED, **kw)
+    for P in Ps:
+        uds = np.array([point(0)] * P)
+        seeds = [SEED + 1 + k for k in range(P)]
+        out = {}
+        for name, fn in (("strat", strat.integrate_sweep_strat), ("classic", classic.integrate_sweep)):
+            fn("vegas", userdata=uds[:min(P, 4)], seeds=seeds[:min(P, 4)], **kw)      # (compile, first launch)
+            best = float("inf")
+            for _ in range(3):
+                t0 = time.perf_counter()
+                rs = fn("vegas", userdata=uds, seeds=seeds, **kw)
+                best = min(best, time.perf_counter() - t0)
+            assert all(r["status"] == 0 for r in rs)
+            out[name] = (best, np.array([r["mean"][0] for r in rs]))
+        n = min(P, 64)       # (a loop is linear in P: up to 64 calls are timed, larger P scaled)
+        tl, means = float("inf"), []
+        for rep in range(3):
+            means = []
+            t0 = time.perf_counter()
+            for k in range(n):
+                loop.set_grid(0, g0)
+                means.append(loop.integrate("vegas", seed=seeds[k], **kw)["mean"][0])
+            tl = min(tl, (time.perf_counter() - t0) * P / n)
+        out["loop"] = (tl, np.array(means))
+
+        def col(name):
+            t, m = out[name]
+            return "%10.3f ms (%8.3f us) scatter %s" % (1e3 * t, 1e6 * t / (P * NITER), "%.3e" % np.std(m, ddof=1) if m.size > 1 else "   -     ")
+        print("P %5d  strat sweep %s | strat loop %s | classic sweep %s | loop / strat sweep %6.2f, classic / strat sweep %5.2f   grid x threads = %s%s"
+              % (P, col("strat"), col("loop"), col("classic"), out["loop"][0] / out["strat"][0], out["classic"][0] / out["strat"][0],
+                 strat.last_sweep_launch(), "  (loop: %d calls timed, scaled)" % n if P > n else ""))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["table", "threads", "once"])
+    ap.add_argument("mode", choices=["table", "threads", "once", "strat"])
     ap.add_argument("--neval", type=int, default=10000)
     ap.add_argument("--points", default="1,16,256,1024,4096")
     ap.add_argument("--threads", type=int, default=0)
@@ -143,6 +198,9 @@ def main():
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
+    if a.mode == "strat":
+        strat_table([P for P in Ps if P <= 1024] if a.points == "1,16,256,1024,4096" else Ps, a.neval)
+        return
     if a.layout == "bubble":
         if a.mode != "table":
             ap.error("--layout bubble goes with the table mode")
