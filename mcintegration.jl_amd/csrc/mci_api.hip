@@ -15,8 +15,10 @@
 #include <link.h>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <atomic>
 #include <map>
@@ -30,8 +32,8 @@
 #include "mci_static_kernels.h"
 #include "mci_check.h" // k_check_vegas: the static yardstick of new :vegas code objects
 #include "mci_strat.h" // StratArgs (the kernel itself is instantiated by the JIT)
-#include "mci_sweep.h" // SweepArgs (likewise)
-#include "mci_sweep_leaves.h" // SweepLeavesArgs (likewise)
+#include "mci_sweep.h" // SweepHead (mci_sweep_common.h; likewise)
+#include "mci_sweep_leaves.h"
 #include "mci_sweep_strat.h" // SweepStratArgs (likewise)
 
 namespace {

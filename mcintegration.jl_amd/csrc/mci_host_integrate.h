@@ -113,7 +113,7 @@ static int compile_persist(mci_problem *p, bool background) {
         // (512 threads for the hand-pipelined loops of 8..16 draws -- what the launch chain runs them at -- was tried: 22.5 instead of 18.3 us
         // per iteration of the 16-D Gaussian at neval = 1e4, against 15.8 as a launch chain; the automatic rule stops at 7 draws)
         c->threads = p->threads;
-        c->rc = mcijit::compile(c->src, c->threads, c->code, c->log, c->cached, &c->path, mcijit::kHdrTrain, /*cache_only=*/background);
+        c->rc = mcijit::compile(c->src, c->threads, c->code, c->log, c->cached, &c->path, mcijit::kUnitVegasPersist, /*cache_only=*/background);
         if (c->rc == -1) { // not in the kernel cache: compile it behind the caller's back ...
             // ... once this process has made kPersistAfterCalls launch-bound calls of this kernel (by this problem or others with the same
             // shape and integrand): the persistent launch saves ~40 us per default-size call and its translation unit costs 0.8 s of hiprtc
@@ -131,7 +131,7 @@ static int compile_persist(mci_problem *p, bool background) {
             p->persist_job->c = std::move(local);
             mci_problem::PersistJob *j = p->persist_job;
             j->th = std::thread([j] {
-                j->c.rc = mcijit::compile(j->c.src, j->c.threads, j->c.code, j->c.log, j->c.cached, &j->c.path, mcijit::kHdrTrain);
+                j->c.rc = mcijit::compile(j->c.src, j->c.threads, j->c.code, j->c.log, j->c.cached, &j->c.path, mcijit::kUnitVegasPersist);
                 j->done.store(true, std::memory_order_release);
             });
             return MCI_OK;

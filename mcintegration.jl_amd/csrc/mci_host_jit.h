@@ -252,7 +252,7 @@ static int compile_spec(mci_problem *p, int solver) {
     c.threads = 256; // (a launch of few chains runs one wave per SIMD: up to 512 registers per lane)
     // In the cache, with the marker of a passed self-check next to it: nothing else to do.  Otherwise the lane-per-chain unit the check
     // compares it with is compiled NEXT to it (hiprtc is re-entrant): the check costs the slower of the two compilations, not their sum.
-    const bool cached = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSpec, /*cache_only=*/true) == 0;
+    const bool cached = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitSpec, /*cache_only=*/true) == 0;
     const bool verified = cached && access((c.path + ".ok").c_str(), F_OK) == 0;
     std::thread side;
     if (!verified && !p->compiled[solver] && !p->ctx->offline && !(g_over.spec_self_check.on && g_over.spec_self_check.v == 0)) {
@@ -261,7 +261,7 @@ static int compile_spec(mci_problem *p, int solver) {
         side = std::thread([&lane] { lane.rc = mcijit::compile(lane.src, lane.threads, lane.code, lane.log, lane.cached, &lane.path); });
     }
     if (!cached) {
-        c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSpec);
+        c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitSpec);
         if (c.rc == 2) {
             // (the unit is built with a backend switch, mci_jit.h: a compiler that does not know it any more gets the unit without it --
             // the self-check below is what stands between such an object and the user's histogram)
@@ -269,7 +269,7 @@ static int compile_spec(mci_problem *p, int solver) {
             Candidate d;
             d.src = c.src;
             d.threads = c.threads;
-            d.rc = mcijit::compile(d.src, d.threads, d.code, log2, d.cached, &d.path, mcijit::kHdrSpec, false, /*no_exec_mask_flag=*/true);
+            d.rc = mcijit::compile(d.src, d.threads, d.code, log2, d.cached, &d.path, mcijit::kUnitSpec, false, /*no_exec_mask_flag=*/true);
             if (d.rc == 0) {
                 d.log = c.log;
                 c = std::move(d);
@@ -542,19 +542,9 @@ int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n)
         snprintf(buf, (size_t)n, "%s", p->strat.code_object.c_str());
         return MCI_OK;
     }
-    if (solver == MCI_VEGAS_SWEEP) {
-        if (!p->sweep.compiled) return fail(MCI_ERR_INVALID, "the sweep kernel has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->sweep.code_object.c_str());
-        return MCI_OK;
-    }
-    if (solver == MCI_VEGAS_SWEEP_LEAVES) {
-        if (!p->sweep.leaves.compiled) return fail(MCI_ERR_INVALID, "the sweep kernel for several leaves has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->sweep.leaves.code_object.c_str());
-        return MCI_OK;
-    }
-    if (solver == MCI_VEGAS_SWEEP_STRAT) {
-        if (!p->sweep.strat.compiled) return fail(MCI_ERR_INVALID, "the sweep kernel for stratified points has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->sweep.strat.code_object.c_str());
+    if (const int w = sweep_unit_of(solver); w >= 0) {
+        if (!p->sweep.unit[w].compiled) return fail(MCI_ERR_INVALID, "the sweep kernel%s has not been compiled yet", kSweepUnits[w].for_what);
+        snprintf(buf, (size_t)n, "%s", p->sweep.unit[w].code_object.c_str());
         return MCI_OK;
     }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
@@ -712,10 +702,8 @@ int mci_check_status(mci_problem *p) {
 static int compile_persist(mci_problem *p, bool background);
 static bool persist_layout_ok(const mci_problem *p);
 static int compile_strat(mci_problem *p); // (mci_host_strat.h)
-static int compile_sweep(mci_problem *p); // (mci_host_sweep.h)
-static int compile_sweep_leaves(mci_problem *p);
+static int compile_sweep_unit(mci_problem *p, int which); // (mci_host_sweep.h)
 static bool sweep_leaves_unit(const mci_problem *p);
-static int compile_sweep_strat(mci_problem *p);
 int mci_compile_solver(mci_problem *p, int32_t solver) {
     if (solver == MCI_VEGAS_PERSISTENT) { // the persistent :vegas kernel (mci_set_persistent), for layouts that allow it
         if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
@@ -726,33 +714,24 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         if (!p->strat.on) return fail(MCI_ERR_INVALID, "the problem is not stratified (mci_set_stratification)");
         return compile_strat(p);
     }
-    if (solver == MCI_VEGAS_SWEEP) { // (mci_host_sweep.h)
+    if (const int w = sweep_unit_of(solver); w >= 0) { // (mci_host_sweep.h: a problem the unit's own query accepts)
         mci_integrate_args a{};
         a.solver = MCI_VEGAS;
         a.measurefreq = 1;
         a.niter = 1;
-        if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
-        if (sweep_leaves_unit(p)) return fail(MCI_ERR_INVALID, "a sweep of this problem runs the sweep kernel for several leaves (MCI_VEGAS_SWEEP_LEAVES; mci_set_sweep_leaves)");
-        return compile_sweep(p);
-    }
-    if (solver == MCI_VEGAS_SWEEP_LEAVES) { // (mci_host_sweep.h: the problem has opted in, mci_set_sweep_leaves, and is no one-grid layout)
-        mci_integrate_args a{};
-        a.solver = MCI_VEGAS;
-        a.measurefreq = 1;
-        a.niter = 1;
-        if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
-        if (!sweep_leaves_unit(p)) return fail(MCI_ERR_INVALID, "a sweep of this problem runs the one-grid sweep kernel (MCI_VEGAS_SWEEP; mci_set_sweep_leaves)");
-        return compile_sweep_leaves(p);
-    }
-    if (solver == MCI_VEGAS_SWEEP_STRAT) { // (mci_host_sweep.h: a stratified problem mci_sweep_strat_supported accepts)
-        mci_integrate_args a{};
-        a.solver = MCI_VEGAS;
-        a.measurefreq = 1;
-        a.niter = 1;
-        a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
-        a.block = 1;
-        if (int rc = mci_sweep_strat_supported(p, &a, nullptr, 0)) return rc;
-        return compile_sweep_strat(p);
+        if (w == mci_problem::Sweep::kStrat) {
+            a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
+            a.block = 1;
+            if (int rc = mci_sweep_strat_supported(p, &a, nullptr, 0)) return rc;
+        } else {
+            if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
+            // (which of the two a sweep of this problem runs: whether it has opted in, mci_set_sweep_leaves, and is no one-grid layout)
+            if (w == mci_problem::Sweep::kOne && sweep_leaves_unit(p))
+                return fail(MCI_ERR_INVALID, "a sweep of this problem runs the sweep kernel for several leaves (MCI_VEGAS_SWEEP_LEAVES; mci_set_sweep_leaves)");
+            if (w == mci_problem::Sweep::kLeaves && !sweep_leaves_unit(p))
+                return fail(MCI_ERR_INVALID, "a sweep of this problem runs the one-grid sweep kernel (MCI_VEGAS_SWEEP; mci_set_sweep_leaves)");
+        }
+        return compile_sweep_unit(p, w);
     }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver); // main.jl:263
     return compile_solver(p, solver);

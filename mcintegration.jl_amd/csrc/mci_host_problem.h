@@ -388,9 +388,8 @@ int mci_problem_destroy(mci_problem *p) {
             if (p->module[k]) (void)hipModuleUnload(p->module[k]);
         if (p->module_persist) (void)hipModuleUnload(p->module_persist);
         if (p->strat.module) (void)hipModuleUnload(p->strat.module);
-        if (p->sweep.module) (void)hipModuleUnload(p->sweep.module);
-        if (p->sweep.leaves.module) (void)hipModuleUnload(p->sweep.leaves.module);
-        if (p->sweep.strat.module) (void)hipModuleUnload(p->sweep.strat.module);
+        for (auto &u : p->sweep.unit)
+            if (u.module) (void)hipModuleUnload(u.module);
     }
     persist_job_drop(p);
     if (!p->ctx->offline) {

@@ -271,7 +271,7 @@ static int compile_strat(mci_problem *p) {
     sh.hcopy = det ? 256 / 64 : 1;
     c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitStrat);
     c.threads = 256;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrStrat);
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitStrat);
     if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (stratified :vegas kernel):\n%s", c.log.c_str());
     if (mcijit::max_static_lds_bytes(c.code) != 0) return fail(MCI_ERR_COMPILE, "the stratified code object declares static LDS");
     st.code_object = c.path;

@@ -1,6 +1,7 @@
 // mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
 // batched :vegas parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
-// one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in).
+// one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in; mci_sweep_strat.h
+// vegas_sweep_strat for stratified points).  One descriptor table (kSweepUnits), one compile, one refusal head, one driver (sweep_run).
 namespace {
 // Points of one sweep, and the device memory one may take.  Per point the launch holds the userdata row, a seed, two maps, niter log
 // rows, nblocks partial rows and as much merge scratch, a statistics head, a histogram row and a status word: ~25 KB at the
@@ -55,11 +56,11 @@ const char *sweep_leaves_refusal(const mci_problem *p, std::string &buf) {
 // the unit a sweep of this problem runs: the one-grid kernel wherever it applies, opted in or not
 bool sweep_uses_leaves(const mci_problem *p) { return p->sweep.leaves_mode == MCI_SWEEP_ALL_LEAVES && !persist_layout(p); }
 
-// Eligibility: persist_layout exactly (one Continuous leaf, table mode 0, one tile, device-source integrand and measure, not
-// deterministic, within 64 KiB including the map copy), measurefreq == 1, one rank.  NOT the draw count: `ndraw <= 7` is
-// persist_plan's rule for when the persistent launch beats the launch chain, nothing a sweep depends on.
-const char *sweep_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
+// What both queries ask first, `strat`: of a stratified sweep.  Eligibility of either: measurefreq == 1, one rank, device-source integrand
+// and measure, not deterministic.
+const char *sweep_common_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, bool strat) {
     const auto &s = p->shape;
+    if (strat && !p->strat.on) return "the problem is not stratified (mci_set_stratification first; mci_integrate_sweep runs the others)";
     if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
     if (a->measurefreq != 1) {
         buf = "measurefreq = " + std::to_string((long long)a->measurefreq) + " (a sweep measures every sample)";
@@ -67,17 +68,34 @@ const char *sweep_refusal(const mci_problem *p, const mci_integrate_args *a, std
     }
     if (a->niter < 1) return "niter < 1";
     if (p->ctx->nranks != 1) return "several ranks (one rank only)";
-    if (p->strat.on) return "the problem is stratified (mci_set_stratification_off first)";
+    if (!strat && p->strat.on) return "the problem is stratified (mci_set_stratification_off first)";
     if (s.host_integrand) return "a host integrand (device source or a traced closure only)";
-    if (s.host_measure) return "a host measure (device source only)";
+    if (s.host_measure) return strat ? "a host measure (the default measure only)" : "a host measure (device source only)";
+    if (strat && !s.measure_body.empty()) return "a user measure (the default measure only)";
     if (p->deterministic) return "deterministic mode";
-    if (p->sweep.leaves_mode == MCI_SWEEP_ALL_LEAVES && !persist_layout(p)) return sweep_leaves_refusal(p, buf); // (opted in: mci_set_sweep_leaves)
+    return nullptr;
+}
+// ONE Continuous leaf whose grid and histogram sit in LDS in one tile: the layout of the one-grid and the stratified unit
+const char *sweep_one_grid_refusal(const mci_problem *p, std::string &buf, bool strat) {
+    const auto &s = p->shape;
     if (s.nleaf != 1 || p->leaves.size() != 1) {
-        buf = std::to_string(s.nleaf) + " variable leaves (a sweep point refines ONE Continuous grid)";
+        buf = std::to_string(s.nleaf) + (strat ? " variable leaves (a stratified sweep point refines ONE Continuous grid; several Continuous leaves are a follow-up)"
+                                                : " variable leaves (a sweep point refines ONE Continuous grid)");
         return buf.c_str();
     }
-    if (p->leaves[0].kind != 0) return "a Discrete or FermiK variable (a sweep point refines ONE Continuous grid)";
+    if (p->leaves[0].kind != 0)
+        return strat ? "a Discrete or FermiK variable (a stratified sweep point refines ONE Continuous grid)" : "a Discrete or FermiK variable (a sweep point refines ONE Continuous grid)";
     if (s.table_mode != 0 || s.ntile != 1 || s.nbin <= 0 || s.ec_doubles > 0) return "the grid and its histogram do not sit in LDS in one tile";
+    return nullptr;
+}
+
+// Eligibility: persist_layout exactly (one Continuous leaf, table mode 0, one tile, device-source integrand and measure, not
+// deterministic, within 64 KiB including the map copy), measurefreq == 1, one rank.  NOT the draw count: `ndraw <= 7` is
+// persist_plan's rule for when the persistent launch beats the launch chain, nothing a sweep depends on.
+const char *sweep_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
+    if (const char *r = sweep_common_refusal(p, a, buf, false)) return r;
+    if (sweep_uses_leaves(p)) return sweep_leaves_refusal(p, buf); // (opted in: mci_set_sweep_leaves)
+    if (const char *r = sweep_one_grid_refusal(p, buf, false)) return r;
     if (persist_lds(p, nullptr) > 64 * 1024) {
         buf = "the sample tables, the refinement scratch and the map copy take " + std::to_string((long long)persist_lds(p, nullptr)) + " bytes of LDS (64 KiB at most)";
         return buf.c_str();
@@ -124,67 +142,45 @@ void sweep_release(mci_ctx *c, void *base, size_t bytes) {
 const int kSweepThreads = 256;
 } // namespace
 
-static int compile_sweep(mci_problem *p) {
-    auto &sw = p->sweep;
-    const int T = sw.want_threads > 0 ? sw.want_threads : kSweepThreads;
-    if (sw.compiled && sw.threads == T) return MCI_OK;
-    if (sw.module) {
-        if (!p->ctx->offline) (void)hipModuleUnload(sw.module);
-        sw.module = nullptr;
-        sw.f = nullptr;
-    }
-    sw.compiled = false;
-    Candidate c;
-    mcijit::ProblemShape sh = p->shape;
-    sh.hcopy = 1;
-    sh.det = 0;
-    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweep, p->leaves[0].alpha);
-    c.threads = T;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweep);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel):\n%s", c.log.c_str());
-    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep") != 0)
-        return fail(MCI_ERR_COMPILE, "the sweep kernel came out with static LDS or scratch at %d threads per workgroup", T);
-    sw.code_object = c.path;
-    sw.threads = T;
-    if (!p->ctx->offline) {
-        HIPCHK(hipSetDevice(p->ctx->device));
-        if (hipModuleLoadData(&sw.module, c.code.data()) != hipSuccess) {
-            if (c.cached) unlink(c.path.c_str()); // a cached code object that does not load (truncated by a crash, foreign file)
-            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object");
-        }
-        HIPCHK(hipModuleGetFunction(&sw.f, sw.module, "mci_vegas_sweep"));
-    }
-    sw.compiled = true;
-    return MCI_OK;
-}
-
 static bool sweep_leaves_unit(const mci_problem *p) { return sweep_uses_leaves(p); }
 
-// the unit of mci_sweep_leaves.h: 256 threads, one histogram copy, every leaf's learning rate read at run time
-static int compile_sweep_leaves(mci_problem *p) {
-    auto &u = p->sweep.leaves;
-    if (u.compiled) return MCI_OK;
+// A sweep unit's code object (kSweepUnits, mci_host_types.h): one histogram copy, kSweepThreads threads -- the one-grid unit is loaded
+// again when mci_debug_sweep_threads asks for another workgroup size --, no static LDS, no scratch
+static int compile_sweep_unit(mci_problem *p, int which) {
+    const SweepUnitDesc &k = kSweepUnits[which];
+    const char *kernel = mcijit::kUnits[k.jit_unit].kernel;
+    auto &u = p->sweep.unit[which];
+    const int T = k.want_threads && p->sweep.want_threads > 0 ? p->sweep.want_threads : kSweepThreads;
+    if (u.compiled && u.threads == T) return MCI_OK;
+    if (u.module) {
+        if (!p->ctx->offline) (void)hipModuleUnload(u.module);
+        u.module = nullptr;
+        u.f = nullptr;
+    }
+    u.compiled = false;
     Candidate c;
     mcijit::ProblemShape sh = p->shape;
     sh.hcopy = 1;
     sh.det = 0;
-    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweepLeaves);
-    c.threads = kSweepThreads;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweepLeaves);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel, several leaves):\n%s", c.log.c_str());
-    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep_leaves") != 0)
-        return fail(MCI_ERR_COMPILE, "the sweep kernel for several leaves came out with static LDS or scratch at %d threads per workgroup", kSweepThreads);
+    c.src = mcijit::generate_source(sh, MCI_VEGAS, k.jit_unit, k.alpha ? p->leaves[0].alpha : 0.0);
+    c.threads = T;
+    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, k.jit_unit);
+    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel%s%s):\n%s", k.tag[0] ? ", " : "", k.tag, c.log.c_str());
+    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, kernel) != 0)
+        return fail(MCI_ERR_COMPILE, "the sweep kernel%s came out with static LDS or scratch at %d threads per workgroup", k.for_what, T);
     u.code_object = c.path;
-    u.threads = kSweepThreads;
+    u.threads = T;
     if (!p->ctx->offline) {
         HIPCHK(hipSetDevice(p->ctx->device));
         if (hipModuleLoadData(&u.module, c.code.data()) != hipSuccess) {
-            if (c.cached) unlink(c.path.c_str());
-            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object (several leaves)");
+            if (c.cached) unlink(c.path.c_str()); // a cached code object that does not load (truncated by a crash, foreign file)
+            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object%s%s%s", k.tag[0] ? " (" : "", k.tag, k.tag[0] ? ")" : "");
         }
-        HIPCHK(hipModuleGetFunction(&u.f, u.module, "mci_vegas_sweep_leaves"));
-        const int64_t lds = sweep_leaves_lds(p, nullptr);
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipModuleGetFunction(&u.f, u.module, kernel));
+        if (which == mci_problem::Sweep::kLeaves) { // (its LDS is the layout's; the stratified unit's is the call's: sweep_run)
+            const int64_t lds = sweep_leaves_lds(p, nullptr);
+            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
     }
     u.compiled = true;
     return MCI_OK;
@@ -236,119 +232,149 @@ int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
     return MCI_OK;
 }
 
-// P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
-int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
-                        double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
-    if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
-    int rc;
-    if ((rc = mci_sweep_supported(p, a, nullptr, 0))) return rc;
-    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
+// ---------------------------------------------------------------------------------------------------
+// the one driver of a sweep launch
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
+// kSegOff, kSegTbase and kSegD are the stratified unit's (none otherwise).  Everything from kSegGhist on is zeroed before the launch:
+// histogram rows, d rows, (the seeds: copied next), status words.
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegGhist, kSegD, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+
+// What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
+struct SweepCall {
+    int unit = 0; // mci_problem::Sweep::kOne | kLeaves | kStrat
+    // the caller's arguments
+    int32_t npoint = 0;
+    const double *userdata = nullptr;
+    const uint64_t *seeds = nullptr;
+    const double *maps_in = nullptr;
+    double *maps_out = nullptr;
+    mci_result *results = nullptr;
+    double *iter_mean = nullptr, *iter_std = nullptr;
+    int32_t *status = nullptr;
+    // plan(): the unit's sizes for this call, made behind the results[] check; it may refuse
+    std::function<int(SweepCall &)> plan;
+    int64_t rows = 0;            // partial rows per point: the statistical blocks, or 1 (stratified)
+    int64_t neval_per_block = 0, blocks = 0; // main.jl:121
+    size_t map_doubles = 0;      // one maps_in / maps_out row
+    size_t off_doubles = 0, tbase_doubles = 0, d_doubles = 0; // per point: kSegOff, kSegTbase, kSegD
+    int maxn = 0;                // bins of the largest leaf
+    int64_t lds = 0;             // bytes of LDS of a workgroup
+    int map_off = 0;             // SweepHead::map_off
+    bool strat_stats = false;    // an iteration's mean | error: strat_mean_std over its log row, else mci_mean_std over the blocks
+    const char *too_big = nullptr; // printf format of "this sweep does not fit": npoint, niter, too_big_count, bytes, limit
+    long long too_big_count = 0;
+    // the kernel's second argument behind its head: `h` is filled, `o` are the segments' offsets in `d`; NULL: the head is the argument
+    std::function<void *(const mci::SweepHead &h, double *d, const size_t *o)> args;
+    // the unit's own copies in front of the launch / behind it (stream st), and what it makes of them once the stream has drained
+    std::function<int(double *d, const size_t *o, hipStream_t st)> copy_in, copy_out;
+    std::function<void()> finish;
+};
+
+// results[] check, buffer, uploads, arguments, launch, read-back, and per point what mci_integrate makes of its log rows
+int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     const auto &s = p->shape;
-    const int nud = (int)p->h_ud.size();
-    if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
-    if (!(a->neval > a->block)) return fail(MCI_ERR_INVALID, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block); // main.jl:222
+    const int npoint = c.npoint, nud = (int)p->h_ud.size(), nstat = p->nstat, niter = a->niter;
+    mci_result *results = c.results;
     for (int q = 0; q < npoint; ++q)
         if (results[q].niter < a->niter || results[q].nobs != s.nobs || !results[q].mean || !results[q].stdev || !results[q].chi2)
             return fail(MCI_ERR_INVALID, "result buffers of point %d too small", q);
-    int64_t nevalperblock, block;
-    mci_standardize_block(a->neval, a->block, 1, &nevalperblock, &block); // main.jl:121
-    if (block > (int64_t)1 << 20) return fail(MCI_ERR_INVALID, "block = %lld: too many blocks for a sweep", (long long)block);
-    const bool lv = sweep_uses_leaves(p); // (else one Continuous leaf: a row is its grid)
-    const int N = sweep_max_nbin(p), nstat = p->nstat, niter = a->niter;
-    const size_t P = (size_t)npoint, nmap = (size_t)sweep_map_doubles(p), rows = (size_t)block * s.ncols;
-    // one buffer (doubles, then the 8-byte seeds, then the status words)
-    const size_t o_ud = 0, o_in = o_ud + P * (size_t)nud, o_out = o_in + (maps_in ? P * nmap : 0), o_log = o_out + P * nmap,
-                 o_part = o_log + P * (size_t)niter * nstat, o_scr = o_part + P * rows, o_pk = o_scr + P * rows, o_gh = o_pk + P * (size_t)nstat,
-                 o_seed = o_gh + P * (size_t)s.nbin, o_st = o_seed + (seeds ? P : 0), ndbl = o_st + (P + 1) / 2;
+    int rc;
+    if ((rc = c.plan(c))) return rc;
+    const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
+    const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, (size_t)nstat,
+                                         c.off_doubles,  c.tbase_doubles, (size_t)s.nbin, c.d_doubles, c.seeds ? (size_t)1 : 0};
+    size_t o[kSegCount + 1] = {0};
+    for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
+    const size_t ndbl = o[kSegStatus] + (P + 1) / 2;
     if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
-        return fail(MCI_ERR_INVALID, "a sweep of %d points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it",
-                    (int)npoint, niter, (long long)block, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
-    if ((rc = lv ? compile_sweep_leaves(p) : compile_sweep(p))) return rc;
+        return fail(MCI_ERR_INVALID, c.too_big, (int)npoint, niter, c.too_big_count, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
+    if ((rc = compile_sweep_unit(p, c.unit))) return rc;
+    const auto &u = p->sweep.unit[c.unit];
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
     void *base = nullptr;
     size_t got = 0;
     if ((rc = sweep_alloc(p->ctx, ndbl * sizeof(double), &base, &got))) return rc;
     double *d = (double *)base;
-    std::vector<double> hlog(P * (size_t)niter * nstat), hmap;
+    std::vector<double> hlog(P * (size_t)niter * nstat);
     std::vector<int> hst(P);
     auto run = [&]() -> int {
         auto t0 = std::chrono::steady_clock::now();
-        if (nud > 0) HIPCHK(hipMemcpyAsync(d + o_ud, userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
-        if (maps_in) HIPCHK(hipMemcpyAsync(d + o_in, maps_in, P * nmap * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d + o_gh, 0, (ndbl - o_gh) * sizeof(double), st)); // histogram rows, (the seeds: copied next), status words
-        if (seeds) HIPCHK(hipMemcpyAsync(d + o_seed, seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (nud > 0) HIPCHK(hipMemcpyAsync(d + o[kSegUd], c.userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
+        if (c.maps_in) HIPCHK(hipMemcpyAsync(d + o[kSegMapsIn], c.maps_in, P * c.map_doubles * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d + o[kSegGhist], 0, (ndbl - o[kSegGhist]) * sizeof(double), st));
+        if (c.copy_in && (rc = c.copy_in(d, o, st))) return rc;
+        if (c.seeds) HIPCHK(hipMemcpyAsync(d + o[kSegSeeds], c.seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         mci::BatchArgs b{};
         fill_batch(p, b); // (the map and the reweight factors are the problem's; everything else lives in the sweep's own allocation)
-        b.ud = d + o_ud;
-        b.part_cols = d + o_part;
+        b.ud = d + o[kSegUd];
+        b.part_cols = d + o[kSegPart];
         b.part_hist = nullptr;
-        b.ghist = d + o_gh;
+        b.ghist = d + o[kSegGhist];
         b.seed = a->seed;
         b.iteration = (mci::u32)a->first_iteration;
-        b.neval_per_block = nevalperblock;
+        b.neval_per_block = c.neval_per_block;
         b.block_lo = 0;
         b.wg_per_block = 1;
         b.measurefreq = 1;
         b.nchain = 1;
         b.hist_atomic = 1;
-        b.status = reinterpret_cast<int *>(d + o_st);
-        b.tile_stride = block * nevalperblock;
-        b.nrows = block;
-        mci::SweepArgs f1{};
-        mci::SweepLeavesArgs fl{};
-        int64_t lds = 0;
-        auto fill = [&](auto &f) { // (SweepArgs and SweepLeavesArgs carry the same fields)
-            mci::MergeArgs &m = f.m;
-            m = merge_args(p, block, 1, block);
-            m.part_cols = d + o_part;
-            m.stage1 = nullptr;
-            m.ngroup = 0;
-            m.ghist = d + o_gh;
-            m.use_ghist = 1;
-            m.packed = d + o_pk;
-            m.status = b.status;
-            m.scratch = d + o_scr;
-            m.npa = 0;
-            mci::TrainArgs &t = f.t;
-            fill_train(p, t);
-            t.packed = d + o_pk;
-            t.nstat = nstat;
-            t.iter_log_row = d + o_log;
-            t.reweight = nullptr;
-            t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
-            t.gamma = a->gamma;
-            t.do_train = a->adapt ? 1 : 0;
-            t.serial_walk = 0;
-            t.status = b.status;
-            t.maxn = N;
-            f.npoint = npoint;
-            f.niter = niter;
-            f.nuserdata = nud;
-            lds = lv ? sweep_leaves_lds(p, &f.map_off) : persist_lds(p, &f.map_off);
-            f.ud = d + o_ud;
-            f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
-            f.maps_in = maps_in ? d + o_in : nullptr;
-            f.maps_out = d + o_out;
-        };
-        if (lv) fill(fl);
-        else fill(f1);
+        b.status = reinterpret_cast<int *>(d + o[kSegStatus]);
+        b.tile_stride = c.blocks * c.neval_per_block;
+        b.nrows = c.rows;
+        mci::SweepHead h{};
+        mci::MergeArgs &m = h.m;
+        m = merge_args(p, c.rows, 1, c.rows);
+        m.part_cols = d + o[kSegPart];
+        m.stage1 = nullptr;
+        m.ngroup = 0;
+        m.ghist = d + o[kSegGhist];
+        m.use_ghist = 1;
+        m.packed = d + o[kSegPacked];
+        m.status = b.status;
+        m.scratch = d + o[kSegScratch];
+        m.npa = 0;
+        m.block_means = nullptr;
+        mci::TrainArgs &t = h.t;
+        fill_train(p, t);
+        t.packed = d + o[kSegPacked];
+        t.nstat = nstat;
+        t.iter_log_row = d + o[kSegLog];
+        t.reweight = nullptr;
+        t.do_reweight = 0; // (:vegas: main.jl:183 runs doReweight! for the chain solvers only)
+        t.gamma = a->gamma;
+        t.do_train = a->adapt ? 1 : 0;
+        t.serial_walk = 0;
+        t.status = b.status;
+        t.maxn = c.maxn;
+        h.npoint = npoint;
+        h.niter = niter;
+        h.nuserdata = nud;
+        h.map_off = c.map_off;
+        h.ud = d + o[kSegUd];
+        h.seeds = c.seeds ? reinterpret_cast<const mci::u64 *>(d + o[kSegSeeds]) : nullptr;
+        h.maps_in = c.maps_in ? d + o[kSegMapsIn] : nullptr;
+        h.maps_out = d + o[kSegMapsOut];
+        void *karg = c.args ? c.args(h, d, o) : (void *)&h;
         // workgroups: two per CU keep a CU's SIMDs busy while one of them sits in its refinement; any grid runs any npoint
         int cus = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
-        // (several leaves: a map block that leaves no room for two workgroups in a CU's 160 KiB of LDS gets one)
-        const int per_cu = lv && lds > 80 * 1024 ? 1 : 2;
+        // (several leaves, stratified points: LDS that leaves no room for two workgroups in a CU's 160 KiB gets one)
+        const int per_cu = c.unit != mci_problem::Sweep::kOne && c.lds > 80 * 1024 ? 1 : 2;
         int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
         if (grid > npoint) grid = npoint;
-        void *args[] = {&b, lv ? (void *)&fl : (void *)&f1};
-        const int threads = lv ? p->sweep.leaves.threads : p->sweep.threads;
-        HIPCHK(hipModuleLaunchKernel(lv ? p->sweep.leaves.f : p->sweep.f, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, (unsigned)lds, st, args, nullptr));
+        if (c.unit == mci_problem::Sweep::kStrat && c.lds > 64 * 1024) // (the chunk is the call's: not known when the unit is compiled)
+            HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
+        void *args[] = {&b, karg};
+        HIPCHK(hipModuleLaunchKernel(u.f, (unsigned)grid, 1, 1, (unsigned)u.threads, 1, 1, (unsigned)c.lds, st, args, nullptr));
         p->sweep.last_grid = (int)grid;
-        p->sweep.last_threads = threads;
-        HIPCHK(hipMemcpyAsync(hlog.data(), d + o_log, hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hst.data(), d + o_st, P * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out, d + o_out, P * nmap * sizeof(double), hipMemcpyDeviceToHost, st));
+        p->sweep.last_threads = u.threads;
+        HIPCHK(hipMemcpyAsync(hlog.data(), d + o[kSegLog], hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hst.data(), d + o[kSegStatus], P * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (c.maps_out) HIPCHK(hipMemcpyAsync(c.maps_out, d + o[kSegMapsOut], P * c.map_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (c.copy_out && (rc = c.copy_out(d, o, st))) return rc;
         HIPCHK(hipStreamSynchronize(st));
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         for (int q = 0; q < npoint; ++q) results[q].seconds = seconds;
@@ -358,29 +384,66 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
     if (rc) (void)hipStreamSynchronize(st); // (nothing of a failed call is still reading the buffer when it goes back)
     sweep_release(p->ctx, base, got);
     if (rc) return rc;
-    // per point what mci_integrate makes of its log rows (main.jl:203, :211)
+    if (c.finish) c.finish();
+    // per point what mci_integrate makes of its log rows (main.jl:203, :211; stratified: strat_mean_std)
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
     std::vector<double> tm((size_t)niter * s.nobs), te((size_t)niter * s.nobs);
     for (int q = 0; q < npoint; ++q) {
         mci_result *res = &results[q];
-        double *im = iter_mean ? iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
-        double *ie = iter_std ? iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
+        double *im = c.iter_mean ? c.iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
+        double *ie = c.iter_std ? c.iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
         res->neval = 0;
         for (int it = 0; it < niter; ++it) {
             const double *row = hlog.data() + ((size_t)q * niter + it) * nstat;
-            mci_mean_std(row, row + s.nobs, s.nobs, block, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
+            if (c.strat_stats) strat_mean_std(row, s.nobs, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
+            else mci_mean_std(row, row + s.nobs, s.nobs, c.blocks, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
             res->neval += (int64_t)row[2 * s.nobs + 1];
             if (res->visited && it == niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
         }
-        if (iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
-        if (iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
-        for (int o = 0; o < s.nobs; ++o) // main.jl:211 -> statistics.jl:24-55
-            mci_average(im + o, ie + o, s.nobs, ignore + 1, niter, &res->mean[o], &res->stdev[o], &res->chi2[o]);
+        if (c.iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
+        if (c.iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
+        for (int o2 = 0; o2 < s.nobs; ++o2) // main.jl:211 -> statistics.jl:24-55
+            mci_average(im + o2, ie + o2, s.nobs, ignore + 1, niter, &res->mean[o2], &res->stdev[o2], &res->chi2[o2]);
         res->correlated = 0;
         res->warmup = 0;
-        if (status) status[q] = hst[q];
+        if (c.status) c.status[q] = hst[q];
     }
     return MCI_OK;
+}
+
+// what both entry points check of their arguments before anything else
+int sweep_check_args(const mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const mci_result *results, bool strat) {
+    if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
+    if (int rc = strat ? mci_sweep_strat_supported(p, a, nullptr, 0) : mci_sweep_supported(p, a, nullptr, 0)) return rc;
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
+    const int nud = (int)p->h_ud.size();
+    if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
+    return MCI_OK;
+}
+} // namespace
+
+// P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
+int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                        double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, false)) return rc;
+    if (!(a->neval > a->block)) return fail(MCI_ERR_INVALID, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block); // main.jl:222
+    SweepCall c;
+    c.unit = sweep_uses_leaves(p) ? mci_problem::Sweep::kLeaves : mci_problem::Sweep::kOne; // (else one Continuous leaf: a row is its grid)
+    c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
+    c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
+    c.plan = [a](SweepCall &c) {
+        mci_standardize_block(a->neval, a->block, 1, &c.neval_per_block, &c.blocks); // main.jl:121
+        if (c.blocks > (int64_t)1 << 20) return fail(MCI_ERR_INVALID, "block = %lld: too many blocks for a sweep", (long long)c.blocks);
+        c.rows = c.blocks;
+        c.too_big_count = (long long)c.blocks;
+        return (int)MCI_OK;
+    };
+    c.map_doubles = (size_t)sweep_map_doubles(p);
+    c.maxn = sweep_max_nbin(p);
+    c.lds = c.unit == mci_problem::Sweep::kLeaves ? sweep_leaves_lds(p, &c.map_off) : persist_lds(p, &c.map_off);
+    c.too_big = "a sweep of %d points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it";
+    return sweep_run(p, a, c);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -423,24 +486,8 @@ int64_t sweep_strat_nsamp(const mci_integrate_args *a, int64_t *nblocks) {
 }
 const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
     const auto &s = p->shape;
-    if (!p->strat.on) return "the problem is not stratified (mci_set_stratification first; mci_integrate_sweep runs the others)";
-    if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
-    if (a->measurefreq != 1) {
-        buf = "measurefreq = " + std::to_string((long long)a->measurefreq) + " (a sweep measures every sample)";
-        return buf.c_str();
-    }
-    if (a->niter < 1) return "niter < 1";
-    if (p->ctx->nranks != 1) return "several ranks (one rank only)";
-    if (s.host_integrand) return "a host integrand (device source or a traced closure only)";
-    if (s.host_measure) return "a host measure (the default measure only)";
-    if (!s.measure_body.empty()) return "a user measure (the default measure only)";
-    if (p->deterministic) return "deterministic mode";
-    if (s.nleaf != 1 || p->leaves.size() != 1) {
-        buf = std::to_string(s.nleaf) + " variable leaves (a stratified sweep point refines ONE Continuous grid; several Continuous leaves are a follow-up)";
-        return buf.c_str();
-    }
-    if (p->leaves[0].kind != 0) return "a Discrete or FermiK variable (a stratified sweep point refines ONE Continuous grid)";
-    if (s.table_mode != 0 || s.ntile != 1 || s.nbin <= 0 || s.ec_doubles > 0) return "the grid and its histogram do not sit in LDS in one tile";
+    if (const char *r = sweep_common_refusal(p, a, buf, true)) return r;
+    if (const char *r = sweep_one_grid_refusal(p, buf, true)) return r;
     if (s.ndraw > mci::kStratMaxDraw) {
         buf = std::to_string(s.ndraw) + " draws per sample (at most " + std::to_string((int)mci::kStratMaxDraw) + ")";
         return buf.c_str();
@@ -472,34 +519,6 @@ const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *
 }
 } // namespace
 
-// the unit of mci_sweep_strat.h: 256 threads, one histogram copy, compiled like the one-grid sweep unit
-static int compile_sweep_strat(mci_problem *p) {
-    auto &u = p->sweep.strat;
-    if (u.compiled) return MCI_OK;
-    Candidate c;
-    mcijit::ProblemShape sh = p->shape;
-    sh.hcopy = 1;
-    sh.det = 0;
-    c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitSweepStrat, p->leaves[0].alpha);
-    c.threads = kSweepThreads;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kHdrSweepStrat);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel, stratified points):\n%s", c.log.c_str());
-    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, "mci_vegas_sweep_strat") != 0)
-        return fail(MCI_ERR_COMPILE, "the sweep kernel for stratified points came out with static LDS or scratch at %d threads per workgroup", kSweepThreads);
-    u.code_object = c.path;
-    u.threads = kSweepThreads;
-    if (!p->ctx->offline) {
-        HIPCHK(hipSetDevice(p->ctx->device));
-        if (hipModuleLoadData(&u.module, c.code.data()) != hipSuccess) {
-            if (c.cached) unlink(c.path.c_str());
-            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object (stratified points)");
-        }
-        HIPCHK(hipModuleGetFunction(&u.f, u.module, "mci_vegas_sweep_strat"));
-    }
-    u.compiled = true;
-    return MCI_OK;
-}
-
 int mci_sweep_strat_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
     if (why && n > 0) why[0] = 0;
     if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
@@ -520,108 +539,60 @@ int mci_sweep_strat_doubles(const mci_problem *p, const mci_integrate_args *a, i
 }
 
 // P independent stratified integrate() loops, one workgroup each, in one launch
+static_assert(offsetof(mci::SweepStratArgs, h) == 0, "sweep_run fills the stratified unit's argument through its head");
 int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                               double *maps_out, const double *d_in, double *d_out, int64_t *counts_out, mci_result *results, double *iter_mean, double *iter_std,
                               int32_t *status) {
-    if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
-    int rc;
-    if ((rc = mci_sweep_strat_supported(p, a, nullptr, 0))) return rc;
-    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, true)) return rc;
     const auto &s = p->shape;
-    const int nud = (int)p->h_ud.size();
-    if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
-    for (int q = 0; q < npoint; ++q)
-        if (results[q].niter < a->niter || results[q].nobs != s.nobs || !results[q].mean || !results[q].stdev || !results[q].chi2)
-            return fail(MCI_ERR_INVALID, "result buffers of point %d too small", q);
-    int64_t block = 0, ncube = 0;
-    const int64_t nsamp = sweep_strat_nsamp(a, &block);
+    const size_t P = (size_t)npoint;
+    int64_t ncube = 0;
     std::vector<int> ns;
-    if ((rc = sweep_strat_plan(p, nsamp, ns, &ncube))) return rc;
-    const int NW = s.ni * s.ncomp, N = p->leaves[0].nbin, nstat = p->nstat, niter = a->niter, ntile = mci::strat_alloc_ntile(ncube);
-    // mblocks: what the ordinary stratified call merges its rows as (strat_run); the chunk: of this kernel's own LDS need
-    int64_t need0[4], need[4];
-    for (int k = 0; k < 4; ++k) {
-        need0[k] = p->lds_bytes + strat_chunk_lds_bytes(strat_nloc(8 >> k), NW);
-        need[k] = sweep_strat_lds(p, strat_nloc(8 >> k), nullptr);
-    }
     StratGeometry g0, g;
-    strat_geometry(nsamp, block, need0, g0);
-    strat_geometry(nsamp, block, need, g);
-    if (!g0.trips || !g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
-    const size_t P = (size_t)npoint, nmap = (size_t)N + 1, nc = (size_t)ncube;
-    // one buffer (doubles; the 8-byte offsets and seeds among them; then the status words)
-    const size_t o_ud = 0, o_in = o_ud + P * (size_t)nud, o_out = o_in + (maps_in ? P * nmap : 0), o_log = o_out + P * nmap,
-                 o_part = o_log + P * (size_t)niter * nstat, o_scr = o_part + P * (size_t)s.ncols, o_pk = o_scr + P * (size_t)s.ncols,
-                 o_off = o_pk + P * (size_t)nstat, o_tb = o_off + P * (nc + 1), o_gh = o_tb + P * (size_t)ntile, o_d = o_gh + P * (size_t)s.nbin,
-                 o_seed = o_d + P * nc, o_st = o_seed + (seeds ? P : 0), ndbl = o_st + (P + 1) / 2;
-    if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
-        return fail(MCI_ERR_INVALID, "a stratified sweep of %d points x %d iterations x %lld hypercubes needs %lld bytes of device memory (limit %lld): split it",
-                    (int)npoint, niter, (long long)ncube, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
-    if ((rc = compile_sweep_strat(p))) return rc;
-    HIPCHK(hipSetDevice(p->ctx->device));
-    hipStream_t st = p->ctx->stream;
-    void *base = nullptr;
-    size_t got = 0;
-    if ((rc = sweep_alloc(p->ctx, ndbl * sizeof(double), &base, &got))) return rc;
-    double *d = (double *)base;
-    std::vector<double> hlog(P * (size_t)niter * nstat);
-    std::vector<long long> hoff(counts_out ? P * (nc + 1) : 0);
-    std::vector<int> hst(P);
-    auto run = [&]() -> int {
-        auto t0 = std::chrono::steady_clock::now();
-        if (nud > 0) HIPCHK(hipMemcpyAsync(d + o_ud, userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
-        if (maps_in) HIPCHK(hipMemcpyAsync(d + o_in, maps_in, P * nmap * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d + o_gh, 0, (ndbl - o_gh) * sizeof(double), st)); // histogram rows, d rows, (the seeds: copied next), status words
-        if (d_in) HIPCHK(hipMemcpyAsync(d + o_d, d_in, P * nc * sizeof(double), hipMemcpyHostToDevice, st));
-        if (seeds) HIPCHK(hipMemcpyAsync(d + o_seed, seeds, P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        mci::BatchArgs b{};
-        fill_batch(p, b); // (the map and the reweight factors are the problem's; everything else lives in the sweep's own allocation)
-        b.ud = d + o_ud;
-        b.part_cols = d + o_part;
-        b.part_hist = nullptr;
-        b.ghist = d + o_gh;
-        b.seed = a->seed;
-        b.iteration = (mci::u32)a->first_iteration;
-        b.neval_per_block = nsamp / block;
-        b.block_lo = 0;
-        b.wg_per_block = 1;
-        b.measurefreq = 1;
-        b.nchain = 1;
-        b.hist_atomic = 1;
-        b.status = reinterpret_cast<int *>(d + o_st);
-        b.tile_stride = nsamp;
-        b.nrows = 1;
-        mci::SweepStratArgs f{};
-        mci::MergeArgs &m = f.m;
-        m = merge_args(p, 1, 1, 1);
-        m.part_cols = d + o_part;
-        m.stage1 = nullptr;
-        m.ngroup = 0;
-        m.ghist = d + o_gh;
-        m.use_ghist = 1;
-        m.packed = d + o_pk;
-        m.status = b.status;
-        m.scratch = d + o_scr;
-        m.npa = 0;
-        m.block_means = nullptr;
-        mci::TrainArgs &t = f.t;
-        fill_train(p, t);
-        t.packed = d + o_pk;
-        t.nstat = nstat;
-        t.iter_log_row = d + o_log;
-        t.reweight = nullptr;
-        t.do_reweight = 0;
-        t.gamma = a->gamma;
-        t.do_train = a->adapt ? 1 : 0;
-        t.serial_walk = 0;
-        t.status = b.status;
-        t.maxn = N;
+    mci::SweepStratArgs f{};
+    std::vector<long long> hoff;
+    SweepCall c;
+    c.unit = mci_problem::Sweep::kStrat;
+    c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
+    c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
+    c.plan = [&, p, a](SweepCall &c) {
+        const int64_t nsamp = sweep_strat_nsamp(a, &c.blocks);
+        if (int rc = sweep_strat_plan(p, nsamp, ns, &ncube)) return rc;
+        // mblocks: what the ordinary stratified call merges its rows as (strat_run); the chunk: of this kernel's own LDS need
+        const int NW = s.ni * s.ncomp;
+        int64_t need0[4], need[4];
+        for (int k = 0; k < 4; ++k) {
+            need0[k] = p->lds_bytes + strat_chunk_lds_bytes(strat_nloc(8 >> k), NW);
+            need[k] = sweep_strat_lds(p, strat_nloc(8 >> k), nullptr);
+        }
+        strat_geometry(nsamp, c.blocks, need0, g0);
+        strat_geometry(nsamp, c.blocks, need, g);
+        if (!g0.trips || !g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+        c.neval_per_block = nsamp / c.blocks;
+        c.rows = 1;
+        c.off_doubles = (size_t)ncube + 1;
+        c.tbase_doubles = (size_t)mci::strat_alloc_ntile(ncube);
+        c.d_doubles = (size_t)ncube;
+        c.lds = sweep_strat_lds(p, (int)(g.S / 2 + 1), &c.map_off);
+        c.too_big_count = (long long)ncube;
+        hoff.resize(counts_out ? P * ((size_t)ncube + 1) : 0);
+        return (int)MCI_OK;
+    };
+    c.map_doubles = (size_t)p->leaves[0].nbin + 1;
+    c.maxn = p->leaves[0].nbin;
+    c.strat_stats = true;
+    c.too_big = "a stratified sweep of %d points x %d iterations x %lld hypercubes needs %lld bytes of device memory (limit %lld): split it";
+    c.copy_in = [&](double *d, const size_t *o, hipStream_t st) {
+        if (d_in) HIPCHK(hipMemcpyAsync(d + o[kSegD], d_in, P * (size_t)ncube * sizeof(double), hipMemcpyHostToDevice, st));
+        return (int)MCI_OK;
+    };
+    c.args = [&, p](const mci::SweepHead &h, double *d, const size_t *o) -> void * {
+        f.h = h;
         mci::StratArgs &sa = f.st;
-        sa.off = reinterpret_cast<const long long *>(d + o_off);
-        sa.dnext = d + o_d;
+        sa.off = reinterpret_cast<const long long *>(d + o[kSegOff]);
+        sa.dnext = d + o[kSegD];
         sa.ncube = ncube;
-        sa.nsamp = nsamp;
+        sa.nsamp = c.neval_per_block * c.blocks;
         sa.chunk = g.S;
         sa.nchunk = g.nchunk;
         sa.first_index = 0;
@@ -633,68 +604,23 @@ int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32
             sa.nstrat[k] = (int)n;
             sa.inv[k] = 1.0 / (double)n;
         }
-        f.npoint = npoint;
-        f.niter = niter;
-        f.nuserdata = nud;
-        const int64_t lds = sweep_strat_lds(p, sa.nloc, &f.map_off);
         f.have_d = d_in ? 1 : 0;
         f.start_uniform = 1;
         f.mblocks = (int)g0.mblocks;
-        f.ntile = ntile;
-        f.tbase = d + o_tb;
-        f.ud = d + o_ud;
-        f.seeds = seeds ? reinterpret_cast<const mci::u64 *>(d + o_seed) : nullptr;
-        f.maps_in = maps_in ? d + o_in : nullptr;
-        f.maps_out = d + o_out;
-        // workgroups: two per CU up to 80 KiB of LDS each, one above; any grid runs any npoint
-        int cus = 0;
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
-        const int per_cu = lds > 80 * 1024 ? 1 : 2;
-        int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
-        if (grid > npoint) grid = npoint;
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)p->sweep.strat.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        void *args[] = {&b, &f};
-        HIPCHK(hipModuleLaunchKernel(p->sweep.strat.f, (unsigned)grid, 1, 1, (unsigned)p->sweep.strat.threads, 1, 1, (unsigned)lds, st, args, nullptr));
-        p->sweep.last_grid = (int)grid;
-        p->sweep.last_threads = p->sweep.strat.threads;
-        HIPCHK(hipMemcpyAsync(hlog.data(), d + o_log, hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(hst.data(), d + o_st, P * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out, d + o_out, P * nmap * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (d_out) HIPCHK(hipMemcpyAsync(d_out, d + o_d, P * nc * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (counts_out) HIPCHK(hipMemcpyAsync(hoff.data(), d + o_off, hoff.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        for (int q = 0; q < npoint; ++q) results[q].seconds = seconds;
-        return MCI_OK;
+        f.ntile = (int)c.tbase_doubles;
+        f.tbase = d + o[kSegTbase];
+        return &f;
     };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st); // (nothing of a failed call is still reading the buffer when it goes back)
-    sweep_release(p->ctx, base, got);
-    if (rc) return rc;
-    if (counts_out)
-        for (size_t q = 0; q < P; ++q)
-            for (size_t h = 0; h < nc; ++h) counts_out[q * nc + h] = hoff[q * (nc + 1) + h + 1] - hoff[q * (nc + 1) + h];
-    // per point what mci_integrate makes of stratified log rows (strat_mean_std, then mci_average)
-    const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
-    std::vector<double> tm((size_t)niter * s.nobs), te((size_t)niter * s.nobs);
-    for (int q = 0; q < npoint; ++q) {
-        mci_result *res = &results[q];
-        double *im = iter_mean ? iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
-        double *ie = iter_std ? iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
-        res->neval = 0;
-        for (int it = 0; it < niter; ++it) {
-            const double *row = hlog.data() + ((size_t)q * niter + it) * nstat;
-            strat_mean_std(row, s.nobs, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
-            res->neval += (int64_t)row[2 * s.nobs + 1];
-            if (res->visited && it == niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
-        }
-        if (iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
-        if (iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
-        for (int o = 0; o < s.nobs; ++o)
-            mci_average(im + o, ie + o, s.nobs, ignore + 1, niter, &res->mean[o], &res->stdev[o], &res->chi2[o]);
-        res->correlated = 0;
-        res->warmup = 0;
-        if (status) status[q] = hst[q];
-    }
-    return MCI_OK;
+    c.copy_out = [&](double *d, const size_t *o, hipStream_t st) {
+        if (d_out) HIPCHK(hipMemcpyAsync(d_out, d + o[kSegD], P * (size_t)ncube * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (counts_out) HIPCHK(hipMemcpyAsync(hoff.data(), d + o[kSegOff], hoff.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+        return (int)MCI_OK;
+    };
+    c.finish = [&] {
+        const size_t nc = (size_t)ncube;
+        if (counts_out)
+            for (size_t q = 0; q < P; ++q)
+                for (size_t h = 0; h < nc; ++h) counts_out[q * nc + h] = hoff[q * (nc + 1) + h + 1] - hoff[q * (nc + 1) + h];
+    };
+    return sweep_run(p, a, c);
 }

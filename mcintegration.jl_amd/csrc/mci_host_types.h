@@ -407,30 +407,50 @@ struct mci_problem {
         double *hstart = nullptr;
         int64_t hstart_n = 0;
     } strat;
-    // Batched :vegas parameter sweeps (mci_integrate_sweep; mci_sweep.h, mci_host_sweep.h): the sweep unit's code object.  A sweep keeps
-    // nothing else here: its maps, logs and status words come in and go out through the call's arguments.
+    // Batched :vegas parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat; mci_host_sweep.h): the code objects of the three
+    // sweep units.  A sweep keeps nothing else here: its maps, logs and status words come in and go out through the call's arguments.
     struct Sweep {
-        bool compiled = false;
-        int threads = 0;              // the workgroup size the loaded code object was compiled for
-        hipModule_t module = nullptr;
-        hipFunction_t f = nullptr;
-        std::string code_object;
-        int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
-        int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default
-        int last_grid = 0, last_threads = 0;
-        // mci_set_sweep_leaves: MCI_SWEEP_ONE_GRID (a sweep point refines ONE Continuous grid, the unit above) or MCI_SWEEP_ALL_LEAVES
-        // (a problem that is no one-grid layout runs the unit of mci_sweep_leaves.h, a code object of its own)
-        int leaves_mode = 0;
         struct Unit {
             bool compiled = false;
-            int threads = 0;
+            int threads = 0;          // the workgroup size the loaded code object was compiled for
             hipModule_t module = nullptr;
             hipFunction_t f = nullptr;
             std::string code_object;
-        } leaves;
-        Unit strat;                   // the unit of mci_sweep_strat.h (mci_integrate_sweep_strat: stratified points)
+        };
+        // mci_sweep.h (one Continuous grid) | mci_sweep_leaves.h (any mix of Continuous and Discrete leaves) | mci_sweep_strat.h
+        // (stratified points): mci_host_sweep.h kSweepUnits describes them in this order
+        enum { kOne = 0, kLeaves = 1, kStrat = 2, kUnits = 3 };
+        Unit unit[kUnits];
+        int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
+        int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default (the one-grid unit only)
+        int last_grid = 0, last_threads = 0;
+        // mci_set_sweep_leaves: MCI_SWEEP_ONE_GRID (a sweep point refines ONE Continuous grid, unit kOne) or MCI_SWEEP_ALL_LEAVES
+        // (a problem that is no one-grid layout runs unit kLeaves)
+        int leaves_mode = 0;
     } sweep;
 };
+
+// The three sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
+// named (mci_host_sweep.h compile_sweep_unit; mci_host_jit.h mci_compile_solver, mci_kernel_code_object).  The headers, the kernel symbol
+// and the #defines are the JIT unit's row (mci_jit.h kUnits).
+struct SweepUnitDesc {
+    int jit_unit;         // mcijit::kUnit*
+    int32_t solver;       // MCI_VEGAS_SWEEP*: the unit's name for mci_compile_solver / mci_kernel_code_object
+    const char *tag;      // in messages: "... (sweep kernel, <tag>)", "... code object (<tag>)"
+    const char *for_what; // in messages: "the sweep kernel<for_what> ..."
+    bool alpha;           // compiled for the one leaf's learning rate (MCI_TRAIN_POWER)
+    bool want_threads;    // mci_debug_sweep_threads applies
+};
+static const SweepUnitDesc kSweepUnits[mci_problem::Sweep::kUnits] = {
+    {mcijit::kUnitSweep, MCI_VEGAS_SWEEP, "", "", true, true},
+    {mcijit::kUnitSweepLeaves, MCI_VEGAS_SWEEP_LEAVES, "several leaves", " for several leaves", false, false},
+    {mcijit::kUnitSweepStrat, MCI_VEGAS_SWEEP_STRAT, "stratified points", " for stratified points", true, false},
+};
+static int sweep_unit_of(int32_t solver) {
+    for (int w = 0; w < mci_problem::Sweep::kUnits; ++w)
+        if (kSweepUnits[w].solver == solver) return w;
+    return -1;
+}
 
 // A repeated iteration (the warm-up of automatic :mcmc chain lengths, mci_integrate) draws from the Philox streams of iteration
 // i + kRepeatStride * attempt: the iteration index has 17 bits (DESIGN.md "RNG streams"), runs of fewer than 16384 iterations leave the upper ones free
@@ -722,23 +742,13 @@ void drop_modules(mci_problem *p) {
         (void)hipModuleUnload(p->strat.module);
         p->strat.module = nullptr;
     }
-    p->sweep.compiled = false;
-    p->sweep.f = nullptr;
-    if (p->sweep.module) {
-        (void)hipModuleUnload(p->sweep.module);
-        p->sweep.module = nullptr;
-    }
-    p->sweep.leaves.compiled = false;
-    p->sweep.leaves.f = nullptr;
-    if (p->sweep.leaves.module) {
-        (void)hipModuleUnload(p->sweep.leaves.module);
-        p->sweep.leaves.module = nullptr;
-    }
-    p->sweep.strat.compiled = false;
-    p->sweep.strat.f = nullptr;
-    if (p->sweep.strat.module) {
-        (void)hipModuleUnload(p->sweep.strat.module);
-        p->sweep.strat.module = nullptr;
+    for (auto &u : p->sweep.unit) {
+        u.compiled = false;
+        u.f = nullptr;
+        if (u.module) {
+            (void)hipModuleUnload(u.module);
+            u.module = nullptr;
+        }
     }
 }
 

@@ -28,20 +28,15 @@
 
 namespace mcijit {
 
-// text of mci_device.h, embedded at build time (see __graft_entry__.build)
-extern const char *const kDeviceHeader;
-// text of mci_train.h (merge + train! device functions and the persistent :vegas kernel): the second header of a kUnitVegasPersist unit
-extern const char *const kTrainHeader;
-// text of mci_spec.h (the chain solvers with several lanes per chain): the second header of a kUnitSpec unit
-extern const char *const kSpecHeader;
-// text of mci_strat.h (the stratified :vegas sample kernel): the second header of a kUnitStrat unit
-extern const char *const kStratHeader;
-// text of mci_sweep.h (batched :vegas parameter sweeps): the third header of a kUnitSweep unit, behind mci_train.h
-extern const char *const kSweepHeader;
-// text of mci_sweep_leaves.h (sweeps of problems with several variable leaves): the third header of a kUnitSweepLeaves unit, behind mci_train.h
-extern const char *const kSweepLeavesHeader;
-// text of mci_sweep_strat.h (stratified points in sweeps): the fourth header of a kUnitSweepStrat unit, behind mci_strat.h and mci_train.h
-extern const char *const kSweepStratHeader;
+// the texts of the device headers, embedded at build time (see __graft_entry__.build); which unit is compiled against which: kUnits
+extern const char *const kDeviceHeader;       // mci_device.h
+extern const char *const kTrainHeader;        // mci_train.h (merge + train! device functions and the persistent :vegas kernel)
+extern const char *const kSpecHeader;         // mci_spec.h (the chain solvers with several lanes per chain)
+extern const char *const kStratHeader;        // mci_strat.h (the stratified :vegas sample kernel)
+extern const char *const kSweepCommonHeader;  // mci_sweep_common.h (what the three sweep kernels share)
+extern const char *const kSweepHeader;        // mci_sweep.h (batched :vegas parameter sweeps)
+extern const char *const kSweepLeavesHeader;  // mci_sweep_leaves.h (sweeps of problems with several variable leaves)
+extern const char *const kSweepStratHeader;   // mci_sweep_strat.h (stratified points in sweeps)
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -111,37 +106,65 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // kUnitSpec: a chain solver's kernel with several lanes per chain (mci_spec.h: vegasmc_chains_spec / mcmc_chains_spec)
 // kUnitStrat: the stratified :vegas sample kernel (mci_strat.h: vegas_strat), measurefreq == 1
 // kUnitSweep: the :vegas loop for measurefreq == 1 inside the sweep kernel of mci_sweep.h (one workgroup runs a point's whole loop);
-// compiled like the persistent unit (scan walk, one Continuous grid) plus MCI_WORK_ITEM_FROM_CALLER, which no other unit sets
+// compiled like the persistent unit (scan walk, one Continuous grid) plus MCI_WORK_ITEM_FROM_CALLER, which no other unit but the next sets
 // kUnitSweepLeaves: the same loop inside the sweep kernel of mci_sweep_leaves.h, for any mix of Continuous and Discrete leaves: the scan
 // walk and MCI_WORK_ITEM_FROM_CALLER like kUnitSweep, but the Discrete form of train! stays in and the learning rate is each leaf's own
 // kUnitSweepStrat: the stratified sample trip (mci_strat.h strat_trip) inside the sweep kernel of mci_sweep_strat.h (one workgroup runs a
 // point's whole VEGAS+ loop); compiled like kUnitSweep (scan walk, one Continuous grid, the leaf's learning rate)
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8 };
-// which headers a unit is compiled against next to mci_device.h
-enum { kHdrNone = 0, kHdrTrain = 1, kHdrSpec = 2, kHdrStrat = 3, kHdrSweep = 4, kHdrSweepLeaves = 5, kHdrSweepStrat = 6 };
+// The three sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitCount = 9 };
+// One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
+struct UnitHeader {
+    const char *name;
+    const char *const *text;
+};
+struct UnitRow {
+    const char *include;       // the one header the generated source includes behind mci_device.h (it includes the others), or nullptr
+    UnitHeader hdr[4];         // the headers hiprtc is given behind mci_device.h, in the order they include one another: the cache key's too
+    const char *kernel, *arg_type, *arg_name, *fn; // extern "C" kernel(mci::BatchArgs a, mci::arg_type arg_name) { mci::fn<Cfg>(a, arg_name); }
+                               // nullptr: the kernels depend on the solver (generate_source)
+    int mf_only;               // MCI_MF_ONLY of a :vegas unit, -1: not defined
+    bool train_power;          // MCI_TRAIN_POWER from the one leaf's learning rate (mci_train.h rescale)
+    int short_sums;            // MCI_TRAIN_SHORT_SUMS (mci_train.h sum_julia) where leaf 0 (1) / every leaf (2) is no longer than Julia's @simd block
+    bool scan_only, continuous_only; // MCI_TRAIN_SCAN_ONLY, MCI_TRAIN_CONTINUOUS_ONLY
+    bool work_item_from_caller;      // MCI_WORK_ITEM_FROM_CALLER (mci_device.h work_item: the row comes from the sweep kernel)
+};
+#define MCI_HDR_TRAIN {"mci_train.h", &kTrainHeader}
+#define MCI_HDR_SWEEP MCI_HDR_TRAIN, {"mci_sweep_common.h", &kSweepCommonHeader}
+constexpr UnitRow kUnits[] = {
+    //                      include, headers, kernel, arg_type, arg_name, fn, mf_only, train_power, short_sums, scan_only, continuous_only, work_item_from_caller
+    /* kUnitSolver       */ {nullptr, {}, nullptr, nullptr, nullptr, nullptr, 0, false, 0, false, false, false},
+    /* kUnitVegasMf1     */ {nullptr, {}, nullptr, nullptr, nullptr, nullptr, 1, false, 0, false, false, false},
+    /* kUnitDump         */ {nullptr, {}, nullptr, nullptr, nullptr, nullptr, -1, false, 0, false, false, false},
+    /* kUnitVegasPersist */ {"mci_train.h", {MCI_HDR_TRAIN}, "mci_vegas_persist", "PersistArgs", "f", "vegas_persist", 1, true, 1, true, true, false},
+    /* kUnitSpec         */ {"mci_spec.h", {{"mci_spec.h", &kSpecHeader}}, nullptr, nullptr, nullptr, nullptr, 0, false, 0, false, false, false},
+    /* kUnitStrat        */ {"mci_strat.h", {{"mci_strat.h", &kStratHeader}}, "mci_vegas_strat", "StratArgs", "st", "vegas_strat", 0, false, 0, false, false, false},
+    /* kUnitSweep        */ {"mci_sweep.h", {MCI_HDR_SWEEP, {"mci_sweep.h", &kSweepHeader}}, "mci_vegas_sweep", "SweepHead", "f", "vegas_sweep", 1, true, 1, true, true, true},
+    // (MCI_TRAIN_POWER undefined: alpha is decided per leaf at run time; the Discrete form of train! sums a whole leaf)
+    /* kUnitSweepLeaves  */ {"mci_sweep_leaves.h", {MCI_HDR_SWEEP, {"mci_sweep_leaves.h", &kSweepLeavesHeader}}, "mci_vegas_sweep_leaves", "SweepHead", "f", "vegas_sweep_leaves", 1, false, 2, true, false, true},
+    /* kUnitSweepStrat   */ {"mci_sweep_strat.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}}, "mci_vegas_sweep_strat", "SweepStratArgs", "f", "vegas_sweep_strat", 1, true, 1, true, true, false},
+};
+#undef MCI_HDR_SWEEP
+#undef MCI_HDR_TRAIN
+static_assert(sizeof kUnits / sizeof kUnits[0] == kUnitCount, "one row per unit");
+
 inline std::string generate_source(const ProblemShape &s, int solver, int unit = kUnitSolver, double persist_alpha = 0.0) {
     std::ostringstream o;
-    if (unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepStrat) { // the learning rate and the size of the one leaf the persistent kernel refines (mci_train.h rescale, sum_julia)
-        o << "#define MCI_TRAIN_POWER " << (persist_alpha == 2.0 ? 2 : persist_alpha == 3.0 ? 3 : persist_alpha == 1.0 ? 1 : 4) << "\n";
-        if (!s.leaf_nbin.empty() && s.leaf_nbin[0] <= 1024) o << "#define MCI_TRAIN_SHORT_SUMS 1\n";
-    }
-    if (unit == kUnitSweepLeaves) { // (sum_julia's short form only where NO leaf is longer than Julia's @simd block: the Discrete form of train! sums a whole leaf)
-        bool all_short = true;
-        for (int n : s.leaf_nbin) all_short = all_short && n <= 1024;
+    const UnitRow &u = kUnits[unit];
+    if (u.train_power) o << "#define MCI_TRAIN_POWER " << (persist_alpha == 2.0 ? 2 : persist_alpha == 3.0 ? 3 : persist_alpha == 1.0 ? 1 : 4) << "\n";
+    if (u.short_sums) {
+        bool all_short = u.short_sums == 2 || !s.leaf_nbin.empty();
+        const size_t n = u.short_sums == 2 ? s.leaf_nbin.size() : 1;
+        for (size_t l = 0; l < n && l < s.leaf_nbin.size(); ++l) all_short = all_short && s.leaf_nbin[l] <= 1024;
         if (all_short) o << "#define MCI_TRAIN_SHORT_SUMS 1\n";
     }
-    if (solver == 0 && unit != kUnitDump) o << "#define MCI_MF_ONLY " << (unit == kUnitVegasMf1 || unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepLeaves || unit == kUnitSweepStrat ? 1 : 0) << "\n";
-    if (unit == kUnitVegasPersist || unit == kUnitSweep || unit == kUnitSweepStrat) o << "#define MCI_TRAIN_SCAN_ONLY 1\n#define MCI_TRAIN_CONTINUOUS_ONLY 1\n";
-    if (unit == kUnitSweepLeaves) o << "#define MCI_TRAIN_SCAN_ONLY 1\n"; // (MCI_TRAIN_POWER undefined: alpha is decided per leaf at run time)
-    if (unit == kUnitSweep || unit == kUnitSweepLeaves) o << "#define MCI_WORK_ITEM_FROM_CALLER 1\n"; // (mci_device.h work_item: the row comes from vegas_sweep)
+    if (solver == 0 && u.mf_only >= 0) o << "#define MCI_MF_ONLY " << u.mf_only << "\n";
+    if (u.scan_only) o << "#define MCI_TRAIN_SCAN_ONLY 1\n";
+    if (u.continuous_only) o << "#define MCI_TRAIN_CONTINUOUS_ONLY 1\n";
+    if (u.work_item_from_caller) o << "#define MCI_WORK_ITEM_FROM_CALLER 1\n";
     if (s.rng_rounds != 10) o << "#define MCI_PHILOX_ROUNDS " << s.rng_rounds << "\n"; // opt-in cheaper stream (mci_set_rng_rounds)
     o << "#include \"mci_device.h\"\n";
-    if (unit == kUnitVegasPersist) o << "#include \"mci_train.h\"\n";
-    if (unit == kUnitSpec) o << "#include \"mci_spec.h\"\n";
-    if (unit == kUnitStrat) o << "#include \"mci_strat.h\"\n";
-    if (unit == kUnitSweep) o << "#include \"mci_sweep.h\"\n"; // (includes mci_train.h)
-    if (unit == kUnitSweepLeaves) o << "#include \"mci_sweep_leaves.h\"\n"; // (likewise)
-    if (unit == kUnitSweepStrat) o << "#include \"mci_sweep_strat.h\"\n"; // (includes mci_strat.h and mci_train.h)
+    if (u.include) o << "#include \"" << u.include << "\"\n";
     o << "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n";
     o << "#ifndef MCI_CHAIN_KERNEL_ATTR\n#define MCI_CHAIN_KERNEL_ATTR\n#endif\n"; // (occupancy experiments on the lane-per-chain kernels: MCI_JIT_FLAGS=-DMCI_CHAIN_KERNEL_ATTR=...)
     o << "namespace {\nstruct Cfg {\n";
@@ -199,24 +222,12 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
          "#define obs_add(k, v) mci::lds_add(&mci_obs_[(k)], (v))\n"
       << s.measure_body << "\n#undef obs_add\n    }\n";
     o << "};\n}\n";
-    if (solver == 0 && unit == kUnitStrat) {
-        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_strat(mci::BatchArgs a, mci::StratArgs st) { "
-             "mci::vegas_strat<Cfg>(a, st); }\n";
-    } else if (solver == 0 && unit == kUnitSweep) {
-        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep(mci::BatchArgs a, mci::SweepArgs f) { "
-             "mci::vegas_sweep<Cfg>(a, f); }\n";
-    } else if (solver == 0 && unit == kUnitSweepStrat) {
-        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep_strat(mci::BatchArgs a, mci::SweepStratArgs f) { "
-             "mci::vegas_sweep_strat<Cfg>(a, f); }\n";
-    } else if (solver == 0 && unit == kUnitSweepLeaves) {
-        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_sweep_leaves(mci::BatchArgs a, mci::SweepLeavesArgs f) { "
-             "mci::vegas_sweep_leaves<Cfg>(a, f); }\n";
+    if (solver == 0 && u.kernel) {
+        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) " << u.kernel << "(mci::BatchArgs a, mci::" << u.arg_type << " " << u.arg_name << ") { "
+          << "mci::" << u.fn << "<Cfg>(a, " << u.arg_name << "); }\n";
     } else if (solver == 0 && unit == kUnitDump) {
         o << "extern \"C\" __global__ void __launch_bounds__(256) mci_sample_dump(mci::DumpArgs a) { "
              "mci::sample_dump<Cfg>(a); }\n";
-    } else if (solver == 0 && unit == kUnitVegasPersist) {
-        o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_persist(mci::BatchArgs a, mci::PersistArgs f) { "
-             "mci::vegas_persist<Cfg>(a, f); }\n";
     } else if (solver == 0) {
         o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) mci_vegas_batch(mci::BatchArgs a) { "
              "mci::vegas_batch<Cfg, (Cfg::NTILE > 1)>(a); }\n";
@@ -405,7 +416,7 @@ inline void write_file_atomic(const std::string &path, const char *data, size_t 
 
 // returns the gfx950 code object for `src`, from the on-disk cache or by compiling with hiprtc
 inline int compile(const std::string &src, int threads, std::vector<char> &code, std::string &log, bool &from_cache, std::string *cache_path = nullptr,
-                   int extra_hdr = kHdrNone, bool cache_only = false, bool no_exec_mask_flag = false) {
+                   int unit = kUnitSolver, bool cache_only = false, bool no_exec_mask_flag = false) {
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics",
                                      "-ffp-contract=off", "-DMCI_THREADS=" + std::to_string(threads)};
     // EVERY unit is compiled WITHOUT the backend's pre-RA exec-mask optimisation.  One layout of the randomised campaigns -- a composite
@@ -419,7 +430,6 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     // is off for all of them.  MCI_JIT_FLAGS that names the switch itself decides it (the A/B; the guard test that re-enables the pass to
     // see the self-check of a new group code object trip, mci_host_jit.h spec_self_check); no_exec_mask_flag: the retry of a unit whose
     // compilation the switch itself broke (a later compiler that no longer knows it).
-    (void)extra_hdr;
     const char *jf = getenv("MCI_JIT_FLAGS");
     if (!no_exec_mask_flag && !(jf && strstr(jf, "amdgpu-opt-exec-mask-pre-ra"))) {
         opts.push_back("-mllvm");
@@ -431,12 +441,9 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
         while (is >> t) opts.push_back(t);
     }
     std::string key = src + "\n//HDR\n" + kDeviceHeader;
-    if (extra_hdr == kHdrTrain) key += std::string("\n//HDR\n") + kTrainHeader;
-    if (extra_hdr == kHdrSpec) key += std::string("\n//HDR\n") + kSpecHeader;
-    if (extra_hdr == kHdrStrat) key += std::string("\n//HDR\n") + kStratHeader;
-    if (extra_hdr == kHdrSweep) key += std::string("\n//HDR\n") + kTrainHeader + "\n//HDR\n" + kSweepHeader;
-    if (extra_hdr == kHdrSweepLeaves) key += std::string("\n//HDR\n") + kTrainHeader + "\n//HDR\n" + kSweepLeavesHeader;
-    if (extra_hdr == kHdrSweepStrat) key += std::string("\n//HDR\n") + kStratHeader + "\n//HDR\n" + kTrainHeader + "\n//HDR\n" + kSweepStratHeader;
+    const UnitRow &u = kUnits[unit];
+    for (const UnitHeader &h : u.hdr)
+        if (h.name) key += std::string("\n//HDR\n") + *h.text;
     for (auto &f : opts) key += "\n//" + f;
     key += "\n//COMPILER " + compiler_id();
     char name[64];
@@ -457,19 +464,14 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     if (cache_only) return -1; // (not in the cache: the caller compiles it elsewhere, e.g. on a thread of its own)
     warm_up_join();
     hiprtcProgram prog;
-    // mci_device.h, then the unit's own headers in the order they include one another (at most four in all: kHdrSweepStrat)
-    const char *hdr[4] = {kDeviceHeader, nullptr, nullptr, nullptr}, *hname[4] = {"mci_device.h", nullptr, nullptr, nullptr};
+    // mci_device.h, then the unit's own headers
+    const char *hdr[5] = {kDeviceHeader}, *hname[5] = {"mci_device.h"};
     int nhdr = 1;
-    auto add = [&](const char *text, const char *name) {
-        hdr[nhdr] = text;
-        hname[nhdr++] = name;
-    };
-    if (extra_hdr == kHdrSpec) add(kSpecHeader, "mci_spec.h");
-    if (extra_hdr == kHdrStrat || extra_hdr == kHdrSweepStrat) add(kStratHeader, "mci_strat.h");
-    if (extra_hdr == kHdrTrain || extra_hdr == kHdrSweep || extra_hdr == kHdrSweepLeaves || extra_hdr == kHdrSweepStrat) add(kTrainHeader, "mci_train.h");
-    if (extra_hdr == kHdrSweep) add(kSweepHeader, "mci_sweep.h");
-    if (extra_hdr == kHdrSweepLeaves) add(kSweepLeavesHeader, "mci_sweep_leaves.h");
-    if (extra_hdr == kHdrSweepStrat) add(kSweepStratHeader, "mci_sweep_strat.h");
+    for (const UnitHeader &h : u.hdr)
+        if (h.name) {
+            hdr[nhdr] = *h.text;
+            hname[nhdr++] = h.name;
+        }
     if (hiprtcCreateProgram(&prog, src.c_str(), "mci_problem.hip", nhdr, hdr, hname) != HIPRTC_SUCCESS) {
         log = "hiprtcCreateProgram failed";
         return 1;

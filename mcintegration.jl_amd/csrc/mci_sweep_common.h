@@ -1,0 +1,96 @@
+// mci_sweep_common.h -- what the three batched-sweep kernels share: mci_sweep.h (one Continuous grid), mci_sweep_leaves.h (any mix of
+// Continuous and Discrete leaves) and mci_sweep_strat.h (stratified points).  Each of them is a translation unit of its own (mci_jit.h
+// kUnits) and includes this header; the host (mci_host_sweep.h) compiles the same text, so the argument layout cannot drift.  Free of
+// host / std headers.
+//
+// In all three ONE workgroup owns a point and runs its whole loop, and no workgroup ever waits for another one: no grid-wide counters, no
+// spinning, no residency condition, and every loop's trip count is a kernel argument or a constant of the translation unit.
+//
+// The ordering argument.  What travels through global memory inside a point -- the partial rows, merge_stats' scratch and head, the
+// histogram row the sample loop adds to with f64 atomics, and whatever a unit adds of its own -- is written and read by the SAME
+// workgroup.  Between the two sides stands sweep_round_trip(): every wave waits for its own stores and atomics (s_waitcnt vmcnt(0): a
+// barrier alone orders nothing in global memory, see persist_signal in mci_train.h), then the workgroup meets at a barrier.  The CU's
+// write-through L1 is coherent for its own workgroup's plain stores, so plain loads see them behind that round trip.  The histogram row is
+// different: the atomics change it in L2 behind that L1, so sweep_take_hist() reads it with agent-scope atomic loads that bypass the L1,
+// and zeroes it the same way.  And no two threads ever touch one bin: flush_workgroup's adds run over the whole row [0, NBIN) with stride
+// T, so bin j of the row belongs to thread j % T; a leaf's slice [boff, boff + N) is read and zeroed by the thread whose index is
+// (boff + i) % T for bin boff + i -- which is `first = (tid + T - boff % T) % T`, and plainly `tid` where boff == 0.  Adds, read and
+// zeroing of a bin are therefore one thread's, in program order, with a round trip between one iteration's zeroing and the next one's adds.
+#pragma once
+#include "mci_train.h"
+
+namespace mci {
+
+// the head of every sweep kernel's second argument (the stratified unit appends its own fields: SweepStratArgs)
+struct SweepHead {
+    MergeArgs m;           // of point 0: part_cols [npoint][rows][ncols], scratch [npoint][rows * ncols], packed [npoint][nstat],
+                           // ghist [npoint][nbin], status [npoint]; use_ghist = 1, wg_per_block = 1; rows: sweep_point's rows_per_point
+    TrainArgs t;           // t.edges / t.dacc / t.ddist: the problem's own map (read only: where a point starts when maps_in == NULL);
+                           // t.iter_log_row: [npoint][niter][nstat]; t.maxn: bins of the largest leaf
+    int npoint, niter, nuserdata;
+    int map_off;           // doubles: where the point's map lies in LDS, behind both the sample loop's carve and the refinement's scratch
+    const double *ud;      // [npoint][nuserdata]
+    const u64 *seeds;      // [npoint] or NULL: BatchArgs::seed for every point
+    const double *maps_in; // [npoint][doubles of a map row] or NULL
+    double *maps_out;      // [npoint][doubles of a map row]
+};
+
+// every wave has performed its global stores and atomics, then the workgroup meets
+__device__ __forceinline__ void sweep_round_trip() {
+    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
+    __syncthreads();
+}
+
+// point p's own rows of the sweep's buffers: m <- f.m, a <- a0, both rebased (the caller sets a's tables: they lie in its LDS)
+template <class Cfg> __device__ __forceinline__ void sweep_point(const SweepHead &f, const BatchArgs &a0, int p, int rows_per_point, MergeArgs &m, BatchArgs &a) {
+    const int ncols = f.m.ncols, nstat = f.t.nstat;
+    m = f.m;
+    m.part_cols = f.m.part_cols + (size_t)p * rows_per_point * ncols;
+    m.scratch = f.m.scratch + (size_t)p * rows_per_point * ncols;
+    m.packed = f.m.packed + (size_t)p * nstat;
+    m.ghist = f.m.ghist + (size_t)p * Cfg::NBIN;
+    m.status = f.m.status + p;
+    a = a0;
+    a.ud = f.ud + (size_t)p * f.nuserdata;
+    a.part_cols = const_cast<double *>(m.part_cols);
+    a.ghist = m.ghist;
+    a.status = m.status;
+    if (f.seeds) a.seed = f.seeds[p];
+}
+
+// iteration_bookkeeping's arguments for point p, iteration `it`
+__device__ __forceinline__ TrainArgs sweep_log_row(const SweepHead &f, int p, int it) {
+    TrainArgs t = f.t;
+    t.packed = f.m.packed + (size_t)p * f.t.nstat;
+    t.iter_log_row = f.t.iter_log_row + ((size_t)p * f.niter + it) * f.t.nstat;
+    return t;
+}
+
+// merge_hist_bin for a slice of N bins at gh: hl <- the clearStatistics! offset + what the sample loop added; the slice is zero again for
+// the next iteration; a bad histogram's bits go to *verdict (LDS).  first: this thread's first bin of the slice (the header comment)
+__device__ __forceinline__ void sweep_take_hist(double *gh, double *hl, int N, int first, double offset, int *verdict) {
+    const int T = blockDim.x;
+    int hbad = 0;
+    for (int base = 0; base < N; base += kTrainQ * T) {
+        double v[kTrainQ];
+#pragma unroll
+        for (int q = 0; q < kTrainQ; ++q) {
+            const int i = base + q * T + first;
+            v[q] = i < N ? __hip_atomic_load(&gh[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < kTrainQ; ++q) {
+            const int i = base + q * T + first;
+            if (i < N) {
+                __hip_atomic_store(&gh[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const double h = offset + v[q];
+                hl[i] = h;
+                if (!isfinite(h)) hbad |= ST_HIST_NONFINITE;      // variable.jl:212
+                else if (!(h > 0.0)) hbad |= ST_HIST_NONPOSITIVE; // variable.jl:213 / common.jl:71
+            }
+        }
+    }
+    if (hbad) atomicOr(verdict, hbad);
+}
+
+} // namespace mci

@@ -1,6 +1,6 @@
 // mci_sweep_leaves.h -- batched :vegas parameter sweeps of problems with SEVERAL variable leaves, Continuous and Discrete (the opt-in
 // mci_set_sweep_leaves(prob, MCI_SWEEP_ALL_LEAVES)): vegas_sweep of mci_sweep.h generalised from one Continuous grid to the whole map.
-// Compiled by hiprtc next to mci_device.h and mci_train.h into a translation unit of its own (mci_jit.h kUnitSweepLeaves): the
+// Compiled by hiprtc next to mci_device.h, mci_train.h and mci_sweep_common.h into a translation unit of its own (mci_jit.h kUnitSweepLeaves): the
 // one-grid sweep unit, the classic, persistent and stratified code objects stay what they were.  Free of host / std headers.
 //
 //     workgroup g   for p = g, g + G, ...:   map of point p (every grid, every Discrete accumulation and distribution) -> LDS;
@@ -9,13 +9,8 @@
 //                   offsets -> train! on the leaf's part of the LDS map (train_leaf: prefix-scan walk, or the Discrete form);
 //                   at the end the map -> maps_out[p]
 //
-// The argument of mci_sweep.h holds unchanged.  No workgroup ever waits for another one: no grid-wide counters, no spinning, every
-// loop's trip count is a kernel argument or a constant of the translation unit.  What travels through global memory inside a point --
-// the blocks' partial rows, merge_stats' scratch and head, the histogram row -- is written and read by the SAME workgroup, every wave
-// waiting for its own stores and atomics (vmcnt(0)) before the workgroup's barrier; the histogram row, which the atomics change in L2
-// behind the CU's L1, is read with agent-scope atomic loads.  Bin j of that row is only ever touched by thread j % T, in program order:
-// flush_workgroup's adds run over the whole row with stride T, and a leaf's slice [boff, boff + nbin) is read and zeroed below by the
-// thread whose index is (boff + i) % T for bin boff + i.
+// The synchronisation is mci_sweep_common.h's, in its general form: a leaf's slice [boff, boff + nbin) of the histogram row is read and
+// zeroed by the thread whose index is (boff + i) % T for bin boff + i.
 //
 // The map block  edges[NEDGE] | dacc[NDACC] | ddist[NDDIST] | flags[4]  (each part starting on 16 bytes) lies behind BOTH the sample
 // loop's carve and the refinement's scratch.  vegas_batch reads all three tables from it once per call (stage_tables) behind a barrier;
@@ -26,29 +21,9 @@
 // merged slice is written before it is read, and the two verdict words are reset before the leaf that uses them (they alternate, so
 // that a reset never meets the atomicOr of the leaf before without a barrier in between).
 #pragma once
-#include "mci_train.h"
+#include "mci_sweep_common.h"
 
 namespace mci {
-
-struct SweepLeavesArgs {
-    MergeArgs m;           // of point 0: part_cols [npoint][nblocks][ncols], scratch [npoint][nblocks * ncols], packed [npoint][nstat],
-                           // ghist [npoint][nbin], status [npoint]; use_ghist = 1, wg_per_block = 1
-    TrainArgs t;           // t.edges / t.dacc / t.ddist: the problem's own map (read only: where a point starts when maps_in == NULL);
-                           // t.iter_log_row: [npoint][niter][nstat]; t.maxn: bins of the largest leaf
-    int npoint, niter, nuserdata;
-    int map_off;           // doubles: LDS behind both the sample loop's carve and the refinement's scratch of the largest leaf
-    const double *ud;      // [npoint][nuserdata]
-    const u64 *seeds;      // [npoint] or NULL: BatchArgs::seed for every point
-    const double *maps_in; // [npoint][sweep_map_doubles] or NULL
-    double *maps_out;      // [npoint][sweep_map_doubles]
-};
-
-// every wave has performed its global stores and atomics, then the workgroup meets (mci_sweep.h sweep_global_round_trip: a barrier
-// alone orders nothing in global memory)
-__device__ __forceinline__ void sweep_leaves_round_trip() {
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
-    __syncthreads();
-}
 
 // One maps_in / maps_out row: the leaves in order; a Continuous leaf its nbin + 1 grid points, a Discrete leaf its accumulation
 // [nbin + 1] and then its distribution [nbin]  (the host's sweep_map_doubles, mci_host_sweep.h)
@@ -101,7 +76,7 @@ template <class Cfg, bool TO_ROW> __device__ __forceinline__ void sweep_copy_row
     });
 }
 
-template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const BatchArgs &a0, const SweepLeavesArgs &f) {
+template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const BatchArgs &a0, const SweepHead &f) {
     static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS (the host checks)");
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -111,7 +86,7 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
     double *sm = smem, *hl = sm + train_lds_doubles(MAXN), *ps = hl + MAXN, *blk = smem + f.map_off;
     double *bedges = blk + B::E, *bdacc = blk + B::DA, *bddist = blk + B::DD, *flags = blk + B::FLAGS;
     int *bad = reinterpret_cast<int *>(flags); // bad[0], bad[1]: the verdicts of the even and the odd leaves; flags[2]: train_leaf's spare word
-    const int nblocks = f.m.nblocks, ncols = f.m.ncols, nstat = f.t.nstat;
+    const int nblocks = f.m.nblocks;
     for (int p = (int)blockIdx.x; p < f.npoint; p += (int)gridDim.x) {
         __syncthreads(); // (the point before: its last LDS reads are through)
         if (f.maps_in) sweep_copy_row<Cfg, false>(blk, nullptr, f.maps_in + (size_t)p * NROW);
@@ -120,21 +95,12 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
             for (int i = tid; i < Cfg::NDACC; i += T) bdacc[i] = f.t.dacc[i];
             for (int i = tid; i < Cfg::NDDIST; i += T) bddist[i] = f.t.ddist[i];
         }
-        MergeArgs m = f.m;
-        m.part_cols = f.m.part_cols + (size_t)p * nblocks * ncols;
-        m.scratch = f.m.scratch + (size_t)p * nblocks * ncols;
-        m.packed = f.m.packed + (size_t)p * nstat;
-        m.ghist = f.m.ghist + (size_t)p * Cfg::NBIN;
-        m.status = f.m.status + p;
-        BatchArgs a = a0;
+        MergeArgs m;
+        BatchArgs a;
+        sweep_point<Cfg>(f, a0, p, nblocks, m, a);
         a.edges = bedges; // (LDS through the generic address space: stage_tables reads the three tables once per call)
         a.dacc = bdacc;
         a.ddist = bddist;
-        a.ud = f.ud + (size_t)p * f.nuserdata;
-        a.part_cols = const_cast<double *>(m.part_cols);
-        a.ghist = m.ghist;
-        a.status = m.status;
-        if (f.seeds) a.seed = f.seeds[p];
         for (int it = 0; it < f.niter; ++it) {
             a.iteration = a0.iteration + (u32)it;
             if (tid == 0) bad[0] = 0;
@@ -143,12 +109,10 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
                 __syncthreads(); // (map and flag complete; whatever read this LDS before is through)
                 vegas_batch<Cfg, false>(a); // tables <- the map block, the block's samples, its partial row, histogram atomics into this point's row
             }
-            sweep_leaves_round_trip();
+            sweep_round_trip();
             merge_stats(m); // main.jl:273-287
             __syncthreads(); // the head of `packed` was written by this workgroup
-            TrainArgs t = f.t;
-            t.packed = m.packed;
-            t.iter_log_row = f.t.iter_log_row + ((size_t)p * f.niter + it) * nstat;
+            const TrainArgs t = sweep_log_row(f, p, it);
             iteration_bookkeeping(t);
 #pragma unroll 1
             for (int l = 0; l < Cfg::NLEAF; ++l) {
@@ -158,30 +122,9 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
                 int *verdict = bad + (l & 1);
                 if (tid == 0) bad[(l + 1) & 1] = 0; // (the next leaf's; its last reader passed the barrier that closed the leaf before this one)
                 // merge_hist_bin: clearStatistics! offsets + what the blocks added; the slice is zero again for the next iteration
-                double *gh = m.ghist + L.boff;
-                const int sh = (tid + T - L.boff % T) % T; // this thread's first bin of the slice: (boff + sh) % T == tid
-                int hbad = 0;
-                for (int base = 0; base < N; base += kTrainQ * T) {
-                    double v[kTrainQ];
-#pragma unroll
-                    for (int q = 0; q < kTrainQ; ++q) {
-                        const int i = base + q * T + sh;
-                        v[q] = i < N ? __hip_atomic_load(&gh[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-                    }
-#pragma unroll
-                    for (int q = 0; q < kTrainQ; ++q) {
-                        const int i = base + q * T + sh;
-                        if (i < N) {
-                            __hip_atomic_store(&gh[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const double h = (double)(nblocks + 1) * 1.0e-10 + v[q];
-                            hl[i] = h;
-                            if (!isfinite(h)) hbad |= ST_HIST_NONFINITE;      // variable.jl:212
-                            else if (!(h > 0.0)) hbad |= ST_HIST_NONPOSITIVE; // variable.jl:213 / common.jl:71
-                        }
-                    }
-                }
-                if (hbad) atomicOr(verdict, hbad);
-                sweep_leaves_round_trip(); // (hl, the verdict; the zeroed slice is out before the next iteration adds to it)
+                // (this thread's first bin of the slice: (boff + first) % T == tid)
+                sweep_take_hist(m.ghist + L.boff, hl, N, (tid + T - L.boff % T) % T, (double)(nblocks + 1) * 1.0e-10, verdict);
+                sweep_round_trip(); // (hl, the verdict; the zeroed slice is out before the next iteration adds to it)
                 // a bad histogram: this leaf's train! refuses (its map stays), the bits go to this point's status word; the other leaves
                 // and the other points never see it
                 if (train) train_leaf(L, hl, nullptr, sm, ps, *verdict, flags[2], bedges, bdacc, bddist, 0, m.status, false, nullptr, true);

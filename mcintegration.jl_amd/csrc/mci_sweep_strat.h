@@ -1,5 +1,5 @@
 // mci_sweep_strat.h -- stratified (VEGAS+) points in batched :vegas parameter sweeps: P independent stratified integrate() loops in ONE
-// launch (mci_integrate_sweep_strat).  Compiled by hiprtc next to mci_device.h, mci_strat.h and mci_train.h into a translation unit of its
+// launch (mci_integrate_sweep_strat).  Compiled by hiprtc next to mci_device.h, mci_strat.h, mci_train.h and mci_sweep_common.h into a translation unit of its
 // own (mci_jit.h kUnitSweepStrat): the classic, persistent, stratified, sweep and sweep-leaves code objects stay what they were.  Free of
 // host / std headers.
 //
@@ -15,41 +15,26 @@
 //                   with the stratified mean | var -> histogram with the clearStatistics! offsets -> train! on the LDS map (train_leaf)
 //                   at the end the map -> maps_out[p]; d[p] and off[p] stay in the sweep's buffer for the host
 //
-// Synchronisation is mci_sweep.h's: nothing waits grid-wide, there are no counters and no spinning, every loop's trip count is a kernel
-// argument or bounded by one.  What travels through global memory inside a point -- off, d, the tile bases, the partial row, the histogram
-// row -- is written and read by the SAME workgroup with a round trip (every wave's vmcnt(0), then a barrier: mci_sweep.h sweep_global_round_trip) between the two sides; the histogram row, which the
-// atomics change in L2, is read with agent-scope atomic loads, bin i by thread i % T.
+// The synchronisation is mci_sweep_common.h's, with the grid's slice at boff = 0 (bin i belongs to thread i % T); every loop's trip count
+// is a kernel argument or bounded by one.  What this unit adds to the traffic through global memory inside a point -- off, d, the tile
+// bases -- is likewise written and read by the SAME workgroup with a sweep_round_trip() between the two sides.
 #pragma once
 #include "mci_strat.h"
-#include "mci_train.h"
+#include "mci_sweep_common.h"
 
 namespace mci {
 
-// mci_sweep.h's sweep_global_round_trip() (that header is no part of this unit): every wave has performed its global stores and atomics,
-// then the workgroup meets
-__device__ __forceinline__ void sweep_strat_round_trip() {
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
-    __syncthreads();
-}
-
 struct SweepStratArgs {
-    MergeArgs m;           // of point 0: part_cols [npoint][ncols], scratch [npoint][ncols], packed [npoint][nstat], ghist [npoint][nbin],
-                           // status [npoint]; nblocks = 1, wg_per_block = 1, use_ghist = 1
-    TrainArgs t;           // t.edges: the problem's own map (read only); t.iter_log_row: [npoint][niter][nstat]
+    SweepHead h;           // m: nblocks = 1, one partial row per point; map_off: LDS behind both the sample carve (+ strat_lds_doubles)
+                           // and the refinement's scratch: the map [N + 2] | flags [4] | the iteration's running sums [2 kStratMaxCols] |
+                           // the cut hypercube's S1 | S2 [2 kStratMaxCols]
     StratArgs st;          // of point 0: off [npoint][ncube + 1], dnext [npoint][ncube]; chunk = S, nchunk, nloc, beta, the cell decode;
                            // part / rec_* / dump_* unused (NULL)
-    int npoint, niter, nuserdata;
-    int map_off;           // doubles: LDS behind both the sample carve (+ strat_lds_doubles) and the refinement's scratch: the map [N + 2] |
-                           // flags [4] | the iteration's running sums [2 kStratMaxCols] | the cut hypercube's S1 | S2 [2 kStratMaxCols]
     int have_d;            // d rows were filled by the host (d_in): every allocation is made from them
     int start_uniform;     // the first iteration of a point without d_in samples every hypercube alike
     int mblocks;           // the blocks the ordinary stratified call merges this N and block as: (mblocks + 1) 1e-10 per histogram bin
     int ntile;             // strat_alloc_ntile(ncube)
     double *tbase;         // [npoint][ntile] allocation scratch: the tile bases
-    const double *ud;      // [npoint][nuserdata]
-    const u64 *seeds;      // [npoint] or NULL
-    const double *maps_in; // [npoint][N + 1] or NULL
-    double *maps_out;      // [npoint][N + 1]
 };
 
 // the allocation of point-local d -> off, by one workgroup of 256 threads; part: 256 doubles of LDS, bc: 2 doubles of LDS
@@ -74,7 +59,7 @@ __device__ __forceinline__ void sweep_strat_alloc(const double *d, long long *of
         bc[0] = base;
         bc[1] = strat_alloc_uniform(ask_uniform, base) ? 1.0 : 0.0;
     }
-    sweep_strat_round_trip(); // (tbase, bc)
+    sweep_round_trip(); // (tbase, bc)
     const double total = bc[0];
     const bool uniform = bc[1] != 0.0;
     for (int g = 0; g < ntile; ++g) {
@@ -89,15 +74,16 @@ __device__ __forceinline__ void sweep_strat_alloc(const double *d, long long *of
         strat_alloc_offsets(d, off, ncube, nsamp, lo, hi, uniform ? 1 : 0, sbase, tb, total);
         if (!uniform) __syncthreads(); // (part is written again for the next tile)
     }
-    sweep_strat_round_trip(); // (off)
+    sweep_round_trip(); // (off)
 }
 
-template <class Cfg> __device__ __forceinline__ void vegas_sweep_strat(const BatchArgs &a0, const SweepStratArgs &f) {
+template <class Cfg> __device__ __forceinline__ void vegas_sweep_strat(const BatchArgs &a0, const SweepStratArgs &fs) {
     static_assert(Cfg::NLEAF == 1 && Cfg::leaf_kind(0) == 0 && Cfg::NTILE == 1, "a sweep point refines ONE Continuous grid in one tile (the host checks)");
     static_assert(Cfg::CUSTOM_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0 && Cfg::HOST_MEASURE == 0, "stratified :vegas: device integrand, default measure");
     static_assert(Cfg::NDRAW <= kStratMaxDraw && Cfg::NW <= kStratMaxCols, "stratified :vegas: draws / columns");
     static_assert(Mode<Cfg>::HIST_LDS && Cfg::HCOPY == 1 && Cfg::DET == 0, "the point's histogram sits in LDS, one copy");
     static_assert(Cfg::NOBS == Cfg::NW, "default measure: one observable per weight column (row[k] = mean, row[nobs + k] = var)");
+    const SweepHead &f = fs.h;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using LD = Lds<Cfg>;
     constexpr int NW = Cfg::NW, N = Cfg::leaf_nbin(0);
@@ -110,42 +96,32 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_strat(const Bat
     // ... and the sample loop's (vegas_strat)
     double *sE = smem + LD::E, *sDA = smem + LD::DA, *sDD = smem + LD::DD, *sH = smem + LD::H, *sO = smem + LD::O;
     long long *sOff = reinterpret_cast<long long *>(smem + LD::END);
-    double *sS = smem + LD::END + f.st.nloc + 1;
-    int *sLane = reinterpret_cast<int *>(sS + f.st.nloc * 2 * NW);
-    double *sV = sS + f.st.nloc * 2 * NW + T;
+    double *sS = smem + LD::END + fs.st.nloc + 1;
+    int *sLane = reinterpret_cast<int *>(sS + fs.st.nloc * 2 * NW);
+    double *sV = sS + fs.st.nloc * 2 * NW + T;
     const LeafDev L = f.t.leaves[0];
     const bool train = f.t.do_train && L.adapt; // variable.jl:208
-    const int ncols = f.m.ncols, nstat = f.t.nstat;
-    const long long ncube = f.st.ncube, nsamp = f.st.nsamp;
+    const long long ncube = fs.st.ncube, nsamp = fs.st.nsamp;
     const double V = 1.0 / (double)ncube;
     for (int p = (int)blockIdx.x; p < f.npoint; p += (int)gridDim.x) {
         __syncthreads(); // (the point before: its last LDS reads are through)
         const double *g0 = f.maps_in ? f.maps_in + (size_t)p * (N + 1) : f.t.edges + L.eoff;
         for (int i = tid; i <= N; i += T) gcur[i] = g0[i];
-        MergeArgs m = f.m;
-        m.part_cols = f.m.part_cols + (size_t)p * ncols;
-        m.scratch = f.m.scratch + (size_t)p * ncols;
-        m.packed = f.m.packed + (size_t)p * nstat;
-        m.ghist = f.m.ghist + (size_t)p * Cfg::NBIN;
-        m.status = f.m.status + p;
-        StratArgs st = f.st;
-        long long *off = const_cast<long long *>(f.st.off) + (size_t)p * (size_t)(ncube + 1);
-        double *d = f.st.dnext + (size_t)p * (size_t)ncube;
+        MergeArgs m;
+        BatchArgs a;
+        sweep_point<Cfg>(f, a0, p, 1, m, a); // (one partial row per point)
+        a.edges = gcur - L.eoff; // (LDS through the generic address space: stage_tables reads it once per iteration)
+        StratArgs st = fs.st;
+        long long *off = const_cast<long long *>(fs.st.off) + (size_t)p * (size_t)(ncube + 1);
+        double *d = fs.st.dnext + (size_t)p * (size_t)ncube;
         st.off = off;
         st.dnext = d;
-        BatchArgs a = a0;
-        a.edges = gcur - L.eoff; // (LDS through the generic address space: stage_tables reads it once per iteration)
-        a.ud = f.ud + (size_t)p * f.nuserdata;
-        a.part_cols = const_cast<double *>(m.part_cols);
-        a.ghist = m.ghist;
-        a.status = m.status;
-        if (f.seeds) a.seed = f.seeds[p];
         const RoundKeys<false> keys = make_round_keys<false>((u32)a.seed, (u32)(a.seed >> 32));
         for (int it = 0; it < f.niter; ++it) {
             a.iteration = a0.iteration + (u32)it;
             __syncthreads(); // (map complete; the refinement of the iteration before has read its scratch)
             // ---- allocation: uniform at a fresh start, from d where one was given or measured; adapt off: the first one stays
-            if (it == 0 || f.t.do_train) sweep_strat_alloc(d, off, f.tbase + (size_t)p * f.ntile, ncube, nsamp, f.ntile, it == 0 && !f.have_d && f.start_uniform ? 1 : 0, ps, flags + 2);
+            if (it == 0 || f.t.do_train) sweep_strat_alloc(d, off, fs.tbase + (size_t)p * fs.ntile, ncube, nsamp, fs.ntile, it == 0 && !fs.have_d && fs.start_uniform ? 1 : 0, ps, flags + 2);
             // ---- the sample loop's tables from the map, empty histogram and sums
             if (tid == 0) *bad = 0;
             stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
@@ -221,38 +197,15 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_strat(const Bat
             }
             // ---- statistics: the one partial row + histogram atomics, the head as merge_stats leaves it, the stratified mean | var over it
             flush_workgroup<Cfg, LD>(a, smem, acc, extra, (i64)0, 0);
-            sweep_strat_round_trip();
+            sweep_round_trip();
             merge_stats(m); // (one block of one row)
             __syncthreads(); // the head of `packed` was written by this workgroup
-            TrainArgs tr = f.t;
-            tr.packed = m.packed;
-            tr.iter_log_row = f.t.iter_log_row + ((size_t)p * f.niter + it) * nstat;
+            const TrainArgs tr = sweep_log_row(f, p, it);
             iteration_bookkeeping(tr);
             if (tid < 2 * NW) tr.iter_log_row[tid < NW ? tid : Cfg::NOBS + (tid - NW)] = tot[tid]; // (the thread that copied this entry: program order)
             // ---- the histogram row: clearStatistics! offsets + what the chunks added; zero again for the next iteration
-            double *gh = m.ghist + L.boff;
-            int hbad = 0;
-            for (int base = 0; base < N; base += kTrainQ * T) {
-                double v[kTrainQ];
-#pragma unroll
-                for (int q = 0; q < kTrainQ; ++q) {
-                    const int i = base + q * T + tid;
-                    v[q] = i < N ? __hip_atomic_load(&gh[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-                }
-#pragma unroll
-                for (int q = 0; q < kTrainQ; ++q) {
-                    const int i = base + q * T + tid;
-                    if (i < N) {
-                        __hip_atomic_store(&gh[i], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double h = (double)(f.mblocks + 1) * 1.0e-10 + v[q];
-                        hl[i] = h;
-                        if (!isfinite(h)) hbad |= ST_HIST_NONFINITE;      // variable.jl:212
-                        else if (!(h > 0.0)) hbad |= ST_HIST_NONPOSITIVE; // variable.jl:213 / common.jl:71
-                    }
-                }
-            }
-            if (hbad) atomicOr(bad, hbad);
-            sweep_strat_round_trip(); // (hl, the verdict, d; the zeroed row is out before the next iteration adds to it)
+            sweep_take_hist(m.ghist + L.boff, hl, N, tid, (double)(fs.mblocks + 1) * 1.0e-10, bad);
+            sweep_round_trip(); // (hl, the verdict, d; the zeroed row is out before the next iteration adds to it)
             if (train) train_leaf(L, hl, nullptr, sm, ps, *bad, flags[1], gcur - L.eoff, f.t.dacc, f.t.ddist, 0, m.status, false, nullptr, true);
             __syncthreads();
         }

@@ -718,13 +718,17 @@ class Engine:
         return _lib.IntegrateArgs(_lib.SOLVERS[solver], int(neval), int(niter), int(block), int(ignore), 1 if adapt else 0, float(gamma),
                                   int(measurefreq), int(seed), 0, int(first_iteration), 0.1, None)
 
-    def sweep_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, **kw):
-        """None when integrate_sweep takes this problem with these arguments, else the reason (mci_sweep_supported)"""
+    def _sweep_refusal(self, query, solver, neval, niter, block, measurefreq):
+        """None when the query (mci_sweep_supported | mci_sweep_strat_supported) takes this problem with these arguments, else its reason"""
         a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, 0)
         why = C.create_string_buffer(512)
-        if lib().mci_sweep_supported(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
+        if query(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
             return None
         return why.value.decode() or lib().mci_last_error().decode(errors="replace")
+
+    def sweep_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, **kw):
+        """None when integrate_sweep takes this problem with these arguments, else the reason (mci_sweep_supported)"""
+        return self._sweep_refusal(lib().mci_sweep_supported, solver, neval, niter, block, measurefreq)
 
     SWEEP_MAX_POINTS = 65536   # include/mci.h mci_integrate_sweep
 
@@ -765,51 +769,65 @@ class Engine:
         for every point (common random numbers), or seeds = P of them; maps: None (every point starts from the engine's current map)
         or [P][grid points] starting maps (the layout of grid()).  The engine's own map, packed buffer and logs are not touched.  Raises MCIError naming the
         reason when the problem or the arguments cannot run as a sweep (sweep_supported): nothing else runs in its place."""
+        ud, sd, mi, _ = self._sweep_inputs("integrate_sweep", userdata, seeds, maps)
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
+        return self._sweep_call(lib().mci_integrate_sweep, a, ud.shape[0], niter, (ud, sd, mi), lambda P: ((), {}))
+
+    def _sweep_inputs(self, name, userdata, seeds, maps, before_maps=None):
+        """(userdata [P][nuserdata], seeds [P] | None, maps [P][sweep_map_doubles()] | None) as contiguous arrays, or the ValueError of
+        entry point `name`; before_maps(): what the entry point checks between the seeds and the maps, its value the fourth of the tuple"""
         nud = len(self.integrand.userdata) if hasattr(self.integrand, "userdata") else 0
         ud = np.ascontiguousarray(userdata if userdata is not None else np.zeros((0, nud)), dtype=np.float64)
         if ud.ndim != 2 or ud.shape[1] != nud:
-            raise ValueError("integrate_sweep: userdata must be a 2-D array [points][%d] (one row of the integrand's userdata per point), got shape %s"
-                             % (nud, ud.shape))
+            raise ValueError("%s: userdata must be a 2-D array [points][%d] (one row of the integrand's userdata per point), got shape %s"
+                             % (name, nud, ud.shape))
         P = ud.shape[0]
         if not 1 <= P <= self.SWEEP_MAX_POINTS:
-            raise ValueError("integrate_sweep: %d points; a sweep takes 1 to %d" % (P, self.SWEEP_MAX_POINTS))
+            raise ValueError("%s: %d points; a sweep takes 1 to %d" % (name, P, self.SWEEP_MAX_POINTS))
         sd = None
         if seeds is not None:
             sd = np.ascontiguousarray(seeds, dtype=np.uint64)
             if sd.shape != (P,):
-                raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got shape %s" % (P, sd.shape))
+                raise ValueError("%s: seeds must hold one seed per point (%d), got shape %s" % (name, P, sd.shape))
+        between = before_maps() if before_maps else None
         nmap = self.sweep_map_doubles()
         mi = None
         if maps is not None:
             mi = np.ascontiguousarray(maps, dtype=np.float64)
             if mi.shape != (P, nmap):
-                raise ValueError("integrate_sweep: maps must be [points = %d][grid points = %d], got shape %s" % (P, nmap, mi.shape))
-        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
-        n = self.nobs
+                raise ValueError("%s: maps must be [points = %d][grid points = %d], got shape %s" % (name, P, nmap, mi.shape))
+        return ud, sd, mi, between
+
+    def _sweep_call(self, fn, a, P, niter, arrays, extra):
+        """fn (mci_integrate_sweep | mci_integrate_sweep_strat) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
+        entry point's own arguments between maps_out and results, and the keys they add to every dict ({key: [P][...] array})"""
+        ud, sd, mi = arrays
+        n, nmap = self.nobs, self.sweep_map_doubles()
         im, ie = np.zeros((P, niter, n)), np.zeros((P, niter, n))
         m, s, c2 = np.zeros((P, n)), np.zeros((P, n)), np.zeros((P, n))
         vis = np.zeros((P, self.config.N + 1))
         mo = np.zeros((P, max(nmap, 1)))
+        own, keys = extra(P)
         st = np.zeros(P, dtype=np.int32)
         res = (_lib.ResultC * P)()
         for q in range(P):
             res[q] = _lib.ResultC(niter, n, None, None, _dp(m[q]), _dp(s[q]), _dp(c2[q]), 0, 0.0, _dp(vis[q]), 0, 0)
-        check(lib().mci_integrate_sweep(self.p, C.byref(a), P, _dp(ud) if ud.size else None,
-                                        sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
-                                        _dp(mi) if mi is not None else None, _dp(mo), res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
-        return [dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
+        check(fn(self.p, C.byref(a), P, _dp(ud) if ud.size else None, sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
+                 _dp(mi) if mi is not None else None, _dp(mo), *own, res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
+        out = []
+        for q in range(P):
+            r = dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
                      visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
                      maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]))
-                for q in range(P)]
+            for k, v in keys.items():
+                r[k] = v[q]
+            out.append(r)
+        return out
 
     def sweep_strat_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, **kw):
         """None when integrate_sweep_strat takes this (stratified) problem with these arguments, else the reason
         (mci_sweep_strat_supported)"""
-        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, 0)
-        why = C.create_string_buffer(512)
-        if lib().mci_sweep_strat_supported(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
-            return None
-        return why.value.decode() or lib().mci_last_error().decode(errors="replace")
+        return self._sweep_refusal(lib().mci_sweep_strat_supported, solver, neval, niter, block, measurefreq)
 
     def sweep_strat_plan(self, neval=10000, block=16):
         """{nstrat, ncube, beta} of the plan a stratified sweep of these arguments runs on: the nstrat set_stratification was given, or
@@ -838,52 +856,23 @@ class Engine:
         iteration used).  d: None (every point starts from a uniform allocation) or [P][ncube] d_h measured on exactly this plan and
         beta -- e.g. the strat_d of an earlier sweep; with adapt=False the allocation made from it stays for the whole call.  The
         engine's own map, logs and allocation are not touched.  Raises MCIError with the reason of sweep_strat_supported()."""
-        nud = len(self.integrand.userdata) if hasattr(self.integrand, "userdata") else 0
-        ud = np.ascontiguousarray(userdata if userdata is not None else np.zeros((0, nud)), dtype=np.float64)
-        if ud.ndim != 2 or ud.shape[1] != nud:
-            raise ValueError("integrate_sweep_strat: userdata must be a 2-D array [points][%d] (one row of the integrand's userdata per point), got shape %s"
-                             % (nud, ud.shape))
+        def plan():
+            a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
+            nc = C.c_int64()
+            check(lib().mci_sweep_strat_doubles(self.p, C.byref(a), C.byref(nc)))
+            return a, int(nc.value)
+        ud, sd, mi, (a, ncube) = self._sweep_inputs("integrate_sweep_strat", userdata, seeds, maps, before_maps=plan)
         P = ud.shape[0]
-        if not 1 <= P <= self.SWEEP_MAX_POINTS:
-            raise ValueError("integrate_sweep_strat: %d points; a sweep takes 1 to %d" % (P, self.SWEEP_MAX_POINTS))
-        sd = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(seeds, dtype=np.uint64)
-            if sd.shape != (P,):
-                raise ValueError("integrate_sweep_strat: seeds must hold one seed per point (%d), got shape %s" % (P, sd.shape))
-        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
-        nc = C.c_int64()
-        check(lib().mci_sweep_strat_doubles(self.p, C.byref(a), C.byref(nc)))
-        ncube = int(nc.value)
-        nmap = self.sweep_map_doubles()
-        mi = None
-        if maps is not None:
-            mi = np.ascontiguousarray(maps, dtype=np.float64)
-            if mi.shape != (P, nmap):
-                raise ValueError("integrate_sweep_strat: maps must be [points = %d][grid points = %d], got shape %s" % (P, nmap, mi.shape))
         di = None
         if d is not None:
             di = np.ascontiguousarray(d, dtype=np.float64)
             if di.shape != (P, ncube):
                 raise ValueError("integrate_sweep_strat: d must be [points = %d][hypercubes = %d], got shape %s" % (P, ncube, di.shape))
-        n = self.nobs
-        im, ie = np.zeros((P, niter, n)), np.zeros((P, niter, n))
-        m, s, c2 = np.zeros((P, n)), np.zeros((P, n)), np.zeros((P, n))
-        vis = np.zeros((P, self.config.N + 1))
-        mo = np.zeros((P, max(nmap, 1)))
-        do, co = np.zeros((P, ncube)), np.zeros((P, ncube), dtype=np.int64)
-        st = np.zeros(P, dtype=np.int32)
-        res = (_lib.ResultC * P)()
-        for q in range(P):
-            res[q] = _lib.ResultC(niter, n, None, None, _dp(m[q]), _dp(s[q]), _dp(c2[q]), 0, 0.0, _dp(vis[q]), 0, 0)
-        check(lib().mci_integrate_sweep_strat(self.p, C.byref(a), P, _dp(ud) if ud.size else None,
-                                              sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
-                                              _dp(mi) if mi is not None else None, _dp(mo), _dp(di) if di is not None else None, _dp(do),
-                                              co.ctypes.data_as(C.POINTER(C.c_int64)), res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
-        return [dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
-                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
-                     maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]), strat_d=do[q], strat_counts=co[q])
-                for q in range(P)]
+
+        def extra(P):
+            do, co = np.zeros((P, ncube)), np.zeros((P, ncube), dtype=np.int64)
+            return (_dp(di) if di is not None else None, _dp(do), co.ctypes.data_as(C.POINTER(C.c_int64))), dict(strat_d=do, strat_counts=co)
+        return self._sweep_call(lib().mci_integrate_sweep_strat, a, P, niter, (ud, sd, mi), extra)
 
     def sweep_workgroups(self, g=0):
         """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""
