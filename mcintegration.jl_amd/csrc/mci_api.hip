@@ -1,5 +1,5 @@
 // mci_api.hip -- host core of libmci_hip.so: the C ABI of include/mci.h.  One translation unit; its sections live in the
-// mci_host_*.h files included at the bottom, in this order: types, ctx, problem, jit, strat, check, iteration, integrate, sweep, access, statistics.
+// mci_host_*.h files included at the bottom, in this order: vegas_plan, types, ctx, problem, jit, strat, check, iteration, integrate, sweep, access, statistics.
 //
 // Owns: the Configuration analogue (src/configuration.jl:105-194), the device-resident state (grids,
 // distributions, histograms, packed statistics), the per-iteration launch chain
@@ -18,6 +18,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <string>
 #include <atomic>
@@ -58,6 +59,7 @@ int fail(int code, const char *fmt, ...) {
 
 } // namespace
 
+#include "mci_host_vegas_plan.h"
 #include "mci_host_types.h"
 
 extern "C" {

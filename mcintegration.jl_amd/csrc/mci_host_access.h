@@ -313,7 +313,7 @@ static int sample_dump_device(mci_problem *p, int32_t iteration, uint64_t seed, 
     a.n = n;
     void *args[] = {&a};
     const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    HIPCHK(hipModuleLaunchKernel(p->f_dump, grid, 1, 1, 256, 1, 1, (unsigned)p->lds_bytes, p->ctx->stream, args, nullptr));
+    HIPCHK(hipModuleLaunchKernel(p->kernel[kSlotDump].f, grid, 1, 1, 256, 1, 1, (unsigned)p->lds_bytes, p->ctx->stream, args, nullptr));
     return MCI_OK;
 }
 

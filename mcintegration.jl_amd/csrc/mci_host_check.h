@@ -67,25 +67,13 @@ static int sample_dump_device(mci_problem *p, int32_t iteration, uint64_t seed, 
 // one histogram copy, the default workgroup size -- what the table_mode / hist_copies overrides and MCI_VEGAS_PLAIN_LOOP select.  The
 // deterministic mode keeps its copy per wave (that is what makes it deterministic) and loses the pipelined loop only.  `slot` is compiled
 // at once, the other cadence variant when a launch next needs it; the persistent launch (its own, pipelined unit) is no longer taken
-// (mci_host_integrate.h persist_plan looks at vegas_conservative).
+// (mci_host_integrate.h persist_plan looks at vegas.conservative).
 static int vegas_make_conservative(mci_problem *p, int slot) {
-    p->vegas_conservative = true;
-    if (!p->deterministic) {
-        p->shape.hcopy = 1;
-        p->hcopy_auto = 1;
-        p->hcopy_plan = false;
-        p->threads_vegas = 0;
-        p->vegas_keys = p->vegas_wide = false;
-    }
-    const int both[2] = {MCI_VEGAS, kSlotVegasAny};
-    for (int k : both) {
-        p->compiled[k] = false;
-        p->vegas_check_done[k == kSlotVegasAny ? 1 : 0] = false;
-        if (p->module[k]) {
-            (void)hipModuleUnload(p->module[k]);
-            p->module[k] = nullptr;
-        }
-    }
+    p->vegas.make_conservative(p->deterministic);
+    if (!p->deterministic) p->shape.hcopy = 1;
+    p->kernel[MCI_VEGAS].drop();
+    p->kernel[kSlotVegasAny].drop();
+    p->vegas_check_done[0] = p->vegas_check_done[1] = false;
     return compile_solver(p, slot);
 }
 
@@ -230,7 +218,7 @@ static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int
         PackedDiff df;
         int64_t bad[2] = {0, 0};
         bool differs = false;
-        const std::string object = p->code_object[slot];
+        const std::string object = p->kernel[slot].code_object;
         rc = vegas_check_round(p, slot, npb, block_lo, nb, iteration, seed, mf, &df, bad, &differs);
         if (rc) break;
         if (!differs) {
@@ -270,7 +258,7 @@ static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int
         // works without it -- one note, nothing verified.  (A conservative unit that did not compile has left its slot empty:
         // mci_iteration_run compiles the slot again behind the gate and reports that error itself.)
         fprintf(stderr, "mci: the self-check of this problem's :vegas code object (%s) could not run: %s -- nothing was verified "
-                        "(mci_vegas_check_status stays %d)\n", p->code_object[slot].c_str(), mci_last_error(), state == -2 ? -2 : 0);
+                        "(mci_vegas_check_status stays %d)\n", p->kernel[slot].code_object.c_str(), mci_last_error(), state == -2 ? -2 : 0);
         p->merge_pending = false;
         if (state == -2) p->vegas_check_state[u] = -2;
         return MCI_OK;
@@ -289,7 +277,7 @@ static int vegas_check_gate(mci_problem *p, int slot, int64_t nevalperblock, int
         p->vegas_check_done[u] = true;
         return MCI_OK;
     }
-    if (!force && access((p->code_object[slot] + ".ok").c_str(), F_OK) == 0) {
+    if (!force && access((p->kernel[slot].code_object + ".ok").c_str(), F_OK) == 0) {
         if (p->vegas_check_state[u] == 0) {
             p->vegas_check_state[u] = 1;
             p->vegas_check_flags |= 2;

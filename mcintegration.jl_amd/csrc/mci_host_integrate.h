@@ -31,7 +31,7 @@ bool persist_layout(const mci_problem *p) {
 // histogram copies and 512-thread workgroups, which this kernel's plain 256-thread layout does not match).
 bool persist_plan(const mci_problem *p, const mci_integrate_args *a, int64_t nevalperblock, int64_t nblocks, int *wpb_out) {
     const auto &s = p->shape;
-    if (p->persistent == 0 || p->persist_failed || p->vegas_conservative) return false; // (conservative: the persistent unit is a pipelined one)
+    if (p->persistent == 0 || p->persist_failed || p->vegas.conservative) return false; // (conservative: the persistent unit is a pipelined one)
     if (a->solver != MCI_VEGAS || a->measurefreq != 1 || a->niter < 1) return false;
     if (p->ctx->nranks != 1) return false; // (a one-rank communicator's all-reduce is the identity)
     if (!persist_layout(p)) return false;
@@ -91,10 +91,11 @@ static void persist_job_drop(mci_problem *p) {
     std::lock_guard<std::mutex> g(g_orphan_mu);
     g_orphans.push_back(j);
 }
-// MCI_OK with p->persist_compiled set: the kernel is loaded.  MCI_OK without: not yet (background == true and the code object is
+// MCI_OK with the unit's `compiled` set: the kernel is loaded.  MCI_OK without: not yet (background == true and the code object is
 // still being compiled) -- the caller takes the launch chain this time.
 static int compile_persist(mci_problem *p, bool background) {
-    if (p->persist_compiled) return MCI_OK;
+    KernelUnit &u = p->kernel[mci_problem::kPersist];
+    if (u.compiled) return MCI_OK;
     Candidate local, *c = &local;
     if (p->persist_job) {
         if (!p->persist_job->done.load(std::memory_order_acquire)) {
@@ -109,12 +110,12 @@ static int compile_persist(mci_problem *p, bool background) {
         mcijit::ProblemShape sh = p->shape;
         sh.hcopy = 1;
         sh.det = 0;
+        c->unit = mcijit::kUnitVegasPersist;
         c->src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitVegasPersist, p->leaves[0].alpha);
         // (512 threads for the hand-pipelined loops of 8..16 draws -- what the launch chain runs them at -- was tried: 22.5 instead of 18.3 us
         // per iteration of the 16-D Gaussian at neval = 1e4, against 15.8 as a launch chain; the automatic rule stops at 7 draws)
         c->threads = p->threads;
-        c->rc = mcijit::compile(c->src, c->threads, c->code, c->log, c->cached, &c->path, mcijit::kUnitVegasPersist, /*cache_only=*/background);
-        if (c->rc == -1) { // not in the kernel cache: compile it behind the caller's back ...
+        if (c->build(/*cache_only=*/background) == -1) { // not in the kernel cache: compile it behind the caller's back ...
             // ... once this process has made kPersistAfterCalls launch-bound calls of this kernel (by this problem or others with the same
             // shape and integrand): the persistent launch saves ~40 us per default-size call and its translation unit costs 0.8 s of hiprtc
             // -- on a thread of its own, but comgr serialises compiles, so another new kernel compiled meanwhile queues behind it (measured:
@@ -131,7 +132,7 @@ static int compile_persist(mci_problem *p, bool background) {
             p->persist_job->c = std::move(local);
             mci_problem::PersistJob *j = p->persist_job;
             j->th = std::thread([j] {
-                j->c.rc = mcijit::compile(j->c.src, j->c.threads, j->c.code, j->c.log, j->c.cached, &j->c.path, mcijit::kUnitVegasPersist);
+                j->c.build();
                 j->done.store(true, std::memory_order_release);
             });
             return MCI_OK;
@@ -139,32 +140,20 @@ static int compile_persist(mci_problem *p, bool background) {
     }
     if (c->rc) {
         p->persist_failed = true; // (the launch chain's own compile reports what is wrong with the integrand)
-        return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c->log.c_str());
+        return c->failed();
     }
-    if (mcijit::max_static_lds_bytes(c->code) != 0 || mcijit::kernel_scratch_bytes(c->code, "mci_vegas_persist") != 0) {
-        p->persist_failed = true; // (not an error of the call: it takes the launch chain)
-        return fail(MCI_ERR_COMPILE, "the persistent :vegas kernel came out with static LDS or scratch");
-    }
-    p->persist_code_object = c->path;
-    p->persist_threads = c->threads;
-    if (p->ctx->offline) {
-        p->persist_compiled = true;
-        return MCI_OK;
-    }
-    HIPCHK(hipSetDevice(p->ctx->device));
-    if (hipModuleLoadData(&p->module_persist, c->code.data()) != hipSuccess) {
-        p->persist_failed = true;
-        if (c->cached) unlink(c->path.c_str()); // a cached code object that does not load (truncated by a crash, foreign file)
-        return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the persistent :vegas code object");
-    }
-    HIPCHK(hipModuleGetFunction(&p->f_persist, p->module_persist, "mci_vegas_persist"));
-    if (!p->d_persist) {
+    if (!p->ctx->offline && !p->d_persist) {
+        HIPCHK(hipSetDevice(p->ctx->device));
         if (int rc = p->d_persist.reserve((int64_t)kPersistWords)) return rc;
         HIPCHK(hipMemsetAsync(p->d_persist, 0, kPersistWords * sizeof(unsigned long long), p->ctx->stream));
         p->persist_arrive = p->persist_done = 0;
     }
-    p->persist_compiled = true;
-    return MCI_OK;
+    // (a refusal is not an error of the call: it takes the launch chain; its LDS stays below the limit that needs raising)
+    static const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true, "the persistent :vegas kernel came out with static LDS or scratch",
+                                            "the persistent :vegas code object"};
+    const int rc = u.load(p->ctx, *c, mcijit::kUnits[c->unit].kernel, 0, rules);
+    if (rc) p->persist_failed = true;
+    return rc;
 }
 
 // queue the one launch that runs iterations first_iteration .. first_iteration + niter - 1 over blocks [lo, hi)
@@ -176,7 +165,7 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     HIPCHK(hipSetDevice(p->ctx->device));
     if ((rc = ensure_capacity(p, 2 * nrows, nblocks))) return rc; // (the partial rows are double-buffered by the turn's parity)
     if ((rc = grow_iteration_log(p, (int64_t)p->log_row + ia->niter))) return rc;
-    const int T = p->persist_threads;
+    const int T = p->kernel[mci_problem::kPersist].threads;
     mci::BatchArgs a{};
     fill_batch(p, a);
     a.seed = ia->seed;
@@ -219,7 +208,7 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     if ((rc = p->d_edges_backup.reserve(p->h_edges.size() ? (int64_t)p->h_edges.size() : 1))) return rc;
     if (p->h_edges.size()) HIPCHK(hipMemcpyAsync(p->d_edges_backup, p->d_edges, p->h_edges.size() * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
     // nrows sampling workgroups + the statistics workgroup
-    HIPCHK(hipModuleLaunchKernel(p->f_persist, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
+    HIPCHK(hipModuleLaunchKernel(p->kernel[mci_problem::kPersist].f, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
     p->persist_arrive += (unsigned long long)(ia->niter + 1) * (unsigned long long)nrows; // (+ one "finished reading" per workgroup at the end)
     p->persist_done += (unsigned long long)ia->niter;
     p->launch.time_this_launch = false;
@@ -273,7 +262,7 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     // (automatic mode: a code object that is not in the kernel cache yet is compiled on a thread of its own, and until it is there the
     // calls go through the launch chain -- a new integrand's first call costs what it did, 0.2 s, not the 0.8 s of the larger unit)
     if (persist) (void)compile_persist(p, p->persistent < 0);
-    persist = persist && p->persist_compiled;
+    persist = persist && p->kernel[mci_problem::kPersist].compiled;
     if (!persist && !strat && (rc = compile_solver(p, kslot(a->solver, a->measurefreq)))) return rc;
     if ((rc = mci_set_reweight_goal(p, a->reweight_goal, a->reweight_goal ? p->ni + 1 : 0))) return rc;
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);

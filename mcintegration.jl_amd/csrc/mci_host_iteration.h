@@ -196,7 +196,7 @@ static int prepare_host_integrand(mci_problem *p, const LaunchRequest &rq, const
     void *dargs[] = {&d};
     const unsigned dgrid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipStream_t hs = p->ctx->stream;
-    HIPCHK(hipModuleLaunchKernel(p->f_dump, dgrid, 1, 1, 256, 1, 1, (unsigned)p->lds_bytes, hs, dargs, nullptr));
+    HIPCHK(hipModuleLaunchKernel(p->kernel[kSlotDump].f, dgrid, 1, 1, 256, 1, 1, (unsigned)p->lds_bytes, hs, dargs, nullptr));
     HIPCHK(hipMemcpyAsync(p->h_hx, p->d_hx, (size_t)n * s.ndraw * sizeof(double), hipMemcpyDeviceToHost, hs));
     HIPCHK(hipStreamSynchronize(hs));
     if ((rc = eval_host_integrand(p, nullptr, p->h_hx, p->h_hw, n))) return rc;
@@ -564,7 +564,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     if (s.host_measure && (rc = prepare_host_measure(p, rq, pl, a))) return rc;
     if (pl.cursor && (rc = prepare_cursor(p, rq, pl, a))) return rc;
     p->launch.last_cursor = pl.cursor;
-    hipFunction_t f = p->f_solver[pl.G > 1 ? (rq.solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec) : rq.kern];
+    hipFunction_t f = p->kernel[pl.G > 1 ? (rq.solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec) : rq.kern].f;
     hipStream_t st = p->ctx->stream;
     const int slot = (int)(p->launch.launches % mci_problem::kEvRing);
     p->launch.time_this_launch = pl.time_this_launch;

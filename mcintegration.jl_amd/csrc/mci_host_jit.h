@@ -12,89 +12,124 @@ namespace {
 struct Candidate { // one hiprtc job
     std::string src;
     int threads = 256;
+    int unit = mcijit::kUnitSolver;
     std::vector<char> code;
     std::string log, path;
     bool cached = false;
     int rc = 0;
     long vgprs() const { return mcijit::kernel_vgprs(code, "mci_vegas_batch"); }
     long scratch() const { return mcijit::kernel_scratch_bytes(code, "mci_vegas_batch"); }
+    int build(bool cache_only = false) { return rc = mcijit::compile(src, threads, code, log, cached, &path, unit, cache_only); }
+    // the message of a candidate that did not compile; `of`: which kernel, for the units that say so (" (stratified :vegas kernel)")
+    int failed(const std::string &of = "") const { return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950%s:\n%s", of.c_str(), log.c_str()); }
 };
 // the candidates of a plan are independent translation units: compiled side by side (hiprtc is re-entrant), so a plan that has to
 // look at two or three of them before it knows which one runs costs the latency of the slowest, not their sum
-void compile_all(std::vector<Candidate *> &cs) {
+void compile_all(const std::vector<Candidate *> &cs) {
     std::vector<std::thread> th;
-    for (size_t i = 1; i < cs.size(); ++i)
-        th.emplace_back([c = cs[i]] { c->rc = mcijit::compile(c->src, c->threads, c->code, c->log, c->cached, &c->path); });
-    if (!cs.empty()) cs[0]->rc = mcijit::compile(cs[0]->src, cs[0]->threads, cs[0]->code, cs[0]->log, cs[0]->cached, &cs[0]->path);
+    for (size_t i = 1; i < cs.size(); ++i) th.emplace_back([c = cs[i]] { c->build(); });
+    if (!cs.empty()) cs[0]->build();
     for (auto &t : th) t.join();
+}
+
+int KernelUnit::load(const mci_ctx *ctx, Candidate &c, const char *kernel, int64_t lds, const Rules &rules) {
+    const long static_lds = mcijit::max_static_lds_bytes(c.code);
+    if (static_lds != 0 || (rules.no_scratch && mcijit::kernel_scratch_bytes(c.code, kernel) != 0)) {
+        if (!rules.refusal.empty()) return fail(MCI_ERR_COMPILE, "%s", rules.refusal.c_str());
+        // (mci_device.h draw_leaf: the pair table is addressed from LDS address 0)
+        return fail(MCI_ERR_COMPILE, "the code object declares static LDS (%ld bytes): the sample kernels expect their dynamic segment at LDS address 0", static_lds);
+    }
+    code_object = c.path;
+    threads = c.threads;
+    if (!ctx->offline) {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (rules.stale == kFail) HIPCHK(hipModuleLoadData(&module, c.code.data()));
+        else if (hipModuleLoadData(&module, c.code.data()) != hipSuccess) {
+            if (c.cached) unlink(c.path.c_str());
+            if (!c.cached || rules.stale == kUnlinkAndFail) return fail(MCI_ERR_HIP, "hipModuleLoadData failed for %s", rules.what.c_str());
+            if (c.build()) return c.failed(); // (compiled afresh, once)
+            HIPCHK(hipModuleLoadData(&module, c.code.data()));
+        }
+        if (int rc = entry(&f, kernel, lds)) return rc;
+    }
+    compiled = true;
+    return MCI_OK;
 }
 } // namespace
 
+static const KernelUnit::Rules kSlotRules = {KernelUnit::kRecompileOnce, false, "", "a freshly compiled code object"};
+// The main kernel of a JIT unit: its row of mcijit::kUnits -- or, for the rows that leave it open, what generate_source calls the
+// solver's kernel in such a unit.
+static const char *unit_kernel(int unit, int solver) {
+    if (const char *k = mcijit::kUnits[unit].kernel) return k;
+    if (unit == mcijit::kUnitDump) return "mci_sample_dump";
+    if (unit == mcijit::kUnitSpec) return solver == MCI_VEGASMC ? "mci_vegasmc_spec" : "mci_mcmc_spec";
+    return solver == MCI_VEGAS ? "mci_vegas_batch" : solver == MCI_VEGASMC ? "mci_vegasmc_chains" : "mci_mcmc_chains";
+}
+// a slot's code object, and the second entry points of the same module
 static int load_slot(mci_problem *p, int slot, Candidate &c, int64_t lds) {
-    if (mcijit::max_static_lds_bytes(c.code) != 0) // (mci_device.h draw_leaf: the pair table is addressed from LDS address 0)
-        return fail(MCI_ERR_COMPILE, "the code object declares static LDS (%ld bytes): the sample kernels expect their dynamic segment at LDS address 0",
-                    mcijit::max_static_lds_bytes(c.code));
-    p->code_object[slot] = c.path;
+    KernelUnit &u = p->kernel[slot];
+    if (int rc = u.load(p->ctx, c, unit_kernel(c.unit, slot_solver(slot)), lds, kSlotRules)) return rc;
     if (p->ctx->offline) return MCI_OK;
-    static const char *const names[mci_problem::kSlots] = {"mci_vegas_batch", "mci_vegasmc_chains", "mci_mcmc_chains", "mci_vegas_batch", "mci_sample_dump",
-                                                            "mci_vegasmc_spec", "mci_mcmc_spec"};
-    HIPCHK(hipSetDevice(p->ctx->device));
-    if (hipModuleLoadData(&p->module[slot], c.code.data()) != hipSuccess) {
-        // a cached code object that does not load (truncated by a crash, foreign file): drop it and compile afresh, once
-        if (!c.cached) return fail(MCI_ERR_HIP, "hipModuleLoadData failed for a freshly compiled code object");
-        unlink(c.path.c_str());
-        if (mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path)) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c.log.c_str());
-        HIPCHK(hipModuleLoadData(&p->module[slot], c.code.data()));
-    }
-    HIPCHK(hipModuleGetFunction(&p->f_solver[slot], p->module[slot], names[slot]));
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)p->f_solver[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (slot == MCI_VEGASMC || slot == kSlotVegasmcSpec) {
-        hipFunction_t &fw = p->f_carryw[slot == MCI_VEGASMC ? 0 : 1];
-        HIPCHK(hipModuleGetFunction(&fw, p->module[slot], "mci_vegasmc_carry_weights"));
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)fw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    if (slot_solver(slot) == MCI_VEGAS && slot != kSlotDump && p->shape.ntile > 1) {
-        HIPCHK(hipModuleGetFunction(&p->f_tiles[slot == kSlotVegasAny ? 1 : 0], p->module[slot], "mci_vegas_tiles"));
-        if (p->lds_bytes > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)p->f_tiles[slot == kSlotVegasAny ? 1 : 0], hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
-    }
+    if (slot == MCI_VEGASMC || slot == kSlotVegasmcSpec)
+        if (int rc = u.entry(&p->f_carryw[slot == MCI_VEGASMC ? 0 : 1], "mci_vegasmc_carry_weights", lds)) return rc;
+    if (slot_solver(slot) == MCI_VEGAS && slot != kSlotDump && p->shape.ntile > 1)
+        if (int rc = u.entry(&p->f_tiles[slot == kSlotVegasAny ? 1 : 0], "mci_vegas_tiles", p->lds_bytes)) return rc;
     return MCI_OK;
 }
 
 // the map + integrand alone (mci_sample_dump, host integrands): its own small code object
 static int ensure_dump(mci_problem *p) {
-    if (p->compiled[kSlotDump]) return MCI_OK;
+    if (p->kernel[kSlotDump].compiled) return MCI_OK;
     Candidate c;
     mcijit::ProblemShape sh = p->shape;
     sh.hcopy = 1;
     sh.det = 0;
+    c.unit = mcijit::kUnitDump;
     c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitDump);
     c.threads = 256;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c.log.c_str());
-    int rc = load_slot(p, kSlotDump, c, p->lds_bytes);
-    if (rc) return rc;
-    p->f_dump = p->f_solver[kSlotDump];
-    p->compiled[kSlotDump] = true;
+    if (c.build()) return c.failed();
+    return load_slot(p, kSlotDump, c, p->lds_bytes);
+}
+
+// vegas/montecarlo.jl:104, mcmc/montecarlo.jl:84
+static int default_measure_fits(const mci_problem *p) {
+    for (int i = 0; i < p->ni && p->shape.measure_body.empty() && !p->shape.host_measure; ++i)
+        if (p->shape.obs_bin_draw[i] < 0 && p->shape.obs_nbin[i] != p->shape.ncomp)
+            return fail(MCI_ERR_INVALID, "the default measure can only handle observable as Vector with %d scalar elements!", p->ni);
     return MCI_OK;
 }
 
 // prefix of a :vegas unit in the conservative layout: no hand-pipelined sample loop (mci_device.h pipe_eligible)
 static const char *const kVegasPlainLoop = "#define MCI_VEGAS_PLAIN_LOOP 1\n";
+static const char *const kVgprKeys = "#define MCI_PIPE_VGPR_KEYS 1\n";
+// The driver of every solver slot: one candidate for the chain solvers and the deterministic mode; for :vegas the candidates
+// vegas_kernel_rule (mci_host_vegas_plan.h) asks for, batch by batch, and of those the one it chose.
 static int compile_solver(mci_problem *p, int slot) {
     if (slot < 0 || slot > kSlotVegasAny) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", slot); // main.jl:263
-    if (p->compiled[slot]) return MCI_OK;
+    if (p->kernel[slot].compiled) return MCI_OK;
     const int solver = slot_solver(slot);
     const int unit = slot == MCI_VEGAS ? mcijit::kUnitVegasMf1 : mcijit::kUnitSolver;
     // (a problem whose :vegas unit failed its self-check, mci_host_check.h: EVERY :vegas unit it compiles from then on -- either cadence,
     // planned or planned again after drop_modules -- is the plain loop)
-    auto gen = [&](const mcijit::ProblemShape &sh) {
-        return std::string(p->vegas_conservative && solver == MCI_VEGAS ? kVegasPlainLoop : "") + mcijit::generate_source(sh, solver, unit);
+    auto gen = [&](const mcijit::ProblemShape &sh, bool keys = false) {
+        return std::string(keys ? kVgprKeys : "") + (p->vegas.conservative && solver == MCI_VEGAS ? kVegasPlainLoop : "") + mcijit::generate_source(sh, solver, unit);
     };
-    if (p->shape.measure_body.empty() && !p->shape.host_measure) // vegas/montecarlo.jl:104, mcmc/montecarlo.jl:84
-        for (int i = 0; i < p->ni; ++i)
-            if (p->shape.obs_bin_draw[i] < 0 && p->shape.obs_nbin[i] != p->shape.ncomp)
-                return fail(MCI_ERR_INVALID, "the default measure can only handle observable as Vector with %d scalar elements!", p->ni);
+    if (int rc = default_measure_fits(p)) return rc;
+    struct Built { VegasVariant v; Candidate c; };
+    std::deque<Built> built; // (every candidate of the call, in the order it was asked for)
+    auto add = [&](const VegasVariant &v) {
+        built.push_back({v, {}});
+        Candidate &c = built.back().c;
+        mcijit::ProblemShape sh = p->shape;
+        sh.hcopy = v.copies;
+        c.unit = unit;
+        c.src = gen(sh, v.keys);
+        c.threads = v.threads;
+        return &c;
+    };
+    Candidate *chosen = nullptr;
+    int64_t lds = p->lds_bytes;
     if (p->deterministic) {
         // one copy of the LDS histograms (and observables) per wave, as many waves as fit: 512 / 256 / 128 / 64 threads
         if (p->shape.ntile > 1 || p->shape.table_mode == 1 || p->shape.table_mode == 2 || p->shape.ec_doubles > 0)
@@ -106,167 +141,65 @@ static int compile_solver(mci_problem *p, int slot) {
         p->threads_det[solver] = T;
         p->shape.det = 1;
         p->shape.hcopy = T / 64;
-        Candidate c;
-        c.src = gen(p->shape);
-        c.threads = T;
-        c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path);
-        if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c.log.c_str());
-        if (int rc = load_slot(p, slot, c, det_lds(p, T))) return rc;
-        p->compiled[slot] = true;
-        return MCI_OK;
-    }
-    p->shape.det = 0;
-    static const char *const kVgprKeys = "#define MCI_PIPE_VGPR_KEYS 1\n";
-    Candidate chosen;
-    if (solver != MCI_VEGAS) {
-        chosen.src = gen(p->shape);
-        chosen.threads = p->threads;
-        chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-        if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-    } else if (p->vegas_planned) {
-        // the other measurefreq variant of a kernel whose plan (workgroup size, histogram copies, round keys) stands
-        chosen.src = (p->vegas_keys ? std::string(kVgprKeys) : std::string()) + gen(p->shape);
-        chosen.threads = p->threads_vegas ? p->threads_vegas : p->vegas_wide ? 512 : p->threads;
-        chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-        if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-        if (p->vegas_keys && (chosen.vgprs() > 128 || chosen.scratch() != 0)) { // (this variant carries a few registers more)
-            chosen.src = gen(p->shape);
-            chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-            if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-        }
-        if (!p->threads_vegas && p->vegas_wide && (chosen.vgprs() > 128 || chosen.scratch() != 0)) {
-            // (the 512-thread launch bound of a light integrand's plain layout was checked on the FIRST variant only: this one does not
-            // fit it -- both variants run 256-thread workgroups from here on, which the first one's code object allows)
-            p->vegas_wide = false;
-            chosen.threads = p->threads;
-            chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-            if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-        }
+        lds = det_lds(p, T);
+    } else p->shape.det = 0;
+    if (p->deterministic || solver != MCI_VEGAS) {
+        chosen = add({p->shape.hcopy, false, p->deterministic ? p->threads_det[solver] : p->threads});
+        if (chosen->build()) return chosen->failed();
     } else {
-        const bool hcopy_plan = p->hcopy_plan && !g_over.hist_copies.on && !p->vegas_conservative;
-        int tcopy = 512;
-        p->shape.hcopy = planned_hcopy(p, &tcopy);
-        if (p->hcopy_plan) p->threads_vegas = tcopy;
-        const int T0 = p->threads_vegas ? p->threads_vegas : p->threads;
-        // (light integrands: a launch bound of 512 threads costs the plain layout nothing -- see vegas_wide; anything that would need scratch
-        // or more than 128 registers under it is compiled for the default size instead)
-        const bool try_wide = !p->vegas_conservative && p->threads == 256 && !p->threads_explicit && !p->deterministic && p->shape.ndraw <= 8 && !p->shape.host_integrand;
-        if (hcopy_plan) {
-            // Histogram copies pay when the kernel runs four or five waves per SIMD either way (81..128 VGPRs: two 512-thread workgroups
-            // share a CU).  More registers: two such workgroups no longer fit.  Fewer: the plain layout runs six or more waves per SIMD
-            // in 256-thread workgroups and the 80 KB of copies would cap it at four (C5 :vegas, 78 VGPRs: 1.88 ms per 1e8 samples plain,
-            // 2.21 ms with 8 copies; profiles/r02_ablation.txt).  And up to 128 VGPRs registers are free on the copy plan: the pipelined
-            // sample loop (mci_device.h draw_sample_pipe) asks for its Philox round keys in VGPRs (20 registers; the all-VGPR v_bitop3_b32
-            // issues faster than the form with an SGPR key: C2 1.358 -> 1.331 ms per 1e8 samples) unless that crosses the line.
-            // Candidates, compiled side by side: [copies + VGPR keys], [plain layout]; [copies, SGPR keys] only if the first is too fat.
-            Candidate keys, plain, nokeys;
-            const std::string with_copies = gen(p->shape);
-            keys.src = kVgprKeys + with_copies;
-            keys.threads = nokeys.threads = T0;
-            nokeys.src = with_copies;
-            mcijit::ProblemShape sh = p->shape;
-            sh.hcopy = 1;
-            plain.src = gen(sh);
-            plain.threads = try_wide ? 512 : p->threads;
-            std::vector<Candidate *> both = {&keys, &plain};
-            compile_all(both);
-            if (keys.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", keys.log.c_str());
-            if (plain.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", plain.log.c_str());
-            Candidate *copy = &keys;
-            p->vegas_keys = true;
-            if (keys.vgprs() > 128 || keys.scratch() != 0) {
-                nokeys.rc = mcijit::compile(nokeys.src, nokeys.threads, nokeys.code, nokeys.log, nokeys.cached, &nokeys.path);
-                if (nokeys.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", nokeys.log.c_str());
-                copy = &nokeys;
-                p->vegas_keys = false;
-            }
-            if (copy->vgprs() > 128 || copy->vgprs() <= 80) { // the plain layout
-                p->shape.hcopy = 1;
-                p->threads_vegas = 0;
-                p->vegas_keys = false;
-                p->vegas_wide = try_wide && plain.scratch() == 0 && plain.vgprs() <= 128;
-                if (try_wide && !p->vegas_wide) {
-                    plain.threads = p->threads;
-                    plain.rc = mcijit::compile(plain.src, plain.threads, plain.code, plain.log, plain.cached, &plain.path);
-                    if (plain.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", plain.log.c_str());
-                }
-                chosen = std::move(plain);
-            } else chosen = std::move(*copy);
-        } else if (p->vegas_plan_a) {
-            // many-grid plans (one workgroup per CU owns the LDS): the largest of 1024 / 768 / 512 threads at which the sample pass shows
-            // no scratch -- the rungs compiled side by side
-            Candidate rung[3];
-            const std::string src = gen(p->shape);
-            const int ts[3] = {1024, 768, 512};
-            std::vector<Candidate *> all;
-            for (int i = 0; i < 3; ++i) {
-                rung[i].src = src;
-                rung[i].threads = ts[i];
-                if (ts[i] <= T0) all.push_back(&rung[i]);
-            }
-            compile_all(all);
-            size_t pick = all.size() - 1;
-            for (size_t i = 0; i < all.size(); ++i) {
-                if (all[i]->rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", all[i]->log.c_str());
-                if (all[i]->scratch() == 0) { pick = i; break; }
-            }
-            p->threads_vegas = all[pick]->threads;
-            chosen = std::move(*all[pick]);
-        } else {
-            chosen.src = gen(p->shape);
-            chosen.threads = try_wide ? 512 : T0;
-            chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-            if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-            p->vegas_wide = try_wide && chosen.scratch() == 0 && chosen.vgprs() <= 128;
-            if (try_wide && !p->vegas_wide) {
-                chosen.threads = T0;
-                chosen.rc = mcijit::compile(chosen.src, chosen.threads, chosen.code, chosen.log, chosen.cached, &chosen.path);
-                if (chosen.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", chosen.log.c_str());
-            }
-        }
-        p->vegas_planned = true;
-    }
-    int64_t lds = p->lds_bytes;
-    if (solver == MCI_VEGAS) {
+        const auto &s = p->shape;
+        const VegasRuleIn in = {p->threads, p->threads_explicit, s.ndraw, s.host_integrand != 0, p->deterministic, g_over.hist_copies.on, sixteen_copies_fit(p), s.hcopy};
+        size_t batch = 0; // where the last batch starts
+        auto build = [&](const std::vector<VegasVariant> &vs, std::vector<VegasBuilt> &out) {
+            batch = built.size();
+            std::vector<Candidate *> cs;
+            for (const VegasVariant &v : vs) cs.push_back(add(v));
+            compile_all(cs);
+            out.clear();
+            for (Candidate *c : cs) out.push_back({c->rc ? 0 : c->vgprs(), c->rc ? 0 : c->scratch(), c->rc == 0});
+        };
+        VegasVariant v{};
+        const int rc = vegas_kernel_rule(p->vegas, in, build, &v);
+        p->shape.hcopy = v.copies;
+        for (size_t i = batch; rc && i < built.size(); ++i)
+            if (built[i].c.rc) return built[i].c.failed();
+        for (Built &b : built) // (the last one built of the chosen variant: of the last batch, or the plain layout of the first)
+            if (b.v.copies == v.copies && b.v.keys == v.keys && b.v.threads == v.threads) chosen = &b.c;
         lds = vegas_lds(p);
-        if (p->shape.ec_doubles > 0 && p->lds_bytes_k1 > lds) lds = p->lds_bytes_k1;
+        if (s.ec_doubles > 0 && p->lds_bytes_k1 > lds) lds = p->lds_bytes_k1;
         if (p->lds_bytes > lds) lds = p->lds_bytes;
     }
-    if (int rc = load_slot(p, slot, chosen, lds)) return rc;
-    p->compiled[slot] = true;
-    return MCI_OK;
+    return load_slot(p, slot, *chosen, lds);
 }
 
 // ---- several lanes per chain (mci_spec.h) ---------------------------------------------------------------------------------
 // the chain solver's kernel with a group of lanes per chain: its own code object (slots 5, 6), compiled when a launch first asks for it
 static int compile_spec(mci_problem *p, int solver) {
     const int slot = solver == MCI_VEGASMC ? kSlotVegasmcSpec : kSlotMcmcSpec;
-    if (p->compiled[slot]) return MCI_OK;
-    if (p->shape.measure_body.empty() && !p->shape.host_measure) // vegas/montecarlo.jl:104, mcmc/montecarlo.jl:84
-        for (int i = 0; i < p->ni; ++i)
-            if (p->shape.obs_bin_draw[i] < 0 && p->shape.obs_nbin[i] != p->shape.ncomp)
-                return fail(MCI_ERR_INVALID, "the default measure can only handle observable as Vector with %d scalar elements!", p->ni);
+    if (p->kernel[slot].compiled) return MCI_OK;
+    if (int rc = default_measure_fits(p)) return rc;
     p->shape.det = 0;
     Candidate c, lane;
+    c.unit = mcijit::kUnitSpec;
     c.src = mcijit::generate_source(p->shape, solver, mcijit::kUnitSpec);
     c.threads = 256; // (a launch of few chains runs one wave per SIMD: up to 512 registers per lane)
     // In the cache, with the marker of a passed self-check next to it: nothing else to do.  Otherwise the lane-per-chain unit the check
     // compares it with is compiled NEXT to it (hiprtc is re-entrant): the check costs the slower of the two compilations, not their sum.
-    const bool cached = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitSpec, /*cache_only=*/true) == 0;
+    const bool cached = c.build(/*cache_only=*/true) == 0;
     const bool verified = cached && access((c.path + ".ok").c_str(), F_OK) == 0;
     std::thread side;
-    if (!verified && !p->compiled[solver] && !p->ctx->offline && !(g_over.spec_self_check.on && g_over.spec_self_check.v == 0)) {
+    if (!verified && !p->kernel[solver].compiled && !p->ctx->offline && !(g_over.spec_self_check.on && g_over.spec_self_check.v == 0)) {
         lane.src = mcijit::generate_source(p->shape, solver, mcijit::kUnitSolver);
         lane.threads = p->threads;
-        side = std::thread([&lane] { lane.rc = mcijit::compile(lane.src, lane.threads, lane.code, lane.log, lane.cached, &lane.path); });
+        side = std::thread([&lane] { lane.build(); });
     }
     if (!cached) {
-        c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitSpec);
-        if (c.rc == 2) {
+        if (c.build() == 2) {
             // (the unit is built with a backend switch, mci_jit.h: a compiler that does not know it any more gets the unit without it --
             // the self-check below is what stands between such an object and the user's histogram)
             std::string log2;
             Candidate d;
+            d.unit = c.unit;
             d.src = c.src;
             d.threads = c.threads;
             d.rc = mcijit::compile(d.src, d.threads, d.code, log2, d.cached, &d.path, mcijit::kUnitSpec, false, /*no_exec_mask_flag=*/true);
@@ -277,9 +210,8 @@ static int compile_spec(mci_problem *p, int solver) {
         }
     }
     if (side.joinable()) side.join();
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950:\n%s", c.log.c_str());
+    if (c.rc) return c.failed();
     if (int rc = load_slot(p, slot, c, p->lds_bytes)) return rc;
-    p->compiled[slot] = true;
     p->spec_need_check[solver - 1] = !verified;
     if (verified && p->spec_state[solver - 1] == 0) p->spec_state[solver - 1] = 1;
     return MCI_OK;
@@ -370,14 +302,14 @@ static int spec_self_check(mci_problem *p, int solver, int G, int64_t nevalperbl
     if (bad == 0) {
         p->spec_state[solver - 1] = 1;
         const std::string id = mcijit::compiler_id() + "\n"; // (the marker: this code object has reproduced the lane-per-chain kernel on a device)
-        mcijit::write_file_atomic(p->code_object[slot] + ".ok", id.data(), id.size());
+        mcijit::write_file_atomic(p->kernel[slot].code_object + ".ok", id.data(), id.size());
         return MCI_OK;
     }
     p->spec_state[solver - 1] = -1;
     fprintf(stderr, "mci: the several-lanes-per-chain kernel of this problem (%s, %s) does not reproduce its lane-per-chain kernel on a %lld-block, %lld-step "
                     "check: %ld of %lld packed entries differ (first at %ld, largest difference %.3g of its section's maximum).  A miscompiled code object -- "
                     "this problem keeps one lane per chain (same chains, slower for launches of few chains); mci_chain_speculation_status reports -1.\n",
-            solver == MCI_VEGASMC ? ":vegasmc" : ":mcmc", p->code_object[slot].c_str(), (long long)nb, (long long)npb, bad, (long long)p->packed_n, first_bad, worst);
+            solver == MCI_VEGASMC ? ":vegasmc" : ":mcmc", p->kernel[slot].code_object.c_str(), (long long)nb, (long long)npb, bad, (long long)p->packed_n, first_bad, worst);
     return MCI_OK;
 }
 
@@ -526,31 +458,17 @@ int mci_compile(mci_problem *p) { return compile_solver(p, MCI_VEGAS); }
 
 int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n) {
     if (!p || !buf || n < 1) return fail(MCI_ERR_INVALID, "NULL argument");
-    if (solver == MCI_VEGAS_PERSISTENT) {
-        if (!p->persist_compiled) return fail(MCI_ERR_INVALID, "the persistent :vegas kernel has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->persist_code_object.c_str());
-        return MCI_OK;
-    }
-    if (solver == MCI_VEGASMC_LANES || solver == MCI_MCMC_LANES) {
-        const int sl = solver == MCI_VEGASMC_LANES ? kSlotVegasmcSpec : kSlotMcmcSpec;
-        if (!p->compiled[sl]) return fail(MCI_ERR_INVALID, "the several-lanes-per-chain kernel has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->code_object[sl].c_str());
-        return MCI_OK;
-    }
-    if (solver == MCI_VEGAS_STRAT) {
-        if (!p->strat.compiled) return fail(MCI_ERR_INVALID, "the stratified :vegas kernel has not been compiled yet");
-        snprintf(buf, (size_t)n, "%s", p->strat.code_object.c_str());
-        return MCI_OK;
-    }
-    if (const int w = sweep_unit_of(solver); w >= 0) {
-        if (!p->sweep.unit[w].compiled) return fail(MCI_ERR_INVALID, "the sweep kernel%s has not been compiled yet", kSweepUnits[w].for_what);
-        snprintf(buf, (size_t)n, "%s", p->sweep.unit[w].code_object.c_str());
-        return MCI_OK;
-    }
-    if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
-    const int slot = (solver == MCI_VEGAS && !p->compiled[solver] && p->compiled[kSlotVegasAny]) ? kSlotVegasAny : solver;
-    if (!p->compiled[slot]) return fail(MCI_ERR_INVALID, "solver %d has not been compiled yet", solver);
-    snprintf(buf, (size_t)n, "%s", p->code_object[slot].c_str());
+    // which unit the name means, and what it is called when it is not there yet
+    int k = -1;
+    std::string what = "solver " + std::to_string(solver);
+    if (solver == MCI_VEGAS_PERSISTENT) k = mci_problem::kPersist, what = "the persistent :vegas kernel";
+    else if (solver == MCI_VEGASMC_LANES || solver == MCI_MCMC_LANES) k = solver == MCI_VEGASMC_LANES ? kSlotVegasmcSpec : kSlotMcmcSpec, what = "the several-lanes-per-chain kernel";
+    else if (solver == MCI_VEGAS_STRAT) k = mci_problem::kStrat, what = "the stratified :vegas kernel";
+    else if (const int w = sweep_unit_of(solver); w >= 0) k = mci_problem::kSweep + w, what = std::string("the sweep kernel") + kSweepUnits[w].for_what;
+    else if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
+    else k = (solver == MCI_VEGAS && !p->kernel[solver].compiled && p->kernel[kSlotVegasAny].compiled) ? kSlotVegasAny : solver;
+    if (!p->kernel[k].compiled) return fail(MCI_ERR_INVALID, "%s has not been compiled yet", what.c_str());
+    snprintf(buf, (size_t)n, "%s", p->kernel[k].code_object.c_str());
     return MCI_OK;
 }
 
@@ -739,7 +657,7 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
 
 int mci_get_histogram_copies(const mci_problem *p, int32_t *copies) {
     if (!p || !copies) return fail(MCI_ERR_INVALID, "NULL argument");
-    *copies = (p->compiled[MCI_VEGAS] || p->compiled[kSlotVegasAny]) ? p->shape.hcopy : planned_hcopy(p, nullptr);
+    *copies = (p->kernel[MCI_VEGAS].compiled || p->kernel[kSlotVegasAny].compiled) ? p->shape.hcopy : planned_hcopy(p, nullptr);
     return MCI_OK;
 }
 

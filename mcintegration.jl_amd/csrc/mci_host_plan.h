@@ -40,8 +40,8 @@ struct LaunchPlan {
 
 void plan_threads(const mci_problem *p, const LaunchRequest &rq, LaunchPlan &pl) {
     pl.T = solver_threads(p, rq.solver);
-    // mid-size :vegas launches of a plain-layout kernel compiled for it: 512-thread workgroups (mci_problem::vegas_wide)
-    if (rq.solver == MCI_VEGAS && p->vegas_wide && !p->threads_vegas && p->wg_per_block <= 0 && rq.nblocks * rq.nevalperblock < ((int64_t)1 << 22) &&
+    // mid-size :vegas launches of a plain-layout kernel compiled for it: 512-thread workgroups (VegasKernelPlan::wide)
+    if (rq.solver == MCI_VEGAS && p->vegas.wide && !p->vegas.threads_vegas && p->wg_per_block <= 0 && rq.nblocks * rq.nevalperblock < ((int64_t)1 << 22) &&
         rq.nblocks * rq.nevalperblock * p->shape.ndraw >= ((int64_t)1 << 19))
         pl.T = 512;
 }

@@ -316,7 +316,7 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
                 while (hc > 1 && (!hist_lds || s.ntile != 1 || (hc & (hc - 1)) || p->lds_bytes + one * (hc - 1) > lim1)) hc >>= 1;
                 if (hc < 1) hc = 1;
             }
-            s.hcopy = p->hcopy_auto = p->hcopy_rule = hc;
+            s.hcopy = hc;
         }
         const int64_t hcopy_bytes = (int64_t)s.htile * 8 * (s.hcopy - 1);
         // one tile, grids gathered from L2 (10 .. 18 independent grids): the LDS left next to the histogram caches the edges of the
@@ -343,14 +343,7 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
         // 32-grid Genz pass needs 146 VGPRs with the gather phase (209 before): 768 threads, 6.97 -> 6.45 ms per 1e8 samples; the 16-grid
         // Gaussian (histogram in the pass, 104 VGPRs) runs 1024 threads: 2.78 -> 2.44 ms (tools/c4_abenv.sh).  compile_solver walks the
         // ladder 1024 -> 768 -> 512 until the code object shows no scratch.
-        if (p->lds_bytes > lim0) {
-            p->vegas_plan_a = true;
-            p->threads_vegas = 1024;
-        }
-        if (s.hcopy > 1 && !p->vegas_plan_a) { // two 512-thread workgroups per CU (the rule above)
-            p->hcopy_plan = true;
-            p->threads_vegas = 512;
-        }
+        p->vegas.created(s.hcopy, p->lds_bytes > lim0);
     }
     p->nstat = 2 * s.nobs + 2 + Nd;
     p->packed_n = p->nstat + s.nbin + 2 * p->npa; // [statistics | histograms | propose | accept]
@@ -384,12 +377,7 @@ int mci_problem_destroy(mci_problem *p) {
     if (!p) return MCI_OK;
     if (!p->ctx->offline) {
         (void)hipStreamSynchronize(p->ctx->stream);
-        for (int k = 0; k < mci_problem::kSlots; ++k)
-            if (p->module[k]) (void)hipModuleUnload(p->module[k]);
-        if (p->module_persist) (void)hipModuleUnload(p->module_persist);
-        if (p->strat.module) (void)hipModuleUnload(p->strat.module);
-        for (auto &u : p->sweep.unit)
-            if (u.module) (void)hipModuleUnload(u.module);
+        for (KernelUnit &u : p->kernel) u.drop();
     }
     persist_job_drop(p);
     if (!p->ctx->offline) {
@@ -509,13 +497,9 @@ int mci_set_launch(mci_problem *p, int32_t threads, int32_t wg_per_block) {
     if (threads > 0) {
         if (threads % 64 || threads > 1024) return fail(MCI_ERR_INVALID, "threads per workgroup must be a multiple of 64, <= 1024");
         p->threads_explicit = true;
-        if (threads != p->threads || p->threads_vegas) {
+        if (threads != p->threads || p->vegas.threads_vegas) {
             p->threads = threads;
-            p->vegas_plan_a = false; // an explicit size: the vegas kernel follows it
-            p->hcopy_plan = false;
-            p->threads_vegas = 0;
-            // histogram copies are sized for two 512-thread workgroups per CU: smaller workgroups would leave the CU half empty
-            p->hcopy_auto = threads >= 512 || g_over.hist_copies.on ? p->hcopy_rule : 1;
+            p->vegas.explicit_threads(threads, g_over.hist_copies.on);
             drop_modules(p);
         }
     }
@@ -523,21 +507,12 @@ int mci_set_launch(mci_problem *p, int32_t threads, int32_t wg_per_block) {
     return MCI_OK;
 }
 
-// What the histogram-copy rule asks of the :vegas kernel the next time it is compiled: copies and workgroup size.  With BOTH opt-in
-// streams on (32 bits per draw, seven rounds) the loop is bound by its LDS pipe again, and sixteen copies -- conflict-free, one
-// 1024-thread workgroup per CU -- beat eight: 84.4 against 77.5 Gsamples/s on the headline configuration; with one opt-in or none
-// eight copies in two 512-thread workgroups win (bench.py: rounds 7: 73.6 against 70.2, 32 bits: 75.5 against 76.2, default: 66.7
-// against 61.7).
-static int planned_hcopy(const mci_problem *p, int *threads) {
+// VegasKernelPlan::planned_copies for this problem: sixteen copies need both opt-in streams and room in the CU's LDS
+static bool sixteen_copies_fit(const mci_problem *p) {
     const auto &s = p->shape;
-    int hc = p->hcopy_auto, t = 512;
-    if (p->hcopy_plan && hc >= 8 && s.rng_bits == 32 && s.rng_rounds == 7 && p->lds_bytes + (int64_t)s.htile * 8 * 15 <= 159 * 1024) {
-        hc = 16;
-        t = 1024;
-    }
-    if (threads) *threads = t;
-    return hc;
+    return s.rng_bits == 32 && s.rng_rounds == 7 && p->lds_bytes + (int64_t)s.htile * 8 * 15 <= 159 * 1024;
 }
+static int planned_hcopy(const mci_problem *p, int *threads) { return p->vegas.planned_copies(sixteen_copies_fit(p), threads); }
 
 // dynamic LDS of the :vegas sample kernel: the tables (+ the edge cache of the many-grid plans) + its histogram copies
 static int64_t vegas_lds(const mci_problem *p) {
@@ -552,7 +527,7 @@ static bool atomic_rows_ok(const mci_problem *p) { return !p->deterministic && k
 // workgroup size / dynamic LDS of a solver's sample kernel
 static int solver_threads(const mci_problem *p, int solver) {
     if (p->deterministic && p->threads_det[solver]) return p->threads_det[solver];
-    return solver == MCI_VEGAS && p->threads_vegas ? p->threads_vegas : p->threads;
+    return solver == MCI_VEGAS ? p->vegas.threads(p->threads) : p->threads;
 }
 static int64_t det_lds(const mci_problem *p, int threads) { // deterministic mode: tables + (threads / 64) histogram and observable copies
     const auto &s = p->shape;
@@ -567,7 +542,7 @@ static int64_t solver_lds(const mci_problem *p, int solver) {
 // the deterministic mode keeps its fixed partition)
 static bool vegas_pipe_unit(const mci_problem *p) {
     const auto &s = p->shape;
-    if (p->vegas_conservative || p->deterministic || s.det) return false;
+    if (p->vegas.conservative || p->deterministic || s.det) return false;
     if (s.ndraw < 8 || s.ndraw > 16 || !s.pair_table || s.table_mode != 0 || s.ntile != 1) return false;
     if (s.host_integrand || s.host_measure || s.ec_doubles > 0) return false;
     for (const auto &l : p->leaves)
@@ -577,7 +552,7 @@ static bool vegas_pipe_unit(const mci_problem *p) {
 // workgroups of `threads` threads of the :vegas kernel in slot `kern` that are resident on the device at once: the runtime's occupancy
 // for the kernel's registers and the launch's LDS, times the CUs (asked again only when the kernel or the launch shape changed)
 static int cursor_resident(mci_problem *p, int kern, int threads, int *out) {
-    hipFunction_t f = p->f_solver[kern];
+    hipFunction_t f = p->kernel[kern].f;
     const int64_t lds = solver_lds(p, MCI_VEGAS);
     if (f != p->cursor_occ_f || threads != p->cursor_occ_threads || lds != p->cursor_occ_lds) {
         int per_cu = 0, cus = 0;

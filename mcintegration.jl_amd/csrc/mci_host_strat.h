@@ -259,29 +259,19 @@ int strat_prepare(mci_problem *p, int64_t N) {
 static int compile_strat(mci_problem *p) {
     auto &st = p->strat;
     const int det = p->deterministic ? 1 : 0;
-    if (st.compiled && st.compiled_det == det) return MCI_OK;
-    if (st.module) {
-        if (!p->ctx->offline) (void)hipModuleUnload(st.module);
-        st.module = nullptr;
-        st.f = nullptr;
-    }
+    KernelUnit &u = p->kernel[mci_problem::kStrat];
+    if (u.compiled && st.compiled_det == det) return MCI_OK;
+    u.drop();
     Candidate c;
     mcijit::ProblemShape sh = p->shape;
     sh.det = det;               // deterministic mode: one histogram copy per wave (mci_device.h hslot)
     sh.hcopy = det ? 256 / 64 : 1;
+    c.unit = mcijit::kUnitStrat;
     c.src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitStrat);
     c.threads = 256;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, mcijit::kUnitStrat);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (stratified :vegas kernel):\n%s", c.log.c_str());
-    if (mcijit::max_static_lds_bytes(c.code) != 0) return fail(MCI_ERR_COMPILE, "the stratified code object declares static LDS");
-    st.code_object = c.path;
-    if (!p->ctx->offline) {
-        HIPCHK(hipSetDevice(p->ctx->device));
-        HIPCHK(hipModuleLoadData(&st.module, c.code.data()));
-        HIPCHK(hipModuleGetFunction(&st.f, st.module, "mci_vegas_strat"));
-        HIPCHK(hipFuncSetAttribute((const void *)st.f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    st.compiled = true;
+    if (c.build()) return c.failed(" (stratified :vegas kernel)");
+    static const KernelUnit::Rules rules = {KernelUnit::kFail, false, "the stratified code object declares static LDS", ""};
+    if (int rc = u.load(p->ctx, c, mcijit::kUnits[c.unit].kernel, 160 * 1024, rules)) return rc;
     st.compiled_det = det;
     return MCI_OK;
 }
@@ -490,7 +480,7 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
     const int slot = (int)(p->launch.launches % mci_problem::kEvRing);
     p->launch.time_this_launch = p->kernel_timing > 0 || (p->kernel_timing < 0 && N >= ((int64_t)1 << 20));
     if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot], p->ctx->stream));
-    HIPCHK(hipModuleLaunchKernel(st.f, (unsigned)nwg, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
+    HIPCHK(hipModuleLaunchKernel(p->kernel[mci_problem::kStrat].f, (unsigned)nwg, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
     if (p->launch.time_this_launch) HIPCHK(hipEventRecord(p->evs[2 * slot + 1], p->ctx->stream));
     p->launch.ev_valid[slot] = p->launch.time_this_launch;
     p->launch.clock_valid[slot] = false;

@@ -148,42 +148,24 @@ static bool sweep_leaves_unit(const mci_problem *p) { return sweep_uses_leaves(p
 // again when mci_debug_sweep_threads asks for another workgroup size --, no static LDS, no scratch
 static int compile_sweep_unit(mci_problem *p, int which) {
     const SweepUnitDesc &k = kSweepUnits[which];
-    const char *kernel = mcijit::kUnits[k.jit_unit].kernel;
-    auto &u = p->sweep.unit[which];
+    KernelUnit &u = p->sweep_unit(which);
     const int T = k.want_threads && p->sweep.want_threads > 0 ? p->sweep.want_threads : kSweepThreads;
     if (u.compiled && u.threads == T) return MCI_OK;
-    if (u.module) {
-        if (!p->ctx->offline) (void)hipModuleUnload(u.module);
-        u.module = nullptr;
-        u.f = nullptr;
-    }
-    u.compiled = false;
+    u.drop();
     Candidate c;
     mcijit::ProblemShape sh = p->shape;
     sh.hcopy = 1;
     sh.det = 0;
+    c.unit = k.jit_unit;
     c.src = mcijit::generate_source(sh, MCI_VEGAS, k.jit_unit, k.alpha ? p->leaves[0].alpha : 0.0);
     c.threads = T;
-    c.rc = mcijit::compile(c.src, c.threads, c.code, c.log, c.cached, &c.path, k.jit_unit);
-    if (c.rc) return fail(MCI_ERR_COMPILE, "integrand failed to compile for gfx950 (sweep kernel%s%s):\n%s", k.tag[0] ? ", " : "", k.tag, c.log.c_str());
-    if (mcijit::max_static_lds_bytes(c.code) != 0 || mcijit::kernel_scratch_bytes(c.code, kernel) != 0)
-        return fail(MCI_ERR_COMPILE, "the sweep kernel%s came out with static LDS or scratch at %d threads per workgroup", k.for_what, T);
-    u.code_object = c.path;
-    u.threads = T;
-    if (!p->ctx->offline) {
-        HIPCHK(hipSetDevice(p->ctx->device));
-        if (hipModuleLoadData(&u.module, c.code.data()) != hipSuccess) {
-            if (c.cached) unlink(c.path.c_str()); // a cached code object that does not load (truncated by a crash, foreign file)
-            return fail(MCI_ERR_HIP, "hipModuleLoadData failed for the sweep code object%s%s%s", k.tag[0] ? " (" : "", k.tag, k.tag[0] ? ")" : "");
-        }
-        HIPCHK(hipModuleGetFunction(&u.f, u.module, kernel));
-        if (which == mci_problem::Sweep::kLeaves) { // (its LDS is the layout's; the stratified unit's is the call's: sweep_run)
-            const int64_t lds = sweep_leaves_lds(p, nullptr);
-            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-    }
-    u.compiled = true;
-    return MCI_OK;
+    const std::string tag = k.tag;
+    if (c.build()) return c.failed(" (sweep kernel" + (tag.empty() ? tag : ", " + tag) + ")");
+    const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true,
+                                     std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
+                                     "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
+    // (the several-leaves unit's LDS is the layout's; the stratified unit's is the call's: sweep_run)
+    return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, which == mci_problem::Sweep::kLeaves ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
 int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
@@ -291,7 +273,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
         return fail(MCI_ERR_INVALID, c.too_big, (int)npoint, niter, c.too_big_count, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
     if ((rc = compile_sweep_unit(p, c.unit))) return rc;
-    const auto &u = p->sweep.unit[c.unit];
+    const KernelUnit &u = p->sweep_unit(c.unit);
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
     void *base = nullptr;

@@ -110,6 +110,41 @@ template <class T, bool kPinned> struct Buf {
 };
 template <class T> using DevBuf = Buf<T, false>;
 template <class T> using PinBuf = Buf<T, true>;
+
+// The owning handle of one loaded code object (DevBuf's counterpart for modules): the module, its main kernel, the kernel-cache file it
+// came from and the workgroup size it was compiled for.  `compiled` is all an offline problem ever has.  What else decides whether a
+// unit can be used as it is (the stratified unit's deterministic flag, a sweep unit's thread count, the persistent unit's background
+// job) is its caller's to ask.
+struct Candidate; // one hiprtc job (mci_host_jit.h)
+struct KernelUnit {
+    hipModule_t module = nullptr;
+    hipFunction_t f = nullptr;
+    bool compiled = false;
+    std::string code_object;
+    int threads = 0;
+    // a code object from the kernel cache that does not load (truncated by a crash, foreign file)
+    enum Stale { kRecompileOnce, kUnlinkAndFail, kFail };
+    struct Rules {
+        Stale stale;
+        bool no_scratch;     // the main kernel must not use scratch either
+        std::string refusal; // the message for static LDS (or scratch); empty: the sample kernels' own
+        std::string what;    // "hipModuleLoadData failed for <what>"
+    };
+    // (mci_host_jit.h) the refusals, then -- unless the context is offline -- module, main kernel and its dynamic-LDS limit
+    int load(const mci_ctx *ctx, Candidate &c, const char *kernel, int64_t lds, const Rules &rules);
+    // another entry point of the same module, with the same limit
+    int entry(hipFunction_t *out, const char *name, int64_t lds) const {
+        HIPCHK(hipModuleGetFunction(out, module, name));
+        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)*out, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return MCI_OK;
+    }
+    void drop() {
+        compiled = false;
+        f = nullptr;
+        if (module) (void)hipModuleUnload(module);
+        module = nullptr;
+    }
+};
 } // namespace
 
 struct mci_problem {
@@ -131,15 +166,13 @@ struct mci_problem {
     DevBuf<int> d_status;
     DevBuf<mci::LeafDev> d_leaves;
     // kernels
-    // one code object per solver, JIT-compiled (or loaded from the kernel cache) the first time the solver runs;
-    // the vegas module also holds the sample-dump kernel
+    // one code object per unit, JIT-compiled (or loaded from the kernel cache) the first time it is needed
     // kernel slots (kslot): :vegas for measurefreq == 1 | :vegasmc | :mcmc | :vegas for any measurefreq | sample dump
     //                      | :vegasmc with several lanes per chain | :mcmc with several lanes per chain (mci_spec.h)
-    static const int kSlots = 7;
-    hipModule_t module[kSlots] = {};
-    hipFunction_t f_solver[kSlots] = {}, f_dump = nullptr;
-    bool compiled[kSlots] = {};
-    std::string code_object[kSlots]; // kernel-cache file each slot's code object was loaded from / written to
+    // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the three sweep units (Sweep)
+    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kKernels = kSweep + 3 };
+    KernelUnit kernel[kKernels];
+    VegasKernelPlan vegas; // which :vegas code object the launches run (mci_host_vegas_plan.h)
     // Several lanes per chain (mci_spec.h, mci_set_chain_speculation): lanes -1 automatic (as many as the launch's chains leave idle),
     // 1 never, 2..64 forced; the acceptance the speculation tree is built for (<= 0: the solver's default) and the most accept edges
     // on a way through it (-1: the solver's default); the tree of the last such launch on the device
@@ -165,13 +198,11 @@ struct mci_problem {
     int vegas_check_state[2] = {0, 0};
     bool vegas_check_done[2] = {false, false}; // nothing left to decide for the loaded code object of that unit
     int vegas_check_flags = 0;                 // bit 0: observables not compared (user measure), bit 1: verified from a marker
-    bool vegas_conservative = false;           // the :vegas units are compiled in the generator's most conservative layout (plain loop, one histogram copy)
     int check_slot = -1;                       // inside vegas_self_check: the kernel slot its launch goes through, whatever its cadence
     int64_t check_launches = 0;                // launches made for vegas_self_check so far (mci_debug_vegas_check_launches)
     int64_t last_discarded_neval = 0;              // evaluations of the warm-up launches the last mci_integrate ran again instead of counting
     int32_t last_discarded_launches = 0;
     static const int64_t kSpecFill = 65536;        // lanes a launch of few chains spreads over: one wave on each of the 1024 SIMDs
-    bool vegas_planned = false, vegas_keys = false; // the :vegas plan (workgroup size, histogram copies, VGPR round keys) stands for both variants
     std::vector<double> h_goal; // reweight_goal (main.jl:81); empty = none
     DevBuf<double> d_goal;
     int npa = 0;                    // 3 * (ni+1) * max(ni+1, npool): entries of config.propose (configuration.jl:185)
@@ -212,26 +243,11 @@ struct mci_problem {
     std::vector<int32_t> h_mitmp;
     int threads = 256, wg_per_block = 0; // 0 = auto
     bool threads_explicit = false;       // mci_set_launch named a workgroup size
-    // Plain-layout :vegas kernels of light integrands are compiled for workgroups of up to 512 threads (they need <= 128 registers anyway),
-    // and mid-size launches -- one workgroup per CU, 2^19 <= samples x draws, samples < 2^22: the sizes the reference's own tests and
-    // examples run -- use them: twice the lanes behind the same 256 prologues, epilogues and partial rows (tools/midsize_sweep.py,
-    // profiles/r05_latency.txt: -7 .. -11 % per iteration on 2-D and 6-D integrands at 3e5 .. 3e6 samples)
-    bool vegas_wide = false;
-    // :vegas kernels whose tables take more than half of a CU's LDS (one workgroup per CU: 16 or 32 independent grids) pick their
-    // workgroup size from the compiled code: the largest of 1024 / 768 / 512 threads (4 / 3 / 2 waves per SIMD) at which the sample
-    // pass shows no scratch (128 / 168 / 256 registers).  threads_vegas = 0: the vegas kernel follows `threads`
-    int threads_vegas = 0;
-    bool vegas_plan_a = false; // the ladder is active (no explicit size was asked for)
-    // histogram copies of the :vegas sample kernel (mci_device.h hslot): what the placement rule picked (shape.hcopy is what the
-    // compiled kernel uses: the rule's choice, or 1 when that kernel needs more than 128 VGPRs and two 512-thread workgroups
-    // would not share a CU)
     int kernel_timing = -1;       // mci_set_kernel_timing
-    int hcopy_auto = 1, hcopy_rule = 1; // in force | what the placement rule picked at create
     // deterministic mode (mci_set_deterministic): every solver's kernel keeps one histogram / observable copy per wave; the workgroup
     // size each was compiled for (the largest of 512 / 256 / 128 / 64 threads whose copies fit the CU's LDS)
     bool deterministic = false;
     int threads_det[3] = {0, 0, 0};
-    bool hcopy_plan = false; // the rule also picked the workgroup size (512 threads) for the :vegas kernel
     // refinement walk of train! (variable.jl:227-234): -1 automatic -- the reference's serial recurrence whenever the sample
     // launch before it is long enough to hide its ~14 us per iteration (>= kSerialWalkSamples samples or chain steps on this
     // rank: 1 % of the headline iteration), the prefix-scan form below that; mci_set_train_walk forces one
@@ -280,13 +296,9 @@ struct mci_problem {
     static const int kEvRing = 512;
     int log_row = 0;
     PinBuf<double> h_log;     // pinned: mci_integrate's read-back of the iteration log (+ the status word behind it)
-    // persistent :vegas iterations (mci_train.h vegas_persist; mci_set_persistent): its own code object -- the plain layout at
-    // `threads` -- and the two grid-wide counters, which only grow (the host keeps their values)
-    hipModule_t module_persist = nullptr;
-    hipFunction_t f_persist = nullptr;
-    bool persist_compiled = false, persist_failed = false;
-    std::string persist_code_object;
-    int persist_threads = 256;    // its workgroup size: 512 for the hand-pipelined loops (8..16 draws), else `threads`
+    // persistent :vegas iterations (mci_train.h vegas_persist; mci_set_persistent): its own code object (kernel[kPersist]) -- the plain
+    // layout at `threads` -- and the two grid-wide counters, which only grow (the host keeps their values)
+    bool persist_failed = false;
     // its translation unit takes twice as long to compile as the plain sample kernel (train! comes with it): in automatic mode a code
     // object that is not in the kernel cache is compiled on a thread of its own while the calls go through the launch chain
     struct PersistJob;
@@ -315,10 +327,10 @@ struct mci_problem {
     // What a sample launch leaves behind on the host (mci_iteration_run and the functions it calls write it).  VALUES ONLY -- no
     // pointer, capacity, handle or module: spec_self_check copies the record out before its two small launches and back after them,
     // and those launches may create or grow buffers (every d_* / h_* is a DevBuf / PinBuf, which cannot be copied).  Outside it:
-    //   resources the check may create -- evs, the modules and compiled[], what describes the speculation trees on the device
+    //   resources the check may create -- evs, the kernel units, what describes the speculation trees on the device
     //     (spec_tab_*, spec_ntree, spec_first, spec_accepts);
     //   settings -- spec_lanes, kernel_timing, chain_carry, threads*, ...;
-    //   the check's own result -- spec_state, spec_need_check, in_self_check, vegas_check_*, vegas_conservative, check_*;
+    //   the check's own result -- spec_state, spec_need_check, in_self_check, vegas_check_*, vegas.conservative, check_*;
     //   the merge hand-off -- merge, merge_pending (mci_get_packed flushes it inside the check);
     //   per-call results of mci_integrate -- last_discarded_*, last_persistent, launch_counted, log_row;
     //   the reduce's bookkeeping -- reduces, cev_valid[] (mci_iteration_reduce alone writes them; the check does not reduce).
@@ -394,11 +406,7 @@ struct mci_problem {
         DevBuf<long long> d_rec_h;
         int64_t last_nchunk = 0;
         bool last_run = false;        // the last mci_iteration_run was stratified: mci_iteration_finish reduces it
-        bool compiled = false;
-        int compiled_det = -1;
-        hipModule_t module = nullptr;
-        hipFunction_t f = nullptr;
-        std::string code_object;
+        int compiled_det = -1;        // the deterministic flag kernel[kStrat] was compiled under
         // test hook (mci_debug_strat_dump): host buffers the next stratified run fills
         double *hx = nullptr, *hy = nullptr, *hjac = nullptr, *hw = nullptr;
         long long *hh = nullptr;
@@ -407,20 +415,12 @@ struct mci_problem {
         double *hstart = nullptr;
         int64_t hstart_n = 0;
     } strat;
-    // Batched :vegas parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat; mci_host_sweep.h): the code objects of the three
-    // sweep units.  A sweep keeps nothing else here: its maps, logs and status words come in and go out through the call's arguments.
+    // Batched :vegas parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat; mci_host_sweep.h): the three sweep units are
+    // kernel[kSweep + which].  A sweep keeps nothing else here: its maps, logs and status words come in and go out through the call's arguments.
     struct Sweep {
-        struct Unit {
-            bool compiled = false;
-            int threads = 0;          // the workgroup size the loaded code object was compiled for
-            hipModule_t module = nullptr;
-            hipFunction_t f = nullptr;
-            std::string code_object;
-        };
         // mci_sweep.h (one Continuous grid) | mci_sweep_leaves.h (any mix of Continuous and Discrete leaves) | mci_sweep_strat.h
         // (stratified points): mci_host_sweep.h kSweepUnits describes them in this order
         enum { kOne = 0, kLeaves = 1, kStrat = 2, kUnits = 3 };
-        Unit unit[kUnits];
         int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
         int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default (the one-grid unit only)
         int last_grid = 0, last_threads = 0;
@@ -428,6 +428,8 @@ struct mci_problem {
         // (a problem that is no one-grid layout runs unit kLeaves)
         int leaves_mode = 0;
     } sweep;
+    KernelUnit &sweep_unit(int which) { return kernel[kSweep + which]; }
+    static_assert(kKernels == kSweep + Sweep::kUnits, "one handle per sweep unit");
 };
 
 // The three sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
@@ -718,38 +720,12 @@ int hold_consume(mci_problem *p) {
 }
 
 void drop_modules(mci_problem *p) {
-    p->vegas_planned = p->vegas_keys = p->vegas_wide = false;
+    p->vegas.modules_dropped();
     p->vegas_check_done[0] = p->vegas_check_done[1] = false; // (new code objects: they prove themselves again, or show their markers)
-    p->f_dump = nullptr;
     p->cursor_occ_f = nullptr; // (the occupancy answer belonged to a kernel of the modules that go)
-    for (int k = 0; k < mci_problem::kSlots; ++k) {
-        p->compiled[k] = false;
-        if (p->module[k]) {
-            (void)hipModuleUnload(p->module[k]);
-            p->module[k] = nullptr;
-        }
-    }
-    p->persist_compiled = p->persist_failed = false;
+    for (KernelUnit &u : p->kernel) u.drop();
+    p->persist_failed = false;
     persist_job_drop(p);
-    p->f_persist = nullptr;
-    if (p->module_persist) {
-        (void)hipModuleUnload(p->module_persist);
-        p->module_persist = nullptr;
-    }
-    p->strat.compiled = false;
-    p->strat.f = nullptr;
-    if (p->strat.module) {
-        (void)hipModuleUnload(p->strat.module);
-        p->strat.module = nullptr;
-    }
-    for (auto &u : p->sweep.unit) {
-        u.compiled = false;
-        u.f = nullptr;
-        if (u.module) {
-            (void)hipModuleUnload(u.module);
-            u.module = nullptr;
-        }
-    }
 }
 
 } // namespace
