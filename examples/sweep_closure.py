@@ -12,7 +12,8 @@ Then the reference's flagship example, the polarisation bubble (test/bubble.jl:1
 over the density parameter rs at a fixed dimensionless temperature: kF, the external momenta and the imaginary-time domain (0, beta)
 follow rs.  Four Continuous variable types, a Discrete external-momentum index and a histogram over it: `leaves="all"` lets such a
 problem run as a sweep.  The momenta are a table the integrand looks up by the Discrete draw (every point's row carries its own), and
-every point starts from a map of its own -- its T grid spans its own (0, beta)."""
+every point starts from a map of its own -- its T grid spans its own (0, beta).  `bubble_scan(solver="vegasmc", chains=64)` runs the
+same scan under the reference's default solver: 64 fresh chains per block and point, still one launch."""
 import math
 import os
 import sys
@@ -104,7 +105,7 @@ def bubble_para(rs, beta=25.0, spin=2, Qsize=4, dim=3, me=0.5):             # te
                                  extQ=[np.array([q, 0.0, 0.0]) for q in np.linspace(0.0, 1.5 * kF, Qsize)])
 
 
-def bubble_scan(points=16, ninc=1000):
+def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None):
     scan = [bubble_para(float(rs)) for rs in np.linspace(1.0, 2.0, points)]
     Qsize = scan[0].Qsize
     var = (mci.Continuous(0.0, 1.0, alpha=3.0), mci.Continuous(0.0, PI, alpha=3.0), mci.Continuous(0.0, 2 * PI, alpha=3.0),
@@ -114,8 +115,10 @@ def bubble_scan(points=16, ninc=1000):
     maps = [np.concatenate([np.linspace(0.0, hi, ninc) for hi in (1.0, PI, 2 * PI, p.beta)] + [np.concatenate([[0.0], np.cumsum(uniform)]), uniform])
             for p in scan]
     results = mci.integrate_sweep(bubble, params=scan, leaves="all", maps=maps, measure=q_histogram, var=var, dof=[[1, 1, 1, 1, 1]],
-                                  obs=[np.zeros(Qsize)], solver="vegas", neval=1e5, niter=10, seed=7)
-    print("bubble batched:", all(r.sweep_batched for r in results), "| %.2f ms for %d points" % (1e3 * results[0].seconds, len(scan)))
+                                  obs=[np.zeros(Qsize)], solver=solver, chains=chains, neval=1e5, niter=10, seed=7)
+    print("bubble (%s) batched:" % solver, all(r.sweep_batched for r in results), "| %.2f ms for %d points" % (1e3 * results[0].seconds, len(scan)))
+    if chains is not None:   # the chain solver's own state, point by point
+        print("reweight factors of the first and the last point:", results[0].reweight, results[-1].reweight)
     print("%6s  %s" % ("rs", "  ".join("q = %.1f kF: avg +- err      " % (q[0] / scan[0].kF) for q in scan[0].extQ)))
     for p, r in list(zip(scan, results))[::max(1, points // 8)]:
         print("%6.3f  %s" % (p.rs, "  ".join("%12.6f +- %-10.6f" % (r.mean[0][i], r.stdev[0][i]) for i in range(Qsize))))
@@ -126,3 +129,4 @@ if __name__ == "__main__":
     main()
     stratified()
     bubble_scan()
+    bubble_scan(solver="vegasmc", chains=64)

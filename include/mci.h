@@ -46,6 +46,8 @@ enum { MCI_VEGAS_SWEEP = 8 };
 enum { MCI_VEGAS_SWEEP_LEAVES = 9 };
 /* ... and the sweep kernel for stratified points (mci_integrate_sweep_strat; problems mci_sweep_strat_supported accepts) */
 enum { MCI_VEGAS_SWEEP_STRAT = 10 };
+/* ... and the sweep kernel of the default solver (mci_integrate_sweep_chains; problems mci_sweep_chains_supported accepts) */
+enum { MCI_VEGASMC_SWEEP = 11 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -305,6 +307,34 @@ int mci_integrate_sweep_strat(mci_problem *prob, const mci_integrate_args *args,
 int mci_sweep_strat_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
 /* hypercubes of the plan mci_integrate_sweep_strat runs these arguments on: the row length of d_in / d_out / counts_out */
 int mci_sweep_strat_doubles(const mci_problem *prob, const mci_integrate_args *args, int64_t *ncube);
+/* A parameter sweep under the reference's default solver (main.jl:72): `npoint` independent :vegasmc loops -- what mci_integrate runs
+ * with args->solver = MCI_VEGASMC, args->nchain chains per block, fresh chains in every iteration (mci_set_chain_carry(prob, 0)) and one
+ * lane per chain (mci_set_chain_speculation(prob, 1, ...)) -- in ONE launch, one workgroup per point.  The opt-in form for the chain
+ * solver: mci_integrate_sweep and mci_sweep_supported keep refusing it.  Per point and iteration the workgroup runs the statistical blocks
+ * one after another, every block's chains one lane each (vegas_mc/montecarlo.jl:112-241: same Philox streams, keyed by seed, iteration,
+ * block, chain and step, same arithmetic per step, burn-in mci_chain_burnin), merges the block rows (main.jl:273-287) and the propose |
+ * accept tables, runs doReweight! on the point's own factors (main.jl:183, :322-346 -- whatever `adapt` says) and train! on every leaf.
+ * userdata, seeds, maps_in, maps_out (rows of mci_sweep_map_doubles doubles, any mix of Continuous and Discrete leaves), results,
+ * iter_mean, iter_std and status are mci_integrate_sweep's; every result has correlated = 0.
+ *   reweight_in   NULL: every point starts from the problem's current factors; else [npoint][nintegrand + 1]
+ *   reweight_out  NULL or [npoint][nintegrand + 1]: every point's factors after its last doReweight! (what a later call passes as
+ *                 reweight_in, with maps_out as maps_in and first_iteration moved on, to go on with a scan)
+ *   pa_out        NULL or [npoint][2][npa]: config.propose | config.accept of every point's last iteration (mci_get_acceptance's layout)
+ * args->nchain >= 1 (0, the automatic policy, sizes chains from carried state a sweep does not have: refused by name) and at most the
+ * steps of a block.  The problem's own map, reweight factors, packed buffer, logs, carry state and last_* queries are not touched.
+ * npoint <= 65536 and at most 4 GiB of device memory (mci_integrate_sweep's buffer plus, per point, the factors, block x 2 npa table
+ * entries and a packed row with the tables): MCI_ERR_INVALID beyond. */
+int mci_integrate_sweep_chains(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                               const double *maps_in, double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out,
+                               mci_result *results, double *iter_mean, double *iter_std, int32_t *status);
+/* MCI_OK when mci_integrate_sweep_chains takes this problem with these arguments; else MCI_ERR_INVALID with the reason in why[n] (and in
+ * mci_last_error): :vegas (mci_integrate_sweep runs it) or :mcmc (a follow-up), nchain = 0 or more chains than a block has steps,
+ * more than 4096 blocks, first_iteration < 0 or first_iteration + niter > 131072 (a chain's streams are addressed by block < 4096 and
+ * iteration < 131072, as in mci_iteration_run),
+ * measurefreq != 1, several ranks, stratification, a host integrand or measure, deterministic mode, a reweight goal, a FermiK variable,
+ * tables that do not sit in LDS in one tile, or more than 159 KiB of LDS for the chain loop's tables and counters or the refinement
+ * scratch plus the point's whole map (named). */
+int mci_sweep_chains_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

@@ -186,6 +186,8 @@ class Configuration:
         self.iterations_done = 0
 
     def _acceptance(self, which):
+        if getattr(self, "_sweep_tables", None) is not None:   # a point of a chain sweep (integrate_sweep(..., chains=K)): its own tables,
+            return self._sweep_tables[which]                   # until the configuration is bound to another run (integrate._bind)
         nd = self.N + 1
         shape = (3, nd, max(nd, len(self.var)))
         if self._engine is not None and hasattr(self._engine, "acceptance"):

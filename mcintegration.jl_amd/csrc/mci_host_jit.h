@@ -637,7 +637,13 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         a.solver = MCI_VEGAS;
         a.measurefreq = 1;
         a.niter = 1;
-        if (w == mci_problem::Sweep::kStrat) {
+        if (w == mci_problem::Sweep::kChains) { // (the layout alone, as below: any chain count the call may bring)
+            a.solver = MCI_VEGASMC;
+            a.nchain = 1;
+            a.neval = (int64_t)1 << 40;
+            a.block = 1;
+            if (int rc = mci_sweep_chains_supported(p, &a, nullptr, 0)) return rc;
+        } else if (w == mci_problem::Sweep::kStrat) {
             a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
             a.block = 1;
             if (int rc = mci_sweep_strat_supported(p, &a, nullptr, 0)) return rc;

@@ -1,7 +1,8 @@
 // mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
-// batched :vegas parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
+// batched parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
 // one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in; mci_sweep_strat.h
-// vegas_sweep_strat for stratified points).  One descriptor table (kSweepUnits), one compile, one refusal head, one driver (sweep_run).
+// vegas_sweep_strat for stratified points; mci_sweep_chains.h vegasmc_sweep for :vegasmc points, by its own entry point).  One descriptor
+// table (kSweepUnits), one compile, one refusal head, one driver (sweep_run).
 namespace {
 // Points of one sweep, and the device memory one may take.  Per point the launch holds the userdata row, a seed, two maps, niter log
 // rows, nblocks partial rows and as much merge scratch, a statistics head, a histogram row and a status word: ~25 KB at the
@@ -9,7 +10,8 @@ namespace {
 const int32_t kSweepMaxPoints = 65536;
 const int64_t kSweepMaxBytes = (int64_t)4 << 30;
 
-// LDS of the sweep kernel for several leaves (mci_sweep_leaves.h), bytes: the sample loop's carve in the plain layout (tables in LDS,
+// LDS of the sweep kernels for several leaves (mci_sweep_leaves.h, mci_sweep_chains.h), bytes: the sample loop's carve (mci_device.h Lds:
+// the chain solvers' propose / accept counters are part of it under either solver) in the plain layout (tables in LDS,
 // one histogram copy -- what that layout WOULD take where the problem was given another one, so that the refusal can name the count) or
 // the refinement's scratch for the largest leaf, whichever is larger, and behind them (map_off, doubles) the point's map block
 // edges | dacc | ddist | flags[4], each part on 16 bytes (SweepBlock)
@@ -58,10 +60,13 @@ bool sweep_uses_leaves(const mci_problem *p) { return p->sweep.leaves_mode == MC
 
 // What both queries ask first, `strat`: of a stratified sweep.  Eligibility of either: measurefreq == 1, one rank, device-source integrand
 // and measure, not deterministic.
-const char *sweep_common_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, bool strat) {
+const char *sweep_common_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, bool strat, bool chains = false) {
     const auto &s = p->shape;
     if (strat && !p->strat.on) return "the problem is not stratified (mci_set_stratification first; mci_integrate_sweep runs the others)";
-    if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
+    if (chains) { // (mci_integrate_sweep_chains: the solver test the other way round)
+        if (a->solver == MCI_MCMC) return "solver is :mcmc (a sweep of :mcmc points is a follow-up)";
+        if (a->solver != MCI_VEGASMC) return "solver is not :vegasmc (mci_integrate_sweep runs :vegas)";
+    } else if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
     if (a->measurefreq != 1) {
         buf = "measurefreq = " + std::to_string((long long)a->measurefreq) + " (a sweep measures every sample)";
         return buf.c_str();
@@ -157,15 +162,16 @@ static int compile_sweep_unit(mci_problem *p, int which) {
     sh.hcopy = 1;
     sh.det = 0;
     c.unit = k.jit_unit;
-    c.src = mcijit::generate_source(sh, MCI_VEGAS, k.jit_unit, k.alpha ? p->leaves[0].alpha : 0.0);
+    c.src = mcijit::generate_source(sh, k.runs, k.jit_unit, k.alpha ? p->leaves[0].alpha : 0.0);
     c.threads = T;
     const std::string tag = k.tag;
     if (c.build()) return c.failed(" (sweep kernel" + (tag.empty() ? tag : ", " + tag) + ")");
     const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true,
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
-    // (the several-leaves unit's LDS is the layout's; the stratified unit's is the call's: sweep_run)
-    return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, which == mci_problem::Sweep::kLeaves ? sweep_leaves_lds(p, nullptr) : 0, rules);
+    // (the several-leaves and the :vegasmc unit's LDS is the layout's; the stratified unit's is the call's: sweep_run)
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kChains;
+    return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
 int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
@@ -219,9 +225,9 @@ int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 // The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
-// kSegOff, kSegTbase and kSegD are the stratified unit's (none otherwise).  Everything from kSegGhist on is zeroed before the launch:
-// histogram rows, d rows, (the seeds: copied next), status words.
-enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegGhist, kSegD, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+// kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the :vegasmc unit's (none otherwise).  Everything from
+// kSegGhist on is zeroed before the launch: histogram rows, d rows, (the seeds: copied next), status words.
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegGhist, kSegD, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
 
 // What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
 struct SweepCall {
@@ -241,6 +247,8 @@ struct SweepCall {
     int64_t neval_per_block = 0, blocks = 0; // main.jl:121
     size_t map_doubles = 0;      // one maps_in / maps_out row
     size_t off_doubles = 0, tbase_doubles = 0, d_doubles = 0; // per point: kSegOff, kSegTbase, kSegD
+    size_t rw_doubles = 0, pa_doubles = 0;                    // per point: kSegRw (reweight factors), kSegPa (the blocks' propose | accept rows)
+    size_t packed_doubles = 0;   // a point's packed row; 0: the statistics head alone
     int maxn = 0;                // bins of the largest leaf
     int64_t lds = 0;             // bytes of LDS of a workgroup
     int map_off = 0;             // SweepHead::map_off
@@ -249,6 +257,7 @@ struct SweepCall {
     long long too_big_count = 0;
     // the kernel's second argument behind its head: `h` is filled, `o` are the segments' offsets in `d`; NULL: the head is the argument
     std::function<void *(const mci::SweepHead &h, double *d, const size_t *o)> args;
+    std::function<void(mci::BatchArgs &b)> batch; // what the unit's sample loop reads of the launch's BatchArgs beyond the :vegas ones
     // the unit's own copies in front of the launch / behind it (stream st), and what it makes of them once the stream has drained
     std::function<int(double *d, const size_t *o, hipStream_t st)> copy_in, copy_out;
     std::function<void()> finish;
@@ -265,8 +274,8 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     int rc;
     if ((rc = c.plan(c))) return rc;
     const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
-    const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, (size_t)nstat,
-                                         c.off_doubles,  c.tbase_doubles, (size_t)s.nbin, c.d_doubles, c.seeds ? (size_t)1 : 0};
+    const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, c.packed_doubles ? c.packed_doubles : (size_t)nstat,
+                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, (size_t)s.nbin, c.d_doubles, c.seeds ? (size_t)1 : 0};
     size_t o[kSegCount + 1] = {0};
     for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
     const size_t ndbl = o[kSegStatus] + (P + 1) / 2;
@@ -306,6 +315,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
         b.status = reinterpret_cast<int *>(d + o[kSegStatus]);
         b.tile_stride = c.blocks * c.neval_per_block;
         b.nrows = c.rows;
+        if (c.batch) c.batch(b);
         mci::SweepHead h{};
         mci::MergeArgs &m = h.m;
         m = merge_args(p, c.rows, 1, c.rows);
@@ -393,11 +403,12 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     return MCI_OK;
 }
 
-// what both entry points check of their arguments before anything else
-int sweep_check_args(const mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const mci_result *results, bool strat) {
+// what every entry point checks of its arguments before anything else; `supported`: its own query
+int sweep_check_args(const mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const mci_result *results,
+                     int (*supported)(const mci_problem *, const mci_integrate_args *, char *, int32_t)) {
     if (!p || !a || !results) return fail(MCI_ERR_INVALID, "NULL argument");
     if (npoint < 1 || npoint > kSweepMaxPoints) return fail(MCI_ERR_INVALID, "npoint = %d: a sweep takes 1 to %d points", (int)npoint, (int)kSweepMaxPoints);
-    if (int rc = strat ? mci_sweep_strat_supported(p, a, nullptr, 0) : mci_sweep_supported(p, a, nullptr, 0)) return rc;
+    if (int rc = supported(p, a, nullptr, 0)) return rc;
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
     const int nud = (int)p->h_ud.size();
     if (nud > 0 && !userdata) return fail(MCI_ERR_INVALID, "userdata is NULL (the integrand reads %d values per point)", nud);
@@ -408,7 +419,7 @@ int sweep_check_args(const mci_problem *p, const mci_integrate_args *a, int32_t 
 // P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
 int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                         double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
-    if (int rc = sweep_check_args(p, a, npoint, userdata, results, false)) return rc;
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_supported)) return rc;
     if (!(a->neval > a->block)) return fail(MCI_ERR_INVALID, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block); // main.jl:222
     SweepCall c;
     c.unit = sweep_uses_leaves(p) ? mci_problem::Sweep::kLeaves : mci_problem::Sweep::kOne; // (else one Continuous leaf: a row is its grid)
@@ -525,7 +536,7 @@ static_assert(offsetof(mci::SweepStratArgs, h) == 0, "sweep_run fills the strati
 int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                               double *maps_out, const double *d_in, double *d_out, int64_t *counts_out, mci_result *results, double *iter_mean, double *iter_std,
                               int32_t *status) {
-    if (int rc = sweep_check_args(p, a, npoint, userdata, results, true)) return rc;
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_strat_supported)) return rc;
     const auto &s = p->shape;
     const size_t P = (size_t)npoint;
     int64_t ncube = 0;
@@ -603,6 +614,113 @@ int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32
         if (counts_out)
             for (size_t q = 0; q < P; ++q)
                 for (size_t h = 0; h < nc; ++h) counts_out[q * nc + h] = hoff[q * (nc + 1) + h + 1] - hoff[q * (nc + 1) + h];
+    };
+    return sweep_run(p, a, c);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// :vegasmc points in a sweep: mci_sweep_chains.h vegasmc_sweep, one workgroup runs a point's whole chain-solver loop
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// what sweep_common_refusal and sweep_leaves_refusal check, the solver test the other way round, and what the chain loop adds
+const char *sweep_chains_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
+    if (const char *r = sweep_common_refusal(p, a, buf, false, true)) return r;
+    if (a->nchain == 0) return "nchain = 0 (the automatic policy sizes chains from carried state a sweep does not have: give nchain >= 1)";
+    if (a->nchain < 0) return "nchain < 0";
+    if (a->reweight_goal || !p->h_goal.empty()) return "a reweight goal (a sweep point reweights without one)";
+    if (const char *r = sweep_leaves_refusal(p, buf)) return r; // (FermiK, the tables in LDS in one tile, the LDS budget: Lds<Cfg> counts the counters)
+    if (!(a->neval > a->block)) return "neval should be larger than nblock";
+    int64_t npb, blocks;
+    mci_standardize_block(a->neval, a->block, 1, &npb, &blocks);
+    // (a chain's streams are addressed by (block < 4096, iteration < 131072), mci_device.h vegasmc_chains: the limits of the ordinary
+    // chain launch, mci_host_iteration.h -- a block or an iteration beyond them would run another one's chains again)
+    if (blocks > 4096) {
+        buf = "block = " + std::to_string((long long)blocks) + " (chain solvers address a chain by block < 4096)";
+        return buf.c_str();
+    }
+    if (a->first_iteration < 0 || (int64_t)a->first_iteration + a->niter > 131072) {
+        buf = "first_iteration = " + std::to_string((long long)a->first_iteration) + ", niter = " + std::to_string((long long)a->niter) +
+              " (chain solvers address a chain by 0 <= iteration < 131072)";
+        return buf.c_str();
+    }
+    if (a->nchain > npb) {
+        buf = "nchain = " + std::to_string((long long)a->nchain) + " exceeds the " + std::to_string((long long)npb) + " steps of a block";
+        return buf.c_str();
+    }
+    return nullptr;
+}
+} // namespace
+
+int mci_sweep_chains_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
+    if (why && n > 0) why[0] = 0;
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    std::string buf;
+    const char *r = sweep_chains_refusal(p, a, buf);
+    if (!r) return MCI_OK;
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
+    return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep of :vegasmc points: %s", r);
+}
+
+// P independent :vegasmc integrate() loops (main.jl:142-207 around vegas_mc/montecarlo.jl:112-241), one workgroup each, in one launch
+static_assert(offsetof(mci::SweepChainArgs, h) == 0, "sweep_run fills the :vegasmc unit's argument through its head");
+int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                               double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, mci_result *results, double *iter_mean,
+                               double *iter_std, int32_t *status) {
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_chains_supported)) return rc;
+    const size_t P = (size_t)npoint, nd = (size_t)p->ni + 1, npa2 = 2 * (size_t)p->npa;
+    const size_t tables = (size_t)p->nstat + p->shape.nbin; // where merge_pa leaves them in a packed row (mci_train.h)
+    mci::SweepChainArgs f{};
+    std::vector<double> hrw;
+    SweepCall c;
+    c.unit = mci_problem::Sweep::kChains;
+    c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
+    c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
+    c.plan = [a, npa2](SweepCall &c) {
+        mci_standardize_block(a->neval, a->block, 1, &c.neval_per_block, &c.blocks); // main.jl:121 (at most 4096 blocks: sweep_chains_refusal)
+        c.rows = c.blocks;
+        c.pa_doubles = (size_t)c.blocks * npa2;
+        c.too_big_count = (long long)c.blocks;
+        return (int)MCI_OK;
+    };
+    c.map_doubles = (size_t)sweep_map_doubles(p);
+    c.maxn = sweep_max_nbin(p);
+    c.lds = sweep_leaves_lds(p, &c.map_off);
+    c.rw_doubles = nd;
+    c.packed_doubles = tables + npa2 + 64; // (+ 64: merge_pa's holding-time histogram, :mcmc's, zeros here)
+    c.too_big = "a sweep of %d :vegasmc points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it";
+    c.batch = [p, a, &c](mci::BatchArgs &b) {
+        int nslots = 0; // (pool, slot) pairs changeVariable can pick (plan_vegasmc_chains)
+        for (int v = 0; v < p->npool; ++v) nslots += p->maxdof[v];
+        b.nchain = a->nchain;
+        b.burnin = mci_chain_burnin(c.neval_per_block / a->nchain, a->nchain, nslots); // (fresh chains in every iteration)
+    };
+    c.copy_in = [&](double *d, const size_t *o, hipStream_t st) {
+        if (!reweight_in) { // every point starts from the problem's current factors (the device's: doReweight! moves them there)
+            hrw.resize(P * nd);
+            HIPCHK(hipMemcpyAsync(hrw.data(), p->d_reweight, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (size_t q = 1; q < P; ++q) memcpy(hrw.data() + q * nd, hrw.data(), nd * sizeof(double));
+        }
+        HIPCHK(hipMemcpyAsync(d + o[kSegRw], reweight_in ? reweight_in : hrw.data(), P * nd * sizeof(double), hipMemcpyHostToDevice, st));
+        return (int)MCI_OK;
+    };
+    c.args = [&, p, a](const mci::SweepHead &h, double *d, const size_t *o) -> void * {
+        f.h = h;
+        f.h.m.npa = p->npa;
+        f.h.t.do_reweight = 1; // main.jl:183
+        f.h.t.goal = nullptr;
+        f.h.t.gamma = a->gamma;
+        f.reweight = d + o[kSegRw];
+        f.part_pa = d + o[kSegPa];
+        f.packed_stride = (int)c.packed_doubles;
+        return &f;
+    };
+    c.copy_out = [&](double *d, const size_t *o, hipStream_t st) {
+        if (reweight_out) HIPCHK(hipMemcpyAsync(reweight_out, d + o[kSegRw], P * nd * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (pa_out)
+            HIPCHK(hipMemcpy2DAsync(pa_out, npa2 * sizeof(double), d + o[kSegPacked] + tables, c.packed_doubles * sizeof(double), npa2 * sizeof(double), P,
+                                    hipMemcpyDeviceToHost, st));
+        return (int)MCI_OK;
     };
     return sweep_run(p, a, c);
 }

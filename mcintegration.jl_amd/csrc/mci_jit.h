@@ -33,10 +33,11 @@ extern const char *const kDeviceHeader;       // mci_device.h
 extern const char *const kTrainHeader;        // mci_train.h (merge + train! device functions and the persistent :vegas kernel)
 extern const char *const kSpecHeader;         // mci_spec.h (the chain solvers with several lanes per chain)
 extern const char *const kStratHeader;        // mci_strat.h (the stratified :vegas sample kernel)
-extern const char *const kSweepCommonHeader;  // mci_sweep_common.h (what the three sweep kernels share)
+extern const char *const kSweepCommonHeader;  // mci_sweep_common.h (what the four sweep kernels share)
 extern const char *const kSweepHeader;        // mci_sweep.h (batched :vegas parameter sweeps)
 extern const char *const kSweepLeavesHeader;  // mci_sweep_leaves.h (sweeps of problems with several variable leaves)
 extern const char *const kSweepStratHeader;   // mci_sweep_strat.h (stratified points in sweeps)
+extern const char *const kSweepChainsHeader;  // mci_sweep_chains.h (batched :vegasmc parameter sweeps)
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -111,8 +112,11 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // walk and MCI_WORK_ITEM_FROM_CALLER like kUnitSweep, but the Discrete form of train! stays in and the learning rate is each leaf's own
 // kUnitSweepStrat: the stratified sample trip (mci_strat.h strat_trip) inside the sweep kernel of mci_sweep_strat.h (one workgroup runs a
 // point's whole VEGAS+ loop); compiled like kUnitSweep (scan walk, one Continuous grid, the leaf's learning rate)
-// The three sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitCount = 9 };
+// kUnitSweepChains: the :vegasmc chain loop (mci_device.h vegasmc_chains, one lane per chain) inside the sweep kernel of mci_sweep_chains.h
+// (one workgroup runs a point's whole :vegasmc loop); generated for MCI_VEGASMC, compiled like kUnitSweepLeaves -- the Discrete form of
+// train! and the doReweight! branch of iteration_bookkeeping stay in
+// The four sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitCount = 10 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -143,6 +147,7 @@ constexpr UnitRow kUnits[] = {
     // (MCI_TRAIN_POWER undefined: alpha is decided per leaf at run time; the Discrete form of train! sums a whole leaf)
     /* kUnitSweepLeaves  */ {"mci_sweep_leaves.h", {MCI_HDR_SWEEP, {"mci_sweep_leaves.h", &kSweepLeavesHeader}}, "mci_vegas_sweep_leaves", "SweepHead", "f", "vegas_sweep_leaves", 1, false, 2, true, false, true},
     /* kUnitSweepStrat   */ {"mci_sweep_strat.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}}, "mci_vegas_sweep_strat", "SweepStratArgs", "f", "vegas_sweep_strat", 1, true, 1, true, true, false},
+    /* kUnitSweepChains  */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep", "SweepChainArgs", "f", "vegasmc_sweep", -1, false, 2, true, false, true},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN
@@ -222,7 +227,7 @@ inline std::string generate_source(const ProblemShape &s, int solver, int unit =
          "#define obs_add(k, v) mci::lds_add(&mci_obs_[(k)], (v))\n"
       << s.measure_body << "\n#undef obs_add\n    }\n";
     o << "};\n}\n";
-    if (solver == 0 && u.kernel) {
+    if (u.kernel) { // (a unit with a kernel of its own: generated for the one solver its row is for)
         o << "extern \"C\" __global__ void __launch_bounds__(MCI_THREADS) " << u.kernel << "(mci::BatchArgs a, mci::" << u.arg_type << " " << u.arg_name << ") { "
           << "mci::" << u.fn << "<Cfg>(a, " << u.arg_name << "); }\n";
     } else if (solver == 0 && unit == kUnitDump) {

@@ -1,0 +1,106 @@
+// mci_sweep_chains.h -- batched :vegasmc parameter sweeps (mci_integrate_sweep_chains): vegas_sweep_leaves of mci_sweep_leaves.h with the
+// chain solver's sample loop (vegasmc_chains, mci_device.h; vegas_mc/montecarlo.jl:112-241) in place of vegas_batch, and the chain
+// solver's per-iteration state: a point's reweight factors (doReweight!, main.jl:183, :322-346) and its propose | accept tables.
+// Compiled by hiprtc next to mci_device.h, mci_train.h and mci_sweep_common.h into a translation unit of its own (mci_jit.h
+// kUnitSweepChains, generated for MCI_VEGASMC): every other code object stays what it was.  Free of host / std headers.
+//
+//     workgroup g   for p = g, g + G, ...:   map of point p -> LDS (the SweepBlock of mci_sweep_common.h);
+//                   for every iteration:  for every statistical block, one after another: its `nchain` chains, one lane per chain,
+//                   lanes striding over the chains (vegasmc_chains with wg_per_block = 1: row = block) -> merge the block rows
+//                   (merge_stats) and the blocks' propose | accept rows (merge_pa) -> statistics head -> this point's log row ->
+//                   doReweight! on this point's factors (iteration_bookkeeping, thread 0) -> leaf by leaf the merged histogram slice
+//                   and train! on the leaf's part of the LDS map;   at the end the map -> maps_out[p]
+//
+// Streams are keyed by (seed, iteration, block, chain, step) as in the ordinary launch, and every chain starts afresh in every iteration
+// (carry_x = store_x = NULL: the semantics of mci_set_chain_carry(prob, 0)), so a point's chains are the chains mci_iteration_run runs for
+// the same nchain with one lane per chain.
+//
+// The synchronisation is mci_sweep_common.h's.  What this unit adds to a point's traffic through global memory is written and read by
+// the point's own workgroup, with a sweep_round_trip() between the two sides:
+//   * the blocks' propose | accept rows (flush_workgroup, plain stores by all threads) -> merge_pa, behind the round trip that follows
+//     the last block;
+//   * the reweight factors: thread 0 writes them in iteration_bookkeeping, every lane reads them at the start of the next vegasmc_chains
+//     call -- the round trip of the first leaf's histogram slice stands in between (NLEAF >= 1), and thread 0's own wait covers its stores.
+// merge_pa sums four entries per call, one wave each: the workgroup has at least four waves (the host launches kSweepThreads = 256).
+//
+// LDS: the chain loop's carve Lds<Cfg> (tables | histogram | observables | reduction scratch | propose / accept counters) and the
+// refinement's scratch share the front of the segment -- each is dead while the other runs --, the point's map block lies behind both
+// (SweepHead::map_off; the host's sweep_leaves_lds counts the carve including the counters).
+#pragma once
+#include "mci_sweep_common.h"
+
+namespace mci {
+
+struct SweepChainArgs {
+    SweepHead h;          // h.m.npa = the problem's, h.m.nrows = the blocks; h.t.do_reweight = 1, h.t.nd, h.t.gamma (h.t.goal: none)
+    double *reweight;     // [npoint][nd]  in: where every point starts; out: its factors after the last doReweight!
+    double *part_pa;      // [npoint][nblocks][2 * npa]  the blocks' propose | accept rows
+    int packed_stride;    // doubles of a point's packed row: statistics [nstat] | (histogram [nbin], unused) | propose | accept [2 npa] | holds [64]
+};
+
+template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) {
+    static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0 &&
+                      Cfg::HOST_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0,
+                  "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS, and measures on the device (the host checks)");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const SweepHead &f = fc.h;
+    const int tid = threadIdx.x, T = blockDim.x;
+    constexpr int MAXN = sweep_max_nbin<Cfg>(), NROW = sweep_row_off<Cfg>(Cfg::NLEAF), NPA2 = 2 * PaTable<Cfg>::N;
+    using B = SweepBlock<Cfg>;
+    double *sm = smem, *hl = sm + train_lds_doubles(MAXN), *ps = hl + MAXN, *blk = smem + f.map_off;
+    double *bedges = blk + B::E, *bdacc = blk + B::DA, *bddist = blk + B::DD, *flags = blk + B::FLAGS;
+    int *bad = reinterpret_cast<int *>(flags); // bad[0], bad[1]: the verdicts of the even and the odd leaves; flags[2]: train_leaf's spare word
+    const int nblocks = f.m.nblocks;
+    for (int p = (int)blockIdx.x; p < f.npoint; p += (int)gridDim.x) {
+        __syncthreads(); // (the point before: its last LDS reads are through)
+        if (f.maps_in) sweep_copy_row<Cfg, false>(blk, nullptr, f.maps_in + (size_t)p * NROW);
+        else {
+            for (int i = tid; i < Cfg::NEDGE; i += T) bedges[i] = f.t.edges[i];
+            for (int i = tid; i < Cfg::NDACC; i += T) bdacc[i] = f.t.dacc[i];
+            for (int i = tid; i < Cfg::NDDIST; i += T) bddist[i] = f.t.ddist[i];
+        }
+        MergeArgs m;
+        BatchArgs a;
+        sweep_point<Cfg>(f, a0, p, nblocks, m, a);
+        double *rw = fc.reweight + (size_t)p * f.t.nd;
+        m.packed = f.m.packed + (size_t)p * fc.packed_stride; // (this unit's rows are longer than the statistics head: the tables follow)
+        m.part_pa = fc.part_pa + (size_t)p * nblocks * NPA2;
+        a.part_pa = fc.part_pa + (size_t)p * nblocks * NPA2;
+        a.reweight = rw;
+        a.edges = bedges; // (LDS through the generic address space: stage_tables reads the three tables once per call)
+        a.dacc = bdacc;
+        a.ddist = bddist;
+        for (int it = 0; it < f.niter; ++it) {
+            a.iteration = a0.iteration + (u32)it;
+            if (tid == 0) bad[0] = 0;
+            for (int b = 0; b < nblocks; ++b) {
+                a.chunk_lo = b;  // work_item: row = block (wg_per_block = 1)
+                __syncthreads(); // (map, flag and -- from the second iteration on -- whatever read this LDS before are through)
+                vegasmc_chains<Cfg>(a); // tables <- the map block, the block's chains, its partial row and its propose | accept row, histogram atomics into this point's row
+            }
+            sweep_round_trip();
+            merge_stats(m); // main.jl:273-287
+            for (int e = 0; e < merge_pa_blocks(m); ++e) merge_pa(m, e); // configuration.jl:297-298
+            __syncthreads(); // the head of `packed` was written by this workgroup
+            TrainArgs t = sweep_log_row(f, p, it);
+            t.packed = m.packed;
+            t.reweight = rw;
+            iteration_bookkeeping(t); // log row; doReweight! by thread 0 (main.jl:183: whatever `adapt` says)
+#pragma unroll 1
+            for (int l = 0; l < Cfg::NLEAF; ++l) {
+                const LeafDev L = f.t.leaves[l];
+                const int N = L.nbin;
+                const bool train = f.t.do_train && L.adapt; // variable.jl:208
+                int *verdict = bad + (l & 1);
+                if (tid == 0) bad[(l + 1) & 1] = 0; // (the next leaf's; its last reader passed the barrier that closed the leaf before this one)
+                sweep_take_hist(m.ghist + L.boff, hl, N, (tid + T - L.boff % T) % T, (double)(nblocks + 1) * 1.0e-10, verdict);
+                sweep_round_trip(); // (hl, the verdict, the reweight factors; the zeroed slice is out before the next iteration adds to it)
+                if (train) train_leaf(L, hl, nullptr, sm, ps, *verdict, flags[2], bedges, bdacc, bddist, 0, m.status, false, nullptr, true);
+                __syncthreads();
+            }
+        }
+        sweep_copy_row<Cfg, true>(blk, f.maps_out + (size_t)p * NROW, nullptr);
+    }
+}
+
+} // namespace mci

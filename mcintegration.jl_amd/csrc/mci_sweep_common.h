@@ -1,9 +1,9 @@
-// mci_sweep_common.h -- what the three batched-sweep kernels share: mci_sweep.h (one Continuous grid), mci_sweep_leaves.h (any mix of
-// Continuous and Discrete leaves) and mci_sweep_strat.h (stratified points).  Each of them is a translation unit of its own (mci_jit.h
+// mci_sweep_common.h -- what the four batched-sweep kernels share: mci_sweep.h (one Continuous grid), mci_sweep_leaves.h (any mix of
+// Continuous and Discrete leaves), mci_sweep_strat.h (stratified points) and mci_sweep_chains.h (:vegasmc points).  Each of them is a translation unit of its own (mci_jit.h
 // kUnits) and includes this header; the host (mci_host_sweep.h) compiles the same text, so the argument layout cannot drift.  Free of
 // host / std headers.
 //
-// In all three ONE workgroup owns a point and runs its whole loop, and no workgroup ever waits for another one: no grid-wide counters, no
+// In all four ONE workgroup owns a point and runs its whole loop, and no workgroup ever waits for another one: no grid-wide counters, no
 // spinning, no residency condition, and every loop's trip count is a kernel argument or a constant of the translation unit.
 //
 // The ordering argument.  What travels through global memory inside a point -- the partial rows, merge_stats' scratch and head, the
@@ -91,6 +91,58 @@ __device__ __forceinline__ void sweep_take_hist(double *gh, double *hl, int N, i
         }
     }
     if (hbad) atomicOr(verdict, hbad);
+}
+
+// ---- the map of a point with several leaves (mci_sweep_leaves.h, mci_sweep_chains.h): its maps_in / maps_out row and its block in LDS
+// One maps_in / maps_out row: the leaves in order; a Continuous leaf its nbin + 1 grid points, a Discrete leaf its accumulation
+// [nbin + 1] and then its distribution [nbin]  (the host's sweep_map_doubles, mci_host_sweep.h)
+template <class Cfg> constexpr int sweep_row_off(int l) {
+    int n = 0;
+    for (int k = 0; k < l; ++k) n += Cfg::leaf_kind(k) == 0 ? Cfg::leaf_nbin(k) + 1 : 2 * Cfg::leaf_nbin(k) + 1;
+    return n;
+}
+template <class Cfg> constexpr int sweep_max_nbin() {
+    int n = 1;
+    for (int k = 0; k < Cfg::NLEAF; ++k) n = Cfg::leaf_nbin(k) > n ? Cfg::leaf_nbin(k) : n;
+    return n;
+}
+template <class Cfg> constexpr bool sweep_kinds_ok() {
+    for (int k = 0; k < Cfg::NLEAF; ++k)
+        if (Cfg::leaf_kind(k) != 0 && Cfg::leaf_kind(k) != 1) return false;
+    return true;
+}
+// the map block's parts, doubles from map_off (the host's sweep_leaves_lds lays out the same)
+template <class Cfg> struct SweepBlock {
+    static constexpr int E = 0;
+    static constexpr int DA = E + ((Cfg::NEDGE + 1) & ~1);
+    static constexpr int DD = DA + ((Cfg::NDACC + 1) & ~1);
+    static constexpr int FLAGS = DD + ((Cfg::NDDIST + 1) & ~1);
+    static constexpr int END = FLAGS + 4;
+};
+
+// row <-> block, leaf by leaf (TO_ROW: block -> maps_out row; else row -> block)
+template <class Cfg, bool TO_ROW> __device__ __forceinline__ void sweep_copy_row(double *blk, double *row_out, const double *row_in) {
+    const int tid = threadIdx.x, T = blockDim.x;
+    static_for<0, Cfg::NLEAF>([&](auto Lf) {
+        constexpr int l = decltype(Lf)::value, N = Cfg::leaf_nbin(l), ro = sweep_row_off<Cfg>(l);
+        if constexpr (Cfg::leaf_kind(l) == 0) {
+            double *g = blk + SweepBlock<Cfg>::E + Cfg::leaf_eoff(l);
+            for (int i = tid; i <= N; i += T) {
+                if constexpr (TO_ROW) row_out[ro + i] = g[i];
+                else g[i] = row_in[ro + i];
+            }
+        } else {
+            double *acc = blk + SweepBlock<Cfg>::DA + Cfg::leaf_eoff(l), *dist = blk + SweepBlock<Cfg>::DD + Cfg::leaf_doff(l);
+            for (int i = tid; i <= N; i += T) {
+                if constexpr (TO_ROW) row_out[ro + i] = acc[i];
+                else acc[i] = row_in[ro + i];
+            }
+            for (int i = tid; i < N; i += T) {
+                if constexpr (TO_ROW) row_out[ro + N + 1 + i] = dist[i];
+                else dist[i] = row_in[ro + N + 1 + i];
+            }
+        }
+    });
 }
 
 } // namespace mci

@@ -25,57 +25,6 @@
 
 namespace mci {
 
-// One maps_in / maps_out row: the leaves in order; a Continuous leaf its nbin + 1 grid points, a Discrete leaf its accumulation
-// [nbin + 1] and then its distribution [nbin]  (the host's sweep_map_doubles, mci_host_sweep.h)
-template <class Cfg> constexpr int sweep_row_off(int l) {
-    int n = 0;
-    for (int k = 0; k < l; ++k) n += Cfg::leaf_kind(k) == 0 ? Cfg::leaf_nbin(k) + 1 : 2 * Cfg::leaf_nbin(k) + 1;
-    return n;
-}
-template <class Cfg> constexpr int sweep_max_nbin() {
-    int n = 1;
-    for (int k = 0; k < Cfg::NLEAF; ++k) n = Cfg::leaf_nbin(k) > n ? Cfg::leaf_nbin(k) : n;
-    return n;
-}
-template <class Cfg> constexpr bool sweep_kinds_ok() {
-    for (int k = 0; k < Cfg::NLEAF; ++k)
-        if (Cfg::leaf_kind(k) != 0 && Cfg::leaf_kind(k) != 1) return false;
-    return true;
-}
-// the map block's parts, doubles from map_off (the host's sweep_leaves_lds lays out the same)
-template <class Cfg> struct SweepBlock {
-    static constexpr int E = 0;
-    static constexpr int DA = E + ((Cfg::NEDGE + 1) & ~1);
-    static constexpr int DD = DA + ((Cfg::NDACC + 1) & ~1);
-    static constexpr int FLAGS = DD + ((Cfg::NDDIST + 1) & ~1);
-    static constexpr int END = FLAGS + 4;
-};
-
-// row <-> block, leaf by leaf (TO_ROW: block -> maps_out row; else row -> block)
-template <class Cfg, bool TO_ROW> __device__ __forceinline__ void sweep_copy_row(double *blk, double *row_out, const double *row_in) {
-    const int tid = threadIdx.x, T = blockDim.x;
-    static_for<0, Cfg::NLEAF>([&](auto Lf) {
-        constexpr int l = decltype(Lf)::value, N = Cfg::leaf_nbin(l), ro = sweep_row_off<Cfg>(l);
-        if constexpr (Cfg::leaf_kind(l) == 0) {
-            double *g = blk + SweepBlock<Cfg>::E + Cfg::leaf_eoff(l);
-            for (int i = tid; i <= N; i += T) {
-                if constexpr (TO_ROW) row_out[ro + i] = g[i];
-                else g[i] = row_in[ro + i];
-            }
-        } else {
-            double *acc = blk + SweepBlock<Cfg>::DA + Cfg::leaf_eoff(l), *dist = blk + SweepBlock<Cfg>::DD + Cfg::leaf_doff(l);
-            for (int i = tid; i <= N; i += T) {
-                if constexpr (TO_ROW) row_out[ro + i] = acc[i];
-                else acc[i] = row_in[ro + i];
-            }
-            for (int i = tid; i < N; i += T) {
-                if constexpr (TO_ROW) row_out[ro + N + 1 + i] = dist[i];
-                else dist[i] = row_in[ro + N + 1 + i];
-            }
-        }
-    });
-}
-
 template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const BatchArgs &a0, const SweepHead &f) {
     static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS (the host checks)");

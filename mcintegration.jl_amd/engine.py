@@ -439,7 +439,8 @@ class Engine:
     # ---- kernels -------------------------------------------------------------------------------
     @staticmethod
     def _kernel_code(solver):
-        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10}.get(solver) or _lib.SOLVERS[solver]
+        return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
+                "vegasmc_sweep": 11}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -447,7 +448,8 @@ class Engine:
         stratified :vegas kernel, csrc/mci_strat.h; the problem must be stratified: set_stratification) | "vegas_sweep" (the kernel of
         integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts) | "vegas_sweep_leaves" (the sweep kernel of a problem with
         several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all")) | "vegas_sweep_strat" (the kernel of
-        integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts)"""
+        integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts) | "vegasmc_sweep" (the kernel of
+        integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -714,13 +716,14 @@ class Engine:
             out["block_mean"] = self.block_means(niter)[0]
         return out
 
-    def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration):
+    def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain=0):
         return _lib.IntegrateArgs(_lib.SOLVERS[solver], int(neval), int(niter), int(block), int(ignore), 1 if adapt else 0, float(gamma),
-                                  int(measurefreq), int(seed), 0, int(first_iteration), 0.1, None)
+                                  int(measurefreq), int(seed), int(nchain), int(first_iteration), 0.1, None)
 
-    def _sweep_refusal(self, query, solver, neval, niter, block, measurefreq):
-        """None when the query (mci_sweep_supported | mci_sweep_strat_supported) takes this problem with these arguments, else its reason"""
-        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, 0)
+    def _sweep_refusal(self, query, solver, neval, niter, block, measurefreq, nchain=0, first_iteration=0):
+        """None when the query (mci_sweep_supported | mci_sweep_strat_supported | mci_sweep_chains_supported) takes this problem with these
+        arguments, else its reason"""
+        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, first_iteration, nchain)
         why = C.create_string_buffer(512)
         if query(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
             return None
@@ -799,7 +802,7 @@ class Engine:
         return ud, sd, mi, between
 
     def _sweep_call(self, fn, a, P, niter, arrays, extra):
-        """fn (mci_integrate_sweep | mci_integrate_sweep_strat) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
+        """fn (mci_integrate_sweep | mci_integrate_sweep_strat | mci_integrate_sweep_chains) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
         entry point's own arguments between maps_out and results, and the keys they add to every dict ({key: [P][...] array})"""
         ud, sd, mi = arrays
         n, nmap = self.nobs, self.sweep_map_doubles()
@@ -873,6 +876,34 @@ class Engine:
             do, co = np.zeros((P, ncube)), np.zeros((P, ncube), dtype=np.int64)
             return (_dp(di) if di is not None else None, _dp(do), co.ctypes.data_as(C.POINTER(C.c_int64))), dict(strat_d=do, strat_counts=co)
         return self._sweep_call(lib().mci_integrate_sweep_strat, a, P, niter, (ud, sd, mi), extra)
+
+    def sweep_chains_supported(self, solver="vegasmc", neval=10000, niter=10, block=16, measurefreq=1, nchain=1, first_iteration=0, **kw):
+        """None when integrate_sweep_chains takes this problem with these arguments, else the reason (mci_sweep_chains_supported)"""
+        return self._sweep_refusal(lib().mci_sweep_chains_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration)
+
+    def integrate_sweep_chains(self, solver="vegasmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
+                               measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None):
+        """A parameter sweep under the default solver in one launch (mci_integrate_sweep_chains): P independent :vegasmc loops -- what
+        integrate("vegasmc", nchain=nchain) runs on this engine with set_chain_carry(0) and one lane per chain -- one workgroup per
+        point, the blocks of a point one after another.  Arguments and result dicts as integrate_sweep (any mix of Continuous and
+        Discrete leaves); every dict gains `reweight` (the point's factors after its last doReweight!, [N + 1]), `propose` and `accept`
+        (the tables of its last iteration, shaped like acceptance()).  reweight: None (every point starts from the engine's current
+        factors) or [P][N + 1], e.g. the `reweight` of an earlier sweep.  nchain >= 1: chains per block.  The engine's own map, factors,
+        packed buffer, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_chains_supported()."""
+        ud, sd, mi, _ = self._sweep_inputs("integrate_sweep_chains", userdata, seeds, maps)
+        P, nd = ud.shape[0], self.config.N + 1
+        m = max(nd, len(self.config.var))
+        ri = None
+        if reweight is not None:
+            ri = np.ascontiguousarray(reweight, dtype=np.float64)
+            if ri.shape != (P, nd):
+                raise ValueError("integrate_sweep_chains: reweight must be [points = %d][integrands + 1 = %d], got shape %s" % (P, nd, ri.shape))
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain)
+
+        def extra(P):
+            ro, pa = np.zeros((P, nd)), np.zeros((P, 2, 3, nd, m))
+            return (_dp(ri) if ri is not None else None, _dp(ro), _dp(pa)), dict(reweight=ro, propose=pa[:, 0], accept=pa[:, 1])
+        return self._sweep_call(lib().mci_integrate_sweep_chains, a, P, niter, (ud, sd, mi), extra)
 
     def sweep_workgroups(self, g=0):
         """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""

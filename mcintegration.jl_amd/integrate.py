@@ -180,6 +180,7 @@ def _bind(config, integrand, measure, solver, *, inplace=False, trace=None, prin
     """The engine of `config` for this integrand and measure (created, or kept when nothing it was built for has changed): closures are
     put into the form the solver calls them in and traced where they can be; grids and reweight factors trained so far survive a change
     of integrand.  Shared by integrate() and the solver seam (Vegas / VegasMC / MCMC .montecarlo)."""
+    config._sweep_tables = None   # (a point of a chain sweep handed on as config=: propose / accept are the engine's again)
     if isinstance(integrand, str):
         integrand = Integrand(integrand, config.userdata)
     elif callable(integrand) and not isinstance(integrand, (Integrand, HostIntegrand)):
@@ -441,7 +442,7 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
                     measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    **kwargs):
+                    chains=None, reweight=None, **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -471,6 +472,15 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     with adapt=False the whole scan keeps it: train, then freeze.  A sweep carries through alloc, never through Stratify(carry=True).
     Where the stratified sweep is refused the points run as integrate(..., stratify=...) calls, as below; alloc= then raises.
 
+    chains: None (default) or an int >= 1 -- with solver="vegasmc", the reference's default solver, every point runs its :vegasmc loop
+    with that many chains per block, fresh in every iteration, still in ONE launch (Engine.integrate_sweep_chains: one workgroup per
+    point, a lane per chain; any mix of Continuous and Discrete leaves, whatever `leaves` says).  Every Result then also carries
+    `reweight` (the point's factors after its last doReweight!), and its config.visited / config.propose / config.accept are the
+    point's own; correlated = False.  reweight = [r.reweight for r in head] together with maps = [r.map for r in head] goes on with a
+    scan.  Without chains= a chain solver is not swept (the loop below, as ever); chains= with solver="vegas", with stratify= or under
+    "mcmc" raises ValueError.  Where the chain sweep is refused (Engine.sweep_chains_supported) the points run as
+    integrate(..., nchain=chains) calls, as below; reweight= then raises.
+
     A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
     measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
     a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
@@ -494,6 +504,19 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
     if maps is not None and len(maps) != P:
         raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
+    if chains is not None:
+        if isinstance(chains, bool) or not isinstance(chains, (int, np.integer)) or chains < 1:
+            raise ValueError("integrate_sweep: chains must be an int >= 1 (chains per block), got %r" % (chains,))
+        if solver != "vegasmc":
+            raise ValueError('integrate_sweep: chains= belongs to solver="vegasmc" (%s)'
+                             % ('"vegas" is swept without it' if solver == "vegas" else 'a sweep of "mcmc" points is a follow-up'))
+        if stratify is not None and stratify is not False:
+            raise ValueError("integrate_sweep: chains= and stratify= do not go together (stratification is :vegas's)")
+        chains = int(chains)
+    if reweight is not None and chains is None:
+        raise ValueError('integrate_sweep: reweight= belongs to a chain sweep (solver="vegasmc", chains=K)')
+    if reweight is not None and len(reweight) != P:
+        raise ValueError("integrate_sweep: reweight must hold one vector per point (%d), got %d" % (P, len(reweight)))
     if alloc is not None and (stratify is None or stratify is False):
         raise ValueError("integrate_sweep: alloc= belongs to a stratified sweep (stratify=True or mci.Stratify(...))")
     if alloc is not None:
@@ -557,6 +580,10 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             else:
                 eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)
                 why = eng.sweep_strat_supported(solver, nevalperblock * block, niter, block, measurefreq)
+        elif chains is not None:
+            why = (eng.sweep_chains_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=chains,
+                                              first_iteration=config.iterations_done)
+                   if hasattr(eng, "sweep_chains_supported") else "this engine has no chain sweep")
         else:
             why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
     if why is None and strat is not None:
@@ -577,6 +604,24 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
                                       carried="same plan" if alloc is not None else "uniform")
             res.strat_d, res.strat_counts = StratD(r["strat_d"], plan["nstrat"], plan["beta"]), r["strat_counts"]
             res.vegas_check, res.warmup, res.neval_discarded = None, 0, 0
+            if print >= 0:
+                report(res)
+            out.append(res)
+        return out
+    if why is None and chains is not None:
+        rs = eng.integrate_sweep_chains(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
+                                        gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
+                                        first_iteration=config.iterations_done, nchain=chains, reweight=reweight)
+        out = []
+        for p, r in zip(params, rs):
+            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, factors and logs alone)
+            c.userdata = p if closure else None
+            c.visited = r["visited"]
+            c._sweep_tables = (r["propose"], r["accept"])   # config.propose / config.accept: this point's, not the engine's
+            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block, correlated=False)
+            res.sweep_batched, res.map, res.status, res.reweight = True, r["maps"], r["status"], r["reweight"]
+            res.maps_by_leaf = r.get("maps_by_leaf")
+            res.stratification, res.vegas_check, res.warmup, res.neval_discarded, res.chain_bias = None, None, 0, 0, None
             if print >= 0:
                 report(res)
             out.append(res)
@@ -606,6 +651,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and maps= needs the batched form" % why)
     if alloc is not None:
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and alloc= needs the batched form" % why)
+    if reweight is not None:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and reweight= needs the batched form" % why)
     warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),
                   RuntimeWarning, stacklevel=2)
     if eng is not None and hasattr(eng, "close"):
@@ -621,7 +668,7 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         if seeds is not None:
             c.seed = int(seeds[k])
         res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
-                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}))
+                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}), **({"nchain": chains} if chains is not None else {}))
         res.sweep_batched, res.map, res.maps_by_leaf, res.status = False, None, None, 0
         out.append(res)
     return out
@@ -652,6 +699,7 @@ def prefill_kernel_cache():
             eng.compile("vegasmc_lanes")   # ... whose launches of few chains (the example's neval = 1e6) give every chain a group of lanes
             eng.set_sweep_leaves("all")    # ... and which is scanned over rs as one launch (integrate_sweep(..., leaves="all"))
             eng.compile("vegas_sweep_leaves")
+            eng.compile("vegasmc_sweep")   # ... or, under its own solver, with integrate_sweep(..., solver="vegasmc", chains=K)
         eng.close()
         n += 1
     # C5: 4 integrands on a 12-D pool, :mcmc
