@@ -13,7 +13,10 @@ over the density parameter rs at a fixed dimensionless temperature: kF, the exte
 follow rs.  Four Continuous variable types, a Discrete external-momentum index and a histogram over it: `leaves="all"` lets such a
 problem run as a sweep.  The momenta are a table the integrand looks up by the Discrete draw (every point's row carries its own), and
 every point starts from a map of its own -- its T grid spans its own (0, beta).  `bubble_scan(solver="vegasmc", chains=64)` runs the
-same scan under the reference's default solver: 64 fresh chains per block and point, still one launch."""
+same scan under the reference's default solver: 64 fresh chains per block and point, still one launch.  `bubble_scan(solver="mcmc",
+mcmc_chains=64)` runs it under :mcmc, the solver the reference runs this example with: the closures are then called in that solver's
+form, integrand(idx, var, config) and measure(idx, var, obs, relative_weight, config), and every point reports its longest holding
+time."""
 import math
 import os
 import sys
@@ -56,13 +59,13 @@ def stratified(points=64):
     (adapt=False) for a second one under other seeds"""
     u = np.array([0.3 + 0.4 * d / (D - 1) for d in range(D)])
     scan = [types.SimpleNamespace(a=float(a), u=u) for a in np.linspace(2.0, 8.0, points)]
-    kw = dict(var=mci.Continuous(0.0, 1.0), dof=[[D]], solver="vegas", neval=1e4, niter=10)
-    trained = mci.integrate_sweep(peak, params=scan, stratify=True, seed=7, **kw)
+    kw = lambda: dict(var=mci.Continuous(0.0, 1.0), dof=[[D]], solver="vegas", neval=1e4, niter=10)   # (a variable object per call: a bound one belongs to its engine)
+    trained = mci.integrate_sweep(peak, params=scan, stratify=True, seed=7, **kw())
     s = trained[0].stratification
     print("stratified, batched:", all(r.sweep_batched for r in trained), "| nstrat %s (%d hypercubes) | %.2f ms for %d points"
           % (s["nstrat"], s["ncube"], 1e3 * trained[0].seconds, len(scan)))
     frozen = mci.integrate_sweep(peak, params=scan, stratify=True, adapt=False, alloc=[r.strat_d for r in trained], maps=[r.map for r in trained],
-                                 seeds=[100 + k for k in range(points)], **kw)
+                                 seeds=[100 + k for k in range(points)], **kw())
     for p, r, f in list(zip(scan, trained, frozen))[::max(1, points // 8)]:
         print("a = %5.2f   adapting %12.5f +- %-10.5f  frozen (%s) %12.5f +- %-10.5f  exact %12.5f" % (p.a, r.mean[0], r.stdev[0], f.stratification["carried"],
                                                                                                      f.mean[0], f.stdev[0], exact(p)))
@@ -99,13 +102,22 @@ def q_histogram(vars, obs, weight, config):                                  # t
     obs[0][Ext[0] - 1] += weight[0]
 
 
+def bubble_mcmc(idx, vars, config):                                           # integrand(idx, var, config): mcmc/montecarlo.jl:34
+    return bubble(vars, config)
+
+
+def q_histogram_mcmc(idx, vars, obs, relative_weight, config):               # measure(idx, var, obs, relative_weight, config): :166-169
+    Ext = vars[-1]
+    obs[0][Ext[0] - 1] += relative_weight
+
+
 def bubble_para(rs, beta=25.0, spin=2, Qsize=4, dim=3, me=0.5):             # test/bubble.jl:12-22
     kF = (9 * PI / (2 * spin)) ** (1 / 3) / rs
     return types.SimpleNamespace(rs=rs, kF=kF, beta=beta / (kF ** 2 / 2 / me), me=me, spin=spin, dim=dim, Qsize=Qsize,
                                  extQ=[np.array([q, 0.0, 0.0]) for q in np.linspace(0.0, 1.5 * kF, Qsize)])
 
 
-def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None):
+def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None, mcmc_chains=None):
     scan = [bubble_para(float(rs)) for rs in np.linspace(1.0, 2.0, points)]
     Qsize = scan[0].Qsize
     var = (mci.Continuous(0.0, 1.0, alpha=3.0), mci.Continuous(0.0, PI, alpha=3.0), mci.Continuous(0.0, 2 * PI, alpha=3.0),
@@ -114,11 +126,15 @@ def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None):
     uniform = np.full(Qsize, 1.0 / Qsize)
     maps = [np.concatenate([np.linspace(0.0, hi, ninc) for hi in (1.0, PI, 2 * PI, p.beta)] + [np.concatenate([[0.0], np.cumsum(uniform)]), uniform])
             for p in scan]
-    results = mci.integrate_sweep(bubble, params=scan, leaves="all", maps=maps, measure=q_histogram, var=var, dof=[[1, 1, 1, 1, 1]],
-                                  obs=[np.zeros(Qsize)], solver=solver, chains=chains, neval=1e5, niter=10, seed=7)
+    f, measure = (bubble_mcmc, q_histogram_mcmc) if solver == "mcmc" else (bubble, q_histogram)
+    results = mci.integrate_sweep(f, params=scan, leaves="all", maps=maps, measure=measure, var=var, dof=[[1, 1, 1, 1, 1]],
+                                  obs=[np.zeros(Qsize)], solver=solver, chains=chains, mcmc_chains=mcmc_chains, neval=1e5, niter=10, seed=7)
     print("bubble (%s) batched:" % solver, all(r.sweep_batched for r in results), "| %.2f ms for %d points" % (1e3 * results[0].seconds, len(scan)))
-    if chains is not None:   # the chain solver's own state, point by point
+    if chains is not None or mcmc_chains is not None:   # the chain solver's own state, point by point
         print("reweight factors of the first and the last point:", results[0].reweight, results[-1].reweight)
+    if mcmc_chains is not None:   # (report(result) says so where 16 x the longest hold exceeds a chain's measured steps)
+        print("longest holding time (upper bound) over the points: %d of %d measured steps per chain"
+              % (max(r.hold_max for r in results), results[0].chain_steps))
     print("%6s  %s" % ("rs", "  ".join("q = %.1f kF: avg +- err      " % (q[0] / scan[0].kF) for q in scan[0].extQ)))
     for p, r in list(zip(scan, results))[::max(1, points // 8)]:
         print("%6.3f  %s" % (p.rs, "  ".join("%12.6f +- %-10.6f" % (r.mean[0][i], r.stdev[0][i]) for i in range(Qsize))))
@@ -130,3 +146,4 @@ if __name__ == "__main__":
     stratified()
     bubble_scan()
     bubble_scan(solver="vegasmc", chains=64)
+    bubble_scan(solver="mcmc", mcmc_chains=64)

@@ -48,6 +48,8 @@ enum { MCI_VEGAS_SWEEP_LEAVES = 9 };
 enum { MCI_VEGAS_SWEEP_STRAT = 10 };
 /* ... and the sweep kernel of the default solver (mci_integrate_sweep_chains; problems mci_sweep_chains_supported accepts) */
 enum { MCI_VEGASMC_SWEEP = 11 };
+/* ... and the sweep kernel of :mcmc (mci_integrate_sweep_mcmc; problems mci_sweep_mcmc_supported accepts) */
+enum { MCI_MCMC_SWEEP = 12 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -269,7 +271,8 @@ int mci_integrate_sweep(mci_problem *prob, const mci_integrate_args *args, int32
 /* MCI_OK when mci_integrate_sweep takes this problem with these arguments; else MCI_ERR_INVALID with the reason in why[n] (and in
  * mci_last_error): solver other than :vegas, measurefreq != 1, several ranks, stratification, a host integrand or measure,
  * deterministic mode, more than one variable leaf, a Discrete or FermiK leaf, tables that do not sit in LDS in one tile, or more than
- * 64 KiB of LDS with the workgroup's copy of the map.  The number of draws per sample is no reason. */
+ * 64 KiB of LDS with the workgroup's copy of the map.  The number of draws per sample is no reason.  (The chain solvers have entry
+ * points of their own: mci_integrate_sweep_chains runs :vegasmc points, mci_integrate_sweep_mcmc runs :mcmc points.) */
 int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
 /* Which problems run as a sweep.  MCI_SWEEP_ONE_GRID (default): one Continuous leaf, as described above.  MCI_SWEEP_ALL_LEAVES: also
  * any :vegas problem whose leaves are all Continuous or Discrete (FermiK: "vegas doesn't work with FermiK"), with the tables and the
@@ -328,13 +331,44 @@ int mci_integrate_sweep_chains(mci_problem *prob, const mci_integrate_args *args
                                const double *maps_in, double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out,
                                mci_result *results, double *iter_mean, double *iter_std, int32_t *status);
 /* MCI_OK when mci_integrate_sweep_chains takes this problem with these arguments; else MCI_ERR_INVALID with the reason in why[n] (and in
- * mci_last_error): :vegas (mci_integrate_sweep runs it) or :mcmc (a follow-up), nchain = 0 or more chains than a block has steps,
+ * mci_last_error): :vegas (mci_integrate_sweep runs it) or :mcmc (a follow-up of this entry point: mci_integrate_sweep_mcmc runs :mcmc
+ * points), nchain = 0 or more chains than a block has steps,
  * more than 4096 blocks, first_iteration < 0 or first_iteration + niter > 131072 (a chain's streams are addressed by block < 4096 and
  * iteration < 131072, as in mci_iteration_run),
  * measurefreq != 1, several ranks, stratification, a host integrand or measure, deterministic mode, a reweight goal, a FermiK variable,
  * tables that do not sit in LDS in one tile, or more than 159 KiB of LDS for the chain loop's tables and counters or the refinement
  * scratch plus the point's whole map (named). */
 int mci_sweep_chains_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* A parameter sweep under :mcmc (main.jl:259): `npoint` independent :mcmc loops -- what mci_integrate runs with args->solver = MCI_MCMC,
+ * args->nchain chains per block, args->thermal_ratio, fresh chains in every iteration (mci_set_chain_carry(prob, 0)) and one lane per
+ * chain (mci_set_chain_speculation(prob, 1, ...)) -- in ONE launch, one workgroup per point.  The opt-in form for this solver:
+ * mci_integrate_sweep, mci_sweep_supported and mci_sweep_chains_supported keep refusing it.  Per point and iteration the workgroup runs
+ * the statistical blocks one after another, every block's chains one lane each (mcmc/montecarlo.jl:72-187 and mcmc/updates.jl: same
+ * Philox streams, keyed by seed, iteration, block, chain and step; starts curr = chain % (nintegrand + 1), or integrand 0 for one chain,
+ * with up to 10000 tries; nburn = mci_mcmc_burnin(steps, nchain, nslots, nintegrand + 1, npool, thermal_ratio) steps before the measured
+ * ones; the 64 chains of a wave share the update-type sequence when nchain > 1), merges the block rows (main.jl:273-287) and the propose
+ * | accept tables, runs doReweight! on the point's own factors (main.jl:183, :322-346 -- whatever `adapt` says) and train! on every
+ * leaf.  No warm-up repetition and no automatic chain count: nchain is explicit.  userdata, seeds, maps_in, maps_out, reweight_in,
+ * reweight_out, pa_out, results, iter_mean, iter_std and status are mci_integrate_sweep_chains's; every result has correlated = 0.
+ *   holds_out     NULL or [npoint][64]: every point's holding-time histogram (mci_get_hold_histogram's bins), summed over all
+ *                 iterations and blocks of the call.  A point whose top occupied bin b has 16 (2^b - 1) beyond the measured steps of a
+ *                 chain ran chains too short for what they held (the rule of mci_mcmc_launch_valid for fresh chains): with nchain
+ *                 fixed by the caller nothing else says so.
+ * A point whose integrands stay zero through the 10000 start tries has ST_MCMC_INIT (16) in its status word ("Cannot find the variables
+ * that makes the integrand nonzero!", mcmc/montecarlo.jl:126); the other points are not affected.
+ * args->nchain >= 1 and at most the steps of a block.  The problem's own map, reweight factors, packed buffer, hold histogram, logs,
+ * carry state and last_* queries are not touched.  npoint <= 65536 and at most 4 GiB of device memory: MCI_ERR_INVALID beyond. */
+int mci_integrate_sweep_mcmc(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                             const double *maps_in, double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out,
+                             uint64_t *holds_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status);
+/* MCI_OK when mci_integrate_sweep_mcmc takes this problem with these arguments (mcmc/montecarlo.jl:72-187, mcmc/updates.jl, main.jl:183,
+ * :322-346 are what it runs); else MCI_ERR_INVALID with the reason in why[n] (and in mci_last_error): a solver other than :mcmc,
+ * nchain = 0 (the automatic policy), nchain < 0 or more chains than a block has steps, more than 4096 blocks, first_iteration < 0 or
+ * first_iteration + niter > 131072, a negative or non-finite thermal_ratio, steps + nburn >= 2^31 - 1 (the holding times are counted in
+ * 32 bits), a reweight goal, measurefreq != 1, several ranks, stratification, a host integrand or measure, deterministic mode, a FermiK
+ * variable (the sweep's map block holds Continuous and Discrete leaves only: a follow-up), tables that do not sit in LDS in one tile, or
+ * more than 159 KiB of LDS for the chain loop's tables and counters or the refinement scratch plus the point's whole map (named). */
+int mci_sweep_mcmc_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

@@ -98,6 +98,9 @@ SIGNATURES = [
     ("mci_integrate_sweep_chains", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
                                              c_double_p, c_double_p, c_double_p, C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_sweep_chains_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
+    ("mci_integrate_sweep_mcmc", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint64), C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
+    ("mci_sweep_mcmc_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
     ("mci_get_iteration_log", C.c_int, [_VP, C.c_int32, c_double_p]),
     ("mci_reserve_iteration_log", C.c_int, [_VP, C.c_int32]),
     ("mci_get_packed", C.c_int, [_VP, c_double_p, C.c_int64]),

@@ -643,6 +643,13 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
             a.neval = (int64_t)1 << 40;
             a.block = 1;
             if (int rc = mci_sweep_chains_supported(p, &a, nullptr, 0)) return rc;
+        } else if (w == mci_problem::Sweep::kMcmc) { // (likewise)
+            a.solver = MCI_MCMC;
+            a.nchain = 1;
+            a.neval = (int64_t)1 << 30; // (steps + nburn of the one chain stay below 2^31 - 1)
+            a.block = 1;
+            a.thermal_ratio = 0.1;
+            if (int rc = mci_sweep_mcmc_supported(p, &a, nullptr, 0)) return rc;
         } else if (w == mci_problem::Sweep::kStrat) {
             a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
             a.block = 1;

@@ -1,7 +1,8 @@
 // mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
 // batched parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
 // one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in; mci_sweep_strat.h
-// vegas_sweep_strat for stratified points; mci_sweep_chains.h vegasmc_sweep for :vegasmc points, by its own entry point).  One descriptor
+// vegas_sweep_strat for stratified points; mci_sweep_chains.h vegasmc_sweep for :vegasmc points and mcmc_sweep for :mcmc points, each by its
+// own entry point).  One descriptor
 // table (kSweepUnits), one compile, one refusal head, one driver (sweep_run).
 namespace {
 // Points of one sweep, and the device memory one may take.  Per point the launch holds the userdata row, a seed, two maps, niter log
@@ -58,12 +59,14 @@ const char *sweep_leaves_refusal(const mci_problem *p, std::string &buf) {
 // the unit a sweep of this problem runs: the one-grid kernel wherever it applies, opted in or not
 bool sweep_uses_leaves(const mci_problem *p) { return p->sweep.leaves_mode == MCI_SWEEP_ALL_LEAVES && !persist_layout(p); }
 
-// What both queries ask first, `strat`: of a stratified sweep.  Eligibility of either: measurefreq == 1, one rank, device-source integrand
+// What every query asks first, `strat`: of a stratified sweep, `chains`: the solver of a chain sweep's entry point.  Eligibility of either: measurefreq == 1, one rank, device-source integrand
 // and measure, not deterministic.
-const char *sweep_common_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, bool strat, bool chains = false) {
+const char *sweep_common_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, bool strat, int32_t chains = MCI_VEGAS) {
     const auto &s = p->shape;
     if (strat && !p->strat.on) return "the problem is not stratified (mci_set_stratification first; mci_integrate_sweep runs the others)";
-    if (chains) { // (mci_integrate_sweep_chains: the solver test the other way round)
+    if (chains == MCI_MCMC) { // (mci_integrate_sweep_mcmc)
+        if (a->solver != MCI_MCMC) return "solver is not :mcmc (mci_integrate_sweep runs :vegas, mci_integrate_sweep_chains :vegasmc)";
+    } else if (chains == MCI_VEGASMC) { // (mci_integrate_sweep_chains: the solver test the other way round)
         if (a->solver == MCI_MCMC) return "solver is :mcmc (a sweep of :mcmc points is a follow-up)";
         if (a->solver != MCI_VEGASMC) return "solver is not :vegasmc (mci_integrate_sweep runs :vegas)";
     } else if (a->solver != MCI_VEGAS) return "solver is not :vegas (chain solvers are not swept)";
@@ -169,8 +172,8 @@ static int compile_sweep_unit(mci_problem *p, int which) {
     const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true,
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
-    // (the several-leaves and the :vegasmc unit's LDS is the layout's; the stratified unit's is the call's: sweep_run)
-    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kChains;
+    // (the several-leaves and the chain solvers' units' LDS is the layout's; the stratified unit's is the call's: sweep_run)
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kChains || which == mci_problem::Sweep::kMcmc;
     return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
@@ -225,13 +228,14 @@ int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 // The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
-// kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the :vegasmc unit's (none otherwise).  Everything from
-// kSegGhist on is zeroed before the launch: histogram rows, d rows, (the seeds: copied next), status words.
-enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegGhist, kSegD, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+// kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the chain solvers' units', kSegHolds the :mcmc unit's (none
+// otherwise).  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
+// bytes per point), (the seeds: copied next), status words.
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegGhist, kSegD, kSegHolds, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
 
 // What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
 struct SweepCall {
-    int unit = 0; // mci_problem::Sweep::kOne | kLeaves | kStrat
+    int unit = 0; // mci_problem::Sweep::kOne | kLeaves | kStrat | kChains | kMcmc
     // the caller's arguments
     int32_t npoint = 0;
     const double *userdata = nullptr;
@@ -249,6 +253,7 @@ struct SweepCall {
     size_t off_doubles = 0, tbase_doubles = 0, d_doubles = 0; // per point: kSegOff, kSegTbase, kSegD
     size_t rw_doubles = 0, pa_doubles = 0;                    // per point: kSegRw (reweight factors), kSegPa (the blocks' propose | accept rows)
     size_t packed_doubles = 0;   // a point's packed row; 0: the statistics head alone
+    size_t holds_doubles = 0;    // per point: kSegHolds (64 or none)
     int maxn = 0;                // bins of the largest leaf
     int64_t lds = 0;             // bytes of LDS of a workgroup
     int map_off = 0;             // SweepHead::map_off
@@ -275,7 +280,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((rc = c.plan(c))) return rc;
     const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
     const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, c.packed_doubles ? c.packed_doubles : (size_t)nstat,
-                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, (size_t)s.nbin, c.d_doubles, c.seeds ? (size_t)1 : 0};
+                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.seeds ? (size_t)1 : 0};
     size_t o[kSegCount + 1] = {0};
     for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
     const size_t ndbl = o[kSegStatus] + (P + 1) / 2;
@@ -619,15 +624,24 @@ int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32
 }
 
 // ---------------------------------------------------------------------------------------------------
-// :vegasmc points in a sweep: mci_sweep_chains.h vegasmc_sweep, one workgroup runs a point's whole chain-solver loop
+// :vegasmc and :mcmc points in a sweep: mci_sweep_chains.h vegasmc_sweep | mcmc_sweep, one workgroup runs a point's whole chain-solver loop
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// what sweep_common_refusal and sweep_leaves_refusal check, the solver test the other way round, and what the chain loop adds
-const char *sweep_chains_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
-    if (const char *r = sweep_common_refusal(p, a, buf, false, true)) return r;
+int sweep_nslots(const mci_problem *p) { // (pool, slot) pairs changeVariable can pick (plan_vegasmc_chains, plan_mcmc_chains)
+    int nslots = 0;
+    for (int v = 0; v < p->npool; ++v) nslots += p->maxdof[v];
+    return nslots;
+}
+// what sweep_common_refusal and sweep_leaves_refusal check, the solver test the other way round, and what the chain loop adds;
+// solver: the entry point's (MCI_VEGASMC: mci_integrate_sweep_chains, MCI_MCMC: mci_integrate_sweep_mcmc)
+const char *sweep_chains_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf, int32_t solver) {
+    const bool mcmc = solver == MCI_MCMC;
+    if (const char *r = sweep_common_refusal(p, a, buf, false, solver)) return r;
     if (a->nchain == 0) return "nchain = 0 (the automatic policy sizes chains from carried state a sweep does not have: give nchain >= 1)";
     if (a->nchain < 0) return "nchain < 0";
     if (a->reweight_goal || !p->h_goal.empty()) return "a reweight goal (a sweep point reweights without one)";
+    // (:mcmc itself runs FermiK pools; the point's map block in LDS, SweepBlock, has no place for them yet)
+    if (mcmc && p->has_fermik) return "a FermiK variable (a sweep point's map block holds Continuous and Discrete leaves only: FermiK points are a follow-up)";
     if (const char *r = sweep_leaves_refusal(p, buf)) return r; // (FermiK, the tables in LDS in one tile, the LDS budget: Lds<Cfg> counts the counters)
     if (!(a->neval > a->block)) return "neval should be larger than nblock";
     int64_t npb, blocks;
@@ -647,32 +661,49 @@ const char *sweep_chains_refusal(const mci_problem *p, const mci_integrate_args 
         buf = "nchain = " + std::to_string((long long)a->nchain) + " exceeds the " + std::to_string((long long)npb) + " steps of a block";
         return buf.c_str();
     }
+    if (mcmc) {
+        if (!std::isfinite(a->thermal_ratio) || a->thermal_ratio < 0.0) {
+            buf = "thermal_ratio = " + std::to_string(a->thermal_ratio) + " (the burn-in is floor(steps * thermal_ratio): finite and >= 0)";
+            return buf.c_str();
+        }
+        // (a chain counts its steps and its holding times in 32 bits, mci_device.h mcmc_chains: the ordinary launch drops the diagnostic
+        // beyond, a sweep point has nothing else to say that its chains were too short)
+        const int64_t steps = npb / a->nchain;
+        // (a ratio whose floor(steps * thermal_ratio) would not fit an int64_t is past the limit whatever else holds)
+        const int64_t nburn = (double)steps * a->thermal_ratio < 9.0e18 ? mci_mcmc_burnin(steps, a->nchain, sweep_nslots(p), p->ni + 1, p->npool, a->thermal_ratio)
+                                                                        : ((int64_t)1 << 62);
+        if (steps + nburn >= ((int64_t)1 << 31) - 1) {
+            buf = "steps + nburn = " + std::to_string((long long)steps) + " + " + std::to_string((long long)nburn) + " per chain (a sweep's :mcmc chain has fewer than 2^31 - 1 steps)";
+            return buf.c_str();
+        }
+    }
     return nullptr;
 }
-} // namespace
 
-int mci_sweep_chains_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
+int sweep_chains_query(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n, int32_t solver) {
     if (why && n > 0) why[0] = 0;
     if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
     std::string buf;
-    const char *r = sweep_chains_refusal(p, a, buf);
+    const char *r = sweep_chains_refusal(p, a, buf, solver);
     if (!r) return MCI_OK;
     if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
-    return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep of :vegasmc points: %s", r);
+    return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep of %s points: %s", solver == MCI_MCMC ? ":mcmc" : ":vegasmc", r);
 }
 
-// P independent :vegasmc integrate() loops (main.jl:142-207 around vegas_mc/montecarlo.jl:112-241), one workgroup each, in one launch
-static_assert(offsetof(mci::SweepChainArgs, h) == 0, "sweep_run fills the :vegasmc unit's argument through its head");
-int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
-                               double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, mci_result *results, double *iter_mean,
-                               double *iter_std, int32_t *status) {
-    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_chains_supported)) return rc;
+// P independent chain-solver integrate() loops (main.jl:142-207 around vegas_mc/montecarlo.jl:112-241 | mcmc/montecarlo.jl:72-187), one
+// workgroup each, in one launch.  What the two entry points share; solver: MCI_VEGASMC | MCI_MCMC (holds_out: the latter's)
+static_assert(offsetof(mci::SweepChainArgs, h) == 0, "sweep_run fills the chain units' argument through its head");
+int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solver, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                      double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, uint64_t *holds_out, mci_result *results,
+                      double *iter_mean, double *iter_std, int32_t *status) {
+    const bool mcmc = solver == MCI_MCMC;
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mcmc ? mci_sweep_mcmc_supported : mci_sweep_chains_supported)) return rc;
     const size_t P = (size_t)npoint, nd = (size_t)p->ni + 1, npa2 = 2 * (size_t)p->npa;
     const size_t tables = (size_t)p->nstat + p->shape.nbin; // where merge_pa leaves them in a packed row (mci_train.h)
     mci::SweepChainArgs f{};
     std::vector<double> hrw;
     SweepCall c;
-    c.unit = mci_problem::Sweep::kChains;
+    c.unit = mcmc ? mci_problem::Sweep::kMcmc : mci_problem::Sweep::kChains;
     c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
     c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
     c.plan = [a, npa2](SweepCall &c) {
@@ -686,13 +717,14 @@ int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int3
     c.maxn = sweep_max_nbin(p);
     c.lds = sweep_leaves_lds(p, &c.map_off);
     c.rw_doubles = nd;
-    c.packed_doubles = tables + npa2 + 64; // (+ 64: merge_pa's holding-time histogram, :mcmc's, zeros here)
-    c.too_big = "a sweep of %d :vegasmc points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it";
-    c.batch = [p, a, &c](mci::BatchArgs &b) {
-        int nslots = 0; // (pool, slot) pairs changeVariable can pick (plan_vegasmc_chains)
-        for (int v = 0; v < p->npool; ++v) nslots += p->maxdof[v];
+    c.packed_doubles = tables + npa2 + 64; // (+ 64: merge_pa's holding-time histogram: zeros under either solver, MergeArgs::hold stays NULL)
+    c.holds_doubles = mcmc ? 64 : 0;       // (64 words of 8 bytes: the kernel adds to them, the host reads them)
+    c.too_big = mcmc ? "a sweep of %d :mcmc points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it"
+                     : "a sweep of %d :vegasmc points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it";
+    c.batch = [p, a, &c, mcmc](mci::BatchArgs &b) { // (fresh chains in every iteration)
         b.nchain = a->nchain;
-        b.burnin = mci_chain_burnin(c.neval_per_block / a->nchain, a->nchain, nslots); // (fresh chains in every iteration)
+        if (mcmc) b.nburn = mci_mcmc_burnin(c.neval_per_block / a->nchain, a->nchain, sweep_nslots(p), p->ni + 1, p->npool, a->thermal_ratio);
+        else b.burnin = mci_chain_burnin(c.neval_per_block / a->nchain, a->nchain, sweep_nslots(p));
     };
     c.copy_in = [&](double *d, const size_t *o, hipStream_t st) {
         if (!reweight_in) { // every point starts from the problem's current factors (the device's: doReweight! moves them there)
@@ -713,6 +745,7 @@ int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int3
         f.reweight = d + o[kSegRw];
         f.part_pa = d + o[kSegPa];
         f.packed_stride = (int)c.packed_doubles;
+        f.holds = mcmc ? reinterpret_cast<unsigned long long *>(d + o[kSegHolds]) : nullptr; // (zeroed with everything from kSegGhist on)
         return &f;
     };
     c.copy_out = [&](double *d, const size_t *o, hipStream_t st) {
@@ -720,7 +753,24 @@ int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int3
         if (pa_out)
             HIPCHK(hipMemcpy2DAsync(pa_out, npa2 * sizeof(double), d + o[kSegPacked] + tables, c.packed_doubles * sizeof(double), npa2 * sizeof(double), P,
                                     hipMemcpyDeviceToHost, st));
+        if (mcmc && holds_out) HIPCHK(hipMemcpyAsync(holds_out, d + o[kSegHolds], P * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         return (int)MCI_OK;
     };
     return sweep_run(p, a, c);
+}
+} // namespace
+
+int mci_sweep_chains_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) { return sweep_chains_query(p, a, why, n, MCI_VEGASMC); }
+int mci_sweep_mcmc_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) { return sweep_chains_query(p, a, why, n, MCI_MCMC); }
+
+int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                               double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, mci_result *results, double *iter_mean,
+                               double *iter_std, int32_t *status) {
+    return sweep_chains_call(p, a, MCI_VEGASMC, npoint, userdata, seeds, maps_in, maps_out, reweight_in, reweight_out, pa_out, nullptr, results, iter_mean, iter_std, status);
+}
+// mcmc/montecarlo.jl:72-187, mcmc/updates.jl, main.jl:183, :322-346
+int mci_integrate_sweep_mcmc(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                             double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, uint64_t *holds_out, mci_result *results,
+                             double *iter_mean, double *iter_std, int32_t *status) {
+    return sweep_chains_call(p, a, MCI_MCMC, npoint, userdata, seeds, maps_in, maps_out, reweight_in, reweight_out, pa_out, holds_out, results, iter_mean, iter_std, status);
 }

@@ -169,8 +169,8 @@ struct mci_problem {
     // one code object per unit, JIT-compiled (or loaded from the kernel cache) the first time it is needed
     // kernel slots (kslot): :vegas for measurefreq == 1 | :vegasmc | :mcmc | :vegas for any measurefreq | sample dump
     //                      | :vegasmc with several lanes per chain | :mcmc with several lanes per chain (mci_spec.h)
-    // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the four sweep units (Sweep)
-    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kKernels = kSweep + 4 };
+    // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the five sweep units (Sweep)
+    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kKernels = kSweep + 5 };
     KernelUnit kernel[kKernels];
     VegasKernelPlan vegas; // which :vegas code object the launches run (mci_host_vegas_plan.h)
     // Several lanes per chain (mci_spec.h, mci_set_chain_speculation): lanes -1 automatic (as many as the launch's chains leave idle),
@@ -415,12 +415,12 @@ struct mci_problem {
         double *hstart = nullptr;
         int64_t hstart_n = 0;
     } strat;
-    // Batched parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat, mci_integrate_sweep_chains; mci_host_sweep.h): the four sweep units are
+    // Batched parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat, mci_integrate_sweep_chains, mci_integrate_sweep_mcmc; mci_host_sweep.h): the five sweep units are
     // kernel[kSweep + which].  A sweep keeps nothing else here: its maps, logs and status words come in and go out through the call's arguments.
     struct Sweep {
         // mci_sweep.h (one Continuous grid) | mci_sweep_leaves.h (any mix of Continuous and Discrete leaves) | mci_sweep_strat.h
-        // (stratified points) | mci_sweep_chains.h (:vegasmc points): mci_host_sweep.h kSweepUnits describes them in this order
-        enum { kOne = 0, kLeaves = 1, kStrat = 2, kChains = 3, kUnits = 4 };
+        // (stratified points) | mci_sweep_chains.h (:vegasmc points | :mcmc points): mci_host_sweep.h kSweepUnits describes them in this order
+        enum { kOne = 0, kLeaves = 1, kStrat = 2, kChains = 3, kMcmc = 4, kUnits = 5 };
         int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
         int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default (the one-grid unit only)
         int last_grid = 0, last_threads = 0;
@@ -432,12 +432,12 @@ struct mci_problem {
     static_assert(kKernels == kSweep + Sweep::kUnits, "one handle per sweep unit");
 };
 
-// The four sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
+// The five sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
 // named (mci_host_sweep.h compile_sweep_unit; mci_host_jit.h mci_compile_solver, mci_kernel_code_object).  The headers, the kernel symbol
 // and the #defines are the JIT unit's row (mci_jit.h kUnits).
 struct SweepUnitDesc {
     int jit_unit;         // mcijit::kUnit*
-    int32_t solver;       // MCI_VEGAS_SWEEP* | MCI_VEGASMC_SWEEP: the unit's name for mci_compile_solver / mci_kernel_code_object
+    int32_t solver;       // MCI_VEGAS_SWEEP* | MCI_VEGASMC_SWEEP | MCI_MCMC_SWEEP: the unit's name for mci_compile_solver / mci_kernel_code_object
     int32_t runs;         // the solver its source is generated for (mci_jit.h generate_source)
     const char *tag;      // in messages: "... (sweep kernel, <tag>)", "... code object (<tag>)"
     const char *for_what; // in messages: "the sweep kernel<for_what> ..."
@@ -449,6 +449,7 @@ static const SweepUnitDesc kSweepUnits[mci_problem::Sweep::kUnits] = {
     {mcijit::kUnitSweepLeaves, MCI_VEGAS_SWEEP_LEAVES, MCI_VEGAS, "several leaves", " for several leaves", false, false},
     {mcijit::kUnitSweepStrat, MCI_VEGAS_SWEEP_STRAT, MCI_VEGAS, "stratified points", " for stratified points", true, false},
     {mcijit::kUnitSweepChains, MCI_VEGASMC_SWEEP, MCI_VEGASMC, ":vegasmc points", " for :vegasmc points", false, false},
+    {mcijit::kUnitSweepMcmc, MCI_MCMC_SWEEP, MCI_MCMC, ":mcmc points", " for :mcmc points", false, false},
 };
 static int sweep_unit_of(int32_t solver) {
     for (int w = 0; w < mci_problem::Sweep::kUnits; ++w)

@@ -33,11 +33,11 @@ extern const char *const kDeviceHeader;       // mci_device.h
 extern const char *const kTrainHeader;        // mci_train.h (merge + train! device functions and the persistent :vegas kernel)
 extern const char *const kSpecHeader;         // mci_spec.h (the chain solvers with several lanes per chain)
 extern const char *const kStratHeader;        // mci_strat.h (the stratified :vegas sample kernel)
-extern const char *const kSweepCommonHeader;  // mci_sweep_common.h (what the four sweep kernels share)
+extern const char *const kSweepCommonHeader;  // mci_sweep_common.h (what the five sweep kernels share)
 extern const char *const kSweepHeader;        // mci_sweep.h (batched :vegas parameter sweeps)
 extern const char *const kSweepLeavesHeader;  // mci_sweep_leaves.h (sweeps of problems with several variable leaves)
 extern const char *const kSweepStratHeader;   // mci_sweep_strat.h (stratified points in sweeps)
-extern const char *const kSweepChainsHeader;  // mci_sweep_chains.h (batched :vegasmc parameter sweeps)
+extern const char *const kSweepChainsHeader;  // mci_sweep_chains.h (batched :vegasmc and :mcmc parameter sweeps)
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -115,8 +115,10 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // kUnitSweepChains: the :vegasmc chain loop (mci_device.h vegasmc_chains, one lane per chain) inside the sweep kernel of mci_sweep_chains.h
 // (one workgroup runs a point's whole :vegasmc loop); generated for MCI_VEGASMC, compiled like kUnitSweepLeaves -- the Discrete form of
 // train! and the doReweight! branch of iteration_bookkeeping stay in
-// The four sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitCount = 10 };
+// kUnitSweepMcmc: the :mcmc chain loop (mci_device.h mcmc_chains, one lane per chain) inside the same header's other instantiation
+// (mcmc_sweep: one workgroup runs a point's whole :mcmc loop); generated for MCI_MCMC, compiled like kUnitSweepChains
+// The five sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitCount = 11 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -148,6 +150,7 @@ constexpr UnitRow kUnits[] = {
     /* kUnitSweepLeaves  */ {"mci_sweep_leaves.h", {MCI_HDR_SWEEP, {"mci_sweep_leaves.h", &kSweepLeavesHeader}}, "mci_vegas_sweep_leaves", "SweepHead", "f", "vegas_sweep_leaves", 1, false, 2, true, false, true},
     /* kUnitSweepStrat   */ {"mci_sweep_strat.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}}, "mci_vegas_sweep_strat", "SweepStratArgs", "f", "vegas_sweep_strat", 1, true, 1, true, true, false},
     /* kUnitSweepChains  */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep", "SweepChainArgs", "f", "vegasmc_sweep", -1, false, 2, true, false, true},
+    /* kUnitSweepMcmc    */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep", "SweepChainArgs", "f", "mcmc_sweep", -1, false, 2, true, false, true},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN

@@ -1,26 +1,37 @@
-// mci_sweep_chains.h -- batched :vegasmc parameter sweeps (mci_integrate_sweep_chains): vegas_sweep_leaves of mci_sweep_leaves.h with the
-// chain solver's sample loop (vegasmc_chains, mci_device.h; vegas_mc/montecarlo.jl:112-241) in place of vegas_batch, and the chain
-// solver's per-iteration state: a point's reweight factors (doReweight!, main.jl:183, :322-346) and its propose | accept tables.
-// Compiled by hiprtc next to mci_device.h, mci_train.h and mci_sweep_common.h into a translation unit of its own (mci_jit.h
-// kUnitSweepChains, generated for MCI_VEGASMC): every other code object stays what it was.  Free of host / std headers.
+// mci_sweep_chains.h -- batched parameter sweeps under the chain solvers (mci_integrate_sweep_chains: :vegasmc points; mci_integrate_sweep_mcmc:
+// :mcmc points): vegas_sweep_leaves of mci_sweep_leaves.h with a chain solver's sample loop (mci_device.h vegasmc_chains,
+// vegas_mc/montecarlo.jl:112-241; mcmc_chains, mcmc/montecarlo.jl:72-187 and mcmc/updates.jl) in place of vegas_batch, and the chain
+// solvers' per-iteration state: a point's reweight factors (doReweight!, main.jl:183, :322-346) and its propose | accept tables.
+// ONE body, chain_sweep<Cfg, MCMC>, two instantiations: vegasmc_sweep and mcmc_sweep differ in the one line that calls the chain loop.
+// Compiled by hiprtc next to mci_device.h, mci_train.h and mci_sweep_common.h into a translation unit of its own per solver (mci_jit.h
+// kUnitSweepChains, generated for MCI_VEGASMC; kUnitSweepMcmc, generated for MCI_MCMC): every other code object stays what it was.
+// Free of host / std headers.
 //
 //     workgroup g   for p = g, g + G, ...:   map of point p -> LDS (the SweepBlock of mci_sweep_common.h);
 //                   for every iteration:  for every statistical block, one after another: its `nchain` chains, one lane per chain,
-//                   lanes striding over the chains (vegasmc_chains with wg_per_block = 1: row = block) -> merge the block rows
+//                   lanes striding over the chains (vegasmc_chains | mcmc_chains with wg_per_block = 1: row = block) -> merge the block rows
 //                   (merge_stats) and the blocks' propose | accept rows (merge_pa) -> statistics head -> this point's log row ->
 //                   doReweight! on this point's factors (iteration_bookkeeping, thread 0) -> leaf by leaf the merged histogram slice
 //                   and train! on the leaf's part of the LDS map;   at the end the map -> maps_out[p]
 //
 // Streams are keyed by (seed, iteration, block, chain, step) as in the ordinary launch, and every chain starts afresh in every iteration
 // (carry_x = store_x = NULL: the semantics of mci_set_chain_carry(prob, 0)), so a point's chains are the chains mci_iteration_run runs for
-// the same nchain with one lane per chain.
+// the same nchain with one lane per chain.  :mcmc: `nburn` is the host's (mci_mcmc_burnin, BatchArgs::nburn, the same for every point),
+// the start of a chain is tried at most 10000 times (mcmc/montecarlo.jl:118-124; a point whose integrand stays zero reports ST_MCMC_INIT
+// in its own status word and goes on), and every loop bound of the chain loop is a kernel argument or a compile-time constant.
 //
 // The synchronisation is mci_sweep_common.h's.  What this unit adds to a point's traffic through global memory is written and read by
 // the point's own workgroup, with a sweep_round_trip() between the two sides:
 //   * the blocks' propose | accept rows (flush_workgroup, plain stores by all threads) -> merge_pa, behind the round trip that follows
 //     the last block;
-//   * the reweight factors: thread 0 writes them in iteration_bookkeeping, every lane reads them at the start of the next vegasmc_chains
-//     call -- the round trip of the first leaf's histogram slice stands in between (NLEAF >= 1), and thread 0's own wait covers its stores.
+//   * the reweight factors: thread 0 writes them in iteration_bookkeeping, every lane reads them at the start of the next vegasmc_chains |
+//     mcmc_chains call -- the round trip of the first leaf's histogram slice stands in between (NLEAF >= 1), and thread 0's own wait covers
+//     its stores.  The same under either solver.
+// What :mcmc adds, its holding-time histogram (SweepChainArgs::holds, 64 words per point), is write-only here: the chain loop's vector
+// atomics add to the point's words, nothing in the kernel reads them (MergeArgs::hold stays NULL: merge_pa leaves zeros in the packed row's
+// last 64 doubles) -- reading them would take loads that bypass the CU's L1 in every iteration after the first, the argument of
+// mci_sweep_common.h for the histogram row.  The host zeroes the words before the launch and copies them out behind it: sums over all
+// iterations and blocks of the call.
 // merge_pa sums four entries per call, one wave each: the workgroup has at least four waves (the host launches kSweepThreads = 256).
 //
 // LDS: the chain loop's carve Lds<Cfg> (tables | histogram | observables | reduction scratch | propose / accept counters) and the
@@ -36,9 +47,10 @@ struct SweepChainArgs {
     double *reweight;     // [npoint][nd]  in: where every point starts; out: its factors after the last doReweight!
     double *part_pa;      // [npoint][nblocks][2 * npa]  the blocks' propose | accept rows
     int packed_stride;    // doubles of a point's packed row: statistics [nstat] | (histogram [nbin], unused) | propose | accept [2 npa] | holds [64]
+    unsigned long long *holds; // [npoint][64] or NULL  :mcmc: the points' holding-time histograms (BatchArgs::hold_hist; zeroed by the host, never read here)
 };
 
-template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) {
+template <class Cfg, bool MCMC> __device__ __forceinline__ void chain_sweep(const BatchArgs &a0, const SweepChainArgs &fc) {
     static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0 &&
                       Cfg::HOST_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS, and measures on the device (the host checks)");
@@ -67,6 +79,7 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchAr
         m.part_pa = fc.part_pa + (size_t)p * nblocks * NPA2;
         a.part_pa = fc.part_pa + (size_t)p * nblocks * NPA2;
         a.reweight = rw;
+        a.hold_hist = fc.holds ? fc.holds + (size_t)p * 64 : nullptr; // (:vegasmc never looks at it)
         a.edges = bedges; // (LDS through the generic address space: stage_tables reads the three tables once per call)
         a.dacc = bdacc;
         a.ddist = bddist;
@@ -76,7 +89,8 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchAr
             for (int b = 0; b < nblocks; ++b) {
                 a.chunk_lo = b;  // work_item: row = block (wg_per_block = 1)
                 __syncthreads(); // (map, flag and -- from the second iteration on -- whatever read this LDS before are through)
-                vegasmc_chains<Cfg>(a); // tables <- the map block, the block's chains, its partial row and its propose | accept row, histogram atomics into this point's row
+                // tables <- the map block, the block's chains, its partial row and its propose | accept row, histogram atomics into this point's row
+                if constexpr (MCMC) mcmc_chains<Cfg>(a); else vegasmc_chains<Cfg>(a);
             }
             sweep_round_trip();
             merge_stats(m); // main.jl:273-287
@@ -102,5 +116,8 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchAr
         sweep_copy_row<Cfg, true>(blk, f.maps_out + (size_t)p * NROW, nullptr);
     }
 }
+
+template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) { chain_sweep<Cfg, false>(a0, fc); }
+template <class Cfg> __device__ __forceinline__ void mcmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) { chain_sweep<Cfg, true>(a0, fc); }
 
 } // namespace mci

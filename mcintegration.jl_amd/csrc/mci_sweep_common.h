@@ -1,5 +1,5 @@
 // mci_sweep_common.h -- what the four batched-sweep kernels share: mci_sweep.h (one Continuous grid), mci_sweep_leaves.h (any mix of
-// Continuous and Discrete leaves), mci_sweep_strat.h (stratified points) and mci_sweep_chains.h (:vegasmc points).  Each of them is a translation unit of its own (mci_jit.h
+// Continuous and Discrete leaves), mci_sweep_strat.h (stratified points) and mci_sweep_chains.h (:vegasmc points; :mcmc points: the same body's other instantiation).  Each of them is a translation unit of its own (mci_jit.h
 // kUnits) and includes this header; the host (mci_host_sweep.h) compiles the same text, so the argument layout cannot drift.  Free of
 // host / std headers.
 //

@@ -440,7 +440,7 @@ class Engine:
     @staticmethod
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
-                "vegasmc_sweep": 11}.get(solver) or _lib.SOLVERS[solver]
+                "vegasmc_sweep": 11, "mcmc_sweep": 12}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -449,7 +449,8 @@ class Engine:
         integrate_sweep, csrc/mci_sweep.h; layouts sweep_supported accepts) | "vegas_sweep_leaves" (the sweep kernel of a problem with
         several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all")) | "vegas_sweep_strat" (the kernel of
         integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts) | "vegasmc_sweep" (the kernel of
-        integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts)"""
+        integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts) | "mcmc_sweep" (the kernel of
+        integrate_sweep_mcmc, the same header's :mcmc instantiation; layouts sweep_mcmc_supported accepts)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -716,14 +717,14 @@ class Engine:
             out["block_mean"] = self.block_means(niter)[0]
         return out
 
-    def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain=0):
+    def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain=0, thermal_ratio=0.1):
         return _lib.IntegrateArgs(_lib.SOLVERS[solver], int(neval), int(niter), int(block), int(ignore), 1 if adapt else 0, float(gamma),
-                                  int(measurefreq), int(seed), int(nchain), int(first_iteration), 0.1, None)
+                                  int(measurefreq), int(seed), int(nchain), int(first_iteration), float(thermal_ratio), None)
 
-    def _sweep_refusal(self, query, solver, neval, niter, block, measurefreq, nchain=0, first_iteration=0):
-        """None when the query (mci_sweep_supported | mci_sweep_strat_supported | mci_sweep_chains_supported) takes this problem with these
-        arguments, else its reason"""
-        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, first_iteration, nchain)
+    def _sweep_refusal(self, query, solver, neval, niter, block, measurefreq, nchain=0, first_iteration=0, thermal_ratio=0.1):
+        """None when the query (mci_sweep_supported | mci_sweep_strat_supported | mci_sweep_chains_supported | mci_sweep_mcmc_supported) takes
+        this problem with these arguments, else its reason"""
+        a = self._integrate_args(solver, neval, niter, block, -1, True, 1.0, measurefreq, 0, first_iteration, nchain, thermal_ratio)
         why = C.create_string_buffer(512)
         if query(self.p, C.byref(a), why, len(why)) == _lib.MCI_OK:
             return None
@@ -802,7 +803,7 @@ class Engine:
         return ud, sd, mi, between
 
     def _sweep_call(self, fn, a, P, niter, arrays, extra):
-        """fn (mci_integrate_sweep | mci_integrate_sweep_strat | mci_integrate_sweep_chains) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
+        """fn (mci_integrate_sweep | mci_integrate_sweep_strat | mci_integrate_sweep_chains | mci_integrate_sweep_mcmc) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
         entry point's own arguments between maps_out and results, and the keys they add to every dict ({key: [P][...] array})"""
         ud, sd, mi = arrays
         n, nmap = self.nobs, self.sweep_map_doubles()
@@ -890,20 +891,56 @@ class Engine:
         (the tables of its last iteration, shaped like acceptance()).  reweight: None (every point starts from the engine's current
         factors) or [P][N + 1], e.g. the `reweight` of an earlier sweep.  nchain >= 1: chains per block.  The engine's own map, factors,
         packed buffer, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_chains_supported()."""
-        ud, sd, mi, _ = self._sweep_inputs("integrate_sweep_chains", userdata, seeds, maps)
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain)
+        return self._sweep_chain_solver("integrate_sweep_chains", lib().mci_integrate_sweep_chains, a, niter, userdata, seeds, maps, reweight, False)
+
+    def _sweep_chain_solver(self, name, fn, a, niter, userdata, seeds, maps, reweight, holds):
+        """what integrate_sweep_chains and integrate_sweep_mcmc share: the arrays, the reweight check, the per-point factors and tables;
+        holds: the entry point also returns every point's holding-time histogram"""
+        ud, sd, mi, _ = self._sweep_inputs(name, userdata, seeds, maps)
         P, nd = ud.shape[0], self.config.N + 1
         m = max(nd, len(self.config.var))
         ri = None
         if reweight is not None:
             ri = np.ascontiguousarray(reweight, dtype=np.float64)
             if ri.shape != (P, nd):
-                raise ValueError("integrate_sweep_chains: reweight must be [points = %d][integrands + 1 = %d], got shape %s" % (P, nd, ri.shape))
-        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain)
+                raise ValueError("%s: reweight must be [points = %d][integrands + 1 = %d], got shape %s" % (name, P, nd, ri.shape))
 
         def extra(P):
             ro, pa = np.zeros((P, nd)), np.zeros((P, 2, 3, nd, m))
-            return (_dp(ri) if ri is not None else None, _dp(ro), _dp(pa)), dict(reweight=ro, propose=pa[:, 0], accept=pa[:, 1])
-        return self._sweep_call(lib().mci_integrate_sweep_chains, a, P, niter, (ud, sd, mi), extra)
+            own, keys = (_dp(ri) if ri is not None else None, _dp(ro), _dp(pa)), dict(reweight=ro, propose=pa[:, 0], accept=pa[:, 1])
+            if holds:
+                ho = np.zeros((P, 64), dtype=np.uint64)
+                own += (ho.ctypes.data_as(C.POINTER(C.c_uint64)),)
+                keys["holds"] = ho
+            return own, keys
+        out = self._sweep_call(fn, a, P, niter, (ud, sd, mi), extra)
+        if holds:
+            for r in out:
+                r["hold_max"] = self.hold_max_of(r["holds"])
+        return out
+
+    @staticmethod
+    def hold_max_of(holds):
+        """the upper bound 2^b - 1 of the highest occupied bin b of a holding-time histogram (hold_histogram's bins), 0 if none"""
+        top = np.flatnonzero(np.asarray(holds))
+        return (1 << int(top[-1])) - 1 if top.size else 0
+
+    def sweep_mcmc_supported(self, solver="mcmc", neval=10000, niter=10, block=16, measurefreq=1, nchain=1, first_iteration=0, thermal_ratio=0.1, **kw):
+        """None when integrate_sweep_mcmc takes this problem with these arguments, else the reason (mci_sweep_mcmc_supported)"""
+        return self._sweep_refusal(lib().mci_sweep_mcmc_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration, thermal_ratio)
+
+    def integrate_sweep_mcmc(self, solver="mcmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
+                             measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, thermal_ratio=0.1):
+        """A parameter sweep under :mcmc in one launch (mci_integrate_sweep_mcmc): P independent :mcmc loops -- what
+        integrate("mcmc", nchain=nchain, thermal_ratio=thermal_ratio) runs on this engine with set_chain_carry(0) and one lane per
+        chain -- one workgroup per point, the blocks of a point one after another.  Arguments and result dicts as
+        integrate_sweep_chains; every dict also carries `holds` (the point's holding-time histogram, 64 counts summed over the call's
+        iterations and blocks: hold_histogram's bins) and `hold_max` (the upper bound 2^b - 1 of its highest occupied bin b, 0 if
+        none).  There is no warm-up repetition and no automatic chain count: nchain >= 1 is explicit.  The engine's own map, factors,
+        packed buffer, hold histogram, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_mcmc_supported()."""
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain, thermal_ratio)
+        return self._sweep_chain_solver("integrate_sweep_mcmc", lib().mci_integrate_sweep_mcmc, a, niter, userdata, seeds, maps, reweight, True)
 
     def sweep_workgroups(self, g=0):
         """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""

@@ -442,7 +442,7 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
                     measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    chains=None, reweight=None, **kwargs):
+                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -481,6 +481,17 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     "mcmc" raises ValueError.  Where the chain sweep is refused (Engine.sweep_chains_supported) the points run as
     integrate(..., nchain=chains) calls, as below; reweight= then raises.
 
+    mcmc_chains: None (default) or an int >= 1 -- with solver="mcmc" every point runs its :mcmc loop with that many chains per block
+    and burn-in floor(steps * thermal_ratio) (mci_mcmc_burnin), fresh in every iteration, still in ONE launch
+    (Engine.integrate_sweep_mcmc; no warm-up repetition, no automatic chain count).  Closures are called in the solver's form,
+    integrand(idx, var, config) and measure(idx, var, obs, relative_weight, config).  Every Result carries what a chains= sweep's
+    does (`reweight`, own visited / propose / accept, correlated = False) and `holds` (the point's holding-time histogram, 64 counts
+    over the call) and `hold_max` (the upper bound 2^b - 1 of its highest occupied bin b, 0 if none); report() adds a note where
+    16 * hold_max exceeds the measured steps of a chain.  reweight= goes with it as with chains=.  mcmc_chains= with another solver,
+    together with chains= or with stratify= raises ValueError; without it an :mcmc scan loops as below.  Where the sweep is refused
+    (Engine.sweep_mcmc_supported) the points run as integrate(..., solver="mcmc", nchain=mcmc_chains, thermal_ratio=...) calls;
+    reweight= then raises.
+
     A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
     measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
     a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
@@ -504,6 +515,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
     if maps is not None and len(maps) != P:
         raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
+    if chains is not None and mcmc_chains is not None:
+        raise ValueError('integrate_sweep: chains= (solver="vegasmc") and mcmc_chains= (solver="mcmc") do not go together')
     if chains is not None:
         if isinstance(chains, bool) or not isinstance(chains, (int, np.integer)) or chains < 1:
             raise ValueError("integrate_sweep: chains must be an int >= 1 (chains per block), got %r" % (chains,))
@@ -513,7 +526,16 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         if stratify is not None and stratify is not False:
             raise ValueError("integrate_sweep: chains= and stratify= do not go together (stratification is :vegas's)")
         chains = int(chains)
-    if reweight is not None and chains is None:
+    if mcmc_chains is not None:
+        if isinstance(mcmc_chains, bool) or not isinstance(mcmc_chains, (int, np.integer)) or mcmc_chains < 1:
+            raise ValueError("integrate_sweep: mcmc_chains must be an int >= 1 (chains per block), got %r" % (mcmc_chains,))
+        if solver != "mcmc":
+            raise ValueError('integrate_sweep: mcmc_chains= belongs to solver="mcmc" (%s)'
+                             % ('"vegas" is swept without it' if solver == "vegas" else '"vegasmc" takes chains='))
+        if stratify is not None and stratify is not False:
+            raise ValueError("integrate_sweep: mcmc_chains= and stratify= do not go together (stratification is :vegas's)")
+        mcmc_chains = int(mcmc_chains)
+    if reweight is not None and chains is None and mcmc_chains is None:
         raise ValueError('integrate_sweep: reweight= belongs to a chain sweep (solver="vegasmc", chains=K)')
     if reweight is not None and len(reweight) != P:
         raise ValueError("integrate_sweep: reweight must hold one vector per point (%d), got %d" % (P, len(reweight)))
@@ -584,6 +606,10 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             why = (eng.sweep_chains_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=chains,
                                               first_iteration=config.iterations_done)
                    if hasattr(eng, "sweep_chains_supported") else "this engine has no chain sweep")
+        elif mcmc_chains is not None:
+            why = (eng.sweep_mcmc_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=mcmc_chains,
+                                            first_iteration=config.iterations_done, thermal_ratio=thermal_ratio)
+                   if hasattr(eng, "sweep_mcmc_supported") else "this engine has no :mcmc sweep")
         else:
             why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
     if why is None and strat is not None:
@@ -608,10 +634,11 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
                 report(res)
             out.append(res)
         return out
-    if why is None and chains is not None:
-        rs = eng.integrate_sweep_chains(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
-                                        gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
-                                        first_iteration=config.iterations_done, nchain=chains, reweight=reweight)
+    if why is None and (chains is not None or mcmc_chains is not None):
+        kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma,
+                  measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done, reweight=reweight)
+        rs = (eng.integrate_sweep_chains(solver, nchain=chains, **kw) if chains is not None
+              else eng.integrate_sweep_mcmc(solver, nchain=mcmc_chains, thermal_ratio=thermal_ratio, **kw))
         out = []
         for p, r in zip(params, rs):
             c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, factors and logs alone)
@@ -622,6 +649,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             res.sweep_batched, res.map, res.status, res.reweight = True, r["maps"], r["status"], r["reweight"]
             res.maps_by_leaf = r.get("maps_by_leaf")
             res.stratification, res.vegas_check, res.warmup, res.neval_discarded, res.chain_bias = None, None, 0, 0, None
+            if mcmc_chains is not None:
+                res.holds, res.hold_max, res.chain_steps = r["holds"], r["hold_max"], nevalperblock // mcmc_chains
             if print >= 0:
                 report(res)
             out.append(res)
@@ -668,7 +697,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         if seeds is not None:
             c.seed = int(seeds[k])
         res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
-                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}), **({"nchain": chains} if chains is not None else {}))
+                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}), **({"nchain": chains} if chains is not None else {}),
+                        **({"nchain": mcmc_chains, "thermal_ratio": thermal_ratio} if mcmc_chains is not None else {}))
         res.sweep_batched, res.map, res.maps_by_leaf, res.status = False, None, None, 0
         out.append(res)
     return out
@@ -700,6 +730,7 @@ def prefill_kernel_cache():
             eng.set_sweep_leaves("all")    # ... and which is scanned over rs as one launch (integrate_sweep(..., leaves="all"))
             eng.compile("vegas_sweep_leaves")
             eng.compile("vegasmc_sweep")   # ... or, under its own solver, with integrate_sweep(..., solver="vegasmc", chains=K)
+            eng.compile("mcmc_sweep")      # ... or under the reference example's, with integrate_sweep(..., solver="mcmc", mcmc_chains=K)
         eng.close()
         n += 1
     # C5: 4 integrands on a 12-D pool, :mcmc

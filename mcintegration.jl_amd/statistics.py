@@ -116,6 +116,9 @@ class Result:
         # set by integrate() after a :vegas run: (status, flags) of the self-check of the problem's :vegas code objects
         # (Engine.vegas_check_status; report() prints a note when the status is negative), else None
         self.vegas_check = None
+        # set by integrate_sweep() for a point of an :mcmc sweep (mcmc_chains=K): its holding-time histogram (64 counts over the call's
+        # iterations and blocks), the upper bound 2^b - 1 of its highest occupied bin b, and the measured steps of one of its chains
+        self.holds = self.hold_max = self.chain_steps = None
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
         self.iterations = [(self._shape(self.iter_mean[i]), self._shape(self.iter_std[i]), config) for i in range(niter)]
 
@@ -143,6 +146,7 @@ class Result:
         r.chain_bias = self.chain_bias
         r.stratification = self.stratification
         r.vegas_check = self.vegas_check
+        r.holds, r.hold_max, r.chain_steps = self.holds, self.hold_max, self.chain_steps
         return r
 
     @property
@@ -157,6 +161,17 @@ class Result:
                     "histogram copy --, which agreed (mci_vegas_check_status = -1)")
         return ("note: NO layout of the :vegas sample kernel compiled for this integrand reproduced the library's static :vegas kernel on its "
                 "self-check (mci_vegas_check_status = -2): the map may have adapted to a wrong histogram, do not trust these numbers")
+
+    @property
+    def hold_note(self):
+        """the sentence report() prints under the tables of a point of an :mcmc sweep whose chains were too short for the holding times
+        they measured themselves (16 x the longest hold beyond a chain's measured steps: the rule of mci_mcmc_launch_valid for fresh
+        chains), or None"""
+        if not self.hold_max or not self.chain_steps or 16 * self.hold_max <= self.chain_steps:
+            return None
+        return ("note: some chain of this :mcmc sweep point went up to %d steps without moving a variable or its integrand index, and a chain "
+                "measures %d steps: fresh chains want at least 16 x their longest hold (%d).  The chain count of a sweep is the caller's: "
+                "fewer chains per block (mcmc_chains=) or more evaluations make them longer" % (self.hold_max, self.chain_steps, 16 * self.hold_max))
 
     @property
     def chain_bias_note(self):
@@ -321,3 +336,5 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
         print("  " + result.chain_bias_note, file=io)
     if getattr(result, "vegas_check_note", None):   # (not in the reference)
         print("  " + result.vegas_check_note, file=io)
+    if getattr(result, "hold_note", None):   # (not in the reference)
+        print("  " + result.hold_note, file=io)

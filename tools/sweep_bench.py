@@ -6,6 +6,7 @@
     python tools/sweep_bench.py table --layout bubble [--neval 10000] [--points 1,16,256,1024]      (profiles/r11_sweep_leaves.txt)
     python tools/sweep_bench.py strat [--neval 10000] [--points 1,16,256,1024]                      (profiles/r12_sweep_strat.txt)
     python tools/sweep_bench.py chains [--nevals 10000,100000,1000000] [--points 1,16,256] [--chains 1,16,64,256]   (profiles/r14_sweep_chains.txt)
+    python tools/sweep_bench.py mcmc   [--nevals 10000,100000] [--points 1,16,256] [--chains 1,16,64,256]          (profiles/r15_sweep_mcmc.txt)
 
 The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
 and of the same points as a loop of Engine.integrate calls with the persistent launch, in the same process.
@@ -21,6 +22,9 @@ seeds of their own at ONE parameter value, so that the scatter of their means is
 per point) against a loop of ordinary Engine.integrate("vegasmc") calls with the SAME nchain and carried chains off, and against a loop of
 default calls (automatic chain count, lanes per chain, carried chains), every call of a loop starting from the untrained map and
 the initial reweight factors; a sweep point-iteration is neval / min(nchain, 256) dependent Markov steps deep, which the last column gives.
+`mcmc`: the same table under :mcmc (Engine.integrate_sweep_mcmc against loops of Engine.integrate("mcmc") calls, thermal_ratio = 0.1; the
+default loop's calls size their chains themselves and may run warm-up launches again); a point-iteration is neval / nchain + nburn steps
+deep per chain.  Both tables give the best and the worst of the timed runs of every column.
 One GPU process; run each mode under its own time limit."""
 import argparse
 import os
@@ -192,14 +196,24 @@ def strat_table(Ps, neval):
                  strat.last_sweep_launch(), "  (loop: %d calls timed, scaled)" % n if P > n else ""))
 
 
-# ---- chains: :vegasmc points (csrc/mci_sweep_chains.h)
-def chains_table(Ps, nevals, chains, budget=3.0):
+# ---- chains | mcmc: :vegasmc | :mcmc points (csrc/mci_sweep_chains.h)
+def mcmc_chain_steps(npb, nchain):
+    """steps of one of the bubble's :mcmc chains in a block of npb evaluations: the measured ones and the burn-in (mci_mcmc_burnin: a tenth
+    of them, and for several chains at least 64 nslots + 16 (npool + 1) nd = 512 for the bubble's 5 pools of one slot and 2 integrands)"""
+    from mcintegration_jl_amd._lib import lib
+    steps = npb // nchain
+    return steps + int(lib().mci_mcmc_burnin(steps, nchain, 5, 2, 5, 0.1))
+
+
+def chains_table(Ps, nevals, chains, budget=3.0, solver="vegasmc"):
     from mcintegration_jl_amd import isa_mix
     eng = bubble_engine(bubble_point(0))
-    eng.compile("vegasmc_sweep")
-    res = isa_mix.resources(eng.code_object("vegasmc_sweep"))["mci_vegasmc_sweep"]
-    print("# bubble (4 Continuous leaves of 999 increments + Discrete(1, 4), q histogram), solver :vegasmc, niter = %d, block = %d" % (NITER, BLOCK))
-    print("# mci_vegasmc_sweep: %d VGPRs, %d bytes of scratch, %d bytes of static LDS" % (res["vgpr"], res["scratch"], res["lds"]))
+    unit = solver + "_sweep"
+    eng.compile(unit)
+    res = isa_mix.resources(eng.code_object(unit))["mci_" + unit]
+    sweep = eng.integrate_sweep_chains if solver == "vegasmc" else eng.integrate_sweep_mcmc
+    print("# bubble (4 Continuous leaves of 999 increments + Discrete(1, 4), q histogram), solver :%s, niter = %d, block = %d" % (solver, NITER, BLOCK))
+    print("# mci_%s: %d VGPRs, %d bytes of scratch, %d bytes of static LDS" % (unit, res["vgpr"], res["scratch"], res["lds"]))
     print("# chain sweep | loop of ordinary calls with the same nchain, carry off | loop of default calls: ms (us per point-iteration)")
     loops = {"same": bubble_engine(bubble_point(0)), "default": bubble_engine(bubble_point(0))}
     loops["same"].set_chain_carry(0)
@@ -207,16 +221,16 @@ def chains_table(Ps, nevals, chains, budget=3.0):
     rw0 = eng.reweight().copy()
 
     def timed(fn, reps=3):
-        """best of up to `reps` runs; a run longer than the budget is not repeated"""
-        best = float("inf")
+        """(best, worst) of up to `reps` runs; a run longer than the budget is not repeated"""
+        best, worst = float("inf"), 0.0
         for _ in range(reps):
             t0 = time.perf_counter()
             out = fn()
             dt = time.perf_counter() - t0
-            best = min(best, dt)
+            best, worst = min(best, dt), max(worst, dt)
             if dt > budget:
                 break
-        return best, out
+        return (best, worst), out
 
     def loop(which, n, nchain, kw):
         e = loops[which]
@@ -224,7 +238,7 @@ def chains_table(Ps, nevals, chains, budget=3.0):
             for l in range(4):
                 e.set_grid(l, g0[l])
             e.set_reweight(rw0)
-            q = e.integrate("vegasmc", nchain=nchain, **kw)
+            q = e.integrate(solver, nchain=nchain, **kw)
         return q
     for neval in nevals:
         kw = dict(neval=neval, niter=NITER, block=BLOCK, seed=SEED)
@@ -235,24 +249,27 @@ def chains_table(Ps, nevals, chains, budget=3.0):
             loop("same", 1, nchain, kw)
             for P in Ps:
                 uds = np.array([bubble_point(k) for k in range(P)])
-                eng.integrate_sweep_chains("vegasmc", userdata=uds[:1], nchain=nchain, **dict(kw, niter=1))     # (first launch)
-                ts, rs = timed(lambda: eng.integrate_sweep_chains("vegasmc", userdata=uds, nchain=nchain, **kw))
+                sweep(solver, userdata=uds[:1], nchain=nchain, **dict(kw, niter=1))     # (first launch)
+                (ts, tsw), rs = timed(lambda: sweep(solver, userdata=uds, nchain=nchain, **kw))
                 assert all(r["status"] == 0 for r in rs)
                 n = min(P, 16)   # (a loop is linear in P: up to 16 calls are timed, larger P scaled; ud stays point 0's, as in time_loop)
-                tl, q = timed(lambda: loop("same", n, nchain, kw))
-                td, _ = timed(lambda: loop("default", n, 0, kw))
-                tl, td = tl * P / n, td * P / n
+                (tl, tlw), q = timed(lambda: loop("same", n, nchain, kw))
+                (td, tdw), _ = timed(lambda: loop("default", n, 0, kw))
+                tl, td, tlw, tdw = tl * P / n, td * P / n, tlw * P / n, tdw * P / n
                 sig = np.max(np.abs(rs[0]["mean"] - q["mean"]) / np.hypot(rs[0]["stdev"], q["stdev"]))
-                print("neval %8d  nchain %4d  P %4d  sweep %11.3f ms (%9.3f us)  same-nchain loop %11.3f ms (%9.3f us)  default loop %11.3f ms (%9.3f us)"
+                deep = neval // min(nchain, 256) if solver == "vegasmc" else BLOCK * mcmc_chain_steps(neval // BLOCK, nchain)
+                print("neval %8d  nchain %4d  P %4d  sweep %11.3f ms (%9.3f us; worst %11.3f)  same-nchain loop %11.3f ms (%9.3f us; worst %11.3f)"
+                      "  default loop %11.3f ms (%9.3f us; worst %11.3f)"
                       "  loop / sweep %7.2f  default / sweep %7.2f   grid x threads = %s  steps deep %8d  point 0: %.1f sigma apart%s"
-                      % (neval, nchain, P, 1e3 * ts, 1e6 * ts / (P * NITER), 1e3 * tl, 1e6 * tl / (P * NITER), 1e3 * td, 1e6 * td / (P * NITER),
-                         tl / ts, td / ts, eng.last_sweep_launch(), neval // min(nchain, 256), sig, "  (loops: %d calls timed, scaled)" % n if P > n else ""),
+                      % (neval, nchain, P, 1e3 * ts, 1e6 * ts / (P * NITER), 1e3 * tsw, 1e3 * tl, 1e6 * tl / (P * NITER), 1e3 * tlw, 1e3 * td,
+                         1e6 * td / (P * NITER), 1e3 * tdw, tl / ts, td / ts, eng.last_sweep_launch(), deep, sig,
+                         "  (loops: %d calls timed, scaled)" % n if P > n else ""),
                       flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["table", "threads", "once", "strat", "chains"])
+    ap.add_argument("mode", choices=["table", "threads", "once", "strat", "chains", "mcmc"])
     ap.add_argument("--nevals", default="10000,100000,1000000")
     ap.add_argument("--chains", default="1,16,64,256")
     ap.add_argument("--neval", type=int, default=10000)
@@ -263,9 +280,9 @@ def main():
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
-    if a.mode == "chains":
+    if a.mode in ("chains", "mcmc"):
         chains_table([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
-                     [int(v) for v in a.chains.split(",")])
+                     [int(v) for v in a.chains.split(",")], solver="vegasmc" if a.mode == "chains" else "mcmc")
         return
     if a.mode == "strat":
         strat_table([P for P in Ps if P <= 1024] if a.points == "1,16,256,1024,4096" else Ps, a.neval)
