@@ -50,6 +50,9 @@ enum { MCI_VEGAS_SWEEP_STRAT = 10 };
 enum { MCI_VEGASMC_SWEEP = 11 };
 /* ... and the sweep kernel of :mcmc (mci_integrate_sweep_mcmc; problems mci_sweep_mcmc_supported accepts) */
 enum { MCI_MCMC_SWEEP = 12 };
+/* ... and the same two sweep kernels with chains carried from one iteration of a point to the next (mci_set_sweep_chain_carry): code
+ * objects of their own */
+enum { MCI_VEGASMC_SWEEP_CARRY = 13, MCI_MCMC_SWEEP_CARRY = 14 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -282,6 +285,25 @@ int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args,
  * leaf's train! per iteration, Discrete leaves included, each refused on its own histogram); a problem with one Continuous leaf runs the
  * same kernel and code object under either mode. */
 int mci_set_sweep_leaves(mci_problem *prob, int32_t mode);
+/* Carried chains in the chain solvers' sweeps.  on = 0 (default): mci_integrate_sweep_chains and mci_integrate_sweep_mcmc start every
+ * chain afresh in every iteration, the semantics of mci_set_chain_carry(prob, 0); nothing about them changes.  on = 1: a point is
+ * mci_integrate(..., nchain = K) on a fresh problem with mci_set_chain_carry(prob, 1) and one lane per chain -- iteration `it` of the call
+ * (0-based) continues the chains iteration it - 1 of the same point and block ended on iff K > 1, it >= 1 and the solver is :mcmc, or
+ * adapt is 0, or it >= 2 (:vegasmc chains are not carried out of the iteration that ran on the map before its first refinement in the
+ * call: the rule of mci_set_chain_carry).  Inside the point's workgroup, between its iterations, block by block: :mcmc -- the block's
+ * stored chains are resampled with probability ~ reweight_now[curr] / reweight_used[curr] (reweight_used: the point's factors before
+ * the storing iteration's doReweight!) and run with nburn = 0; :vegasmc -- pi_new / pi_old is evaluated at every stored configuration on
+ * the refined map and the moved factors, the block is resampled with these weights and runs with the burn-in mci_chain_burnin(steps,
+ * 1, nslots).  The chain count is K in every iteration; with K = 1 nothing is ever carried.  The FIRST iteration of every call starts
+ * afresh: chain state does not travel between calls (no chain state comes in or goes out).
+ * Results: when at least one iteration of a point was carried and niter > ignore + 1, the point's stdev is the block-lineage error
+ * (the blocks' means of every iteration, mci_lineage_sums + mci_mean_std as in mci_integrate) and correlated = 1; mean and chi2 stay
+ * the reference's.  Such calls run kernels of their own (MCI_VEGASMC_SWEEP_CARRY, MCI_MCMC_SWEEP_CARRY) and take, per point, two
+ * buffers of the chains' end configurations [ndraw][block * K] with their integrand index (:mcmc) or target (:vegasmc), the picks,
+ * the running weights and niter x block x nobs block means more of the 4 GiB.  The setting adds no refusal to mci_sweep_chains_supported /
+ * mci_sweep_mcmc_supported, and the signatures of the two entry points do not change. */
+int mci_set_sweep_chain_carry(mci_problem *prob, int32_t on);
+int mci_get_sweep_chain_carry(const mci_problem *prob, int32_t *on);
 /* doubles of one maps_in / maps_out row of mci_integrate_sweep for this problem (nbin + 1 for one Continuous leaf) */
 int mci_sweep_map_doubles(const mci_problem *prob, int32_t *n);
 /* A stratified parameter sweep: `npoint` independent VEGAS+ loops -- what mci_integrate runs on a stratified problem
@@ -318,7 +340,8 @@ int mci_sweep_strat_doubles(const mci_problem *prob, const mci_integrate_args *a
  * block, chain and step, same arithmetic per step, burn-in mci_chain_burnin), merges the block rows (main.jl:273-287) and the propose |
  * accept tables, runs doReweight! on the point's own factors (main.jl:183, :322-346 -- whatever `adapt` says) and train! on every leaf.
  * userdata, seeds, maps_in, maps_out (rows of mci_sweep_map_doubles doubles, any mix of Continuous and Discrete leaves), results,
- * iter_mean, iter_std and status are mci_integrate_sweep's; every result has correlated = 0.
+ * iter_mean, iter_std and status are mci_integrate_sweep's; every result has correlated = 0 (mci_set_sweep_chain_carry(prob, 1): chains
+ * carried from iteration to iteration, correlated and stdev as in mci_integrate).
  *   reweight_in   NULL: every point starts from the problem's current factors; else [npoint][nintegrand + 1]
  *   reweight_out  NULL or [npoint][nintegrand + 1]: every point's factors after its last doReweight! (what a later call passes as
  *                 reweight_in, with maps_out as maps_in and first_iteration moved on, to go on with a scan)
@@ -349,7 +372,9 @@ int mci_sweep_chains_supported(const mci_problem *prob, const mci_integrate_args
  * ones; the 64 chains of a wave share the update-type sequence when nchain > 1), merges the block rows (main.jl:273-287) and the propose
  * | accept tables, runs doReweight! on the point's own factors (main.jl:183, :322-346 -- whatever `adapt` says) and train! on every
  * leaf.  No warm-up repetition and no automatic chain count: nchain is explicit.  userdata, seeds, maps_in, maps_out, reweight_in,
- * reweight_out, pa_out, results, iter_mean, iter_std and status are mci_integrate_sweep_chains's; every result has correlated = 0.
+ * reweight_out, pa_out, results, iter_mean, iter_std and status are mci_integrate_sweep_chains's; every result has correlated = 0
+ * (mci_set_sweep_chain_carry(prob, 1): chains carried from iteration to iteration, no burn-in in carried iterations, correlated and
+ * stdev as in mci_integrate).
  *   holds_out     NULL or [npoint][64]: every point's holding-time histogram (mci_get_hold_histogram's bins), summed over all
  *                 iterations and blocks of the call.  A point whose top occupied bin b has 16 (2^b - 1) beyond the measured steps of a
  *                 chain ran chains too short for what they held (the rule of mci_mcmc_launch_valid for fresh chains): with nchain

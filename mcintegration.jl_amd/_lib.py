@@ -90,6 +90,8 @@ SIGNATURES = [
                                       C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_sweep_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
     ("mci_set_sweep_leaves", C.c_int, [_VP, C.c_int32]),
+    ("mci_set_sweep_chain_carry", C.c_int, [_VP, C.c_int32]),
+    ("mci_get_sweep_chain_carry", C.c_int, [_VP, c_int32_p]),
     ("mci_sweep_map_doubles", C.c_int, [_VP, c_int32_p]),
     ("mci_integrate_sweep_strat", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
                                             c_double_p, c_double_p, C.POINTER(C.c_int64), C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),

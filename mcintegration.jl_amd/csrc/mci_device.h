@@ -2058,9 +2058,27 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_chains(const BatchA
 
 // The NEW target at every stored configuration over the old one (BatchArgs::carry_w): one lane per stored chain; the same arithmetic in
 // the same order as a chain's start (montecarlo.jl:155-166) on the refined map and the moved reweight factors.
+// One stored chain: j = local block * carry_nchain + stored chain.  Shared by the grid-strided launch below and by a sweep point's
+// workgroup, which strides over one block's stored chains between two of its iterations (mci_sweep_chains.h).
+template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weight(const BatchArgs &a, const Tables<Cfg> &t, const double (&rw)[Cfg::NI + 1], const i64 j) {
+    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    const i64 lb = j / a.carry_nchain, from = j % a.carry_nchain;
+    Chain<Cfg> c;
+    load_carried<Cfg>(a, t, lb, from, c);
+    double w[Cfg::NW], pad[NI + 1];
+    if constexpr (Cfg::HOST_INTEGRAND != 0) // (a host closure: evaluated at the stored configurations before this launch, host_w[q * carry_total + j])
+        static_for<0, Cfg::NW>([&](auto Q) { w[decltype(Q)::value] = a.host_w[decltype(Q)::value * a.carry_total + j]; });
+    else
+    Cfg::integrand(c.x, w, a.ud, -1);
+    static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); });
+    double probability = rw[NORMI] * pad[NORMI];
+    static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; probability += absw<Cfg, i>(w) * rw[i] * pad[i]; });
+    const double r = probability / a.carry_P[lb * a.carry_nchain + from];
+    a.carry_w[j] = (r == r && r < 1.7976931348623157e308 && r > 0.0) ? r : 0.0; // (a configuration neither target can have produced continues nothing)
+}
 template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weights(const BatchArgs &a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    constexpr int NI = Cfg::NI;
     const int tid = threadIdx.x, T = blockDim.x;
     double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
     stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
@@ -2072,21 +2090,7 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weights(const
     t.DD = sDD;
     double rw[NI + 1];
     static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
-    for (i64 j = (i64)blockIdx.x * T + tid; j < a.carry_total; j += (i64)gridDim.x * T) {
-        const i64 lb = j / a.carry_nchain, from = j % a.carry_nchain;
-        Chain<Cfg> c;
-        load_carried<Cfg>(a, t, lb, from, c);
-        double w[Cfg::NW], pad[NI + 1];
-        if constexpr (Cfg::HOST_INTEGRAND != 0) // (a host closure: evaluated at the stored configurations before this launch, host_w[q * carry_total + j])
-            static_for<0, Cfg::NW>([&](auto Q) { w[decltype(Q)::value] = a.host_w[decltype(Q)::value * a.carry_total + j]; });
-        else
-        Cfg::integrand(c.x, w, a.ud, -1);
-        static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); });
-        double probability = rw[NORMI] * pad[NORMI];
-        static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; probability += absw<Cfg, i>(w) * rw[i] * pad[i]; });
-        const double r = probability / a.carry_P[lb * a.carry_nchain + from];
-        a.carry_w[j] = (r == r && r < 1.7976931348623157e308 && r > 0.0) ? r : 0.0; // (a configuration neither target can have produced continues nothing)
-    }
+    for (i64 j = (i64)blockIdx.x * T + tid; j < a.carry_total; j += (i64)gridDim.x * T) vegasmc_carry_weight<Cfg>(a, t, rw, j);
 }
 
 // ---------------------------------------------------------------------------------------------

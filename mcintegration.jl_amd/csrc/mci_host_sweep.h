@@ -173,13 +173,24 @@ static int compile_sweep_unit(mci_problem *p, int which) {
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
     // (the several-leaves and the chain solvers' units' LDS is the layout's; the stratified unit's is the call's: sweep_run)
-    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kChains || which == mci_problem::Sweep::kMcmc;
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || which >= mci_problem::Sweep::kChains;
     return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
 int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
     if (!p || (mode != MCI_SWEEP_ONE_GRID && mode != MCI_SWEEP_ALL_LEAVES)) return fail(MCI_ERR_INVALID, "sweep leaves: MCI_SWEEP_ONE_GRID (0) or MCI_SWEEP_ALL_LEAVES (1)");
     p->sweep.leaves_mode = mode;
+    return MCI_OK;
+}
+
+int mci_set_sweep_chain_carry(mci_problem *p, int32_t on) {
+    if (!p || (on != 0 && on != 1)) return fail(MCI_ERR_INVALID, "sweep chain carry: 0 (every iteration of a point starts its chains afresh) or 1 (it continues the chains of the one before)");
+    p->sweep.chain_carry = on;
+    return MCI_OK;
+}
+int mci_get_sweep_chain_carry(const mci_problem *p, int32_t *on) {
+    if (!p || !on) return fail(MCI_ERR_INVALID, "NULL argument");
+    *on = p->sweep.chain_carry;
     return MCI_OK;
 }
 
@@ -228,10 +239,10 @@ int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
 // ---------------------------------------------------------------------------------------------------
 namespace {
 // The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
-// kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the chain solvers' units', kSegHolds the :mcmc unit's (none
-// otherwise).  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
+// kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the chain solvers' units', kSegHolds the :mcmc unit's,
+// kSegCarry (the stored chains, the picks, the weights) and kSegBlk (the block means) the carried chain units' (none otherwise).  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
 // bytes per point), (the seeds: copied next), status words.
-enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegGhist, kSegD, kSegHolds, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegCarry, kSegBlk, kSegGhist, kSegD, kSegHolds, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
 
 // What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
 struct SweepCall {
@@ -254,6 +265,8 @@ struct SweepCall {
     size_t rw_doubles = 0, pa_doubles = 0;                    // per point: kSegRw (reweight factors), kSegPa (the blocks' propose | accept rows)
     size_t packed_doubles = 0;   // a point's packed row; 0: the statistics head alone
     size_t holds_doubles = 0;    // per point: kSegHolds (64 or none)
+    size_t carry_doubles = 0, blk_doubles = 0; // per point: kSegCarry, kSegBlk (carried chains)
+    const double *block_means = nullptr; // carried chains, set by finish(): [npoint][niter][blocks][nobs] on the host -- the points' errors come from their blocks' lineages
     int maxn = 0;                // bins of the largest leaf
     int64_t lds = 0;             // bytes of LDS of a workgroup
     int map_off = 0;             // SweepHead::map_off
@@ -280,7 +293,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((rc = c.plan(c))) return rc;
     const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
     const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, c.packed_doubles ? c.packed_doubles : (size_t)nstat,
-                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.seeds ? (size_t)1 : 0};
+                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, c.carry_doubles, c.blk_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.seeds ? (size_t)1 : 0};
     size_t o[kSegCount + 1] = {0};
     for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
     const size_t ndbl = o[kSegStatus] + (P + 1) / 2;
@@ -403,6 +416,14 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
             mci_average(im + o2, ie + o2, s.nobs, ignore + 1, niter, &res->mean[o2], &res->stdev[o2], &res->chi2[o2]);
         res->correlated = 0;
         res->warmup = 0;
+        // carried chains: the error from the scatter of the blocks' weighted averages over the run, as in mci_integrate (mci_host_integrate.h)
+        if (c.block_means && niter > ignore + 1) {
+            std::vector<double> sums(2 * (size_t)s.nobs), lm(s.nobs), le(s.nobs);
+            mci_lineage_sums(c.block_means + (size_t)q * niter * c.blocks * s.nobs, niter, c.blocks, s.nobs, ie, ignore + 1, niter, sums.data(), sums.data() + s.nobs);
+            mci_mean_std(sums.data(), sums.data() + s.nobs, s.nobs, c.blocks, lm.data(), le.data());
+            for (int o2 = 0; o2 < s.nobs; ++o2) res->stdev[o2] = le[o2] > 0.0 ? le[o2] : res->stdev[o2];
+            res->correlated = 1;
+        }
         if (c.status) c.status[q] = hst[q];
     }
     return MCI_OK;
@@ -693,6 +714,7 @@ int sweep_chains_query(const mci_problem *p, const mci_integrate_args *a, char *
 // P independent chain-solver integrate() loops (main.jl:142-207 around vegas_mc/montecarlo.jl:112-241 | mcmc/montecarlo.jl:72-187), one
 // workgroup each, in one launch.  What the two entry points share; solver: MCI_VEGASMC | MCI_MCMC (holds_out: the latter's)
 static_assert(offsetof(mci::SweepChainArgs, h) == 0, "sweep_run fills the chain units' argument through its head");
+static_assert(offsetof(mci::SweepChainCarryArgs, c) == 0, "one object serves the four chain units: the uncarried ones read its first member");
 int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solver, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                       double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, uint64_t *holds_out, mci_result *results,
                       double *iter_mean, double *iter_std, int32_t *status) {
@@ -700,17 +722,37 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
     if (int rc = sweep_check_args(p, a, npoint, userdata, results, mcmc ? mci_sweep_mcmc_supported : mci_sweep_chains_supported)) return rc;
     const size_t P = (size_t)npoint, nd = (size_t)p->ni + 1, npa2 = 2 * (size_t)p->npa;
     const size_t tables = (size_t)p->nstat + p->shape.nbin; // where merge_pa leaves them in a packed row (mci_train.h)
-    mci::SweepChainArgs f{};
-    std::vector<double> hrw;
+    mci::SweepChainCarryArgs fa{}; // (the uncarried units' argument is its first member)
+    mci::SweepChainArgs &f = fa.c;
+    mci::SweepCarryArgs &fk = fa.k;
+    std::vector<double> hrw, hbm;
     SweepCall c;
-    c.unit = mcmc ? mci_problem::Sweep::kMcmc : mci_problem::Sweep::kChains;
+    // mci_set_sweep_chain_carry: the units with carried chains.  What a point keeps between its iterations, per point, in doubles of
+    // kSegCarry (cap = blocks * nchain stored chains a buffer): x [2][ndraw][cap] | P [2][cap] (:vegasmc) or curr [2][cap] ints (:mcmc) |
+    // W [cap] | w [cap] (:vegasmc) or reweight_used [nd] (:mcmc) | src [cap] ints
+    const bool carry = p->sweep.chain_carry != 0;
+    const int carry_first = (mcmc || !a->adapt) ? 1 : 2; // (plan_may_carry: :vegasmc not out of the iteration on the map before its first refinement)
+    const bool carried = carry && a->nchain > 1 && a->niter > carry_first; // some iteration of every point continues the one before
+    size_t cx = 0, cp = 0, cw = 0, cw2 = 0, csrc = 0; // offsets of the parts behind x, doubles
+    c.unit = carry ? (mcmc ? mci_problem::Sweep::kMcmcCarry : mci_problem::Sweep::kChainsCarry) : (mcmc ? mci_problem::Sweep::kMcmc : mci_problem::Sweep::kChains);
     c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
     c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
-    c.plan = [a, npa2](SweepCall &c) {
+    c.plan = [&, a, npa2](SweepCall &c) {
         mci_standardize_block(a->neval, a->block, 1, &c.neval_per_block, &c.blocks); // main.jl:121 (at most 4096 blocks: sweep_chains_refusal)
         c.rows = c.blocks;
         c.pa_doubles = (size_t)c.blocks * npa2;
         c.too_big_count = (long long)c.blocks;
+        if (carry) {
+            const size_t cap = (size_t)c.blocks * (size_t)a->nchain, half = (cap + 1) / 2;
+            cx = 2 * (size_t)p->shape.ndraw * cap;
+            cp = cx;                            // P [2][cap] | curr [2][cap] ints
+            cw = cp + (mcmc ? 2 * half : 2 * cap);
+            cw2 = cw + cap;                     // w [cap] | reweight_used [nd]
+            csrc = cw2 + (mcmc ? nd : cap);
+            c.carry_doubles = csrc + half;
+            c.blk_doubles = (size_t)a->niter * (size_t)c.blocks * (size_t)p->shape.nobs;
+            hbm.resize(carried ? P * c.blk_doubles : 0);
+        }
         return (int)MCI_OK;
     };
     c.map_doubles = (size_t)sweep_map_doubles(p);
@@ -746,7 +788,27 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
         f.part_pa = d + o[kSegPa];
         f.packed_stride = (int)c.packed_doubles;
         f.holds = mcmc ? reinterpret_cast<unsigned long long *>(d + o[kSegHolds]) : nullptr; // (zeroed with everything from kSegGhist on)
-        return &f;
+        if (carry) { // (a point's parts lie one behind the other in its kSegCarry row: the kernel strides by the part's own length, so
+            // every part is laid out [npoint][part] -- the segment is cut part by part, not point by point)
+            const size_t cap = (size_t)c.blocks * (size_t)a->nchain, half = (cap + 1) / 2;
+            double *g = d + o[kSegCarry];
+            fk.chain_x = g;
+            g += P * cx;
+            if (mcmc) fk.chain_curr = reinterpret_cast<int *>(g), g += P * 2 * half;
+            else fk.chain_P = g, g += P * 2 * cap;
+            fk.carry_W = g;
+            g += P * cap;
+            if (mcmc) fk.rw_used = g, g += P * nd;
+            else fk.carry_w = g, g += P * cap;
+            fk.carry_src = reinterpret_cast<int *>(g);
+            fk.block_means = d + o[kSegBlk];
+            const int64_t steps = c.neval_per_block / a->nchain;
+            fk.nburn_carried = 0;                                          // plan_mcmc_chains: carried chains have no start to burn in
+            fk.burnin_carried = mci_chain_burnin(steps, 1, sweep_nslots(p)); // plan_vegasmc_chains: the reference's own neval / 100
+            fk.carry_first = carry_first;
+            fk.lds_w = c.map_off - (int)mci::kResampleThreads;
+        }
+        return &fa;
     };
     c.copy_out = [&](double *d, const size_t *o, hipStream_t st) {
         if (reweight_out) HIPCHK(hipMemcpyAsync(reweight_out, d + o[kSegRw], P * nd * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -754,8 +816,10 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
             HIPCHK(hipMemcpy2DAsync(pa_out, npa2 * sizeof(double), d + o[kSegPacked] + tables, c.packed_doubles * sizeof(double), npa2 * sizeof(double), P,
                                     hipMemcpyDeviceToHost, st));
         if (mcmc && holds_out) HIPCHK(hipMemcpyAsync(holds_out, d + o[kSegHolds], P * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (!hbm.empty()) HIPCHK(hipMemcpyAsync(hbm.data(), d + o[kSegBlk], hbm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         return (int)MCI_OK;
     };
+    c.finish = [&] { c.block_means = hbm.empty() ? nullptr : hbm.data(); };
     return sweep_run(p, a, c);
 }
 } // namespace

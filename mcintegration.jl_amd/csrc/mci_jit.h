@@ -117,8 +117,10 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // train! and the doReweight! branch of iteration_bookkeeping stay in
 // kUnitSweepMcmc: the :mcmc chain loop (mci_device.h mcmc_chains, one lane per chain) inside the same header's other instantiation
 // (mcmc_sweep: one workgroup runs a point's whole :mcmc loop); generated for MCI_MCMC, compiled like kUnitSweepChains
-// The five sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitCount = 11 };
+// kUnitSweepChainsCarry, kUnitSweepMcmcCarry: the two units above with chains carried from one iteration of a point to the next
+// (mci_sweep_chains.h chain_sweep<Cfg, MCMC, true>; mci_set_sweep_chain_carry): kernels and code objects of their own, compiled like them
+// The seven sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitCount = 13 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -151,6 +153,8 @@ constexpr UnitRow kUnits[] = {
     /* kUnitSweepStrat   */ {"mci_sweep_strat.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}}, "mci_vegas_sweep_strat", "SweepStratArgs", "f", "vegas_sweep_strat", 1, true, 1, true, true, false},
     /* kUnitSweepChains  */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep", "SweepChainArgs", "f", "vegasmc_sweep", -1, false, 2, true, false, true},
     /* kUnitSweepMcmc    */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep", "SweepChainArgs", "f", "mcmc_sweep", -1, false, 2, true, false, true},
+    /* kUnitSweepChainsCarry */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep_carry", "SweepChainCarryArgs", "f", "vegasmc_sweep_carry", -1, false, 2, true, false, true},
+    /* kUnitSweepMcmcCarry   */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep_carry", "SweepChainCarryArgs", "f", "mcmc_sweep_carry", -1, false, 2, true, false, true},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN

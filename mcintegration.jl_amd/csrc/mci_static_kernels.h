@@ -57,131 +57,12 @@ __global__ void __launch_bounds__(256) k_finalize(MergeArgs m) {
     merge_stats(m);
 }
 
-// Carried :mcmc chains (this engine's many-chain decomposition; DESIGN.md "Chains"): which stored chain every chain of the next launch
-// continues.  The chains a block stored are a sample of the finished iteration's target ~ reweight_old[idx] |f_idx(x)|; doReweight! has
-// moved the factors since, so the next target differs from it by the known ratio w[idx] = reweight_new[idx] / reweight_old[idx]:
-// systematic resampling of the block's stored chains (chain order, one fixed offset u -- deterministic) with probability ~ w[curr].
-//   W[j] = sum_i w[i] * #(stored chains j' <= j that ended on integrand i)        (added over i = 0 .. nd-1 in that order)
-//   new chain c continues the first stored chain j with W[j] > (c + u) * (W[n_old-1] / n_new),  u = (sqrt(5) - 1) / 2  (with u = 1/2
-//   many chain counts make (c + u) n_old / n_new an integer: exact ties, decided by the last bit of w, whenever a block's stored chains
-//   all sit on one integrand)
-// One workgroup per block; mirrored by mcio_resample_chains (same operations in the same order: same picks).
-struct ResampleArgs {
-    const int *curr_old;   // [nblocks][n_old]
-    long long n_old, n_new;
-    int nd;
-    const double *rw_now, *rw_used; // [nd]
-    int *src;              // [nblocks][n_new]
-    double *W;             // [nblocks][n_old] scratch
-    const double *w_chain; // [nblocks][n_old] or NULL: a weight per stored chain (:vegasmc: new target / old target, vegasmc_carry_weights)
-                           // instead of a weight per integrand index
-};
+// Carried chains: which stored chain every chain of the next launch continues -- one workgroup per block runs resample_block
+// (mci_train.h: the rule, ResampleArgs and the body, which a sweep point's workgroup runs too, mci_sweep_chains.h).
 __global__ void __launch_bounds__(256) k_resample_chains(ResampleArgs a) {
-    constexpr int kLdsW = 8192; // stored chains per block whose running weights also sit in LDS: the bisections below then read LDS
-    __shared__ double sW[kLdsW];
-    __shared__ long long part[256];
-    const int tid = threadIdx.x, T = 256;
-    const int *co = a.curr_old + (size_t)blockIdx.x * a.n_old;
-    double *W = a.W + (size_t)blockIdx.x * a.n_old;
-    int *src = a.src + (size_t)blockIdx.x * a.n_new;
-    const long long per = (a.n_old + T - 1) / T, j0 = tid * per < a.n_old ? tid * per : a.n_old, j1 = j0 + per < a.n_old ? j0 + per : a.n_old;
-    constexpr int kNd = 16; // integrands (+ the normalisation) whose running counts a thread keeps in registers
-    if (a.w_chain) {
-        // W[j] = (sum of the stretches before this thread's, added in thread order) + (running sum along the thread's own stretch): a
-        // fixed association the oracle repeats (mcio_resample_weighted)
-        __shared__ double dpart[256];
-        const double *wc = a.w_chain + (size_t)blockIdx.x * a.n_old;
-        double mine = 0.0;
-        for (long long j = j0; j < j1; ++j) mine += wc[j];
-        dpart[tid] = mine;
-        __syncthreads();
-        double below = 0.0;
-        for (int t = 0; t < tid; ++t) below += dpart[t];
-        double run = 0.0;
-        for (long long j = j0; j < j1; ++j) {
-            run += wc[j];
-            const double v = below + run;
-            W[j] = v;
-            if (a.n_old <= kLdsW) sW[j] = v;
-        }
-    } else
-    if (a.nd <= kNd) {
-        // Two passes over the thread's stretch of the stored chains instead of one read-modify-write pass over W per integrand: the
-        // per-integrand counts below the stretch first, then W[j] = sum_i w[i] * cnt_i(j), the terms added over i = 0 .. nd-1 in that
-        // order -- the same numbers in the same order as the pass per integrand (the counts are integers, every product is formed once).
-        long long cnt[kNd];
-        double w[kNd];
-#pragma unroll
-        for (int i = 0; i < kNd; ++i) {
-            cnt[i] = 0;
-            w[i] = i < a.nd ? a.rw_now[i] / a.rw_used[i] : 0.0;
-        }
-        for (long long j = j0; j < j1; ++j) {
-            const int c = co[j];
-#pragma unroll
-            for (int i = 0; i < kNd; ++i) cnt[i] += c == i ? 1 : 0;
-        }
-        for (int i = 0; i < a.nd; ++i) { // this thread's counts -> the counts of everything before its stretch
-            long long mine = 0;
-#pragma unroll
-            for (int q = 0; q < kNd; ++q) mine = q == i ? cnt[q] : mine;
-            __syncthreads();
-            part[tid] = mine;
-            __syncthreads();
-            long long below = 0;
-            for (int t = 0; t < tid; ++t) below += part[t];
-#pragma unroll
-            for (int q = 0; q < kNd; ++q) cnt[q] = q == i ? below : cnt[q];
-        }
-        for (long long j = j0; j < j1; ++j) {
-            const int c = co[j];
-            double acc = 0.0;
-#pragma unroll
-            for (int i = 0; i < kNd; ++i) {
-                cnt[i] += c == i ? 1 : 0;
-                if (i < a.nd) {
-                    const double term = w[i] * (double)cnt[i];
-                    acc = i == 0 ? term : acc + term;
-                }
-            }
-            W[j] = acc;
-            if (a.n_old <= kLdsW) sW[j] = acc;
-        }
-    } else
-    for (int i = 0; i < a.nd; ++i) { // one pass per integrand: its running count along the stored chains, times its ratio, onto W
-        const double w = a.rw_now[i] / a.rw_used[i];
-        long long mine = 0;
-        for (long long j = j0; j < j1; ++j) mine += co[j] == i ? 1 : 0;
-        __syncthreads();
-        part[tid] = mine;
-        __syncthreads();
-        long long cnt = 0;
-        for (int t = 0; t < tid; ++t) cnt += part[t];
-        for (long long j = j0; j < j1; ++j) {
-            cnt += co[j] == i ? 1 : 0;
-            const double term = w * (double)cnt;
-            W[j] = i == 0 ? term : W[j] + term;
-        }
-    }
-    __threadfence_block();
-    __syncthreads();
-    const bool in_lds = (a.w_chain != nullptr || a.nd <= kNd) && a.n_old <= kLdsW;
-    const double step = W[a.n_old - 1] / (double)a.n_new;
-    if (!(W[a.n_old - 1] > 0.0)) { // every stored chain has weight zero (or the total is not a number): nothing to resample BY -- spread the
-        // new chains over the stored ones instead of continuing all of them from the last (they burn in from there like fresh starts)
-        for (long long c = tid; c < a.n_new; c += T) src[c] = (int)(c % a.n_old);
-        return;
-    }
-    for (long long c = tid; c < a.n_new; c += T) {
-        const double target = ((double)c + 0.6180339887498949) * step;
-        long long lo = 0, hi = a.n_old - 1; // smallest j with W[j] > target
-        while (lo < hi) {
-            const long long mid = (lo + hi) >> 1;
-            if ((in_lds ? sW[mid] : W[mid]) > target) hi = mid;
-            else lo = mid + 1;
-        }
-        src[c] = (int)lo;
-    }
+    constexpr int kLdsW = 8192; // stored chains per block whose running weights also sit in LDS: the bisections then read LDS
+    __shared__ double scratch[kResampleThreads + kLdsW];
+    resample_block(a, (long long)blockIdx.x, scratch, kLdsW);
 }
 
 // One workgroup per leaf: Dist.train! then clearStatistics!; workgroup `nleaf`: bookkeeping.

@@ -34,6 +34,27 @@
 // iterations and blocks of the call.
 // merge_pa sums four entries per call, one wave each: the workgroup has at least four waves (the host launches kSweepThreads = 256).
 //
+// Carried chains (chain_sweep<Cfg, MCMC, true>: the units kUnitSweepChainsCarry | kUnitSweepMcmcCarry, mci_set_sweep_chain_carry; the two units
+// above keep their instructions -- everything below stands under `if constexpr (CARRY)` and reads an argument of its own, SweepCarryArgs).  A carried point is integrate(..., nchain = K) on a
+// fresh problem with mci_set_chain_carry(prob, 1) and one lane per chain: iteration `it` of the call (0-based) continues the chains of
+// iteration it - 1 iff K > 1 and it >= carry_first (1 under :mcmc or with adapt = false; 2 under :vegasmc with adapt = true, whose chains are
+// not carried out of the iteration that ran on the map before its first refinement in this call: plan_may_carry).  The first iteration
+// of every call starts afresh: chain state does not travel between calls.  Every iteration of such a point stores its chains' ends
+// (BatchArgs::store_x | store_curr | store_P) in one of the point's two buffers -- two, because with K > 256 a lane's second chain starts
+// after other chains of the block have stored their ends --, and before block b's chains of a carried iteration the workgroup
+//   * (:vegasmc) strides over the block's K stored chains with vegasmc_carry_weight (mci_device.h: pi_new / pi_old on the refined map and
+//     the moved factors) -> carry_w;
+//   * resamples the block with resample_block (mci_train.h; scratch: the front of the LDS segment, where the chain loop's carve is dead;
+//     running weights that do not fit there are bisected in the global W) -> carry_src: :mcmc with probability ~ reweight_now[curr] /
+//     reweight_used[curr], reweight_used being the factors as they stood when the storing iteration's chains ran (copied before that
+//     iteration's doReweight!);
+//   * runs the chain loop with carry_* / store_* on the point's rows and the burn-in of a carried launch (nburn = 0; mci_chain_burnin(steps, 1,
+//     nslots)).
+// All of it is written and read by the point's own workgroup with plain stores and loads, and a sweep_round_trip() stands between each
+// writer and its readers: chain ends -> next iteration's weights / resampling (the round trip behind the last block), carry_w ->
+// resampling, carry_src -> chain starts, reweight_used -> resampling (the round trips of the leaves' histogram slices).  merge_stats writes
+// the blocks' means of every iteration (MergeArgs::block_means) for the host's block-lineage error (mci_lineage_sums).
+//
 // LDS: the chain loop's carve Lds<Cfg> (tables | histogram | observables | reduction scratch | propose / accept counters) and the
 // refinement's scratch share the front of the segment -- each is dead while the other runs --, the point's map block lies behind both
 // (SweepHead::map_off; the host's sweep_leaves_lds counts the carve including the counters).
@@ -49,8 +70,47 @@ struct SweepChainArgs {
     int packed_stride;    // doubles of a point's packed row: statistics [nstat] | (histogram [nbin], unused) | propose | accept [2 npa] | holds [64]
     unsigned long long *holds; // [npoint][64] or NULL  :mcmc: the points' holding-time histograms (BatchArgs::hold_hist; zeroed by the host, never read here)
 };
+// the second argument of the two units with carried chains: the one above, then what a point keeps between its iterations
+// (cap = nblocks * nchain).  An argument type of their own, so that the uncarried units' argument -- and with it the offsets their
+// instructions address the launch's hidden arguments by -- stays what it was.
+struct SweepCarryArgs {
+    double *chain_x;      // [npoint][2][ndraw][cap]  the chains' end configurations, two buffers: iteration `it` writes it & 1, reads the other
+    int *chain_curr;      // [npoint][2][cap]         :mcmc: the integrand each chain ended on
+    double *chain_P;      // [npoint][2][cap]         :vegasmc: the target at each end configuration
+    int *carry_src;       // [npoint][cap]            which stored chain of its block each chain continues
+    double *carry_W;      // [npoint][cap]            resample_block's running weights
+    double *carry_w;      // [npoint][cap]            :vegasmc: pi_new / pi_old of the stored chains
+    double *rw_used;      // [npoint][nd]             :mcmc: the factors the stored chains ran under
+    double *block_means;  // [npoint][niter][nblocks][nobs]
+    double burnin_carried; // BatchArgs::burnin | nburn of a carried iteration (a0 holds those of fresh chains)
+    i64 nburn_carried;
+    int carry_first;      // the first iteration of the call that continues the one before: 1 | 2
+    int lds_w;            // doubles of LDS behind resample_block's partial sums: map_off - kResampleThreads
+};
+struct SweepChainCarryArgs {
+    SweepChainArgs c; // (first: the host fills one object for all four units)
+    SweepCarryArgs k;
+};
 
-template <class Cfg, bool MCMC> __device__ __forceinline__ void chain_sweep(const BatchArgs &a0, const SweepChainArgs &fc) {
+// pi_new / pi_old of block lb's stored chains: the workgroup's lanes stride over them (vegasmc_carry_weights for one block)
+template <class Cfg> __device__ __forceinline__ void carry_weights_block(const BatchArgs &a, const i64 lb) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NI = Cfg::NI;
+    const int tid = threadIdx.x, T = blockDim.x;
+    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
+    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
+    __syncthreads();
+    Tables<Cfg> t;
+    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
+    else t.E = a.edges;
+    t.DA = sDA;
+    t.DD = sDD;
+    double rw[NI + 1];
+    static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
+    for (i64 from = tid; from < a.carry_nchain; from += T) vegasmc_carry_weight<Cfg>(a, t, rw, lb * a.carry_nchain + from);
+}
+
+template <class Cfg, bool MCMC, bool CARRY = false> __device__ __forceinline__ void chain_sweep(const BatchArgs &a0, const SweepChainArgs &fc, const SweepCarryArgs *kp = nullptr) {
     static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0 &&
                       Cfg::HOST_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS, and measures on the device (the host checks)");
@@ -83,16 +143,74 @@ template <class Cfg, bool MCMC> __device__ __forceinline__ void chain_sweep(cons
         a.edges = bedges; // (LDS through the generic address space: stage_tables reads the three tables once per call)
         a.dacc = bdacc;
         a.ddist = bddist;
+        // carried chains: this point's rows (cap stored chains a buffer); nothing is kept or continued with one chain per block
+        const i64 cap = (i64)nblocks * a0.nchain;
+        const bool keep = CARRY && a0.nchain > 1;
+        double *rwu = nullptr;
+        if constexpr (CARRY) rwu = kp->rw_used + (size_t)p * f.t.nd;
         for (int it = 0; it < f.niter; ++it) {
             a.iteration = a0.iteration + (u32)it;
             if (tid == 0) bad[0] = 0;
+            bool cont = false; // this iteration's chains continue those of the one before
+            if constexpr (CARRY) {
+                const SweepCarryArgs &fk = *kp;
+                cont = keep && it >= fk.carry_first;
+                if (keep) {
+                    const int wb = it & 1;
+                    double *x2 = fk.chain_x + (size_t)p * 2 * Cfg::NDRAW * cap;
+                    a.store_x = x2 + (size_t)wb * Cfg::NDRAW * cap;
+                    a.store_cap = cap;
+                    if constexpr (MCMC) a.store_curr = fk.chain_curr + ((size_t)p * 2 + wb) * cap;
+                    else a.store_P = fk.chain_P + ((size_t)p * 2 + wb) * cap;
+                    a.carry_x = cont ? x2 + (size_t)(1 - wb) * Cfg::NDRAW * cap : nullptr;
+                    a.carry_nchain = a0.nchain;
+                    a.carry_cap = cap;
+                    a.carry_src = cont ? fk.carry_src + (size_t)p * cap : nullptr;
+                    if constexpr (MCMC) {
+                        a.carry_curr = fk.chain_curr + ((size_t)p * 2 + (1 - wb)) * cap;
+                        a.nburn = cont ? fk.nburn_carried : a0.nburn;
+                    } else {
+                        a.carry_P = fk.chain_P + ((size_t)p * 2 + (1 - wb)) * cap;
+                        a.carry_w = fk.carry_w + (size_t)p * cap;
+                        a.carry_total = cap;
+                        a.burnin = cont ? fk.burnin_carried : a0.burnin;
+                    }
+                }
+                m.block_means = fk.block_means + ((size_t)p * f.niter + it) * nblocks * f.m.nobs;
+            }
             for (int b = 0; b < nblocks; ++b) {
                 a.chunk_lo = b;  // work_item: row = block (wg_per_block = 1)
+                if constexpr (CARRY) {
+                    if (cont) { // which stored chain of block b each of its chains continues: the stored ones resampled to the moved target
+                        const SweepCarryArgs &fk = *kp;
+                        ResampleArgs ra;
+                        ra.curr_old = a.carry_curr;
+                        ra.n_old = ra.n_new = a0.nchain;
+                        ra.nd = f.t.nd;
+                        ra.rw_now = rw;
+                        ra.rw_used = rwu;
+                        ra.src = fk.carry_src + (size_t)p * cap;
+                        ra.W = fk.carry_W + (size_t)p * cap;
+                        ra.w_chain = nullptr;
+                        __syncthreads(); // (whatever read the front of the LDS segment before is through)
+                        if constexpr (!MCMC) {
+                            carry_weights_block<Cfg>(a, b);
+                            sweep_round_trip(); // carry_w -> resampling (and the staged tables are read: the scratch takes their place)
+                            ra.w_chain = a.carry_w;
+                        }
+                        resample_block(ra, b, smem, fk.lds_w);
+                        sweep_round_trip(); // carry_src -> chain starts
+                    }
+                }
                 __syncthreads(); // (map, flag and -- from the second iteration on -- whatever read this LDS before are through)
                 // tables <- the map block, the block's chains, its partial row and its propose | accept row, histogram atomics into this point's row
                 if constexpr (MCMC) mcmc_chains<Cfg>(a); else vegasmc_chains<Cfg>(a);
             }
             sweep_round_trip();
+            if constexpr (CARRY && MCMC) { // the factors this iteration's chains ran under: doReweight! moves them below
+                if (keep)
+                    for (int i = tid; i < f.t.nd; i += T) rwu[i] = rw[i];
+            }
             merge_stats(m); // main.jl:273-287
             for (int e = 0; e < merge_pa_blocks(m); ++e) merge_pa(m, e); // configuration.jl:297-298
             __syncthreads(); // the head of `packed` was written by this workgroup
@@ -119,5 +237,8 @@ template <class Cfg, bool MCMC> __device__ __forceinline__ void chain_sweep(cons
 
 template <class Cfg> __device__ __forceinline__ void vegasmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) { chain_sweep<Cfg, false>(a0, fc); }
 template <class Cfg> __device__ __forceinline__ void mcmc_sweep(const BatchArgs &a0, const SweepChainArgs &fc) { chain_sweep<Cfg, true>(a0, fc); }
+// ... and with chains carried from iteration to iteration (mci_set_sweep_chain_carry): two more units, the same body
+template <class Cfg> __device__ __forceinline__ void vegasmc_sweep_carry(const BatchArgs &a0, const SweepChainCarryArgs &f) { chain_sweep<Cfg, false, true>(a0, f.c, &f.k); }
+template <class Cfg> __device__ __forceinline__ void mcmc_sweep_carry(const BatchArgs &a0, const SweepChainCarryArgs &f) { chain_sweep<Cfg, true, true>(a0, f.c, &f.k); }
 
 } // namespace mci

@@ -440,7 +440,7 @@ class Engine:
     @staticmethod
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
-                "vegasmc_sweep": 11, "mcmc_sweep": 12}.get(solver) or _lib.SOLVERS[solver]
+                "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -450,7 +450,8 @@ class Engine:
         several variable leaves, csrc/mci_sweep_leaves.h; after set_sweep_leaves("all")) | "vegas_sweep_strat" (the kernel of
         integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts) | "vegasmc_sweep" (the kernel of
         integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts) | "mcmc_sweep" (the kernel of
-        integrate_sweep_mcmc, the same header's :mcmc instantiation; layouts sweep_mcmc_supported accepts)"""
+        integrate_sweep_mcmc, the same header's :mcmc instantiation; layouts sweep_mcmc_supported accepts) | "vegasmc_sweep_carry" |
+        "mcmc_sweep_carry" (the same two kernels with chains carried from iteration to iteration: set_sweep_chain_carry)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -744,6 +745,19 @@ class Engine:
             raise ValueError('set_sweep_leaves: "one" or "all", got %r' % (mode,))
         check(lib().mci_set_sweep_leaves(self.p, 1 if mode == "all" else 0))
 
+    def set_sweep_chain_carry(self, on=True):
+        """carried chains in integrate_sweep_chains / integrate_sweep_mcmc (mci_set_sweep_chain_carry; default off): every iteration of
+        a point after its first continues the chains of the one before, resampled to the target train! and doReweight! have moved --
+        what set_chain_carry(1) does for integrate(); :vegasmc with adapt=True from the third iteration on.  The first iteration of
+        every call starts afresh: chain state does not travel between calls."""
+        check(lib().mci_set_sweep_chain_carry(self.p, 1 if on else 0))
+
+    def sweep_chain_carry(self):
+        """what set_sweep_chain_carry set (mci_get_sweep_chain_carry)"""
+        on = C.c_int32()
+        check(lib().mci_get_sweep_chain_carry(self.p, C.byref(on)))
+        return bool(on.value)
+
     def sweep_map_doubles(self):
         """doubles of one `maps` row of integrate_sweep (mci_sweep_map_doubles): the leaves in order, a Continuous leaf its grid, a
         Discrete leaf its accumulation and then its distribution"""
@@ -821,7 +835,7 @@ class Engine:
         out = []
         for q in range(P):
             r = dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,
-                     visited=vis[q], correlated=False, block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
+                     visited=vis[q], correlated=bool(res[q].correlated), block_mean=None, warmup=0, neval_discarded=0, maps=mo[q],
                      maps_by_leaf=self._split_sweep_map(mo[q]), status=int(st[q]))
             for k, v in keys.items():
                 r[k] = v[q]
@@ -883,20 +897,29 @@ class Engine:
         return self._sweep_refusal(lib().mci_sweep_chains_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration)
 
     def integrate_sweep_chains(self, solver="vegasmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
-                               measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None):
+                               measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, carry=False):
         """A parameter sweep under the default solver in one launch (mci_integrate_sweep_chains): P independent :vegasmc loops -- what
         integrate("vegasmc", nchain=nchain) runs on this engine with set_chain_carry(0) and one lane per chain -- one workgroup per
         point, the blocks of a point one after another.  Arguments and result dicts as integrate_sweep (any mix of Continuous and
         Discrete leaves); every dict gains `reweight` (the point's factors after its last doReweight!, [N + 1]), `propose` and `accept`
         (the tables of its last iteration, shaped like acceptance()).  reweight: None (every point starts from the engine's current
         factors) or [P][N + 1], e.g. the `reweight` of an earlier sweep.  nchain >= 1: chains per block.  The engine's own map, factors,
-        packed buffer, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_chains_supported()."""
+        packed buffer, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_chains_supported().
+        carry=True: this call runs with set_sweep_chain_carry(True) -- what integrate("vegasmc", nchain=nchain) runs with
+        set_chain_carry(1); `correlated` and `stdev` are then integrate()'s (the block-lineage error); False: whatever
+        set_sweep_chain_carry says (off by default)."""
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain)
-        return self._sweep_chain_solver("integrate_sweep_chains", lib().mci_integrate_sweep_chains, a, niter, userdata, seeds, maps, reweight, False)
+        return self._sweep_chain_solver("integrate_sweep_chains", lib().mci_integrate_sweep_chains, a, niter, userdata, seeds, maps, reweight, False, carry)
 
-    def _sweep_chain_solver(self, name, fn, a, niter, userdata, seeds, maps, reweight, holds):
+    def _sweep_chain_solver(self, name, fn, a, niter, userdata, seeds, maps, reweight, holds, carry=False):
         """what integrate_sweep_chains and integrate_sweep_mcmc share: the arrays, the reweight check, the per-point factors and tables;
-        holds: the entry point also returns every point's holding-time histogram"""
+        holds: the entry point also returns every point's holding-time histogram; carry: set_sweep_chain_carry(True) for this call"""
+        if carry and not self.sweep_chain_carry():
+            self.set_sweep_chain_carry(True)
+            try:
+                return self._sweep_chain_solver(name, fn, a, niter, userdata, seeds, maps, reweight, holds)
+            finally:
+                self.set_sweep_chain_carry(False)
         ud, sd, mi, _ = self._sweep_inputs(name, userdata, seeds, maps)
         P, nd = ud.shape[0], self.config.N + 1
         m = max(nd, len(self.config.var))
@@ -931,16 +954,21 @@ class Engine:
         return self._sweep_refusal(lib().mci_sweep_mcmc_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration, thermal_ratio)
 
     def integrate_sweep_mcmc(self, solver="mcmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
-                             measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, thermal_ratio=0.1):
+                             measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, thermal_ratio=0.1, carry=False):
         """A parameter sweep under :mcmc in one launch (mci_integrate_sweep_mcmc): P independent :mcmc loops -- what
         integrate("mcmc", nchain=nchain, thermal_ratio=thermal_ratio) runs on this engine with set_chain_carry(0) and one lane per
         chain -- one workgroup per point, the blocks of a point one after another.  Arguments and result dicts as
         integrate_sweep_chains; every dict also carries `holds` (the point's holding-time histogram, 64 counts summed over the call's
         iterations and blocks: hold_histogram's bins) and `hold_max` (the upper bound 2^b - 1 of its highest occupied bin b, 0 if
         none).  There is no warm-up repetition and no automatic chain count: nchain >= 1 is explicit.  The engine's own map, factors,
-        packed buffer, hold histogram, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_mcmc_supported()."""
+        packed buffer, hold histogram, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_mcmc_supported().
+        carry=True: as in integrate_sweep_chains -- every iteration after a point's first continues the stored chains, resampled to the
+        moved reweight factors, with no burn-in; every dict's `carried` says whether the point's later iterations were."""
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain, thermal_ratio)
-        return self._sweep_chain_solver("integrate_sweep_mcmc", lib().mci_integrate_sweep_mcmc, a, niter, userdata, seeds, maps, reweight, True)
+        out = self._sweep_chain_solver("integrate_sweep_mcmc", lib().mci_integrate_sweep_mcmc, a, niter, userdata, seeds, maps, reweight, True, carry)
+        for r in out:
+            r["carried"] = bool((carry or self.sweep_chain_carry()) and nchain > 1 and niter > 1)
+        return out
 
     def sweep_workgroups(self, g=0):
         """test hook of csrc/mci_debug.h: workgroups of the next sweeps (0 = the default), so that one workgroup runs several points"""

@@ -442,7 +442,7 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
                     measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, **kwargs):
+                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -492,6 +492,14 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     (Engine.sweep_mcmc_supported) the points run as integrate(..., solver="mcmc", nchain=mcmc_chains, thermal_ratio=...) calls;
     reweight= then raises.
 
+    carry: False (default) or True -- with chains= or mcmc_chains= every iteration of a point after its first continues the chains of
+    the one before, resampled to the target train! and doReweight! have moved (Engine.set_sweep_chain_carry: what integrate() does by
+    default; :vegasmc with adapt=True from the third iteration on; one chain per block carries nothing).  :mcmc chains then burn in
+    only in a point's first iteration.  The first iteration of every call starts afresh -- chain state does not travel between calls.
+    Results of carried points have correlated = True and the block-lineage error as `stdev` (with_ignore() falls back to the
+    reference's); report()'s hold note asks for 4 x hold_max instead of 16 x.  carry=True without chains= / mcmc_chains=, with
+    stratify= or under "vegas" raises ValueError.  Where the sweep is refused, the looped integrate() calls carry by their own default.
+
     A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
     measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
     a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
@@ -515,6 +523,15 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
     if maps is not None and len(maps) != P:
         raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
+    if carry not in (False, True):
+        raise ValueError("integrate_sweep: carry must be True or False, got %r" % (carry,))
+    if carry:
+        if stratify is not None and stratify is not False:
+            raise ValueError("integrate_sweep: carry= and stratify= do not go together (stratification is :vegas's)")
+        if solver == "vegas":
+            raise ValueError('integrate_sweep: carry= belongs to a chain sweep (solver="vegasmc", chains=K or solver="mcmc", mcmc_chains=K); "vegas" has no chains')
+        if chains is None and mcmc_chains is None:
+            raise ValueError("integrate_sweep: carry= belongs to a chain sweep: give chains=K (solver=\"vegasmc\") or mcmc_chains=K (solver=\"mcmc\")")
     if chains is not None and mcmc_chains is not None:
         raise ValueError('integrate_sweep: chains= (solver="vegasmc") and mcmc_chains= (solver="mcmc") do not go together')
     if chains is not None:
@@ -637,20 +654,24 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     if why is None and (chains is not None or mcmc_chains is not None):
         kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma,
                   measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done, reweight=reweight)
-        rs = (eng.integrate_sweep_chains(solver, nchain=chains, **kw) if chains is not None
-              else eng.integrate_sweep_mcmc(solver, nchain=mcmc_chains, thermal_ratio=thermal_ratio, **kw))
+        rs = (eng.integrate_sweep_chains(solver, nchain=chains, carry=carry, **kw) if chains is not None
+              else eng.integrate_sweep_mcmc(solver, nchain=mcmc_chains, thermal_ratio=thermal_ratio, carry=carry, **kw))
         out = []
         for p, r in zip(params, rs):
             c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, factors and logs alone)
             c.userdata = p if closure else None
             c.visited = r["visited"]
             c._sweep_tables = (r["propose"], r["accept"])   # config.propose / config.accept: this point's, not the engine's
-            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block, correlated=False)
+            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block, correlated=r["correlated"])
+            if r["correlated"]:              # (carried chains: the block-lineage error, made by the library from the point's block means)
+                res._flat_std = np.asarray(r["stdev"], dtype=np.float64)
+                res.stdev = res._shape(res._flat_std)
             res.sweep_batched, res.map, res.status, res.reweight = True, r["maps"], r["status"], r["reweight"]
             res.maps_by_leaf = r.get("maps_by_leaf")
             res.stratification, res.vegas_check, res.warmup, res.neval_discarded, res.chain_bias = None, None, 0, 0, None
             if mcmc_chains is not None:
                 res.holds, res.hold_max, res.chain_steps = r["holds"], r["hold_max"], nevalperblock // mcmc_chains
+                res.chains_carried = bool(r.get("carried"))
             if print >= 0:
                 report(res)
             out.append(res)

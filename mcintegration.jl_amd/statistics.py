@@ -119,6 +119,8 @@ class Result:
         # set by integrate_sweep() for a point of an :mcmc sweep (mcmc_chains=K): its holding-time histogram (64 counts over the call's
         # iterations and blocks), the upper bound 2^b - 1 of its highest occupied bin b, and the measured steps of one of its chains
         self.holds = self.hold_max = self.chain_steps = None
+        # ... and whether the point's iterations continued each other's chains (integrate_sweep(..., carry=True)): hold_note's factor
+        self.chains_carried = False
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
         self.iterations = [(self._shape(self.iter_mean[i]), self._shape(self.iter_std[i]), config) for i in range(niter)]
 
@@ -146,7 +148,7 @@ class Result:
         r.chain_bias = self.chain_bias
         r.stratification = self.stratification
         r.vegas_check = self.vegas_check
-        r.holds, r.hold_max, r.chain_steps = self.holds, self.hold_max, self.chain_steps
+        r.holds, r.hold_max, r.chain_steps, r.chains_carried = self.holds, self.hold_max, self.chain_steps, self.chains_carried
         return r
 
     @property
@@ -166,12 +168,14 @@ class Result:
     def hold_note(self):
         """the sentence report() prints under the tables of a point of an :mcmc sweep whose chains were too short for the holding times
         they measured themselves (16 x the longest hold beyond a chain's measured steps: the rule of mci_mcmc_launch_valid for fresh
-        chains), or None"""
-        if not self.hold_max or not self.chain_steps or 16 * self.hold_max <= self.chain_steps:
+        chains; 4 x where the point's iterations were carried, the factor of plan_mcmc_chains for chains that start stationary), or None"""
+        k = 4 if self.chains_carried else 16
+        if not self.hold_max or not self.chain_steps or k * self.hold_max <= self.chain_steps:
             return None
         return ("note: some chain of this :mcmc sweep point went up to %d steps without moving a variable or its integrand index, and a chain "
-                "measures %d steps: fresh chains want at least 16 x their longest hold (%d).  The chain count of a sweep is the caller's: "
-                "fewer chains per block (mcmc_chains=) or more evaluations make them longer" % (self.hold_max, self.chain_steps, 16 * self.hold_max))
+                "measures %d steps: %s chains want at least %d x their longest hold (%d).  The chain count of a sweep is the caller's: "
+                "fewer chains per block (mcmc_chains=) or more evaluations make them longer"
+                % (self.hold_max, self.chain_steps, "carried" if self.chains_carried else "fresh", k, k * self.hold_max))
 
     @property
     def chain_bias_note(self):

@@ -25,6 +25,9 @@ the initial reweight factors; a sweep point-iteration is neval / min(nchain, 256
 `mcmc`: the same table under :mcmc (Engine.integrate_sweep_mcmc against loops of Engine.integrate("mcmc") calls, thermal_ratio = 0.1; the
 default loop's calls size their chains themselves and may run warm-up launches again); a point-iteration is neval / nchain + nburn steps
 deep per chain.  Both tables give the best and the worst of the timed runs of every column.
+`chains --carry` | `mcmc --carry` (profiles/r16_sweep_carry.txt): the sweep with chains carried from iteration to iteration
+(set_sweep_chain_carry) against the uncarried sweep at the same nchain and against a loop of ordinary calls with the same nchain and
+carried chains (set_chain_carry(1)); the last columns give the dependent steps of a point-iteration without and with carrying.
 One GPU process; run each mode under its own time limit."""
 import argparse
 import os
@@ -267,6 +270,81 @@ def chains_table(Ps, nevals, chains, budget=3.0, solver="vegasmc"):
                       flush=True)
 
 
+def carry_table(Ps, nevals, chains, budget=3.0, solver="vegasmc"):
+    """carried sweep | uncarried sweep | loop of ordinary calls with the same nchain and carried chains"""
+    from mcintegration_jl_amd import isa_mix
+    from mcintegration_jl_amd._lib import lib
+    eng = bubble_engine(bubble_point(0))
+    unit = solver + "_sweep_carry"
+    eng.compile(unit)
+    res = isa_mix.resources(eng.code_object(unit))["mci_" + unit]
+    sweep = eng.integrate_sweep_chains if solver == "vegasmc" else eng.integrate_sweep_mcmc
+    print("# bubble (4 Continuous leaves of 999 increments + Discrete(1, 4), q histogram), solver :%s, niter = %d, block = %d" % (solver, NITER, BLOCK))
+    print("# mci_%s: %d VGPRs, %d bytes of scratch, %d bytes of static LDS" % (unit, res["vgpr"], res["scratch"], res["lds"]))
+    print("# carried sweep | uncarried sweep, same nchain | loop of ordinary calls, same nchain, carried chains: ms (us per point-iteration)")
+    ordinary = bubble_engine(bubble_point(0))
+    ordinary.set_chain_carry(1)
+    g0 = [eng.grid(l).copy() for l in range(4)]
+    rw0 = eng.reweight().copy()
+
+    def timed(fn, reps=3):
+        best, worst = float("inf"), 0.0
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            out = fn()
+            dt = time.perf_counter() - t0
+            best, worst = min(best, dt), max(worst, dt)
+            if dt > budget:
+                break
+        return (best, worst), out
+
+    def loop(n, nchain, kw):
+        for k in range(n):
+            for l in range(4):
+                ordinary.set_grid(l, g0[l])
+            ordinary.set_reweight(rw0)
+            ordinary.set_chain_carry(1)      # (drops nothing; a call's first iteration follows another problem state: starts afresh)
+            q = ordinary.integrate(solver, nchain=nchain, **kw)
+        return q
+    for neval in nevals:
+        kw = dict(neval=neval, niter=NITER, block=BLOCK, seed=SEED)
+        for nchain in chains:
+            if nchain > neval // BLOCK:
+                continue
+            loop(1, nchain, kw)                                                                # (compile, first launches)
+            steps = neval // BLOCK // nchain
+            if solver == "mcmc":
+                fresh = BLOCK * -(-nchain // 256) * (steps + int(lib().mci_mcmc_burnin(steps, nchain, 5, 2, 5, 0.1)))
+                deep = (fresh, BLOCK * -(-nchain // 256) * steps)
+            else:
+                deep = (BLOCK * -(-nchain // 256) * steps,) * 2
+            for P in Ps:
+                uds = np.array([bubble_point(k) for k in range(P)])
+                for carry in (True, False):
+                    sweep(solver, userdata=uds[:1], nchain=nchain, carry=carry, **dict(kw, niter=1))     # (first launch)
+                (tc, tcw), rc = timed(lambda: sweep(solver, userdata=uds, nchain=nchain, carry=True, **kw))
+                (tu, tuw), ru = timed(lambda: sweep(solver, userdata=uds, nchain=nchain, **kw))
+                assert all(r["status"] == 0 for r in rc) and all(r["status"] == 0 for r in ru)
+                n = min(P, 16)   # (a loop is linear in P: up to 16 calls are timed, larger P scaled)
+                (tl, tlw), q = timed(lambda: loop(n, nchain, kw))
+                tl, tlw = tl * P / n, tlw * P / n
+                # (the timed loop reuses one problem, whose map has been trained by the calls before: its :vegasmc chains are carried out of a
+                # call's first iteration too, plan_may_carry.  The comparison of point 0 is with a FRESH problem's call, one lane per chain.)
+                fresh = bubble_engine(bubble_point(0))
+                fresh.set_chain_carry(1)
+                fresh.set_chain_speculation(1)
+                q = fresh.integrate(solver, nchain=nchain, **kw)
+                fresh.close()
+                sig = np.max(np.abs(rc[0]["mean"] - q["mean"]) / np.hypot(rc[0]["stdev"], q["stdev"]))
+                print("neval %8d  nchain %4d  P %4d  carried sweep %11.3f ms (%9.3f us; worst %11.3f)  uncarried sweep %11.3f ms (%9.3f us; worst %11.3f)"
+                      "  carried loop %11.3f ms (%9.3f us; worst %11.3f)  uncarried / carried %6.2f  loop / carried %6.2f"
+                      "   grid x threads = %s  steps deep %7d -> %7d (first iteration: %d)  correlated %s  point 0: %.1f sigma from a fresh problem's carried call%s"
+                      % (neval, nchain, P, 1e3 * tc, 1e6 * tc / (P * NITER), 1e3 * tcw, 1e3 * tu, 1e6 * tu / (P * NITER), 1e3 * tuw, 1e3 * tl,
+                         1e6 * tl / (P * NITER), 1e3 * tlw, tu / tc, tl / tc, eng.last_sweep_launch(), deep[0], deep[1], deep[0], rc[0]["correlated"], sig,
+                         "  (loop: %d calls timed, scaled)" % n if P > n else ""),
+                      flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=["table", "threads", "once", "strat", "chains", "mcmc"])
@@ -277,11 +355,14 @@ def main():
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--layout", choices=["genz", "bubble"], default="genz")
+    ap.add_argument("--carry", action="store_true", help="chains | mcmc: the sweep with carried chains against the uncarried one and a loop of carried calls")
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
+    if a.carry and a.mode not in ("chains", "mcmc"):
+        ap.error("--carry goes with the chains and mcmc modes")
     if a.mode in ("chains", "mcmc"):
-        chains_table([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
+        (carry_table if a.carry else chains_table)([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
                      [int(v) for v in a.chains.split(",")], solver="vegasmc" if a.mode == "chains" else "mcmc")
         return
     if a.mode == "strat":
