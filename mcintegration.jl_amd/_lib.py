@@ -187,6 +187,8 @@ DEBUG_SIGNATURES = [
     ("mci_debug_sweep_threads", C.c_int, [_VP, C.c_int32]),
     ("mci_debug_sweep_last_launch", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_debug_sweep_lds_bytes", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("mci_debug_resample", C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p]),
+    ("mci_debug_sweep_resample_lds", C.c_int, [_VP, C.POINTER(C.c_int64)]),
 ]
 
 _lib = None

@@ -88,6 +88,18 @@ int mci_debug_sweep_threads(mci_problem *prob, int32_t threads);
 int mci_debug_sweep_last_launch(const mci_problem *prob, int32_t *workgroups, int32_t *threads);
 /* (tools/sweep_bench.py) dynamic LDS bytes per workgroup of this problem's sweeps under its present mci_set_sweep_leaves mode */
 int mci_debug_sweep_lds_bytes(const mci_problem *prob, int64_t *bytes);
+/* test hook: the carried chains' resampler (k_resample_chains, mci_static_kernels.h) on its own -- nblocks workgroups of 256 threads over
+ * the given stored chains, launched as an ordinary carried launch launches it: curr_old[nblocks][n_old] the integrand every stored chain
+ * ended on, rw_now[nd] / rw_used[nd] the reweight factors now and those the chains ran under, w_chain[nblocks][n_old] a weight per stored
+ * chain instead (NULL: the :mcmc rule), src[nblocks][n_new] the picks, W[nblocks][n_old] the running weights (NULL: not wanted).  The
+ * problem gives its device and stream only: its own stored chains and the record of its last launch stay as they are.  Synchronises.
+ * Both outputs are filled with 0xFF bytes before the launch: what the kernel leaves unwritten comes back as -1 | NaN.
+ * Refused: nblocks, n_old or n_new < 1, nd outside 1 .. 64, blocks of 2^31 chains or more. */
+int mci_debug_resample(mci_problem *prob, int64_t nblocks, int64_t n_old, int64_t n_new, int32_t nd, const int32_t *curr_old,
+                       const double *rw_now, const double *rw_used, const double *w_chain, int32_t *src, double *W);
+/* stored chains per block up to which a carried sweep point's resampler (mci_sweep_chains.h) keeps the running weights in LDS: the
+ * map_off - kResampleThreads the carried sweep units are handed (beyond: its bisections read them in global memory); no device needed */
+int mci_debug_sweep_resample_lds(const mci_problem *prob, int64_t *lds_w);
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,57 @@ static int prepare_carried_chains(mci_problem *p, const LaunchRequest &rq, const
     return MCI_OK;
 }
 
+// csrc/mci_debug.h: k_resample_chains alone, over chains the caller made up, launched as above; buffers of its own, nothing of the
+// problem's but the device and the stream
+int mci_debug_resample(mci_problem *p, int64_t nblocks, int64_t n_old, int64_t n_new, int32_t nd, const int32_t *curr_old, const double *rw_now,
+                       const double *rw_used, const double *w_chain, int32_t *src, double *W) {
+    if (!p || !src || (!w_chain && (!curr_old || !rw_now || !rw_used))) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (nblocks < 1 || n_old < 1 || n_new < 1) return fail(MCI_ERR_INVALID, "resample: %lld blocks of %lld stored and %lld new chains (each >= 1)", (long long)nblocks, (long long)n_old, (long long)n_new);
+    if (nd < 1 || nd > 64) return fail(MCI_ERR_INVALID, "resample: %d integrands (1 .. 64)", (int)nd);
+    if (n_old > INT32_MAX || n_new > INT32_MAX || nblocks > INT32_MAX / n_old || nblocks > INT32_MAX / n_new)
+        return fail(MCI_ERR_INVALID, "resample: %lld blocks of %lld stored and %lld new chains are more than a test hook takes", (long long)nblocks, (long long)n_old, (long long)n_new);
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const size_t told = (size_t)nblocks * (size_t)n_old, tnew = (size_t)nblocks * (size_t)n_new;
+    DevBuf<int> d_curr, d_src;
+    DevBuf<double> d_rw, d_w, d_W;
+    int rc;
+    if ((rc = d_src.reserve((int64_t)tnew)) || (rc = d_W.reserve((int64_t)told))) return rc;
+    HIPCHK(hipMemsetAsync(d_src, 0xFF, tnew * sizeof(int), st)); // (a pick the kernel does not write comes back as -1, a running weight it
+    HIPCHK(hipMemsetAsync(d_W, 0xFF, told * sizeof(double), st)); // does not write, or adds to what was there, as NaN)
+    mci::ResampleArgs ra{};
+    if (curr_old) {
+        if ((rc = d_curr.reserve((int64_t)told))) return rc;
+        HIPCHK(hipMemcpyAsync(d_curr, curr_old, told * sizeof(int), hipMemcpyHostToDevice, st));
+        ra.curr_old = d_curr;
+    }
+    if (rw_now && rw_used) {
+        if ((rc = d_rw.reserve(2 * (int64_t)nd))) return rc;
+        HIPCHK(hipMemcpyAsync(d_rw, rw_now, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_rw + nd, rw_used, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+        ra.rw_now = d_rw;
+        ra.rw_used = d_rw + nd;
+    }
+    if (w_chain) {
+        if ((rc = d_w.reserve((int64_t)told))) return rc;
+        HIPCHK(hipMemcpyAsync(d_w, w_chain, told * sizeof(double), hipMemcpyHostToDevice, st));
+        ra.w_chain = d_w;
+    }
+    ra.n_old = n_old;
+    ra.n_new = n_new;
+    ra.nd = nd;
+    ra.src = d_src;
+    ra.W = d_W;
+    HIPCHK(hipStreamSynchronize(st)); // (the uploads have read the caller's pageable memory)
+    hipLaunchKernelGGL(mci::k_resample_chains, dim3((unsigned)nblocks), dim3(256), 0, st, ra);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(src, d_src, tnew * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (W) HIPCHK(hipMemcpyAsync(W, d_W, told * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // (the buffers are freed behind it)
+    return MCI_OK;
+}
+
 // the :mcmc holding-time histogram, the speculation trees of a several-lanes-per-chain launch
 static int prepare_chain_tables(mci_problem *p, const LaunchRequest &rq, const LaunchPlan &pl, mci::BatchArgs &a) {
     const auto &s = p->shape;

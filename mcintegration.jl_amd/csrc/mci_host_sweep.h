@@ -234,6 +234,19 @@ int mci_debug_sweep_lds_bytes(const mci_problem *p, int64_t *bytes) {
     return MCI_OK;
 }
 
+namespace {
+// stored chains per block whose running weights a carried sweep point's resample_block keeps in LDS (SweepChainCarry::lds_w): the
+// front of the segment up to the point's map block, less the threads' partial sums
+int sweep_resample_lds(int map_off) { return map_off - (int)mci::kResampleThreads; }
+} // namespace
+int mci_debug_sweep_resample_lds(const mci_problem *p, int64_t *lds_w) {
+    if (!p || !lds_w) return fail(MCI_ERR_INVALID, "NULL argument");
+    int map_off = 0;
+    sweep_leaves_lds(p, &map_off); // (what sweep_chains_call lays its launch out by)
+    *lds_w = sweep_resample_lds(map_off);
+    return MCI_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // the one driver of a sweep launch
 // ---------------------------------------------------------------------------------------------------
@@ -806,7 +819,7 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
             fk.nburn_carried = 0;                                          // plan_mcmc_chains: carried chains have no start to burn in
             fk.burnin_carried = mci_chain_burnin(steps, 1, sweep_nslots(p)); // plan_vegasmc_chains: the reference's own neval / 100
             fk.carry_first = carry_first;
-            fk.lds_w = c.map_off - (int)mci::kResampleThreads;
+            fk.lds_w = sweep_resample_lds(c.map_off);
         }
         return &fa;
     };

@@ -542,6 +542,29 @@ class Engine:
         check(lib().mci_get_hold_histogram(self.p, out))
         return np.array(list(out), dtype=np.uint64)
 
+    def resample(self, curr_old, rw_now, rw_used, n_new, w_chain=None):
+        """test hook (csrc/mci_debug.h mci_debug_resample): the carried chains' resampler kernel on its own over curr_old [nblocks, n_old]
+        (w_chain [nblocks, n_old]: a weight per stored chain instead of rw_now / rw_used [nd]) -> (src [nblocks, n_new], W [nblocks,
+        n_old]); this engine gives its device only, its own stored chains stay as they are"""
+        co = np.ascontiguousarray(curr_old, dtype=np.int32)
+        a, b = np.ascontiguousarray(rw_now, dtype=np.float64), np.ascontiguousarray(rw_used, dtype=np.float64)
+        wc = None if w_chain is None else np.ascontiguousarray(w_chain, dtype=np.float64)
+        if co.ndim != 2 or a.shape != b.shape or a.ndim != 1 or (wc is not None and wc.shape != co.shape):
+            raise ValueError("curr_old [nblocks, n_old], rw_now and rw_used [nd], w_chain None or shaped like curr_old")
+        nblocks, n_old = co.shape
+        src = np.full((nblocks, max(int(n_new), 0)), -1, dtype=np.int32)
+        W = np.full((nblocks, n_old), np.nan)
+        check(lib().mci_debug_resample(self.p, nblocks, n_old, int(n_new), len(a), co.ctypes.data_as(c_int32_p), _dp(a), _dp(b),
+                                       None if wc is None else _dp(wc), src.ctypes.data_as(c_int32_p), _dp(W)))
+        return src, W
+
+    def sweep_resample_lds(self):
+        """stored chains per block up to which a carried sweep point's resampler keeps its running weights in LDS (csrc/mci_debug.h
+        mci_debug_sweep_resample_lds)"""
+        n = C.c_int64()
+        check(lib().mci_debug_sweep_resample_lds(self.p, C.byref(n)))
+        return int(n.value)
+
     def stream(self):
         """the library's hipStream_t (as an integer), for callers that order their own work with ours"""
         return lib().mci_ctx_stream(context(self.device)) or 0

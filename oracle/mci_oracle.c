@@ -1603,10 +1603,13 @@ void mcio_result_destroy(mcio_result *r) {
  *   W[j] = sum_i w[i] * #(stored chains j' <= j that ended on integrand i)     (sum over i = 0 .. Nd-1 in that order)
  *   new chain c continues the first stored chain j with W[j] > (c + u) * (W[n_old-1] / n_new),  u = (sqrt(5) - 1) / 2
  * (any offset in [0, 1) is a valid systematic resampling; 1/2 makes (c + u) n_old / n_new an integer for many chain counts -- with all
- * stored chains on one integrand the comparison is then an exact tie, decided by the last bit of w)                                  */
+ * stored chains on one integrand the comparison is then an exact tie, decided by the last bit of w)
+ * A total W[n_old-1] that is not > 0 (every stored chain has weight zero, or the total is not a number) leaves nothing to resample by:
+ * new chain c then continues stored chain c % n_old -- the kernel's branch, at the kernel's place (behind W, before the step is used);
+ * without it the bisection ends on n_old - 1 for every chain.  Both mirrors below.                                                     */
 /* Carried :vegasmc chains: one weight per stored chain (new target / old target).  Mirror of k_resample_chains' w_chain path, association
  * included: the stored chains are cut into 256 stretches of ceil(n_old / 256); W[j] = (sum of the stretches before, added in order) +
- * (running sum along the own stretch); then the same systematic pick. */
+ * (running sum along the own stretch); then the same systematic pick, or c % n_old where the total is not > 0. */
 void mcio_resample_weighted(const double *w, long n_old, long n_new, long *src) {
     double *W = (double *)malloc((size_t)n_old * sizeof(double));
     const long T = 256, per = (n_old + T - 1) / T;
@@ -1627,6 +1630,11 @@ void mcio_resample_weighted(const double *w, long n_old, long n_new, long *src) 
         }
     }
     const double step = W[n_old - 1] / (double)n_new;
+    if (!(W[n_old - 1] > 0.0)) { /* total weight zero or not a number: the new chains spread over the stored ones (resample_block) */
+        for (long c = 0; c < n_new; ++c) src[c] = c % n_old;
+        free(W);
+        return;
+    }
     for (long c = 0; c < n_new; ++c) {
         const double target = ((double)c + 0.6180339887498949) * step;
         long lo = 0, hi = n_old - 1; /* smallest j with W[j] > target */
@@ -1655,6 +1663,11 @@ void mcio_resample_chains(const int *curr_old, long n_old, int nd, const double 
         W[j] = s;
     }
     const double step = W[n_old - 1] / (double)n_new;
+    if (!(W[n_old - 1] > 0.0)) { /* total weight zero or not a number: the new chains spread over the stored ones (resample_block) */
+        for (long c = 0; c < n_new; ++c) src[c] = c % n_old;
+        free(W);
+        return;
+    }
     for (long c = 0; c < n_new; ++c) {
         const double target = ((double)c + 0.6180339887498949) * step;
         long lo = 0, hi = n_old - 1; /* smallest j with W[j] > target */

@@ -156,7 +156,8 @@ typedef struct {
 } mcio_result;
 
 void mcio_resample_chains(const int *curr_old, long n_old, int nd, const double *rw_now, const double *rw_used, long n_new, long *src);
-/* ... with one weight per stored chain (mirror of k_resample_chains' w_chain path: the same association of the running sums) */
+/* ... with one weight per stored chain (mirror of k_resample_chains' w_chain path: the same association of the running sums).  Either
+ * one: a total that is not > 0 gives src[c] = c % n_old, as the kernel has it. */
 void mcio_resample_weighted(const double *w, long n_old, long n_new, long *src);
 void mcio_set_chain_carry(mcio_config *c, int mode); /* -1 automatic (:vegasmc) | 0 off | 1 :vegasmc and :mcmc */
 

@@ -177,10 +177,18 @@ def check_carried_iterations(oracle, case_id, seed=20260930):
     counts = [int(rng.choice([2, 5, 8, 16, 40])) for _ in range(4)]
     mfreq = int(rng.choice([1, 1, 3]))
     what = "case %d: pools=%d ni=%d ndraw=%d blocks=%d npb=%d nchain=%s measurefreq=%d" % (case_id, len(var), len(dof), ndraw, nblk, npb, counts, mfreq)
+    return carried_iterations(oracle, what, var, oleaves, dof, body, nblk, npb, counts, mfreq, seed, case_id=case_id)
+
+
+def carried_iterations(oracle, what, var, oleaves, dof, body, nblk, npb, counts, mfreq, seed, solvers=("vegasmc", "mcmc"), case_id=0):
+    """the body of check_carried_iterations on a given layout: len(counts) consecutive iterations of each solver, counts[it] chains per
+    block, against the oracle's carried iterations"""
+    import numpy as np
     oracle.set_rng_rounds(10)
     fn = oracle.compile_c_integrand(body)
     ni = len(dof)
-    for solver, osolver in (("vegasmc", oracle.VEGASMC), ("mcmc", oracle.MCMC)):
+    for solver in solvers:
+        osolver = oracle.MCMC if solver == "mcmc" else oracle.VEGASMC
         cfg = mci.Configuration(var=var, dof=dof, seed=seed)
         eng = mci.Engine(cfg, mci.Integrand(body))
         note = vary_chain_lanes(eng, case_id)

@@ -19,7 +19,7 @@ import pytest
 
 import mcintegration_jl_amd as mci
 from catalog_params import bubble_userdata, genz_userdata
-from layout_cases import check_carried_iterations, pipe_case
+from layout_cases import carried_iterations, check_carried_iterations, pipe_case
 
 pytestmark = pytest.mark.gpu
 PI = math.pi
@@ -332,6 +332,18 @@ def test_carried_chains_on_random_layouts_match_oracle(oracle, case_id):
     iterations (the resampling of stored :mcmc chains picks every new chain's ancestor), doReweight! and train! in between"""
     check_carried_iterations(oracle, case_id)
     oracle.set_rng_rounds(10)
+
+
+def test_carried_mcmc_chains_over_seventeen_integrands_match_oracle(oracle):
+    """the resampler keeps the running counts of up to 16 integrands (the normalisation included) in registers; with 17 integrands and
+    the normalisation it makes one pass per integrand over the running weights in global memory instead (csrc/mci_train.h
+    resample_block) -- reached through the real caller here: four carried :mcmc iterations whose chain count changes every time
+    (stored and new chains differ in number, over two blocks), with check_carried_iterations' assertions and tolerances"""
+    body = "\n".join("w[%d] = %d.0 * pow(x[0], %d.0);" % (i, i + 1, i % 4) for i in range(17))
+    what = carried_iterations(oracle, "17 integrands", (mci.Continuous(0.0, 1.0),), [ocont()], [[1]] * 17, body, 2, 2400, [8, 40, 300, 16], 1,
+                              20260930, solvers=("mcmc",))
+    oracle.set_rng_rounds(10)
+    print(what)
 
 
 @pytest.mark.parametrize("solver", ["vegas", "vegasmc", "mcmc"])

@@ -88,6 +88,52 @@ def test_every_iteration_is_the_oracles_carried_iteration(oracle, name, solver, 
                 np.testing.assert_allclose(parts[1], ocfg.distribution(l), rtol=0, atol=1e-4)
 
 
+@pytest.mark.parametrize("side", [0, 1])
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("name", ["discrete", "sphere2_padding"])
+def test_both_sides_of_the_resamplers_lds_limit_are_the_oracles_carried_iterations(oracle, name, solver, side):
+    """A point's workgroup resamples in the front of its LDS segment, where the chain loop's carve is dead: the running weights of a block
+    of up to lds_w = map_off - 256 stored chains sit there and the bisections read them, beyond that they read W in global memory
+    (resample_block).  nchain = lds_w and lds_w + 1, the limit taken from the library (Engine.sweep_resample_lds), two blocks, chains of
+    two steps; the body and the tolerances of test_every_iteration_is_the_oracles_carried_iteration.  `discrete` has the smallest map
+    and with it the smallest limit, 144: fewer than the resampler's 256 threads, so either side is one chain per thread there.
+    sphere2_padding's 4128 puts both sides at several chains per thread, and a lane of the chain loop runs 17 chains."""
+    c, cfg, eng = engine(name, oracle)
+    lds_w = eng.sweep_resample_lds()
+    if name == "discrete":
+        assert lds_w >= 2
+    else:
+        assert lds_w + 1 > 256                   # a thread's stretch of the resampling is several chains on either side
+    nchain, block = lds_w + side, 2
+    npb = 2 * nchain
+    uds = rows(name, c)
+    rs = sweep(eng, solver, uds, carry=True, neval=npb * block, niter=4, block=block, seed=SEED, nchain=nchain)
+    assert eng.last_sweep_launch() == (2, 256)
+    nobs, nd = eng.nobs, cfg.N + 1
+    osolver = oracle.MCMC if solver == "mcmc" else oracle.VEGASMC
+    for ud, r in zip(uds, rs):
+        ocfg = carried_oracle(oracle, c)
+        neval = 0
+        for it in range(4):
+            packed = ocfg.iteration(osolver, c["oname"], ud or None, npb, 0, block, it, SEED, nchain=nchain)
+            om, oe = oracle.mean_std(packed[:nobs], packed[nobs:2 * nobs], block)
+            neval += int(packed[2 * nobs + 1])
+            print(name, solver, nchain, "it", it, "mean", r["iter_mean"][it], om, "std", r["iter_std"][it], oe)
+            np.testing.assert_allclose(r["iter_mean"][it], om, rtol=1e-8 * 10 ** it, atol=1e-300, err_msg="iteration %d" % it)
+            np.testing.assert_allclose(r["iter_std"][it], oe, rtol=1e-5 * 10 ** it, atol=1e-300, err_msg="iteration %d" % it)
+            ocfg.set_reweight(oracle.do_reweight(ocfg.reweight, packed[2 * nobs + 2:2 * nobs + 2 + nd]))
+            ocfg.train()
+        assert r["neval"] == neval and r["status"] == 0 and r["correlated"] is True
+        if solver == "mcmc":
+            assert r["holds"].sum() == 4 * block * nchain and r["carried"] is True
+        np.testing.assert_allclose(r["reweight"], ocfg.reweight, rtol=1e-4)
+        for l, (lf, parts) in enumerate(zip(c["oleaves"], unpack(c["oleaves"], r["maps"]))):
+            if lf["kind"] == 0:
+                check_map(parts[0], ocfg.grid(l), 1e-4)
+            else:
+                np.testing.assert_allclose(parts[1], ocfg.distribution(l), rtol=0, atol=1e-4)
+
+
 @pytest.mark.parametrize("solver", SOLVERS)
 @pytest.mark.parametrize("name", NAMES)
 def test_carrying_shows_where_it_must_and_nowhere_else(oracle, name, solver):
