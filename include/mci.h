@@ -53,6 +53,9 @@ enum { MCI_MCMC_SWEEP = 12 };
 /* ... and the same two sweep kernels with chains carried from one iteration of a point to the next (mci_set_sweep_chain_carry): code
  * objects of their own */
 enum { MCI_VEGASMC_SWEEP_CARRY = 13, MCI_MCMC_SWEEP_CARRY = 14 };
+/* ... and the big :vegas unit: the measurefreq == 1 kernel with sixteen histogram copies in 1024-thread workgroups, which big launches of
+ * layouts on the eight-copy plan run instead (compiled the first time a launch selects it; layouts without one refuse the name) */
+enum { MCI_VEGAS_BIG = 15 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -582,7 +585,8 @@ int mci_chain_speculation_status(const mci_problem *prob, int32_t solver, int32_
  * the triggering call still returns MCI_OK.  flags (NULL: not wanted): bit 0 = the observable sums were not compared (a user measure,
  * whose body the static kernel cannot run; histogram, neval, normalization and the draws still count), bit 1 = verified from a marker an
  * earlier process left, not in this one, bit 2 = the check ran but its histogram was empty on both sides (every weight of its 1024
- * samples underflowed): nothing to compare, status stays 0 and no marker is written. */
+ * samples underflowed): nothing to compare, status stays 0 and no marker is written, bit 3 = the big :vegas unit (MCI_VEGAS_BIG) went
+ * through the same check and FAILED it -- one warning, big launches keep the standing unit, whose own status is what `status` reports. */
 int mci_vegas_check_status(const mci_problem *prob, int32_t *status, int32_t *flags);
 /* lanes per chain of the last chain-solver launch (1: one lane per chain) and the accept levels of its tree */
 int mci_last_chain_speculation(const mci_problem *prob, int32_t *lanes, int32_t *max_accepts);

@@ -37,6 +37,8 @@ int mci_debug_persist_spin_ticks(mci_problem *prob, unsigned long long ticks);
  *                            section): never | every such launch, whatever its size and with a forced wg_per_block too
  *   cursor_log2_big  n       (per launch) log2 of the units in a big range, 1 .. 16 (4)
  *   cursor_ones      n       (per launch) single-unit ranges per wave at the end of a block, 1 .. 4096 (4)
+ *   vegas_big_unit   0 | 1   (per launch) the big :vegas unit (sixteen histogram copies, 1024 threads; mci_host_vegas_plan.h): never | at
+ *                            any size and with a forced wg_per_block too, together with vegas_cursor = 1
  * (The library reads two environment variables and no others: MCI_KERNEL_CACHE -- the directory code objects are cached in -- and
  * MCI_JIT_FLAGS -- extra hiprtc options; INTEGRATION.md.) */
 int mci_debug_override(const char *key, int64_t value, int32_t on);

@@ -200,6 +200,10 @@ static int vegas_check_round(mci_problem *p, int slot, int64_t npb, int64_t bloc
 
 static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int64_t block_lo, int64_t block_hi, int32_t iteration, uint64_t seed,
                             int64_t measurefreq) {
+    // The big unit (mci_host_vegas_plan.h) goes through the same rounds with its own marker.  A big unit that disagrees is never
+    // selected again -- one warning, flag bit 3, the standing units and their status untouched, no conservative layout compiled: the
+    // launch that triggered the check runs the standing unit.
+    const bool big = slot == mci_problem::kVegasBig;
     const int u = slot == kSlotVegasAny ? 1 : 0;
     const int64_t nb = block_hi - block_lo < 2 ? block_hi - block_lo : 2, npb = nevalperblock < 512 ? nevalperblock : 512;
     const int64_t mf = measurefreq * 4 <= npb ? measurefreq : 1;
@@ -235,6 +239,16 @@ static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int
             mcijit::write_file_atomic(object + ".ok", id.data(), id.size());
             break;
         }
+        if (big) {
+            fprintf(stderr, "mci: the big :vegas unit of this problem (%s) does not reproduce the library's static :vegas kernel on a %lld-block, "
+                            "%lld-sample check: %ld of %lld packed entries differ (first at %ld; statistics %ld, histogram %ld), draws of %lld samples and "
+                            "Jacobians of %lld differ.  A miscompiled code object -- big launches of this problem keep the standing :vegas unit; "
+                            "mci_vegas_check_status sets flag bit 3.\n",
+                    object.c_str(), (long long)nb, (long long)npb, df.bad, (long long)p->packed_n, df.first_bad, df.bad_sec[0], df.bad_sec[1], (long long)bad[0],
+                    (long long)bad[1]);
+            state = -1;
+            break;
+        }
         fprintf(stderr, "mci: the :vegas sample kernel of this problem (%s%s) does not reproduce the library's static :vegas kernel on a %lld-block, "
                         "%lld-sample check: %ld of %lld packed entries differ (first at %ld; statistics %ld, histogram %ld), draws of %lld samples and "
                         "Jacobians of %lld differ.  A miscompiled code object -- %s; mci_vegas_check_status reports %d.\n",
@@ -252,6 +266,19 @@ static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int
     p->kernel_timing = kernel_timing;
     if (p->d_status) (void)hipMemcpy(p->d_status, h_status, sizeof(h_status), hipMemcpyHostToDevice); // (what the small launches flagged is theirs)
     p->merge.hist_no_offset = 0;
+    if (big) { // (state 0 -- an empty histogram, a check that could not run -- leaves the unit usable and unverified, as it leaves the standing ones)
+        p->vegas_big.check_done = true;
+        if (state < 0) {
+            p->vegas_big.state = VegasBigUnit::kFailedCheck;
+            p->vegas_check_flags |= 8;
+        }
+        if (rc) {
+            fprintf(stderr, "mci: the self-check of this problem's big :vegas unit (%s) could not run: %s -- nothing was verified\n",
+                    p->kernel[slot].code_object.c_str(), mci_last_error());
+            p->merge_pending = false;
+        }
+        return MCI_OK;
+    }
     p->vegas_check_done[u] = true;
     if (rc) {
         // advisory: a check that could not run (the dump unit does not compile, no memory for its buffers) must not fail a launch that
@@ -271,18 +298,21 @@ static int vegas_self_check(mci_problem *p, int slot, int64_t nevalperblock, int
 static int vegas_check_gate(mci_problem *p, int slot, int64_t nevalperblock, int64_t block_lo, int64_t block_hi, int32_t iteration, uint64_t seed,
                             int64_t measurefreq) {
     const int u = slot == kSlotVegasAny ? 1 : 0;
+    const bool big = slot == mci_problem::kVegasBig;
+    bool &done = big ? p->vegas_big.check_done : p->vegas_check_done[u];
     const bool force = g_over.vegas_self_check.on && g_over.vegas_self_check.v == 1;
     if (g_over.vegas_self_check.on && g_over.vegas_self_check.v == 0) return MCI_OK;
     if (!vegas_check_covers(p) || p->ctx->offline) { // (status 0: nobody looked)
-        p->vegas_check_done[u] = true;
+        done = true;
         return MCI_OK;
     }
     if (!force && access((p->kernel[slot].code_object + ".ok").c_str(), F_OK) == 0) {
+        done = true;
+        if (big) return MCI_OK; // (the status is the standing units')
         if (p->vegas_check_state[u] == 0) {
             p->vegas_check_state[u] = 1;
             p->vegas_check_flags |= 2;
         }
-        p->vegas_check_done[u] = true;
         return MCI_OK;
     }
     return vegas_self_check(p, slot, nevalperblock, block_lo, block_hi, iteration, seed, measurefreq);

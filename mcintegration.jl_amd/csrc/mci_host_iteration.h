@@ -397,7 +397,7 @@ static int launch_sample_chunks(mci_problem *p, const LaunchRequest &rq, const L
             a.chunk_hi = a.chunk_lo + pl.chunk_len < rq.nevalperblock ? a.chunk_lo + pl.chunk_len : rq.nevalperblock;
             a.accum = c > 0 ? 1 : 0;
         }
-        HIPCHK(hipModuleLaunchKernel(f, (unsigned)pl.nwg, 1, 1, (unsigned)pl.T_launch, 1, 1, (unsigned)solver_lds(p, rq.solver), st, args, nullptr));
+        HIPCHK(hipModuleLaunchKernel(f, (unsigned)pl.nwg, 1, 1, (unsigned)pl.T_launch, 1, 1, (unsigned)plan_launch_lds(p, rq), st, args, nullptr));
         if (pl.split && c + 1 < pl.nchunks && (rc = launch_replay(p, rq, pl, a))) return rc;
     }
     return MCI_OK;
@@ -515,6 +515,27 @@ static int queue_merge(mci_problem *p, const LaunchRequest &rq, const LaunchPlan
     return MCI_OK;
 }
 
+// Does this :vegas launch run the big unit (mci_host_vegas_plan.h vegas_big_rule)?  Asked first as if the unit were usable; a launch
+// that would take it compiles it (once per problem) and lets it prove itself (mci_host_check.h), then the rule is asked again with what
+// the unit turned out to be.  Yes: rq.kern names it.  Anything else -- a unit over its register budget, one that did not compile (one
+// note) or failed its check (one warning) -- leaves the request as it came: the standing unit runs.
+static int select_vegas_big(mci_problem *p, LaunchRequest &rq) {
+    if (vegas_big_rule(plan_big_in(p, rq, g_over, /*assume_unit=*/true)) != kBigTake) return MCI_OK;
+    if (p->vegas_big.state == 0) {
+        const int rc = compile_vegas_big(p);
+        if (rc == MCI_ERR_COMPILE || p->vegas_big.state == VegasBigUnit::kNoCompile) {
+            p->vegas_big.state = VegasBigUnit::kNoCompile;
+            fprintf(stderr, "mci: the big :vegas unit of this problem did not compile; big launches keep the standing unit\n%s\n", mci_last_error());
+            return MCI_OK;
+        }
+        if (rc) return rc;
+    }
+    if (p->vegas_big.state == 1 && !p->vegas_big.check_done)
+        if (int rc = vegas_check_gate(p, mci_problem::kVegasBig, rq.nevalperblock, rq.block_lo, rq.block_hi, rq.iteration, rq.seed, rq.measurefreq)) return rc;
+    if (vegas_big_rule(plan_big_in(p, rq, g_over, /*assume_unit=*/false)) == kBigTake) rq.kern = mci_problem::kVegasBig;
+    return MCI_OK;
+}
+
 int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int64_t block_lo, int64_t block_hi,
                       int32_t iteration, uint64_t seed, int64_t measurefreq, int64_t nchain, double thermal_ratio) {
     // ---- validate ----
@@ -526,15 +547,18 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     if (p->has_fermik && solver != MCI_MCMC) return fail(MCI_ERR_INVALID, "FermiK variables work with solver=:mcmc only"); // test/bubble_FermiK.jl:2,:133
     if (p->strat.on) { // stratified :vegas (mci_host_strat.h): its own sample kernel and launch
         if (solver != MCI_VEGAS) return fail(MCI_ERR_INVALID, "stratification works with solver = :vegas only (mci_set_stratification_off first)");
+        p->launch.last_vegas_big = false;
         return strat_run(p, nevalperblock, block_lo, block_hi, iteration, seed, measurefreq);
     }
     // ---- compile and gate ----
     // (inside vegas_self_check: the code object under test, whatever the cadence of its small launch)
     const int kern = (p->in_self_check && p->check_slot >= 0 && solver == MCI_VEGAS) ? p->check_slot : kslot(solver, measurefreq);
-    const LaunchRequest rq{solver, nevalperblock, block_lo, block_hi, nblocks, iteration, seed, measurefreq, thermal_ratio, /*auto_chains=*/nchain <= 0, kern};
+    LaunchRequest rq{solver, nevalperblock, block_lo, block_hi, nblocks, iteration, seed, measurefreq, thermal_ratio, /*auto_chains=*/nchain <= 0, kern};
+    // (the big :vegas unit is no solver slot: compile_vegas_big loads it, select_vegas_big below or -- for its own check's launches -- before that)
+    auto compile_unit = [&]() { return rq.kern == mci_problem::kVegasBig ? MCI_OK : compile_solver(p, rq.kern); };
     // (a chain solver's lane-per-chain kernel is compiled once the launch is known to run one lane per chain: a launch of few chains
     // runs the several-lanes-per-chain kernel instead, mci_spec.h, and pays for that code object only)
-    int rc = (rq.solver == MCI_VEGAS || p->deterministic || p->shape.host_integrand || p->spec_lanes == 1) ? compile_solver(p, rq.kern) : MCI_OK;
+    int rc = (rq.solver == MCI_VEGAS || p->deterministic || p->shape.host_integrand || p->spec_lanes == 1) ? compile_unit() : MCI_OK;
     if (rc) return rc;
     // a :vegas code object that has neither a marker nor a passed check yet proves itself first (mci_host_check.h); afterwards this
     // launch runs as if nothing had happened
@@ -543,7 +567,9 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         return rc;
     // (a check that fell back to the conservative layout has unloaded the slot's module; if that unit did not compile the slot is empty:
     // compiled here again -- a no-op otherwise -- so that the launch below never goes through a handle of an unloaded module)
-    if (rq.solver == MCI_VEGAS && (rc = compile_solver(p, rq.kern))) return rc;
+    if (rq.solver == MCI_VEGAS && (rc = compile_unit())) return rc;
+    // a big launch of a layout on the eight-copy plan: the big unit instead, if it is (or turns out) usable -- else exactly as before
+    if (rq.solver == MCI_VEGAS && !p->in_self_check && (rc = select_vegas_big(p, rq))) return rc;
     if (rq.solver == MCI_VEGAS && p->shape.host_integrand && (rc = ensure_dump(p))) return rc;
     if ((rc = flush_merge(p))) return rc; // a previous batch nobody looked at: merge it (resets the global histogram)
     HIPCHK(hipSetDevice(p->ctx->device));
@@ -590,7 +616,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
         pl.units = pl.nchain * pl.G;
         pl.T_launch = pl.units >= 256 ? 256 : (int)((pl.units + 63) / 64) * 64;
     }
-    if (pl.G == 1 && (rc = compile_solver(p, rq.kern))) return rc;
+    if (pl.G == 1 && (rc = compile_unit())) return rc;
     p->launch.last_spec_lanes = pl.G;
     p->launch.last_spec_maxacc = pl.spec_maxacc;
     plan_grid(p, rq, pl);
@@ -642,6 +668,7 @@ int mci_iteration_run(mci_problem *p, int32_t solver, int64_t nevalperblock, int
     // ---- record ----
     record_launch(p, nblocks * nevalperblock, pl.nwg, pl.T_launch, nblocks);
     if (solver != MCI_VEGAS) p->launch.last_nchain = pl.nchain;
+    else p->launch.last_vegas_big = rq.kern == mci_problem::kVegasBig; // (mci_get_histogram_copies, mci_kernel_code_object describe this unit)
     return queue_merge(p, rq, pl, a.hold_hist);
 }
 

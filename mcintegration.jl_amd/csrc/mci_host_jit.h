@@ -172,6 +172,64 @@ static int compile_solver(mci_problem *p, int slot) {
     return load_slot(p, slot, *chosen, lds);
 }
 
+// ---- the big :vegas unit (mci_host_vegas_plan.h) ------------------------------------------------------------------------------
+// Does the layout have one at all?  What can be said without the standing unit's registers: the create-time half of vegas_big_rule.
+static bool vegas_big_layout(const mci_problem *p) {
+    return vegas_pipe_unit(p) && p->vegas.hcopy_plan && p->vegas.hcopy_auto >= 8 && !g_over.hist_copies.on && !p->threads_explicit && sixteen_copies_fit_lds(p);
+}
+// The measurefreq == 1 source of the problem with sixteen histogram copies, bound to 1024 threads, in kernel[kVegasBig]: its own
+// candidate and cache entry (the source differs in HCOPY, the key in the launch bound too), compiled the first time a launch selects
+// it.  Reads the problem's shape through a copy: the standing plan, shape.hcopy and the standing code objects stay as they are.
+// VGPR round keys if the unit stays within 128 registers without scratch, else SGPR keys, else VegasBigUnit::kOverBudget.  What the
+// call leaves is vegas_big.state; != MCI_OK only when the unit did not compile or load.
+static int compile_vegas_big(mci_problem *p) {
+    VegasBigUnit &b = p->vegas_big;
+    if (b.state != 0) return MCI_OK;
+    if (int rc = default_measure_fits(p)) return rc;
+    mcijit::ProblemShape sh = p->shape;
+    sh.hcopy = kBigCopies;
+    sh.det = 0;
+    const std::string src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitVegasMf1);
+    Candidate c[2]; // [0] VGPR keys | [1] SGPR keys
+    for (int i = 0; i < 2; ++i) {
+        c[i].unit = mcijit::kUnitVegasMf1;
+        c[i].src = std::string(i == 0 ? kVgprKeys : "") + src;
+        c[i].threads = kBigThreads;
+    }
+    auto built = [](const Candidate &k) { return VegasBuilt{k.vgprs(), k.scratch(), true}; };
+    if (c[0].build()) {
+        b.state = VegasBigUnit::kNoCompile;
+        return c[0].failed(" (big :vegas unit)");
+    }
+    VegasBuilt with = built(c[0]), without{0, 0, false};
+    if (too_fat(with)) {
+        if (c[1].build()) {
+            b.state = VegasBigUnit::kNoCompile;
+            return c[1].failed(" (big :vegas unit)");
+        }
+        without = built(c[1]);
+    }
+    bool keys = false;
+    if (vegas_big_budget(with, without.ok ? &without : nullptr, &keys) != 1) {
+        b.state = VegasBigUnit::kOverBudget;
+        return MCI_OK;
+    }
+    const int64_t lds = sixteen_copies_lds(p);
+    if (int rc = p->kernel[mci_problem::kVegasBig].load(p->ctx, c[keys ? 0 : 1], "mci_vegas_batch", lds, kSlotRules)) {
+        b.state = VegasBigUnit::kNoCompile;
+        return rc;
+    }
+    if (!p->ctx->offline) { // the grid of its cursor launches: what the runtime says is resident at once (one workgroup per CU)
+        int per_cu = 0, cus = 0;
+        HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->kernel[mci_problem::kVegasBig].f, kBigThreads, (size_t)lds));
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
+        b.resident = per_cu * cus;
+    }
+    b.keys = keys;
+    b.state = 1;
+    return MCI_OK;
+}
+
 // ---- several lanes per chain (mci_spec.h) ---------------------------------------------------------------------------------
 // the chain solver's kernel with a group of lanes per chain: its own code object (slots 5, 6), compiled when a launch first asks for it
 static int compile_spec(mci_problem *p, int solver) {
@@ -465,8 +523,11 @@ int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n)
     else if (solver == MCI_VEGASMC_LANES || solver == MCI_MCMC_LANES) k = solver == MCI_VEGASMC_LANES ? kSlotVegasmcSpec : kSlotMcmcSpec, what = "the several-lanes-per-chain kernel";
     else if (solver == MCI_VEGAS_STRAT) k = mci_problem::kStrat, what = "the stratified :vegas kernel";
     else if (const int w = sweep_unit_of(solver); w >= 0) k = mci_problem::kSweep + w, what = std::string("the sweep kernel") + kSweepUnits[w].for_what;
+    else if (solver == MCI_VEGAS_BIG) k = mci_problem::kVegasBig, what = "the big :vegas unit";
     else if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver);
-    else k = (solver == MCI_VEGAS && !p->kernel[solver].compiled && p->kernel[kSlotVegasAny].compiled) ? kSlotVegasAny : solver;
+    // (:vegas: the unit the last :vegas launch ran -- the big one behind a big launch, the standing one before any launch and behind a small one)
+    else if (solver == MCI_VEGAS && p->launch.last_vegas_big && p->kernel[mci_problem::kVegasBig].compiled) k = mci_problem::kVegasBig;
+    else k =(solver == MCI_VEGAS && !p->kernel[solver].compiled && p->kernel[kSlotVegasAny].compiled) ? kSlotVegasAny : solver;
     if (!p->kernel[k].compiled) return fail(MCI_ERR_INVALID, "%s has not been compiled yet", what.c_str());
     snprintf(buf, (size_t)n, "%s", p->kernel[k].code_object.c_str());
     return MCI_OK;
@@ -664,13 +725,21 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         }
         return compile_sweep_unit(p, w);
     }
+    if (solver == MCI_VEGAS_BIG) { // the big :vegas unit, for layouts that have one (launches compile it by themselves when they first select it)
+        if (!vegas_big_layout(p)) return fail(MCI_ERR_INVALID, "this layout has no big :vegas unit (the eight-copy plan of the pipelined one-tile loop, sixteen copies within the CU's LDS)");
+        if (int rc = compile_vegas_big(p)) return rc;
+        if (p->vegas_big.state == VegasBigUnit::kOverBudget) return fail(MCI_ERR_COMPILE, "the big :vegas unit needs more than %ld VGPRs or scratch at 1024 threads: big launches keep the standing unit", kVgprsTwoWide);
+        if (p->vegas_big.state == VegasBigUnit::kNoCompile) return fail(MCI_ERR_COMPILE, "the big :vegas unit did not compile");
+        return MCI_OK;
+    }
     if (solver < 0 || solver > 2) return fail(MCI_ERR_INVALID, "Solver %d is not supported!", solver); // main.jl:263
     return compile_solver(p, solver);
 }
 
 int mci_get_histogram_copies(const mci_problem *p, int32_t *copies) {
     if (!p || !copies) return fail(MCI_ERR_INVALID, "NULL argument");
-    *copies = (p->kernel[MCI_VEGAS].compiled || p->kernel[kSlotVegasAny].compiled) ? p->shape.hcopy : planned_hcopy(p, nullptr);
+    if (p->launch.last_vegas_big) *copies = kBigCopies; // (the unit the last :vegas launch ran)
+    else *copies = (p->kernel[MCI_VEGAS].compiled || p->kernel[kSlotVegasAny].compiled) ? p->shape.hcopy : planned_hcopy(p, nullptr);
     return MCI_OK;
 }
 

@@ -44,6 +44,49 @@ void plan_threads(const mci_problem *p, const LaunchRequest &rq, LaunchPlan &pl)
     if (rq.solver == MCI_VEGAS && p->vegas.wide && !p->vegas.threads_vegas && p->wg_per_block <= 0 && rq.nblocks * rq.nevalperblock < ((int64_t)1 << 22) &&
         rq.nblocks * rq.nevalperblock * p->shape.ndraw >= ((int64_t)1 << 19))
         pl.T = 512;
+    if (rq.kern == mci_problem::kVegasBig) pl.T = kBigThreads; // (the big unit's launches, its self-check's included)
+}
+
+// dynamic LDS of the sample launch: the solver's, or the big unit's sixteen copies
+int64_t plan_launch_lds(const mci_problem *p, const LaunchRequest &rq) {
+    return rq.kern == mci_problem::kVegasBig ? sixteen_copies_lds(p) : solver_lds(p, rq.solver);
+}
+
+// Which launches take the big :vegas unit (mci_host_vegas_plan.h vegas_big_rule): everything the rule looks at, from the problem, the
+// request and the overrides.  `assume_unit`: ask as if the unit were loaded and resident (before it is compiled).
+// kVegasBigSamples: the smallest launch that takes it.  2^25 keeps the standing geometry; at 2^26 (16 x 2^22, bench.py --neval-per-gpu
+// 67108864, three alternating pairs against the parent) 0.9029 / 0.9036 / 0.9043 -> 0.8986 / 0.8986 / 0.9002 ms per step: -0.0050 ms
+// = 3.6 x the parent's spread, every new run below every parent run; at the headline's 1e8 (five pairs) 1.3313 -> 1.3118 ms, 6.5 x
+// the spread (profiles/vegas_sixteen_copies.txt).  (Never below the cursor's own 2^25: the unit runs by cursor only.)
+// kVegasBigAdds: the fewest histogram adds per sample.  The lightest layout measured is the 8-D Gaussian at 1e8 (8 adds per sample;
+// override off | natural, three alternating pairs): 0.7224 / 0.7225 / 0.7230 -> 0.7150 / 0.7157 / 0.7160 ms per step -- it wins there
+// too, so the floor is no measured loss but the edge of what was measured; with fewer adds the conflicts the unit removes weigh less.
+const int64_t kVegasBigSamples = (int64_t)1 << 26;
+const int kVegasBigAdds = 8;
+VegasBigIn plan_big_in(const mci_problem *p, const LaunchRequest &rq, const Overrides &ov, bool assume_unit) {
+    VegasBigIn in{};
+    in.vegas = rq.solver == MCI_VEGAS;
+    in.mf1 = rq.measurefreq == 1;
+    in.pipe_unit = !p->in_self_check && vegas_pipe_unit(p) && !(ov.vegas_cursor.on && ov.vegas_cursor.v == 0);
+    in.forced_grid = p->wg_per_block > 0;
+    in.deterministic = p->deterministic;
+    in.override_big = ov.vegas_big_unit.on ? (ov.vegas_big_unit.v != 0 ? 1 : 0) : -1;
+    in.cursor_forced = ov.vegas_cursor.on && ov.vegas_cursor.v == 1;
+    in.copy_plan = p->vegas.hcopy_plan;
+    in.conservative = p->vegas.conservative;
+    in.copies_forced = ov.hist_copies.on;
+    in.threads_explicit = p->threads_explicit;
+    in.copies = p->shape.hcopy;
+    in.threads = solver_threads(p, MCI_VEGAS);
+    in.sixteen_fit_lds = sixteen_copies_fit_lds(p);
+    in.samples = rq.nblocks * rq.nevalperblock;
+    in.threshold = kVegasBigSamples;
+    in.adds = vegas_adds_per_sample(p);
+    in.adds_floor = kVegasBigAdds;
+    in.nblocks = rq.nblocks;
+    in.resident = assume_unit ? rq.nblocks : p->vegas_big.resident;
+    in.state = assume_unit && p->vegas_big.state == 0 ? 1 : p->vegas_big.state;
+    return in;
 }
 
 // Does this launch continue the chains of the previous one?  (the next iteration of the same solver over the same blocks;
@@ -200,8 +243,9 @@ int plan_cursor_candidate(const mci_problem *p, const LaunchRequest &rq, const O
 }
 void plan_cursor_grid(const LaunchRequest &rq, int resident, LaunchPlan &pl) {
     // (a resident grid of at most kAtomicRows rows would flush its histograms by atomics, the plan of launch-bound
-    // iterations: such layouts -- one workgroup per CU -- keep the fixed partition and its partial rows)
-    if (resident >= rq.nblocks && (resident / rq.nblocks) * rq.nblocks > kAtomicRows) {
+    // iterations: such layouts -- one workgroup per CU -- keep the fixed partition and its partial rows; the big unit's launches are
+    // one 1024-thread workgroup per CU by design and keep their partial rows, plan_tiles)
+    if (resident >= rq.nblocks && ((resident / rq.nblocks) * rq.nblocks > kAtomicRows || rq.kern == mci_problem::kVegasBig)) {
         pl.cursor = true;
         pl.wpb = (int)(resident / rq.nblocks);
         const int64_t maxw = (pl.units + pl.T - 1) / pl.T;
@@ -226,7 +270,9 @@ void plan_tiles(const mci_problem *p, const LaunchRequest &rq, const Overrides &
     pl.split = rq.solver == MCI_VEGAS && s.ntile > 1;
     if (!pl.split && pl.wpb * s.ntile > 4096 / rq.nblocks && s.ntile > 1) pl.wpb = (int)(4096 / rq.nblocks / s.ntile) > 0 ? (int)(4096 / rq.nblocks / s.ntile) : 1;
     pl.nrows = rq.nblocks * pl.wpb;   // partial rows: one per (block, slice)
-    pl.atomic_flush = rq.solver == MCI_VEGAS && pl.hist_lds && s.ntile == 1 && atomic_rows_ok(p) && pl.nrows <= kAtomicRows && !s.host_integrand;
+    // (a cursor launch of the big unit -- 256 rows on the headline -- is no launch-bound iteration: partial rows and k_hist_stage1)
+    pl.atomic_flush = rq.solver == MCI_VEGAS && pl.hist_lds && s.ntile == 1 && atomic_rows_ok(p) && pl.nrows <= kAtomicRows && !s.host_integrand &&
+                      !(pl.cursor && rq.kern == mci_problem::kVegasBig);
     pl.nwg = pl.split ? pl.nrows : pl.nrows * s.ntile;
     // (three buffers from 64 rows on: x^2 + y^2 at neval = 1e6, 256 rows: see tools/latency.py)
     pl.ghist_buffers = pl.atomic_flush ? (pl.nrows > 64 ? 3 : 1) : 0;

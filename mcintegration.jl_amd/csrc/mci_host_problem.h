@@ -303,6 +303,10 @@ int mci_problem_create(mci_ctx *ctx, const mci_problem_desc *d, mci_problem **ou
         // workgroups per CU (4 waves per SIMD when the kernel needs <= 128 VGPRs; compile_solver checks).  Measured on C2
         // (tools/hcopy_sweep.sh, kernel ms per 1e8 samples): 1 copy x 256 threads 1.715 | 4 x 512 1.663 | 8 x 512 1.625 |
         // 16 x 1024 (one workgroup per CU) 1.662 | 8 x 1024 1.694.  The override hist_copies forces a count (1 = off).
+        // (The 16 x 1024 figure is round 2's: four rounds of fat workgroups under the fixed partition and a unit that spilled at the
+        // 128-register cap.  Under the cursor's one resident round, with today's 123-VGPR unit, 16 x 1024 beats 8 x 512 from 2^26
+        // samples on -- 1.2983 -> 1.2790 ms kernel time at 1e8, profiles/vegas_sixteen_copies.txt -- and runs as the big unit,
+        // mci_host_vegas_plan.h VegasBigUnit, next to this rule's eight copies, which smaller launches keep.)
         s.hcopy = 1;
         {
             int hc = 1;
@@ -508,9 +512,19 @@ int mci_set_launch(mci_problem *p, int32_t threads, int32_t wg_per_block) {
 }
 
 // VegasKernelPlan::planned_copies for this problem: sixteen copies need both opt-in streams and room in the CU's LDS
+// (the LDS half of it is all the big unit asks: mci_host_vegas_plan.h vegas_big_rule)
+static int64_t sixteen_copies_lds(const mci_problem *p) { return p->lds_bytes + (int64_t)p->shape.htile * 8 * (kBigCopies - 1); }
+static bool sixteen_copies_fit_lds(const mci_problem *p) { return sixteen_copies_lds(p) <= 159 * 1024; }
 static bool sixteen_copies_fit(const mci_problem *p) {
     const auto &s = p->shape;
-    return s.rng_bits == 32 && s.rng_rounds == 7 && p->lds_bytes + (int64_t)s.htile * 8 * 15 <= 159 * 1024;
+    return s.rng_bits == 32 && s.rng_rounds == 7 && sixteen_copies_fit_lds(p);
+}
+// ds_add_f64 per sample of the :vegas sample loop: the draws whose bins take histogram adds
+static int vegas_adds_per_sample(const mci_problem *p) {
+    const auto &s = p->shape;
+    int nadd = 0;
+    for (int k = 0; k < s.ndraw; ++k) nadd += (p->leaves[(size_t)s.draw_leaf[(size_t)k]].adapt && s.cover_mask[(size_t)k]) ? 1 : 0;
+    return nadd;
 }
 static int planned_hcopy(const mci_problem *p, int *threads) { return p->vegas.planned_copies(sixteen_copies_fit(p), threads); }
 
@@ -552,6 +566,10 @@ static bool vegas_pipe_unit(const mci_problem *p) {
 // workgroups of `threads` threads of the :vegas kernel in slot `kern` that are resident on the device at once: the runtime's occupancy
 // for the kernel's registers and the launch's LDS, times the CUs (asked again only when the kernel or the launch shape changed)
 static int cursor_resident(mci_problem *p, int kern, int threads, int *out) {
+    if (kern == mci_problem::kVegasBig) { // (asked once, when the unit was loaded: compile_vegas_big)
+        *out = p->vegas_big.resident;
+        return MCI_OK;
+    }
     hipFunction_t f = p->kernel[kern].f;
     const int64_t lds = solver_lds(p, MCI_VEGAS);
     if (f != p->cursor_occ_f || threads != p->cursor_occ_threads || lds != p->cursor_occ_lds) {

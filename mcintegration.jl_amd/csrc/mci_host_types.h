@@ -170,9 +170,11 @@ struct mci_problem {
     // kernel slots (kslot): :vegas for measurefreq == 1 | :vegasmc | :mcmc | :vegas for any measurefreq | sample dump
     //                      | :vegasmc with several lanes per chain | :mcmc with several lanes per chain (mci_spec.h)
     // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the five sweep units (Sweep)
-    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kKernels = kSweep + 7 };
+    // ... and the big :vegas unit (sixteen histogram copies, 1024 threads: mci_host_vegas_plan.h VegasBigUnit)
+    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kVegasBig = kSweep + 7, kKernels = kVegasBig + 1 };
     KernelUnit kernel[kKernels];
     VegasKernelPlan vegas; // which :vegas code object the launches run (mci_host_vegas_plan.h)
+    VegasBigUnit vegas_big; // ... and whether big launches have a third one to run (kernel[kVegasBig])
     // Several lanes per chain (mci_spec.h, mci_set_chain_speculation): lanes -1 automatic (as many as the launch's chains leave idle),
     // 1 never, 2..64 forced; the acceptance the speculation tree is built for (<= 0: the solver's default) and the most accept edges
     // on a way through it (-1: the solver's default); the tree of the last such launch on the device
@@ -195,9 +197,10 @@ struct mci_problem {
     // kernel without a marker is preceded by <= 2 blocks x <= 512 samples through it, and the packed buffer is compared with what the
     // static kernel k_check_vegas (mci_check.h) makes of the same samples.  [0] the measurefreq == 1 unit, [1] the any-cadence unit.
     // vegas_check_state: 0 not looked at, 1 verified, -1 fell back to the conservative layout, -2 no layout agreed
+    // (the big unit goes through the same check; what it leaves is in vegas_big -- state, check_done -- and in flag bit 3)
     int vegas_check_state[2] = {0, 0};
     bool vegas_check_done[2] = {false, false}; // nothing left to decide for the loaded code object of that unit
-    int vegas_check_flags = 0;                 // bit 0: observables not compared (user measure), bit 1: verified from a marker
+    int vegas_check_flags = 0;                 // bit 0: observables not compared (user measure), bit 1: verified from a marker, bit 3: the big unit failed
     int check_slot = -1;                       // inside vegas_self_check: the kernel slot its launch goes through, whatever its cadence
     int64_t check_launches = 0;                // launches made for vegas_self_check so far (mci_debug_vegas_check_launches)
     int64_t last_discarded_neval = 0;              // evaluations of the warm-up launches the last mci_integrate ran again instead of counting
@@ -342,6 +345,7 @@ struct mci_problem {
         int last_spec_lanes = 1, last_spec_maxacc = 0; // of the last chain launch (1: one lane per chain)
         bool last_carried = false;                     // the last chain launch continued the one before it
         bool last_cursor = false;                      // the last sample launch handed its ranges out by cursor (mci_debug_vegas_cursor)
+        bool last_vegas_big = false;                   // the last :vegas launch ran the big unit (what the reporting calls describe)
         int64_t last_split_chunks = 0, last_split_bytes = 0; // chunks of the last many-grid :vegas launch | bytes of parked stream it held at a time
         // the event ring (evs, d_clocks): sample launches so far, and per slot what its launch left there
         int64_t launches = 0;
@@ -432,7 +436,7 @@ struct mci_problem {
         int chain_carry = 0;
     } sweep;
     KernelUnit &sweep_unit(int which) { return kernel[kSweep + which]; }
-    static_assert(kKernels == kSweep + Sweep::kUnits, "one handle per sweep unit");
+    static_assert(kVegasBig == kSweep + Sweep::kUnits, "one handle per sweep unit");
 };
 
 // The seven sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
@@ -477,7 +481,7 @@ int64_t mci_problem::kMcmcCarryHalfFloors = 2;
 // are cached) and MCI_JIT_FLAGS (extra hiprtc options), mci_jit.h.
 namespace {
 struct Override { bool on = false; int64_t v = 0; };
-struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk, vegas_self_check, vegas_cursor, cursor_log2_big, cursor_ones; } g_over;
+struct Overrides { Override table_mode, hist_tile_bins, no_split_all, l1_phase, train_walk, hist_copies, fresh_floors, fresh_burnin_pct, spec_self_check, split_chunk, vegas_self_check, vegas_cursor, cursor_log2_big, cursor_ones, vegas_big_unit; } g_over;
 Override *override_slot(const char *key) {
     if (!key) return nullptr;
     if (!strcmp(key, "table_mode")) return &g_over.table_mode;
@@ -494,6 +498,7 @@ Override *override_slot(const char *key) {
     if (!strcmp(key, "vegas_cursor")) return &g_over.vegas_cursor;
     if (!strcmp(key, "cursor_log2_big")) return &g_over.cursor_log2_big;
     if (!strcmp(key, "cursor_ones")) return &g_over.cursor_ones;
+    if (!strcmp(key, "vegas_big_unit")) return &g_over.vegas_big_unit;
     return nullptr;
 }
 } // namespace
@@ -729,6 +734,8 @@ int hold_consume(mci_problem *p) {
 
 void drop_modules(mci_problem *p) {
     p->vegas.modules_dropped();
+    p->vegas_big.modules_dropped();
+    p->launch.last_vegas_big = false; // (the reporting calls describe the standing plan again)
     p->vegas_check_done[0] = p->vegas_check_done[1] = false; // (new code objects: they prove themselves again, or show their markers)
     p->cursor_occ_f = nullptr; // (the occupancy answer belonged to a kernel of the modules that go)
     for (KernelUnit &u : p->kernel) u.drop();

@@ -55,6 +55,11 @@ struct VegasKernelPlan {
     // 1024-thread workgroup per CU -- beat eight: 84.4 against 77.5 Gsamples/s on the headline configuration; with one opt-in or none
     // eight copies in two 512-thread workgroups win (bench.py: rounds 7: 73.6 against 70.2, 32 bits: 75.5 against 76.2, default: 66.7
     // against 61.7).  sixteen_fit: both streams are on and sixteen copies fit the CU's LDS
+    // (Those default-stream numbers are round 2's, under the fixed partition: the fat workgroups ran in four rounds, each draining its
+    // CU and zeroing and flushing 128 KB, and the unit of the day spilled at the 128-register cap, profiles/r02_ablation.txt.  Neither
+    // holds any more -- the cursor runs one resident round and today's 16 x 1024 unit needs 123 VGPRs without scratch -- and on the
+    // default stream sixteen copies now win for big launches: 1.3313 -> 1.3118 ms per step at 1e8 samples,
+    // profiles/vegas_sixteen_copies.txt.  They run as an ADDITIONAL unit, VegasBigUnit below; this plan stays at eight.)
     int planned_copies(bool sixteen_fit, int *threads) const {
         const bool sixteen = hcopy_plan && hcopy_auto >= 8 && sixteen_fit;
         if (threads) *threads = sixteen ? 1024 : 512;
@@ -175,6 +180,69 @@ inline int vegas_kernel_rule(VegasKernelPlan &pl, const VegasRuleIn &in, const V
     }
     pl.planned = true;
     return 0;
+}
+
+// ---- the big unit ----------------------------------------------------------------------------------------------------------------------
+// A third :vegas code object next to the two cadence variants: the measurefreq == 1 source compiled for SIXTEEN histogram copies in one
+// 1024-thread workgroup per CU (every lane of a 16-lane group adds to a bank-pair column of its own: conflict-free adds,
+// profiles/r02_issue_costs.txt 26.8 -> 13.5 ns per wave-instruction), taken by big cursor launches only.  The standing plan above, its
+// code objects and shape.hcopy are never touched by it: a launch that does not take the big unit runs exactly as it would without it.
+const int kBigCopies = 16, kBigThreads = 1024;
+struct VegasBigUnit {
+    // 0 nothing decided (not compiled yet) | 1 loaded, within budget | kOverBudget more than 128 VGPRs or scratch with either kind of
+    // round keys | kFailedCheck its self-check disagreed with the static kernel (never selected again) | kNoCompile it did not compile
+    enum { kOverBudget = -1, kFailedCheck = -2, kNoCompile = -3 };
+    int state = 0;
+    bool keys = false;       // compiled with VGPR round keys
+    bool check_done = false; // nothing left to decide for the loaded code object (mci_host_check.h)
+    int resident = 0;        // workgroups the runtime reports as resident at once (asked once, when the unit is loaded)
+    void modules_dropped() { *this = VegasBigUnit(); }
+};
+// everything the choice looks at.  The last two describe the unit itself: a caller that has not compiled it yet asks with state = 1
+// and resident = nblocks -- "would this launch take it if it turned out usable?" -- and compiles only then.
+struct VegasBigIn {
+    bool vegas, mf1;                  // a :vegas launch | of measurefreq == 1
+    bool pipe_unit;                   // plan_cursor_candidate's first condition: the pipelined one-tile loop, no self-check launch, cursor not overridden off
+    bool forced_grid, deterministic;  // a forced wg_per_block | mci_set_deterministic
+    int override_big;                 // override vegas_big_unit: -1 not set | 0 never | 1 at any size, with ...
+    bool cursor_forced;               // ... override vegas_cursor = 1
+    bool copy_plan;                   // VegasKernelPlan::hcopy_plan
+    bool conservative, copies_forced, threads_explicit;
+    int copies, threads;              // what the standing unit runs: shape.hcopy, its workgroup size
+    bool sixteen_fit_lds;             // sixteen copies fit the CU's LDS next to the tables
+    long long samples, threshold;     // of the launch, all blocks | kVegasBigSamples
+    int adds, adds_floor;             // ds_add_f64 per sample | kVegasBigAdds
+    long long nblocks, resident;      // blocks of the launch | VegasBigUnit::resident
+    int state;                        // VegasBigUnit::state
+};
+enum VegasBigRefusal {
+    kBigTake = 0, kBigNotMf1, kBigNoCursor, kBigForcedGrid, kBigDeterministic, kBigOverrideOff, kBigStandingPlan, kBigLds, kBigSmall, kBigFewAdds,
+    kBigNotResident, kBigOverBudget, kBigFailedCheck, kBigNoCompile
+};
+inline VegasBigRefusal vegas_big_rule(const VegasBigIn &in) {
+    const bool forced_on = in.override_big == 1 && in.cursor_forced; // (tests: any size, any grid)
+    if (!in.vegas || !in.mf1) return kBigNotMf1;
+    if (!in.pipe_unit) return kBigNoCursor;
+    if (in.deterministic) return kBigDeterministic;
+    if (in.override_big == 0) return kBigOverrideOff;
+    if (in.forced_grid && !forced_on) return kBigForcedGrid;
+    // the standing plan is the copy plan as the rule above leaves it for the headline kind of kernel: eight copies, 512 threads
+    if (!in.copy_plan || in.conservative || in.copies_forced || in.threads_explicit || in.copies < 8 || in.threads != 512) return kBigStandingPlan;
+    if (!in.sixteen_fit_lds) return kBigLds;
+    if (!forced_on && in.samples < in.threshold) return kBigSmall;
+    if (!forced_on && in.adds < in.adds_floor) return kBigFewAdds;
+    if (in.state == VegasBigUnit::kOverBudget) return kBigOverBudget;
+    if (in.state == VegasBigUnit::kFailedCheck) return kBigFailedCheck;
+    if (in.state == VegasBigUnit::kNoCompile) return kBigNoCompile;
+    // one resident round: every block gets a whole number (>= 1) of the workgroups that run at once
+    if (!forced_on && in.resident < in.nblocks) return kBigNotResident;
+    return kBigTake;
+}
+// the unit's registers against the budget of four waves per SIMD: VGPR round keys if they fit, else SGPR keys, else no big unit
+inline int vegas_big_budget(const VegasBuilt &with_keys, const VegasBuilt *without, bool *keys) {
+    *keys = !too_fat(with_keys);
+    if (*keys) return 1;
+    return without && !too_fat(*without) ? 1 : VegasBigUnit::kOverBudget;
 }
 
 } // namespace

@@ -440,7 +440,7 @@ class Engine:
     @staticmethod
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
-                "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14}.get(solver) or _lib.SOLVERS[solver]
+                "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -451,7 +451,8 @@ class Engine:
         integrate_sweep_strat, csrc/mci_sweep_strat.h; stratified problems sweep_strat_supported accepts) | "vegasmc_sweep" (the kernel of
         integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts) | "mcmc_sweep" (the kernel of
         integrate_sweep_mcmc, the same header's :mcmc instantiation; layouts sweep_mcmc_supported accepts) | "vegasmc_sweep_carry" |
-        "mcmc_sweep_carry" (the same two kernels with chains carried from iteration to iteration: set_sweep_chain_carry)"""
+        "mcmc_sweep_carry" (the same two kernels with chains carried from iteration to iteration: set_sweep_chain_carry) | "vegas_big" (the
+        :vegas kernel with sixteen histogram copies in 1024-thread workgroups that big launches of eight-copy layouts run)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):

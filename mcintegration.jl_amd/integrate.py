@@ -745,6 +745,8 @@ def prefill_kernel_cache():
     for cfg, f, meas in jobs:
         eng = Engine(cfg, f, measure=meas, device=-1)
         eng.compile("vegas")
+        if n == 1:
+            eng.compile("vegas_big")       # ... whose launches of 2^26 samples and more (bench.py's 1e8) run sixteen histogram copies
         if meas is not None:
             eng.compile("vegasmc")  # C3 is a :vegasmc config
             eng.compile("vegasmc_lanes")   # ... whose launches of few chains (the example's neval = 1e6) give every chain a group of lanes
