@@ -4,7 +4,8 @@ The closure reads its parameters off `config.userdata` (a struct of floats); mci
 point's parameters from its object, and runs all points in one launch -- one workgroup per point runs that point's whole :vegas loop.
 Every result is what mci.integrate(peak, userdata=that object, ...) returns on a fresh configuration; all points share the seed, so the
 curve over `a` is smooth (common random numbers).  `stratified()` runs the same scan with stratify=True (VEGAS+ at every point, still one
-launch) and then freezes what it learned for a second scan.
+launch) and then freezes what it learned for a second scan.  `stratified_two_types()` is one short stratified scan over two variable
+types with ranges of their own: `leaves="all"` lets it run as one launch too.
 
 Reference pattern:  for a in as;  integrate((x, c) -> ...; userdata = Para(a, u), var = Continuous(0, 1), dof = [[4]], solver = :vegas)  end
 
@@ -70,6 +71,24 @@ def stratified(points=64):
         print("a = %5.2f   adapting %12.5f +- %-10.5f  frozen (%s) %12.5f +- %-10.5f  exact %12.5f" % (p.a, r.mean[0], r.stdev[0], f.stratification["carried"],
                                                                                                      f.mean[0], f.stdev[0], exact(p)))
     return scan, trained, frozen
+
+
+def ellipse(X, c):
+    x, y = X
+    return x[0] ** 2 + c.userdata.a * y[0] ** 2
+
+
+def stratified_two_types(points=8):
+    """a stratified scan over two Continuous variable types, x in (0, 1) and y in (0, 2), each with a grid of its own: with leaves="all"
+    the points run as ONE launch (without it they would run as integrate(..., stratify=True) calls, one after another)"""
+    scan = [types.SimpleNamespace(a=float(a)) for a in np.linspace(0.5, 2.0, points)]
+    results = mci.integrate_sweep(ellipse, params=scan, stratify=True, leaves="all", var=(mci.Continuous(0.0, 1.0), mci.Continuous(0.0, 2.0)),
+                                  solver="vegas", neval=2e4, niter=5, seed=7)
+    print("stratified over two variable types, batched:", all(r.sweep_batched for r in results), "| grids of",
+          [len(g) for g in results[0].maps_by_leaf], "points")
+    for p, r in zip(scan, results):
+        print("a = %5.2f   %10.6f +- %-9.6f  exact %10.6f" % (p.a, r.mean[0], r.stdev[0], 2.0 / 3.0 + 8.0 * p.a / 3.0))
+    return scan, results
 
 
 PI = math.pi
@@ -144,6 +163,7 @@ def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None, mcmc_chains=N
 if __name__ == "__main__":
     main()
     stratified()
+    stratified_two_types()
     bubble_scan()
     bubble_scan(solver="vegasmc", chains=64)
     bubble_scan(solver="mcmc", mcmc_chains=64)

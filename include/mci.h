@@ -56,7 +56,10 @@ enum { MCI_VEGASMC_SWEEP_CARRY = 13, MCI_MCMC_SWEEP_CARRY = 14 };
 /* ... and the big :vegas unit: the measurefreq == 1 kernel with sixteen histogram copies in 1024-thread workgroups, which big launches of
  * layouts on the eight-copy plan run instead (compiled the first time a launch selects it; layouts without one refuse the name) */
 enum { MCI_VEGAS_BIG = 15 };
-/* mci_set_sweep_leaves: which problems mci_integrate_sweep takes */
+/* ... and the sweep kernel for stratified points of problems with several Continuous variable leaves (mci_integrate_sweep_strat on a
+ * problem that opted in with mci_set_sweep_strat_leaves and is no one-grid layout) */
+enum { MCI_VEGAS_SWEEP_STRAT_LEAVES = 16 };
+/* mci_set_sweep_leaves: which problems mci_integrate_sweep takes; mci_set_sweep_strat_leaves: which ones mci_integrate_sweep_strat takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
 typedef struct mci_ctx mci_ctx;
@@ -333,6 +336,18 @@ int mci_integrate_sweep_strat(mci_problem *prob, const mci_integrate_args *args,
  * measure, a user measure, deterministic mode, more than one variable leaf or a leaf that is not Continuous, tables that do not sit in
  * LDS in one tile, more than 32 draws or 8 weight columns, more hypercubes than neval / 2, or more than 159 KiB of LDS (named). */
 int mci_sweep_strat_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* Which stratified problems run as a sweep.  MCI_SWEEP_ONE_GRID (default): one Continuous leaf, as described above; every answer of
+ * mci_sweep_strat_supported is what it was.  MCI_SWEEP_ALL_LEAVES: also a stratified problem with several Continuous variable leaves --
+ * pools with ranges of their own, a composite variable with one grid per axis.  An opt-in of its own: mci_set_sweep_leaves does not
+ * reach the stratified query, and this one does not reach mci_sweep_supported.  What still keeps such a problem out: a leaf that is not
+ * Continuous, more than 159 KiB of LDS for the sample tables with the smallest chunk's hypercubes or the refinement scratch of the
+ * largest leaf plus the point's whole map (the byte count is named), tables and histograms that do not sit in LDS in one tile; the
+ * draws, weight columns, hypercube count and every common refusal as before.  Such a problem runs a kernel of its own
+ * (MCI_VEGAS_SWEEP_STRAT_LEAVES: every leaf's histogram slice and train! per iteration, each refused on its own histogram); maps_in /
+ * maps_out rows then hold mci_sweep_map_doubles doubles, the leaves in order, nbin + 1 grid points each.  A problem with one Continuous
+ * leaf runs the same kernel and code object (MCI_VEGAS_SWEEP_STRAT) under either mode.  d_in / d_out / counts_out, seeds, adapt = 0 and
+ * the signature of mci_integrate_sweep_strat do not change. */
+int mci_set_sweep_strat_leaves(mci_problem *prob, int32_t mode);
 /* hypercubes of the plan mci_integrate_sweep_strat runs these arguments on: the row length of d_in / d_out / counts_out */
 int mci_sweep_strat_doubles(const mci_problem *prob, const mci_integrate_args *args, int64_t *ncube);
 /* A parameter sweep under the reference's default solver (main.jl:72): `npoint` independent :vegasmc loops -- what mci_integrate runs

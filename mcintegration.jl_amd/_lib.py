@@ -91,6 +91,7 @@ SIGNATURES = [
     ("mci_sweep_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
     ("mci_set_sweep_leaves", C.c_int, [_VP, C.c_int32]),
     ("mci_set_sweep_chain_carry", C.c_int, [_VP, C.c_int32]),
+    ("mci_set_sweep_strat_leaves", C.c_int, [_VP, C.c_int32]),
     ("mci_get_sweep_chain_carry", C.c_int, [_VP, c_int32_p]),
     ("mci_sweep_map_doubles", C.c_int, [_VP, c_int32_p]),
     ("mci_integrate_sweep_strat", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
@@ -189,6 +190,8 @@ DEBUG_SIGNATURES = [
     ("mci_debug_sweep_lds_bytes", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("mci_debug_resample", C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p]),
     ("mci_debug_sweep_resample_lds", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("mci_debug_sweep_strat_geometry", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32)]),
 ]
 
 _lib = None

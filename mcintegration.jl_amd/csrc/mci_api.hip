@@ -36,6 +36,7 @@
 #include "mci_sweep.h" // SweepHead (mci_sweep_common.h; likewise)
 #include "mci_sweep_leaves.h"
 #include "mci_sweep_strat.h" // SweepStratArgs (likewise)
+#include "mci_sweep_strat_leaves.h"
 #include "mci_sweep_chains.h" // SweepChainArgs (likewise)
 
 namespace {

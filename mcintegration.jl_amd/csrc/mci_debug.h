@@ -90,6 +90,11 @@ int mci_debug_sweep_threads(mci_problem *prob, int32_t threads);
 int mci_debug_sweep_last_launch(const mci_problem *prob, int32_t *workgroups, int32_t *threads);
 /* (tools/sweep_bench.py) dynamic LDS bytes per workgroup of this problem's sweeps under its present mci_set_sweep_leaves mode */
 int mci_debug_sweep_lds_bytes(const mci_problem *prob, int64_t *bytes);
+/* (tests, tools/sweep_bench.py) what mci_integrate_sweep_strat lays a launch of these arguments out as, under the problem's present
+ * mci_set_sweep_strat_leaves mode: samples per chunk, dynamic LDS bytes per workgroup, where the point's map lies in it (doubles), and the
+ * blocks the ordinary stratified call merges its rows as.  No device needed; refused as mci_sweep_strat_supported refuses.  NULL: not wanted. */
+int mci_debug_sweep_strat_geometry(const mci_problem *prob, const mci_integrate_args *args, int64_t *chunk, int64_t *lds_bytes, int32_t *map_off,
+                                   int32_t *mblocks);
 /* test hook: the carried chains' resampler (k_resample_chains, mci_static_kernels.h) on its own -- nblocks workgroups of 256 threads over
  * the given stored chains, launched as an ordinary carried launch launches it: curr_old[nblocks][n_old] the integrand every stored chain
  * ended on, rw_now[nd] / rw_used[nd] the reweight factors now and those the chains ran under, w_chain[nblocks][n_old] a weight per stored

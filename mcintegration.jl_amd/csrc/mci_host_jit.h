@@ -683,6 +683,7 @@ static bool persist_layout_ok(const mci_problem *p);
 static int compile_strat(mci_problem *p); // (mci_host_strat.h)
 static int compile_sweep_unit(mci_problem *p, int which); // (mci_host_sweep.h)
 static bool sweep_leaves_unit(const mci_problem *p);
+static bool sweep_strat_leaves_unit(const mci_problem *p);
 int mci_compile_solver(mci_problem *p, int32_t solver) {
     if (solver == MCI_VEGAS_PERSISTENT) { // the persistent :vegas kernel (mci_set_persistent), for layouts that allow it
         if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
@@ -711,10 +712,15 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
             a.block = 1;
             a.thermal_ratio = 0.1;
             if (int rc = mci_sweep_mcmc_supported(p, &a, nullptr, 0)) return rc;
-        } else if (w == mci_problem::Sweep::kStrat) {
+        } else if (w == mci_problem::Sweep::kStrat || w == mci_problem::Sweep::kStratLeaves) {
             a.neval = (int64_t)1 << 40; // (the plan is the call's: here only the layout is asked about)
             a.block = 1;
             if (int rc = mci_sweep_strat_supported(p, &a, nullptr, 0)) return rc;
+            // (which of the two a stratified sweep of this problem runs: whether it has opted in, mci_set_sweep_strat_leaves, and is no one-grid layout)
+            if (w == mci_problem::Sweep::kStrat && sweep_strat_leaves_unit(p))
+                return fail(MCI_ERR_INVALID, "a stratified sweep of this problem runs the sweep kernel for several leaves (MCI_VEGAS_SWEEP_STRAT_LEAVES; mci_set_sweep_strat_leaves)");
+            if (w == mci_problem::Sweep::kStratLeaves && !sweep_strat_leaves_unit(p))
+                return fail(MCI_ERR_INVALID, "a stratified sweep of this problem runs the one-grid stratified sweep kernel (MCI_VEGAS_SWEEP_STRAT; mci_set_sweep_strat_leaves)");
         } else {
             if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
             // (which of the two a sweep of this problem runs: whether it has opted in, mci_set_sweep_leaves, and is no one-grid layout)

@@ -1,7 +1,8 @@
 // mci_host_sweep.h -- part of the ONE translation unit mci_api.hip (included there, in order; not a stand-alone header):
 // batched parameter sweeps -- eligibility, the sweep units' JIT, the one launch and the P results (mci_sweep.h vegas_sweep for
 // one Continuous leaf; mci_sweep_leaves.h vegas_sweep_leaves for any mix of Continuous and Discrete leaves, by opt-in; mci_sweep_strat.h
-// vegas_sweep_strat for stratified points; mci_sweep_chains.h vegasmc_sweep for :vegasmc points and mcmc_sweep for :mcmc points, each by its
+// vegas_sweep_strat for stratified points, mci_sweep_strat_leaves.h vegas_sweep_strat_leaves for those of several Continuous leaves, by an
+// opt-in of its own; mci_sweep_chains.h vegasmc_sweep for :vegasmc points and mcmc_sweep for :mcmc points, each by its
 // own entry point).  One descriptor
 // table (kSweepUnits), one compile, one refusal head, one driver (sweep_run).
 namespace {
@@ -172,14 +173,20 @@ static int compile_sweep_unit(mci_problem *p, int which) {
     const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true,
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
-    // (the several-leaves and the chain solvers' units' LDS is the layout's; the stratified unit's is the call's: sweep_run)
-    const bool whole_map = which == mci_problem::Sweep::kLeaves || which >= mci_problem::Sweep::kChains;
+    // (the several-leaves and the chain solvers' units' LDS is the layout's; the two stratified units' is the call's: sweep_run)
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || (which >= mci_problem::Sweep::kChains && which != mci_problem::Sweep::kStratLeaves);
     return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
 int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
     if (!p || (mode != MCI_SWEEP_ONE_GRID && mode != MCI_SWEEP_ALL_LEAVES)) return fail(MCI_ERR_INVALID, "sweep leaves: MCI_SWEEP_ONE_GRID (0) or MCI_SWEEP_ALL_LEAVES (1)");
     p->sweep.leaves_mode = mode;
+    return MCI_OK;
+}
+
+int mci_set_sweep_strat_leaves(mci_problem *p, int32_t mode) {
+    if (!p || (mode != MCI_SWEEP_ONE_GRID && mode != MCI_SWEEP_ALL_LEAVES)) return fail(MCI_ERR_INVALID, "sweep strat leaves: MCI_SWEEP_ONE_GRID (0) or MCI_SWEEP_ALL_LEAVES (1)");
+    p->sweep.strat_leaves_mode = mode;
     return MCI_OK;
 }
 
@@ -388,7 +395,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
         const int per_cu = c.unit != mci_problem::Sweep::kOne && c.lds > 80 * 1024 ? 1 : 2;
         int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
         if (grid > npoint) grid = npoint;
-        if (c.unit == mci_problem::Sweep::kStrat && c.lds > 64 * 1024) // (the chunk is the call's: not known when the unit is compiled)
+        if ((c.unit == mci_problem::Sweep::kStrat || c.unit == mci_problem::Sweep::kStratLeaves) && c.lds > 64 * 1024) // (the chunk is the call's: not known when the unit is compiled)
             HIPCHK(hipFuncSetAttribute((const void *)u.f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds));
         void *args[] = {&b, karg};
         HIPCHK(hipModuleLaunchKernel(u.f, (unsigned)grid, 1, 1, (unsigned)u.threads, 1, 1, (unsigned)c.lds, st, args, nullptr));
@@ -509,6 +516,59 @@ int64_t sweep_strat_lds(const mci_problem *p, int nloc, int *map_off) {
     if (map_off) *map_off = (int)off;
     return (off + (N + 2) + 4 + 4 * (int64_t)mci::kStratMaxCols) * 8;
 }
+// The unit a stratified sweep of this problem runs: the one-grid kernel wherever it applies, opted in (mci_set_sweep_strat_leaves) or not
+bool sweep_strat_uses_leaves(const mci_problem *p) {
+    std::string buf;
+    return p->sweep.strat_leaves_mode == MCI_SWEEP_ALL_LEAVES && sweep_one_grid_refusal(p, buf, true) != nullptr;
+}
+// LDS of the stratified sweep kernel for several leaves (mci_sweep_strat_leaves.h), bytes, for chunks of nloc hypercubes: the sample carve
+// (in the plain layout -- what it WOULD take where the problem was given another one, so that the refusal can name the count, as in
+// sweep_leaves_lds) + the chunk's hypercubes or the refinement's scratch for the largest leaf, whichever is larger, and behind them
+// (map_off, doubles) the map block edges | dacc | ddist | flags [4] (SweepBlock) | running sums and the cut hypercube's sums
+// [4 kStratMaxCols] | sweep_strat_alloc's broadcast pair [2].  The only place this byte count is made.
+int64_t sweep_strat_leaves_lds(const mci_problem *p, int nloc, int *map_off) {
+    const auto &s = p->shape;
+    const int maxn = sweep_max_nbin(p), NW = s.ni * s.ncomp;
+    const int64_t plain = (int64_t)s.ndacc + s.nddist + s.nobs + 16 * (int64_t)s.ncols + 2 * (int64_t)p->npa + s.nedge + s.nbin;
+    const int64_t carve = s.table_mode == 0 && s.ntile == 1 && s.ec_doubles == 0 ? (p->lds_bytes + 7) / 8 : plain;
+    const int64_t a = carve + strat_chunk_lds_bytes(nloc, NW) / 8, b = (int64_t)mci::train_lds_doubles(maxn) + maxn + 256;
+    const int64_t off = ((a > b ? a : b) + 1) & ~(int64_t)1;
+    if (map_off) *map_off = (int)off;
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    return (off + even(s.nedge) + even(s.ndacc) + even(s.nddist) + 4 + 4 * (int64_t)mci::kStratMaxCols + 2) * 8;
+}
+// what is left to check of the layout of a stratified problem that opted in to sweeps over all its leaves and is no one-grid layout
+const char *sweep_strat_leaves_refusal(const mci_problem *p, std::string &buf) {
+    const auto &s = p->shape;
+    for (const Leaf &L : p->leaves)
+        if (L.kind != MCI_CONTINUOUS) return "a Discrete or FermiK variable (a stratified sweep point refines Continuous grids only)";
+    if (p->leaves.empty() || s.nleaf != (int)p->leaves.size() || s.nbin <= 0) return "no variable leaves";
+    const int64_t lds = sweep_strat_leaves_lds(p, strat_nloc(1), nullptr); // (the smallest chunk: one trip)
+    if (lds > kSweepLeavesMaxLds) {
+        buf = "the sample tables, one chunk's hypercubes, the refinement scratch and the point's map take " + std::to_string((long long)lds) + " bytes of LDS (" +
+              std::to_string((long long)kSweepLeavesMaxLds) + " at most)";
+        return buf.c_str();
+    }
+    if (s.table_mode != 0 || s.ntile != 1 || s.ec_doubles > 0) return "the tables and their histograms do not sit in LDS in one tile";
+    return nullptr;
+}
+// LDS of the unit a stratified sweep of this problem runs, and the two geometries of a call of nsamp samples in `blocks` blocks: g0 the
+// ordinary stratified call's (its mblocks: what strat_run merges the rows as), g this kernel's own (its chunk)
+int64_t sweep_strat_unit_lds(const mci_problem *p, bool leaves, int nloc, int *map_off) {
+    return leaves ? sweep_strat_leaves_lds(p, nloc, map_off) : sweep_strat_lds(p, nloc, map_off);
+}
+int sweep_strat_geometry(const mci_problem *p, bool leaves, int64_t nsamp, int64_t blocks, StratGeometry &g0, StratGeometry &g) {
+    const int NW = p->shape.ni * p->shape.ncomp;
+    int64_t need0[4], need[4];
+    for (int k = 0; k < 4; ++k) {
+        need0[k] = p->lds_bytes + strat_chunk_lds_bytes(strat_nloc(8 >> k), NW);
+        need[k] = sweep_strat_unit_lds(p, leaves, strat_nloc(8 >> k), nullptr);
+    }
+    strat_geometry(nsamp, blocks, need0, g0);
+    strat_geometry(nsamp, blocks, need, g);
+    if (!g0.trips || !g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+    return MCI_OK;
+}
 // samples per iteration of a call (main.jl:121 on one rank)
 int64_t sweep_strat_nsamp(const mci_integrate_args *a, int64_t *nblocks) {
     int64_t nevalperblock, block;
@@ -519,7 +579,10 @@ int64_t sweep_strat_nsamp(const mci_integrate_args *a, int64_t *nblocks) {
 const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *a, std::string &buf) {
     const auto &s = p->shape;
     if (const char *r = sweep_common_refusal(p, a, buf, true)) return r;
-    if (const char *r = sweep_one_grid_refusal(p, buf, true)) return r;
+    const bool leaves = sweep_strat_uses_leaves(p); // (opted in: mci_set_sweep_strat_leaves)
+    if (leaves) {
+        if (const char *r = sweep_strat_leaves_refusal(p, buf)) return r;
+    } else if (const char *r = sweep_one_grid_refusal(p, buf, true)) return r;
     if (s.ndraw > mci::kStratMaxDraw) {
         buf = std::to_string(s.ndraw) + " draws per sample (at most " + std::to_string((int)mci::kStratMaxDraw) + ")";
         return buf.c_str();
@@ -541,6 +604,7 @@ const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *
               std::to_string((long long)N);
         return buf.c_str();
     }
+    if (leaves) return nullptr; // (its LDS: sweep_strat_leaves_refusal)
     const int64_t lds = sweep_strat_lds(p, strat_nloc(1), nullptr); // (the smallest chunk: one trip)
     if (lds > kSweepLeavesMaxLds) {
         buf = "the sample tables, one chunk's hypercubes, the refinement scratch and the map copy take " + std::to_string((long long)lds) + " bytes of LDS (" +
@@ -550,6 +614,26 @@ const char *sweep_strat_refusal(const mci_problem *p, const mci_integrate_args *
     return nullptr;
 }
 } // namespace
+
+static bool sweep_strat_leaves_unit(const mci_problem *p) { return sweep_strat_uses_leaves(p); }
+
+// csrc/mci_debug.h
+int mci_debug_sweep_strat_geometry(const mci_problem *p, const mci_integrate_args *a, int64_t *chunk, int64_t *lds_bytes, int32_t *map_off, int32_t *mblocks) {
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (int rc = mci_sweep_strat_supported(p, a, nullptr, 0)) return rc;
+    const bool leaves = sweep_strat_uses_leaves(p);
+    int64_t blocks = 0;
+    const int64_t nsamp = sweep_strat_nsamp(a, &blocks);
+    StratGeometry g0, g;
+    if (int rc = sweep_strat_geometry(p, leaves, nsamp, blocks, g0, g)) return rc;
+    int off = 0;
+    const int64_t lds = sweep_strat_unit_lds(p, leaves, (int)(g.S / 2 + 1), &off);
+    if (chunk) *chunk = g.S;
+    if (lds_bytes) *lds_bytes = lds;
+    if (map_off) *map_off = off;
+    if (mblocks) *mblocks = (int32_t)g0.mblocks;
+    return MCI_OK;
+}
 
 int mci_sweep_strat_supported(const mci_problem *p, const mci_integrate_args *a, char *why, int32_t n) {
     if (why && n > 0) why[0] = 0;
@@ -584,34 +668,26 @@ int mci_integrate_sweep_strat(mci_problem *p, const mci_integrate_args *a, int32
     mci::SweepStratArgs f{};
     std::vector<long long> hoff;
     SweepCall c;
-    c.unit = mci_problem::Sweep::kStrat;
+    const bool leaves = sweep_strat_uses_leaves(p); // (several Continuous leaves, opted in: mci_sweep_strat_leaves.h)
+    c.unit = leaves ? mci_problem::Sweep::kStratLeaves : mci_problem::Sweep::kStrat;
     c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
     c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
     c.plan = [&, p, a](SweepCall &c) {
         const int64_t nsamp = sweep_strat_nsamp(a, &c.blocks);
         if (int rc = sweep_strat_plan(p, nsamp, ns, &ncube)) return rc;
-        // mblocks: what the ordinary stratified call merges its rows as (strat_run); the chunk: of this kernel's own LDS need
-        const int NW = s.ni * s.ncomp;
-        int64_t need0[4], need[4];
-        for (int k = 0; k < 4; ++k) {
-            need0[k] = p->lds_bytes + strat_chunk_lds_bytes(strat_nloc(8 >> k), NW);
-            need[k] = sweep_strat_lds(p, strat_nloc(8 >> k), nullptr);
-        }
-        strat_geometry(nsamp, c.blocks, need0, g0);
-        strat_geometry(nsamp, c.blocks, need, g);
-        if (!g0.trips || !g.trips) return fail(MCI_ERR_INVALID, "stratification: the tables and the chunk's hypercubes do not fit one CU's LDS");
+        if (int rc = sweep_strat_geometry(p, leaves, nsamp, c.blocks, g0, g)) return rc;
         c.neval_per_block = nsamp / c.blocks;
         c.rows = 1;
         c.off_doubles = (size_t)ncube + 1;
         c.tbase_doubles = (size_t)mci::strat_alloc_ntile(ncube);
         c.d_doubles = (size_t)ncube;
-        c.lds = sweep_strat_lds(p, (int)(g.S / 2 + 1), &c.map_off);
+        c.lds = sweep_strat_unit_lds(p, leaves, (int)(g.S / 2 + 1), &c.map_off);
         c.too_big_count = (long long)ncube;
         hoff.resize(counts_out ? P * ((size_t)ncube + 1) : 0);
         return (int)MCI_OK;
     };
-    c.map_doubles = (size_t)p->leaves[0].nbin + 1;
-    c.maxn = p->leaves[0].nbin;
+    c.map_doubles = leaves ? (size_t)sweep_map_doubles(p) : (size_t)p->leaves[0].nbin + 1;
+    c.maxn = leaves ? sweep_max_nbin(p) : p->leaves[0].nbin;
     c.strat_stats = true;
     c.too_big = "a stratified sweep of %d points x %d iterations x %lld hypercubes needs %lld bytes of device memory (limit %lld): split it";
     c.copy_in = [&](double *d, const size_t *o, hipStream_t st) {

@@ -38,6 +38,7 @@ extern const char *const kSweepHeader;        // mci_sweep.h (batched :vegas par
 extern const char *const kSweepLeavesHeader;  // mci_sweep_leaves.h (sweeps of problems with several variable leaves)
 extern const char *const kSweepStratHeader;   // mci_sweep_strat.h (stratified points in sweeps)
 extern const char *const kSweepChainsHeader;  // mci_sweep_chains.h (batched :vegasmc and :mcmc parameter sweeps)
+extern const char *const kSweepStratLeavesHeader; // mci_sweep_strat_leaves.h (stratified points of problems with several Continuous leaves)
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -119,8 +120,10 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // (mcmc_sweep: one workgroup runs a point's whole :mcmc loop); generated for MCI_MCMC, compiled like kUnitSweepChains
 // kUnitSweepChainsCarry, kUnitSweepMcmcCarry: the two units above with chains carried from one iteration of a point to the next
 // (mci_sweep_chains.h chain_sweep<Cfg, MCMC, true>; mci_set_sweep_chain_carry): kernels and code objects of their own, compiled like them
-// The seven sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitCount = 13 };
+// kUnitSweepStratLeaves: the stratified sample trip inside the sweep kernel of mci_sweep_strat_leaves.h, for several Continuous leaves
+// (mci_set_sweep_strat_leaves); compiled like kUnitSweepLeaves (scan walk, every leaf's own learning rate) without MCI_WORK_ITEM_FROM_CALLER
+// The eight sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitSweepStratLeaves = 13, kUnitCount = 14 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -128,7 +131,7 @@ struct UnitHeader {
 };
 struct UnitRow {
     const char *include;       // the one header the generated source includes behind mci_device.h (it includes the others), or nullptr
-    UnitHeader hdr[4];         // the headers hiprtc is given behind mci_device.h, in the order they include one another: the cache key's too
+    UnitHeader hdr[5];         // the headers hiprtc is given behind mci_device.h, in the order they include one another: the cache key's too
     const char *kernel, *arg_type, *arg_name, *fn; // extern "C" kernel(mci::BatchArgs a, mci::arg_type arg_name) { mci::fn<Cfg>(a, arg_name); }
                                // nullptr: the kernels depend on the solver (generate_source)
     int mf_only;               // MCI_MF_ONLY of a :vegas unit, -1: not defined
@@ -155,6 +158,7 @@ constexpr UnitRow kUnits[] = {
     /* kUnitSweepMcmc    */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep", "SweepChainArgs", "f", "mcmc_sweep", -1, false, 2, true, false, true},
     /* kUnitSweepChainsCarry */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep_carry", "SweepChainCarryArgs", "f", "vegasmc_sweep_carry", -1, false, 2, true, false, true},
     /* kUnitSweepMcmcCarry   */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep_carry", "SweepChainCarryArgs", "f", "mcmc_sweep_carry", -1, false, 2, true, false, true},
+    /* kUnitSweepStratLeaves */ {"mci_sweep_strat_leaves.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}, {"mci_sweep_strat_leaves.h", &kSweepStratLeavesHeader}}, "mci_vegas_sweep_strat_leaves", "SweepStratArgs", "f", "vegas_sweep_strat_leaves", 1, false, 2, true, false, false},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN
@@ -477,7 +481,8 @@ inline int compile(const std::string &src, int threads, std::vector<char> &code,
     warm_up_join();
     hiprtcProgram prog;
     // mci_device.h, then the unit's own headers
-    const char *hdr[5] = {kDeviceHeader}, *hname[5] = {"mci_device.h"};
+    constexpr int kMaxHdr = 1 + (int)(sizeof u.hdr / sizeof u.hdr[0]);
+    const char *hdr[kMaxHdr] = {kDeviceHeader}, *hname[kMaxHdr] = {"mci_device.h"};
     int nhdr = 1;
     for (const UnitHeader &h : u.hdr)
         if (h.name) {

@@ -440,7 +440,8 @@ class Engine:
     @staticmethod
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
-                "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15}.get(solver) or _lib.SOLVERS[solver]
+                "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15,
+                "vegas_sweep_strat_leaves": 16}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -452,7 +453,9 @@ class Engine:
         integrate_sweep_chains, csrc/mci_sweep_chains.h; layouts sweep_chains_supported accepts) | "mcmc_sweep" (the kernel of
         integrate_sweep_mcmc, the same header's :mcmc instantiation; layouts sweep_mcmc_supported accepts) | "vegasmc_sweep_carry" |
         "mcmc_sweep_carry" (the same two kernels with chains carried from iteration to iteration: set_sweep_chain_carry) | "vegas_big" (the
-        :vegas kernel with sixteen histogram copies in 1024-thread workgroups that big launches of eight-copy layouts run)"""
+        :vegas kernel with sixteen histogram copies in 1024-thread workgroups that big launches of eight-copy layouts run) |
+        "vegas_sweep_strat_leaves" (the kernel of integrate_sweep_strat for a stratified problem with several Continuous leaves,
+        csrc/mci_sweep_strat_leaves.h; after set_sweep_strat_leaves("all"))"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -769,6 +772,15 @@ class Engine:
             raise ValueError('set_sweep_leaves: "one" or "all", got %r' % (mode,))
         check(lib().mci_set_sweep_leaves(self.p, 1 if mode == "all" else 0))
 
+    def set_sweep_strat_leaves(self, mode="one"):
+        """which stratified problems integrate_sweep_strat takes (mci_set_sweep_strat_leaves): "one" (default) = one Continuous leaf;
+        "all" = also several Continuous leaves (pools with ranges of their own, a composite with one grid per axis) whose tables, chunk
+        and map fit a workgroup's LDS -- those run a kernel of their own (compile("vegas_sweep_strat_leaves")).  An opt-in of its own:
+        set_sweep_leaves does not reach the stratified query.  sweep_strat_supported() names what still keeps a problem out"""
+        if mode not in ("one", "all"):
+            raise ValueError('set_sweep_strat_leaves: "one" or "all", got %r' % (mode,))
+        check(lib().mci_set_sweep_strat_leaves(self.p, 1 if mode == "all" else 0))
+
     def set_sweep_chain_carry(self, on=True):
         """carried chains in integrate_sweep_chains / integrate_sweep_mcmc (mci_set_sweep_chain_carry; default off): every iteration of
         a point after its first continues the chains of the one before, resampled to the target train! and doReweight! have moved --
@@ -837,7 +849,8 @@ class Engine:
         if maps is not None:
             mi = np.ascontiguousarray(maps, dtype=np.float64)
             if mi.shape != (P, nmap):
-                raise ValueError("%s: maps must be [points = %d][grid points = %d], got shape %s" % (name, P, nmap, mi.shape))
+                raise ValueError("%s: maps must be [points = %d][grid points = %d] (sweep_map_doubles(): every leaf's row, one behind the other), got shape %s"
+                                 % (name, P, nmap, mi.shape))
         return ud, sd, mi, between
 
     def _sweep_call(self, fn, a, P, niter, arrays, extra):
@@ -871,6 +884,15 @@ class Engine:
         (mci_sweep_strat_supported)"""
         return self._sweep_refusal(lib().mci_sweep_strat_supported, solver, neval, niter, block, measurefreq)
 
+    def sweep_strat_geometry(self, neval=10000, block=16):
+        """{chunk, lds_bytes, map_off, mblocks} of the launch integrate_sweep_strat lays these arguments out as: samples per chunk,
+        dynamic LDS per workgroup, the map's place in it (doubles), the blocks the ordinary stratified call merges its rows as; see
+        csrc/mci_debug.h mci_debug_sweep_strat_geometry (no device needed)"""
+        a = self._integrate_args("vegas", neval, 1, block, -1, True, 1.0, 1, 0, 0)
+        ch, lds, off, mb = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(lib().mci_debug_sweep_strat_geometry(self.p, C.byref(a), C.byref(ch), C.byref(lds), C.byref(off), C.byref(mb)))
+        return dict(chunk=int(ch.value), lds_bytes=int(lds.value), map_off=int(off.value), mblocks=int(mb.value))
+
     def sweep_strat_plan(self, neval=10000, block=16):
         """{nstrat, ncube, beta} of the plan a stratified sweep of these arguments runs on: the nstrat set_stratification was given, or
         the default plan for this neval (mci_strat_plan)"""
@@ -893,7 +915,9 @@ class Engine:
     def integrate_sweep_strat(self, solver="vegas", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1,
                               seed=1234, seeds=None, maps=None, first_iteration=0, d=None):
         """A stratified parameter sweep in one launch (mci_integrate_sweep_strat): P independent VEGAS+ loops -- what integrate() runs on
-        this stratified engine -- one workgroup per point.  Arguments and result dicts as integrate_sweep (one Continuous leaf); every
+        this stratified engine -- one workgroup per point.  Arguments and result dicts as integrate_sweep (one Continuous leaf; after
+        set_sweep_strat_leaves("all") several: `maps` rows then hold sweep_map_doubles() doubles, the leaves' grids in order, and
+        `maps_by_leaf` gives them leaf by leaf); every
         dict gains `strat_d` (the d_h the point's last iteration measured, [ncube]) and `strat_counts` (n_h of the allocation that
         iteration used).  d: None (every point starts from a uniform allocation) or [P][ncube] d_h measured on exactly this plan and
         beta -- e.g. the strat_d of an earlier sweep; with adapt=False the allocation made from it stays for the whole call.  The

@@ -464,13 +464,16 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     closure is traced on the same point as the integrand; one that reads a value off config.userdata is refused (ValueError).
 
     stratify: True or Stratify(beta, nstrat, max_nhcube) -- every point runs VEGAS+ adaptive stratified sampling, what
-    integrate(..., stratify=...) runs, still in ONE launch (Engine.integrate_sweep_strat; one Continuous variable leaf).  Every Result
+    integrate(..., stratify=...) runs, still in ONE launch (Engine.integrate_sweep_strat; one Continuous variable leaf, or with
+    leaves="all" several of them: variable types with ranges of their own, a composite with one grid per axis --
+    Engine.set_sweep_strat_leaves; `map` is then the flat row of every leaf's grid, `maps_by_leaf` the grids one by one).  Every Result
     then carries `stratification` (nstrat, ncube, beta, carried = "uniform" | "same plan"), `strat_d` (the d_h its last iteration
     measured) and `strat_counts` (the allocation that iteration used).  alloc: a list of P strat_d arrays, e.g. [r.strat_d for r in
     trained] -- every point's first allocation is made from its entry, which must have been measured on this call's plan and beta
     (there is no remap in a sweep: a strat_d remembers the plan and beta it was measured under, and another one raises ValueError);
     with adapt=False the whole scan keeps it: train, then freeze.  A sweep carries through alloc, never through Stratify(carry=True).
-    Where the stratified sweep is refused the points run as integrate(..., stratify=...) calls, as below; alloc= then raises.
+    Where the stratified sweep is refused (Engine.sweep_strat_supported: several Continuous leaves without leaves="all", a map that does
+    not fit a workgroup's LDS, ...) the points run as integrate(..., stratify=...) calls, as below; alloc= then raises.
 
     chains: None (default) or an int >= 1 -- with solver="vegasmc", the reference's default solver, every point runs its :vegasmc loop
     with that many chains per block, fresh in every iteration, still in ONE launch (Engine.integrate_sweep_chains: one workgroup per
@@ -613,6 +616,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         eng = _bind(config, bound, bound_measure if closure else measure, solver, trace=trace, print=print, device=device)
         if hasattr(eng, "set_sweep_leaves"):
             eng.set_sweep_leaves(leaves)
+        if strat is not None and hasattr(eng, "set_sweep_strat_leaves"):
+            eng.set_sweep_strat_leaves(leaves)      # (leaves="all" opts in to both leaf modes)
         if strat is not None:
             if not hasattr(eng, "integrate_sweep_strat"):
                 why = "this engine has no stratified sweep"

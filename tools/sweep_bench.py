@@ -5,6 +5,7 @@
     python tools/sweep_bench.py once --points 1024       (one warm sweep and nothing else: the run a kernel trace is taken of)
     python tools/sweep_bench.py table --layout bubble [--neval 10000] [--points 1,16,256,1024]      (profiles/r11_sweep_leaves.txt)
     python tools/sweep_bench.py strat [--neval 10000] [--points 1,16,256,1024]                      (profiles/r12_sweep_strat.txt)
+    python tools/sweep_bench.py strat --layout leaves [--nevals 10000,100000] [--points 1,16,256]   (profiles/r17_sweep_strat_leaves.txt)
     python tools/sweep_bench.py chains [--nevals 10000,100000,1000000] [--points 1,16,256] [--chains 1,16,64,256]   (profiles/r14_sweep_chains.txt)
     python tools/sweep_bench.py mcmc   [--nevals 10000,100000] [--points 1,16,256] [--chains 1,16,64,256]          (profiles/r15_sweep_mcmc.txt)
 
@@ -18,6 +19,9 @@ the header line gives the sweep kernel's LDS bytes, workgroups per CU, VGPRs and
 `strat`: the stratified sweep (Engine.integrate_sweep_strat, the default plan) against a loop of ordinary stratified calls
 (Engine.integrate on a stratified engine: the launch chain of csrc/mci_host_strat.h) and against the classic sweep, the points under
 seeds of their own at ONE parameter value, so that the scatter of their means is the error: sigma^2 x time can be read off each column.
+`strat --layout leaves`: the Watson integrand 1 / (1 - c cos x cos y cos z) / pi^3 on Continuous([(0, pi)] * 3) -- three grids, one per
+axis -- scanned over c: the stratified sweep with set_sweep_strat_leaves("all") (csrc/mci_sweep_strat_leaves.h) against a loop of ordinary
+stratified calls, which is what such a scan runs without the opt-in; the header gives the kernel's LDS bytes, chunk, VGPRs and scratch.
 `chains`: the bubble under the default solver -- the chain sweep (Engine.integrate_sweep_chains, `nchain` chains per block, one workgroup
 per point) against a loop of ordinary Engine.integrate("vegasmc") calls with the SAME nchain and carried chains off, and against a loop of
 default calls (automatic chain count, lanes per chain, carried chains), every call of a loop starting from the untrained map and
@@ -199,6 +203,67 @@ def strat_table(Ps, neval):
                  strat.last_sweep_launch(), "  (loop: %d calls timed, scaled)" % n if P > n else ""))
 
 
+# ---- strat --layout leaves: stratified points with several Continuous leaves (csrc/mci_sweep_strat_leaves.h)
+WATSON3 = "w[0] = 1.0 / (1.0 - ud[0] * cos(x[0]) * cos(x[1]) * cos(x[2])) / (M_PI * M_PI * M_PI);"
+
+
+def watson_point(k):
+    return [0.5 + 0.49 * ((k * 0.37) % 1.0)]
+
+
+def watson_engine(leaves="one"):
+    import math
+    cfg = mci.Configuration(var=mci.Continuous([(0.0, math.pi)] * 3), dof=[[1]], seed=SEED)
+    eng = mci.Engine(cfg, mci.Integrand(WATSON3, watson_point(0), "watson3"))
+    eng.set_sweep_strat_leaves(leaves)
+    eng.set_stratification()
+    return eng
+
+
+def strat_leaves_table(Ps, nevals):
+    from mcintegration_jl_amd import isa_mix
+    eng = watson_engine("all")
+    eng.compile("vegas_sweep_strat_leaves")
+    res = isa_mix.resources(eng.code_object("vegas_sweep_strat_leaves"))["mci_vegas_sweep_strat_leaves"]
+    print("# Watson integrand on Continuous([(0, pi)] * 3) (three grids of 999 increments), scanned over c; niter = %d, block = %d" % (NITER, BLOCK))
+    print("# mci_vegas_sweep_strat_leaves: %d VGPRs, %d bytes of scratch" % (res["vgpr"], res["scratch"]))
+    print("# stratified sweep | loop of ordinary stratified calls (what the scan runs without the opt-in): ms (us per point-iteration)")
+    loop = watson_engine()
+    g0 = [loop.grid(l).copy() for l in range(3)]
+    for neval in nevals:
+        kw = dict(neval=neval, niter=NITER, block=BLOCK, seed=SEED)
+        assert eng.sweep_strat_supported(**kw) is None and "3 variable leaves" in loop.sweep_strat_supported(**kw)
+        plan, geo = eng.sweep_strat_plan(neval, BLOCK), eng.sweep_strat_geometry(neval, BLOCK)
+        print("# neval = %d: plan nstrat = %s (%d hypercubes), chunk %d samples, %d bytes of LDS per workgroup -> %d workgroup(s) per CU"
+              % (neval, plan["nstrat"], plan["ncube"], geo["chunk"], geo["lds_bytes"], 2 if geo["lds_bytes"] <= 80 * 1024 else 1))
+        loop.integrate("vegas", **kw)                                                            # (compile, first launches)
+        for P in Ps:
+            uds = np.array([watson_point(k) for k in range(P)])
+            eng.integrate_sweep_strat("vegas", userdata=uds[:min(P, 4)], **kw)                   # (first launch)
+            ts, tsw = float("inf"), 0.0
+            for _ in range(3):
+                t0 = time.perf_counter()
+                rs = eng.integrate_sweep_strat("vegas", userdata=uds, **kw)
+                dt = time.perf_counter() - t0
+                ts, tsw = min(ts, dt), max(tsw, dt)
+            assert all(r["status"] == 0 for r in rs)
+            n = min(P, 16)       # (a loop is linear in P: up to 16 calls are timed, larger P scaled; ud stays point 0's, as in time_loop)
+            tl, tlw = float("inf"), 0.0
+            for _ in range(3):
+                t0 = time.perf_counter()
+                for k in range(n):
+                    for l in range(3):
+                        loop.set_grid(l, g0[l])
+                    q = loop.integrate("vegas", **kw)
+                dt = (time.perf_counter() - t0) * P / n
+                tl, tlw = min(tl, dt), max(tlw, dt)
+            same = abs(rs[0]["mean"][0] - q["mean"][0]) / abs(q["mean"][0])
+            print("neval %7d  P %4d  strat sweep %10.3f ms (%9.3f us; worst %10.3f)  strat loop %10.3f ms (%9.3f us; worst %10.3f)  loop / sweep %6.2f"
+                  "   grid x threads = %s   point 0: means differ by %.1e%s"
+                  % (neval, P, 1e3 * ts, 1e6 * ts / (P * NITER), 1e3 * tsw, 1e3 * tl, 1e6 * tl / (P * NITER), 1e3 * tlw, tl / ts, eng.last_sweep_launch(), same,
+                     "  (loop: %d calls timed, scaled)" % n if P > n else ""), flush=True)
+
+
 # ---- chains | mcmc: :vegasmc | :mcmc points (csrc/mci_sweep_chains.h)
 def mcmc_chain_steps(npb, nchain):
     """steps of one of the bubble's :mcmc chains in a block of npb evaluations: the measured ones and the burn-in (mci_mcmc_burnin: a tenth
@@ -354,7 +419,7 @@ def main():
     ap.add_argument("--points", default="1,16,256,1024,4096")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=1)
-    ap.add_argument("--layout", choices=["genz", "bubble"], default="genz")
+    ap.add_argument("--layout", choices=["genz", "bubble", "leaves"], default="genz")
     ap.add_argument("--carry", action="store_true", help="chains | mcmc: the sweep with carried chains against the uncarried one and a loop of carried calls")
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
@@ -364,6 +429,12 @@ def main():
     if a.mode in ("chains", "mcmc"):
         (carry_table if a.carry else chains_table)([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
                      [int(v) for v in a.chains.split(",")], solver="vegasmc" if a.mode == "chains" else "mcmc")
+        return
+    if a.layout == "leaves":
+        if a.mode != "strat":
+            ap.error("--layout leaves goes with the strat mode")
+        strat_leaves_table([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps,
+                           [10000, 100000] if a.nevals == "10000,100000,1000000" else [int(v) for v in a.nevals.split(",")])
         return
     if a.mode == "strat":
         strat_table([P for P in Ps if P <= 1024] if a.points == "1,16,256,1024,4096" else Ps, a.neval)
