@@ -41,6 +41,13 @@ class IntegrateArgs(C.Structure):
                 ("thermal_ratio", C.c_double), ("reweight_goal", c_double_p)]
 
 
+class DebugMergeIO(C.Structure):   # csrc/mci_debug.h mci_debug_merge_io
+    _fields_ = [("nblocks", C.c_int32), ("wg_per_block", C.c_int32), ("nrows", C.c_int32), ("hist_rows", C.c_int32), ("use_ghist", C.c_int32),
+                ("hist_no_offset", C.c_int32), ("path", C.c_int32), ("part_cols", c_double_p), ("part_hist", c_double_p), ("ghist", c_double_p),
+                ("part_pa", c_double_p), ("hold", C.POINTER(C.c_uint64)), ("obs", c_double_p), ("packed", c_double_p), ("stage1", c_double_p),
+                ("scratch", c_double_p), ("block_means", c_double_p), ("status", c_int32_p), ("part_cols_out", c_double_p), ("ghist_out", c_double_p)]
+
+
 HOST_INTEGRAND_FN = C.CFUNCTYPE(C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p)
 HOST_INTEGRAND_IDX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p)
 HOST_MEASURE_FN = C.CFUNCTYPE(C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, c_double_p, C.c_int32, C.c_void_p)
@@ -190,6 +197,8 @@ DEBUG_SIGNATURES = [
     ("mci_debug_sweep_lds_bytes", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("mci_debug_resample", C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p]),
     ("mci_debug_sweep_resample_lds", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("mci_debug_merge", C.c_int, [_VP, C.POINTER(DebugMergeIO)]),
+    ("mci_debug_merge_shape", C.c_int, [_VP, c_int32_p, c_int32_p]),
     ("mci_debug_sweep_strat_geometry", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_int32)]),
 ]

@@ -104,6 +104,42 @@ int mci_debug_sweep_strat_geometry(const mci_problem *prob, const mci_integrate_
  * Refused: nblocks, n_old or n_new < 1, nd outside 1 .. 64, blocks of 2^31 chains or more. */
 int mci_debug_resample(mci_problem *prob, int64_t nblocks, int64_t n_old, int64_t n_new, int32_t nd, const int32_t *curr_old,
                        const double *rw_now, const double *rw_used, const double *w_chain, int32_t *src, double *W);
+/* test hook: the merge kernels (mci_static_kernels.h k_add_host_obs, k_hist_stage1, k_finalize | k_finish; the device functions
+ * merge_stats, merge_hist_bin, merge_pa of mci_train.h) on their own over partial rows the caller made up, launched with the grids, thread
+ * counts and dynamic LDS the product launches them with (the same helpers give both).  The problem gives its device, its stream and its
+ * shape -- nobs, ni, ncols, nbin, npa, nstat and the leaf table, mci_debug_merge_shape -- and nothing else: every buffer the kernels read
+ * or write is the hook's own, the status word included; the problem's partial rows, `packed`, pending merge and status stay as they are.
+ * Every output is filled with 0xFF bytes before the launches: what the kernels leave unwritten comes back as NaN (status: its own word
+ * starts at 0).  Synchronises.
+ * Refused (MCI_ERR_INVALID): nblocks, wg_per_block or nrows < 1, nrows < nblocks * wg_per_block, neither or both of hist_rows and
+ * use_ghist, use_ghist > 64, a missing part_cols | part_hist | ghist | packed, products that do not fit an int, path other than 0 | 1;
+ * an offline context (MCI_ERR_NO_DEVICE). */
+typedef struct mci_debug_merge_io {
+    int32_t nblocks, wg_per_block; /* statistical blocks and partial rows per block: merge_stats reads rows [0, nblocks * wg_per_block) */
+    int32_t nrows;                 /* rows of part_cols and part_pa (merge_pa sums all of them) */
+    int32_t hist_rows;             /* rows of part_hist (k_hist_stage1 runs), or 0 */
+    int32_t use_ghist;             /* or: the number of global histogram buffers in `ghist` (no first stage) */
+    int32_t hist_no_offset;        /* MergeArgs::hist_no_offset */
+    int32_t path;                  /* 0: k_hist_stage1 -> k_finalize | 1: k_hist_stage1 -> k_finish (do_train = 0, no reweighting, no log row) */
+    const double *part_cols;       /* [nrows][ncols] */
+    const double *part_hist;       /* [hist_rows][nbin] */
+    const double *ghist;           /* [use_ghist][nbin] */
+    const double *part_pa;         /* [nrows][2 npa] or NULL (a :vegas pass) */
+    const unsigned long long *hold; /* [64] or NULL */
+    const double *obs;             /* [nblocks][nobs] or NULL: k_add_host_obs runs first, as behind a host measure */
+    /* out; NULL: not wanted (block_means = NULL: the kernels are not asked for them either) */
+    double *packed;                /* [mci_reduce_size] */
+    double *stage1;                /* [32][nbin] */
+    double *scratch;               /* [nblocks][ncols] */
+    double *block_means;           /* [nblocks][nobs] */
+    int32_t *status;               /* the hook's own ST_* word */
+    double *part_cols_out;         /* [nrows][ncols] as the kernels left them */
+    double *ghist_out;             /* [use_ghist + 1][nbin]: the buffers as left behind, then a guard row the hook filled with NaN */
+} mci_debug_merge_io;
+int mci_debug_merge(mci_problem *prob, const mci_debug_merge_io *io);
+/* shape[8] = nobs, ni, ncols, nbin, npa, nstat, leaves, bins of the largest leaf; leaves[nleaf][2] (or NULL) = offset into the histogram
+ * section, bins.  No device needed. */
+int mci_debug_merge_shape(const mci_problem *prob, int32_t *shape, int32_t *leaves);
 /* stored chains per block up to which a carried sweep point's resampler (mci_sweep_chains.h) keeps the running weights in LDS: the
  * map_off - kResampleThreads the carried sweep units are handed (beyond: its bisections read them in global memory); no device needed */
 int mci_debug_sweep_resample_lds(const mci_problem *prob, int64_t *lds_w);

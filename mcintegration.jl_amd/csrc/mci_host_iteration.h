@@ -483,11 +483,10 @@ static int queue_merge(mci_problem *p, const LaunchRequest &rq, const LaunchPlan
     const auto &s = p->shape;
     hipStream_t st = p->ctx->stream;
     int rc;
-    const int nb256 = (s.nbin + 255) / 256;
     // (reading a few partial rows directly in the second stage instead -- no first-stage launch when an iteration is launch-bound --
     // was measured at neval = 1e4: k_finish grows by what the launch took, 26 us per iteration either way)
     if (pl.hist_lds && s.nbin > 0 && !pl.atomic_flush)
-        hipLaunchKernelGGL(mci::k_hist_stage1, dim3(nb256, mci_problem::kGroups), dim3(256), 0, st, p->d_part_hist, (int)pl.hist_rows, s.nbin,
+        hipLaunchKernelGGL(mci::k_hist_stage1, hist_stage1_grid(s.nbin), dim3(256), 0, st, p->d_part_hist, (int)pl.hist_rows, s.nbin,
                            (int)mci_problem::kGroups, p->d_stage1);
     HIPCHK(hipGetLastError());
     mci::MergeArgs &m = p->merge;
@@ -677,8 +676,7 @@ static int flush_merge(mci_problem *p) {
     if (!p->merge_pending) return MCI_OK;
     p->merge_pending = false;
     HIPCHK(hipSetDevice(p->ctx->device));
-    const int nb256 = (p->shape.nbin + 255) / 256;
-    hipLaunchKernelGGL(mci::k_finalize, dim3(nb256 + 1 + (2 * p->npa + 3) / 4), dim3(256), 0, p->ctx->stream, p->merge);
+    hipLaunchKernelGGL(mci::k_finalize, finalize_grid(p->shape.nbin, p->npa), dim3(256), 0, p->ctx->stream, p->merge);
     HIPCHK(hipGetLastError());
     return MCI_OK;
 }
@@ -757,8 +755,7 @@ int mci_comm_times_ms(mci_problem *p, float *ms, int32_t n, int32_t *got) {
 
 static int launch_train(mci_problem *p, int do_train, int do_reweight, double gamma, double *log_row) {
     const auto &s = p->shape;
-    int maxn = 1;
-    for (auto &L : p->leaves) maxn = L.nbin > maxn ? L.nbin : maxn;
+    const int maxn = max_leaf_bins(p);
     mci::TrainArgs a{};
     fill_train(p, a);
     a.iter_log_row = log_row;
@@ -770,13 +767,8 @@ static int launch_train(mci_problem *p, int do_train, int do_reweight, double ga
     a.serial_walk = p->train_serial >= 0 ? p->train_serial : (p->launch.last_samples == 0 || p->launch.last_samples >= mci_problem::kSerialWalkSamples) ? 1 : 0;
     if (p->debug_wrong_decision && a.serial_walk == 1) a.serial_walk = 3;
     a.maxn = maxn;
-    // d | sg | wa (train_leaf) | the serial walk's slots and their record, where they fit (grids of up to ~2700 increments), else k_finish's merged histogram alone
-    a.spare = (size_t)(mci::train_lds_doubles(maxn) + mci::train_spare_doubles(maxn)) * sizeof(double) <= (size_t)kTrainLdsMax ? 1 : 0;
-    const size_t sm = (size_t)(mci::train_lds_doubles(maxn) + (a.spare ? mci::train_spare_doubles(maxn) : maxn)) * sizeof(double);
-    // two bins per thread for the default 999-bin grids: the rescale (a pow and a log per bin) and the second merge stage are the
-    // latency chains of a lone workgroup; with four bins per thread (256 threads) a launch-bound iteration took 24.7 us, with two
-    // 22.2, with one (1024 threads) 22.3 (tools/latency.py, neval = 1e4)
-    const unsigned tt = maxn > 256 ? 512u : 256u;
+    const size_t sm = train_lds_bytes(maxn, &a.spare);
+    const unsigned tt = train_threads(maxn);
     if (sm > 64 * 1024 && !p->train_lds_raised) { // grids of more than ~1600 increments
         HIPCHK(hipFuncSetAttribute((const void *)mci::k_train, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsMax));
         HIPCHK(hipFuncSetAttribute((const void *)mci::k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsMax));
@@ -784,11 +776,135 @@ static int launch_train(mci_problem *p, int do_train, int do_reweight, double ga
     }
     if (p->merge_pending) { // nothing looked at `packed` since the sample batch: merge + refine in one launch
         p->merge_pending = false;
-        hipLaunchKernelGGL(mci::k_finish, dim3(s.nleaf + 1 + (2 * p->npa + 3) / 4), dim3(tt), sm, p->ctx->stream, p->merge, a);
+        hipLaunchKernelGGL(mci::k_finish, finish_grid(s.nleaf, p->npa), dim3(tt), sm, p->ctx->stream, p->merge, a);
     } else {
         hipLaunchKernelGGL(mci::k_train, dim3(s.nleaf + 1), dim3(tt), sm, p->ctx->stream, a);
     }
     HIPCHK(hipGetLastError());
+    return MCI_OK;
+}
+
+// csrc/mci_debug.h: the problem's shape as the merge sees it
+int mci_debug_merge_shape(const mci_problem *p, int32_t *shape, int32_t *leaves) {
+    if (!p || !shape) return fail(MCI_ERR_INVALID, "NULL argument");
+    const auto &s = p->shape;
+    const int32_t v[8] = {s.nobs, s.ni, s.ncols, s.nbin, p->npa, p->nstat, s.nleaf, max_leaf_bins(p)};
+    memcpy(shape, v, sizeof v);
+    if (leaves)
+        for (size_t l = 0; l < p->leaves.size(); ++l) {
+            leaves[2 * l] = p->leaves[l].boff;
+            leaves[2 * l + 1] = p->leaves[l].nbin;
+        }
+    return MCI_OK;
+}
+
+// csrc/mci_debug.h: the merge kernels alone, over rows the caller made up, launched as queue_merge / finish_host_measure, flush_merge and
+// launch_train launch them; buffers of its own, nothing of the problem's but the device, the stream, the shape and the leaf table
+int mci_debug_merge(mci_problem *p, const mci_debug_merge_io *io) {
+    if (!p || !io || !io->part_cols || !io->packed) return fail(MCI_ERR_INVALID, "NULL argument");
+    const auto &s = p->shape;
+    const int64_t nblocks = io->nblocks, wpb = io->wg_per_block, nrows = io->nrows, hrows = io->hist_rows, k = io->use_ghist;
+    if (nblocks < 1 || wpb < 1 || nrows < 1) return fail(MCI_ERR_INVALID, "merge: %lld blocks of %lld rows in %lld rows (each >= 1)", (long long)nblocks, (long long)wpb, (long long)nrows);
+    if (hrows < 0 || k < 0 || k > 64) return fail(MCI_ERR_INVALID, "merge: %lld histogram rows, %lld global histogram buffers (0 .. 64)", (long long)hrows, (long long)k);
+    if (hrows > 0 && k > 0) return fail(MCI_ERR_INVALID, "merge: hist_rows and use_ghist exclude each other");
+    if (hrows == 0 && k == 0) return fail(MCI_ERR_INVALID, "merge: one of hist_rows and use_ghist must be given");
+    if ((hrows > 0 && !io->part_hist) || (k > 0 && !io->ghist)) return fail(MCI_ERR_INVALID, "merge: the histogram rows are missing");
+    if (io->path != 0 && io->path != 1) return fail(MCI_ERR_INVALID, "merge: path %d (0: k_finalize, 1: k_finish)", (int)io->path);
+    const int64_t nbin1 = s.nbin ? s.nbin : 1, wide = std::max<int64_t>(std::max<int64_t>(s.ncols, 2 * (int64_t)p->npa), 1);
+    if (nblocks > INT32_MAX / wpb || nrows > INT32_MAX / wide || nblocks > INT32_MAX / wide || hrows > INT32_MAX / nbin1 || (k + 1) > INT32_MAX / nbin1)
+        return fail(MCI_ERR_INVALID, "merge: %lld blocks, %lld rows and %lld histogram rows are more than a test hook takes", (long long)nblocks, (long long)nrows, (long long)hrows);
+    if (nrows < nblocks * wpb) return fail(MCI_ERR_INVALID, "merge: %lld rows for %lld blocks of %lld", (long long)nrows, (long long)nblocks, (long long)wpb);
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    const size_t ncell = (size_t)nrows * s.ncols, nhist = (size_t)hrows * s.nbin, ngh = (size_t)(k + 1) * nbin1, npart = (size_t)nrows * 2 * p->npa;
+    const size_t npacked = (size_t)p->packed_n + 64, nst1 = (size_t)mci_problem::kGroups * nbin1, nscr = (size_t)nblocks * s.ncols, nbm = (size_t)nblocks * s.nobs;
+    DevBuf<double> d_cols, d_hist, d_gh, d_pa, d_obs, d_packed, d_st1, d_scr, d_bm;
+    DevBuf<unsigned long long> d_hold;
+    DevBuf<int> d_stat;
+    int rc;
+    if ((rc = d_cols.reserve((int64_t)ncell)) || (rc = d_packed.reserve((int64_t)npacked)) || (rc = d_st1.reserve((int64_t)nst1)) || (rc = d_scr.reserve((int64_t)nscr)) ||
+        (rc = d_bm.reserve((int64_t)(nbm ? nbm : 1))) || (rc = d_gh.reserve((int64_t)ngh)) || (rc = d_stat.reserve(4)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(d_cols, io->part_cols, ncell * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_packed, 0xFF, npacked * sizeof(double), st)); // (what the kernels do not write comes back as NaN)
+    HIPCHK(hipMemsetAsync(d_st1, 0xFF, nst1 * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(d_scr, 0xFF, nscr * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(d_bm, 0xFF, (nbm ? nbm : 1) * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(d_gh, 0xFF, ngh * sizeof(double), st)); // (the guard row behind the k buffers stays like this)
+    HIPCHK(hipMemsetAsync(d_stat, 0, 4 * sizeof(int), st));
+    if (k > 0) HIPCHK(hipMemcpyAsync(d_gh, io->ghist, (size_t)k * s.nbin * sizeof(double), hipMemcpyHostToDevice, st));
+    if (hrows > 0) {
+        if ((rc = d_hist.reserve((int64_t)(nhist ? nhist : 1)))) return rc;
+        HIPCHK(hipMemcpyAsync(d_hist, io->part_hist, nhist * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (io->part_pa) {
+        if ((rc = d_pa.reserve((int64_t)npart))) return rc;
+        HIPCHK(hipMemcpyAsync(d_pa, io->part_pa, npart * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (io->hold) {
+        if ((rc = d_hold.reserve(64))) return rc;
+        HIPCHK(hipMemcpyAsync(d_hold, io->hold, 64 * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    }
+    if (io->obs && nbm) {
+        if ((rc = d_obs.reserve((int64_t)nbm))) return rc;
+        HIPCHK(hipMemcpyAsync(d_obs, io->obs, nbm * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st)); // (the uploads have read the caller's pageable memory)
+    if (io->obs && nbm) { // finish_host_measure
+        hipLaunchKernelGGL(mci::k_add_host_obs, dim3((unsigned)((nblocks * s.nobs + 255) / 256)), dim3(256), 0, st, d_obs, (int)nblocks, s.nobs, s.ncols, (int)wpb, d_cols);
+        HIPCHK(hipGetLastError());
+    }
+    if (hrows > 0 && s.nbin > 0) { // queue_merge
+        hipLaunchKernelGGL(mci::k_hist_stage1, hist_stage1_grid(s.nbin), dim3(256), 0, st, d_hist, (int)hrows, s.nbin, (int)mci_problem::kGroups, d_st1);
+        HIPCHK(hipGetLastError());
+    }
+    mci::MergeArgs m{};
+    m.part_cols = d_cols;
+    m.ncols = s.ncols;
+    m.nobs = s.nobs;
+    m.ni = s.ni;
+    m.nblocks = (int)nblocks;
+    m.wg_per_block = (int)wpb;
+    m.stage1 = d_st1;
+    m.ngroup = (int)mci_problem::kGroups;
+    m.ghist = d_gh;
+    m.use_ghist = (int)k;
+    m.nbin = s.nbin;
+    m.packed = d_packed;
+    m.status = d_stat;
+    m.scratch = d_scr;
+    m.part_pa = io->part_pa ? d_pa.get() : nullptr;
+    m.npa = p->npa;
+    m.nrows = (int)nrows;
+    m.block_means = io->block_means ? d_bm.get() : nullptr;
+    m.hold = io->hold ? d_hold.get() : nullptr;
+    m.hist_no_offset = io->hist_no_offset ? 1 : 0;
+    if (io->path == 0) { // flush_merge
+        hipLaunchKernelGGL(mci::k_finalize, finalize_grid(s.nbin, p->npa), dim3(256), 0, st, m);
+    } else { // launch_train with a pending merge, told to do nothing but merge
+        const int maxn = max_leaf_bins(p);
+        mci::TrainArgs a{};
+        a.leaves = p->d_leaves;
+        a.nleaf = s.nleaf;
+        a.packed = d_packed;
+        a.nstat = p->nstat;
+        a.nd = s.ni + 1;
+        a.status = d_stat;
+        a.maxn = maxn;
+        const size_t sm = train_lds_bytes(maxn, &a.spare);
+        if (sm > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)mci::k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsMax));
+        hipLaunchKernelGGL(mci::k_finish, finish_grid(s.nleaf, p->npa), dim3(train_threads(maxn)), sm, st, m, a);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(io->packed, d_packed, npacked * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (io->stage1) HIPCHK(hipMemcpyAsync(io->stage1, d_st1, (size_t)mci_problem::kGroups * s.nbin * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (io->scratch) HIPCHK(hipMemcpyAsync(io->scratch, d_scr, nscr * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (io->block_means && nbm) HIPCHK(hipMemcpyAsync(io->block_means, d_bm, nbm * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (io->status) HIPCHK(hipMemcpyAsync(io->status, d_stat, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (io->part_cols_out) HIPCHK(hipMemcpyAsync(io->part_cols_out, d_cols, ncell * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (io->ghist_out) HIPCHK(hipMemcpyAsync(io->ghist_out, d_gh, (size_t)(k + 1) * s.nbin * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st)); // (the buffers are freed behind it)
     return MCI_OK;
 }
 

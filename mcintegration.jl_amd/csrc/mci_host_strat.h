@@ -496,9 +496,8 @@ static int strat_run(mci_problem *p, int64_t nevalperblock, int64_t block_lo, in
         st.hn = 0;
     }
     // merge: the nwg rows as mblocks blocks (the statistics head is replaced by the stratified estimate in strat_finish)
-    const int nb256 = (s.nbin + 255) / 256;
     if (s.nbin > 0)
-        hipLaunchKernelGGL(mci::k_hist_stage1, dim3(nb256, mci_problem::kGroups), dim3(256), 0, p->ctx->stream, p->d_part_hist, (int)nwg, s.nbin,
+        hipLaunchKernelGGL(mci::k_hist_stage1, hist_stage1_grid(s.nbin), dim3(256), 0, p->ctx->stream, p->d_part_hist, (int)nwg, s.nbin,
                            (int)mci_problem::kGroups, p->d_stage1);
     HIPCHK(hipGetLastError());
     p->merge = merge_args(p, mblocks, (int)(nwg / mblocks), nwg);

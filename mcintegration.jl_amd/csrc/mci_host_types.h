@@ -620,6 +620,26 @@ mci::MergeArgs merge_args(const mci_problem *p, int64_t nblocks, int wpb, int64_
     m.nrows = (int)nrows;
     return m;
 }
+// The launch geometry of the merge kernels (mci_static_kernels.h), in ONE place: the product's launches (queue_merge, strat_run,
+// flush_merge, launch_train) and the test hook mci_debug_merge both ask here, so that the hook runs the kernels as the product does.
+dim3 hist_stage1_grid(int nbin) { return dim3((unsigned)((nbin + 255) / 256), (unsigned)mci_problem::kGroups); }
+dim3 finalize_grid(int nbin, int npa) { return dim3((unsigned)((nbin + 255) / 256 + 1 + (2 * npa + 3) / 4)); } // histogram | statistics | merge_pa
+dim3 finish_grid(int nleaf, int npa) { return dim3((unsigned)(nleaf + 1 + (2 * npa + 3) / 4)); }               // leaves | statistics | merge_pa
+// two bins per thread for the default 999-bin grids: the rescale (a pow and a log per bin) and the second merge stage are the
+// latency chains of a lone workgroup; with four bins per thread (256 threads) a launch-bound iteration took 24.7 us, with two
+// 22.2, with one (1024 threads) 22.3 (tools/latency.py, neval = 1e4)
+unsigned train_threads(int maxn) { return maxn > 256 ? 512u : 256u; }
+// dynamic LDS of k_train | k_finish for a largest leaf of maxn bins: d | sg | wa (train_leaf) | the serial walk's slots and their record,
+// where they fit (grids of up to ~2700 increments; *spare = 1), else k_finish's merged histogram alone
+size_t train_lds_bytes(int maxn, int *spare) {
+    *spare = (size_t)(mci::train_lds_doubles(maxn) + mci::train_spare_doubles(maxn)) * sizeof(double) <= (size_t)kTrainLdsMax ? 1 : 0;
+    return (size_t)(mci::train_lds_doubles(maxn) + (*spare ? mci::train_spare_doubles(maxn) : maxn)) * sizeof(double);
+}
+int max_leaf_bins(const mci_problem *p) {
+    int maxn = 1;
+    for (auto &L : p->leaves) maxn = L.nbin > maxn ? L.nbin : maxn;
+    return maxn;
+}
 // the problem-wide part of train!'s arguments (what to do, the walk, the log row and the LDS plan are the caller's)
 void fill_train(const mci_problem *p, mci::TrainArgs &t) {
     fill_tables(p, t);

@@ -562,6 +562,54 @@ class Engine:
                                        None if wc is None else _dp(wc), src.ctypes.data_as(c_int32_p), _dp(W)))
         return src, W
 
+    def merge_shape(self):
+        """the problem's shape as the merge kernels see it (csrc/mci_debug.h mci_debug_merge_shape; no device needed): a dict of nobs, ni,
+        ncols, nbin, npa, nstat, maxn (bins of the largest leaf) and leaves [(offset into the histogram section, bins)]"""
+        sh = np.zeros(8, dtype=np.int32)
+        check(lib().mci_debug_merge_shape(self.p, sh.ctypes.data_as(c_int32_p), None))
+        lv = np.zeros((int(sh[6]), 2), dtype=np.int32)
+        check(lib().mci_debug_merge_shape(self.p, sh.ctypes.data_as(c_int32_p), lv.ctypes.data_as(c_int32_p)))
+        out = dict(zip(("nobs", "ni", "ncols", "nbin", "npa", "nstat"), (int(v) for v in sh[:6])))
+        out["maxn"], out["leaves"] = int(sh[7]), [(int(a), int(b)) for a, b in lv]
+        return out
+
+    def merge_rows(self, nblocks, wg_per_block, part_cols, part_hist=None, ghist=None, part_pa=None, hold=None, obs=None, hist_no_offset=False,
+                   block_means=True, path="finalize"):
+        """test hook (csrc/mci_debug.h mci_debug_merge): the merge kernels on their own over rows the caller made up -- part_cols [nrows,
+        ncols], part_hist [hist_rows, nbin] (through k_hist_stage1) or ghist [k, nbin] (use_ghist = k), part_pa [nrows, 2 npa], hold [64]
+        (uint64), obs [nblocks, nobs] (k_add_host_obs runs first); path "finalize" (k_finalize) | "finish" (k_finish, told to merge only).
+        -> dict of packed [reduce_size], stage1 [32, nbin], scratch [nblocks, ncols], block_means [nblocks, nobs] (None if not wanted),
+        status, part_cols [nrows, ncols] and ghist [k + 1, nbin] (the last row: the hook's NaN guard) as left behind.  This engine gives its
+        device and its shape only; nothing of its own state is read or written"""
+        sh = self.merge_shape()
+        pc = np.ascontiguousarray(part_cols, dtype=np.float64)
+        ph = None if part_hist is None else np.ascontiguousarray(part_hist, dtype=np.float64)
+        gh = None if ghist is None else np.ascontiguousarray(ghist, dtype=np.float64)
+        pa = None if part_pa is None else np.ascontiguousarray(part_pa, dtype=np.float64)
+        hd = None if hold is None else np.ascontiguousarray(hold, dtype=np.uint64)
+        ob = None if obs is None else np.ascontiguousarray(obs, dtype=np.float64)
+        nblocks, wg_per_block = int(nblocks), int(wg_per_block)
+        if (pc.ndim != 2 or pc.shape[1] != sh["ncols"] or (ph is not None and (ph.ndim != 2 or ph.shape[1] != sh["nbin"]))
+                or (gh is not None and (gh.ndim != 2 or gh.shape[1] != sh["nbin"])) or (pa is not None and pa.shape != (pc.shape[0], 2 * sh["npa"]))
+                or (hd is not None and hd.shape != (64,)) or (ob is not None and ob.shape != (nblocks, sh["nobs"])) or path not in ("finalize", "finish")):
+            raise ValueError("part_cols [nrows, ncols], part_hist [hist_rows, nbin], ghist [k, nbin], part_pa [nrows, 2 npa], hold [64], "
+                             "obs [nblocks, nobs], path 'finalize' or 'finish'")
+        nrows, k = pc.shape[0], 0 if gh is None else gh.shape[0]
+        nb = max(min(nblocks, nrows), 0)   # (more blocks than rows: refused before anything is written)
+        out = dict(packed=np.full(self.reduce_size, np.nan), stage1=np.full((32, sh["nbin"]), np.nan), scratch=np.full((nb, sh["ncols"]), np.nan),
+                   block_means=np.full((nb, sh["nobs"]), np.nan) if block_means else None, part_cols=np.full(pc.shape, np.nan),
+                   ghist=np.full((k + 1, sh["nbin"]), np.nan))
+        status = C.c_int32(-1)
+        io = _lib.DebugMergeIO(nblocks, wg_per_block, nrows, 0 if ph is None else ph.shape[0], k, 1 if hist_no_offset else 0,
+                               0 if path == "finalize" else 1, _dp(pc), None if ph is None else _dp(ph), None if gh is None else _dp(gh),
+                               None if pa is None else _dp(pa), None if hd is None else hd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                               None if ob is None else _dp(ob), _dp(out["packed"]), _dp(out["stage1"]), _dp(out["scratch"]),
+                               None if out["block_means"] is None else _dp(out["block_means"]), C.pointer(status), _dp(out["part_cols"]),
+                               _dp(out["ghist"]))
+        check(lib().mci_debug_merge(self.p, C.byref(io)))
+        out["status"] = int(status.value)
+        return out
+
     def sweep_resample_lds(self):
         """stored chains per block up to which a carried sweep point's resampler keeps its running weights in LDS (csrc/mci_debug.h
         mci_debug_sweep_resample_lds)"""
