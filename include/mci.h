@@ -59,6 +59,9 @@ enum { MCI_VEGAS_BIG = 15 };
 /* ... and the sweep kernel for stratified points of problems with several Continuous variable leaves (mci_integrate_sweep_strat on a
  * problem that opted in with mci_set_sweep_strat_leaves and is no one-grid layout) */
 enum { MCI_VEGAS_SWEEP_STRAT_LEAVES = 16 };
+/* ... and the two sweep kernels of mci_integrate_sweep with a target error per point (mci_integrate_sweep_until): the one-grid kernel
+ * and the one for several variable leaves, code objects of their own */
+enum { MCI_VEGAS_SWEEP_UNTIL = 17, MCI_VEGAS_SWEEP_LEAVES_UNTIL = 18 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes; mci_set_sweep_strat_leaves: which ones mci_integrate_sweep_strat takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -283,6 +286,41 @@ int mci_integrate_sweep(mci_problem *prob, const mci_integrate_args *args, int32
  * 64 KiB of LDS with the workgroup's copy of the map.  The number of draws per sample is no reason.  (The chain solvers have entry
  * points of their own: mci_integrate_sweep_chains runs :vegasmc points, mci_integrate_sweep_mcmc runs :mcmc points.) */
 int mci_sweep_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* The target of mci_integrate_sweep_until: a point stops once every statistics column has E <= max(atol, rtol |M|), from iteration
+ * max(ignore + 2, min_niter) on.  rtol = atol = 0 never stops a point early. */
+typedef struct {
+    double rtol, atol;  /* >= 0 and finite */
+    int32_t min_niter;  /* >= 0 */
+} mci_sweep_target;
+/* mci_integrate_sweep with a target error: every point runs its loop until it has converged, at most args->niter iterations, still in ONE
+ * launch.  After iteration n (1-based) of a point, per statistics column o and with `ignore` as mci_integrate resolves it (< 0: 1 with
+ * adapt, else 0): (m_i, s_i) = mci_mean_std of log row i (main.jl:297-317), w_i = 1 / (s_i + 1e-10)^2, W = sum of w_i over
+ * i = ignore + 1 .. n, M = sum w_i m_i / W, E = 1 / sqrt(W) -- mci_average, statistics.jl:186-204.  The point has converged at n when
+ * n >= max(ignore + 2, min_niter) and E <= max(atol, rtol |M|) for every one of the nobs columns.  ignore + 2: with fewer than two
+ * averaged iterations mci_average returns iteration 1 (statistics.jl:189-191), which is no error estimate of the average.  A column
+ * whose E or M is NaN or infinite never converges: such a point runs all niter iterations.  A converged point runs the train! of
+ * iteration n as usual and leaves its loop; its workgroup takes the next point nobody has begun.  n_p = that n, or niter.
+ * Point p's results are what mci_integrate_sweep returns for it when called with niter = n_p and nothing else changed: iter_mean /
+ * iter_std rows 0 .. n_p - 1 (the rows from n_p on are zero), mean, stdev and chi2 over those rows, neval of n_p iterations, visited of
+ * row n_p - 1, its maps_out row, its status word.  results[p].niter stays the caller's capacity (>= args->niter).  Which workgroup ran a
+ * point never shows in its results.
+ *   target     see mci_sweep_target
+ *   niter_run  NULL or [npoint]: n_p
+ * Everything else is mci_integrate_sweep's.  Such calls run kernels of their own (MCI_VEGAS_SWEEP_UNTIL, MCI_VEGAS_SWEEP_LEAVES_UNTIL)
+ * and take, per point, 2 nobs doubles and one word more of the 4 GiB.  These kernels keep one histogram and one observable copy per wave
+ * of the workgroup, summed in a fixed order (the layout of mci_set_deterministic), so a point's results are the same bytes whichever
+ * workgroup runs it, whatever ran before it, from call to call; mci_integrate_sweep's own differ in their last bits between two calls
+ * when adapt is on.  The stratified, :vegasmc and :mcmc sweeps have no such form. */
+int mci_integrate_sweep_until(mci_problem *prob, const mci_integrate_args *args, const mci_sweep_target *target, int32_t npoint,
+                              const double *userdata, const uint64_t *seeds, const double *maps_in, double *maps_out, mci_result *results,
+                              double *iter_mean, double *iter_std, int32_t *status, int32_t *niter_run);
+/* MCI_OK when mci_integrate_sweep_until takes this problem with these arguments and this target; else MCI_ERR_INVALID with the reason in
+ * why[n] (and in mci_last_error): whatever mci_sweep_supported refuses, with that reason; a NULL target; an rtol or atol that is negative
+ * or not finite (a NaN or infinite bound would stop nothing, or everything: the rule treats a non-finite COLUMN as never converged, a
+ * non-finite target is an error); min_niter < 0; a layout whose sample tables with one histogram copy per wave, refinement scratch and map
+ * take more than 64 KiB of LDS (one Continuous leaf) or 159 KiB (several leaves), with the byte count.  rtol = atol = 0 is legal and
+ * never stops a point early. */
+int mci_sweep_until_supported(const mci_problem *prob, const mci_integrate_args *args, const mci_sweep_target *target, char *why, int32_t n);
 /* Which problems run as a sweep.  MCI_SWEEP_ONE_GRID (default): one Continuous leaf, as described above.  MCI_SWEEP_ALL_LEAVES: also
  * any :vegas problem whose leaves are all Continuous or Discrete (FermiK: "vegas doesn't work with FermiK"), with the tables and the
  * histograms in LDS in one tile and at most 159 KiB of LDS for the sample tables or the refinement scratch of the largest leaf plus the

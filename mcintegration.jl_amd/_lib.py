@@ -55,6 +55,10 @@ HOST_MEASURE_IDX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int32), c_double_p, c_d
                                   C.c_int32, C.c_void_p)
 
 
+class SweepTarget(C.Structure):   # include/mci.h mci_sweep_target
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("min_niter", C.c_int32)]
+
+
 class ResultC(C.Structure):
     _fields_ = [("niter", C.c_int32), ("nobs", C.c_int32), ("iter_mean", c_double_p), ("iter_std", c_double_p),
                 ("mean", c_double_p), ("stdev", c_double_p), ("chi2", c_double_p), ("neval", C.c_int64),
@@ -96,6 +100,9 @@ SIGNATURES = [
     ("mci_integrate_sweep", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
                                       C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_sweep_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
+    ("mci_integrate_sweep_until", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p,
+                                            c_double_p, C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p, c_int32_p]),
+    ("mci_sweep_until_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.c_char_p, C.c_int32]),
     ("mci_set_sweep_leaves", C.c_int, [_VP, C.c_int32]),
     ("mci_set_sweep_chain_carry", C.c_int, [_VP, C.c_int32]),
     ("mci_set_sweep_strat_leaves", C.c_int, [_VP, C.c_int32]),

@@ -7,9 +7,9 @@ namespace {
 // LDS of the persistent kernel (bytes): the sample loop's carve (plain layout) or the refinement's (scratch, merged histogram, scan
 // scratch), whichever is larger -- each is dead while the other runs --, and behind them (map_off, doubles) the workgroup's own copy of
 // the map and the flag words (mci_train.h PersistArgs)
-int64_t persist_lds(const mci_problem *p, int *map_off) {
+int64_t persist_lds(const mci_problem *p, int *map_off, int64_t more_carve = 0) { // more_carve: doubles a unit's sample carve takes beyond the plain one (sweep_until_carve)
     const int N = p->leaves.empty() ? 1 : p->leaves[0].nbin;
-    const int64_t a = (p->lds_bytes + 7) / 8, b = (int64_t)mci::train_lds_doubles(N) + N + 256;
+    const int64_t a = (p->lds_bytes + 7) / 8 + more_carve, b = (int64_t)mci::train_lds_doubles(N) + N + 256;
     const int64_t off = ((a > b ? a : b) + 1) & ~(int64_t)1;
     if (map_off) *map_off = (int)off;
     return (off + (N + 2) + 4) * 8;

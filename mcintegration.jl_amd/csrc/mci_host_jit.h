@@ -722,11 +722,13 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
             if (w == mci_problem::Sweep::kStratLeaves && !sweep_strat_leaves_unit(p))
                 return fail(MCI_ERR_INVALID, "a stratified sweep of this problem runs the one-grid stratified sweep kernel (MCI_VEGAS_SWEEP_STRAT; mci_set_sweep_strat_leaves)");
         } else {
-            if (int rc = mci_sweep_supported(p, &a, nullptr, 0)) return rc;
+            const bool until = w == mci_problem::Sweep::kUntil || w == mci_problem::Sweep::kLeavesUntil;
+            const mci_sweep_target any{0.0, 0.0, 0}; // (the `until` units: their own query, for the LDS their histogram copies take)
+            if (int rc = until ? mci_sweep_until_supported(p, &a, &any, nullptr, 0) : mci_sweep_supported(p, &a, nullptr, 0)) return rc;
             // (which of the two a sweep of this problem runs: whether it has opted in, mci_set_sweep_leaves, and is no one-grid layout)
-            if (w == mci_problem::Sweep::kOne && sweep_leaves_unit(p))
+            if ((w == mci_problem::Sweep::kOne || w == mci_problem::Sweep::kUntil) && sweep_leaves_unit(p))
                 return fail(MCI_ERR_INVALID, "a sweep of this problem runs the sweep kernel for several leaves (MCI_VEGAS_SWEEP_LEAVES; mci_set_sweep_leaves)");
-            if (w == mci_problem::Sweep::kLeaves && !sweep_leaves_unit(p))
+            if ((w == mci_problem::Sweep::kLeaves || w == mci_problem::Sweep::kLeavesUntil) && !sweep_leaves_unit(p))
                 return fail(MCI_ERR_INVALID, "a sweep of this problem runs the one-grid sweep kernel (MCI_VEGAS_SWEEP; mci_set_sweep_leaves)");
         }
         return compile_sweep_unit(p, w);

@@ -22,11 +22,11 @@ int sweep_max_nbin(const mci_problem *p) {
     for (const Leaf &L : p->leaves) n = L.nbin > n ? L.nbin : n;
     return n;
 }
-int64_t sweep_leaves_lds(const mci_problem *p, int *map_off) {
+int64_t sweep_leaves_lds(const mci_problem *p, int *map_off, int64_t more_carve = 0) { // more_carve: sweep_until_carve
     const auto &s = p->shape;
     const int maxn = sweep_max_nbin(p);
     const int64_t plain = (int64_t)s.ndacc + s.nddist + s.nobs + 16 * (int64_t)s.ncols + 2 * (int64_t)p->npa + s.nedge + s.nbin;
-    const int64_t a = s.table_mode == 0 && s.ntile == 1 && s.ec_doubles == 0 ? (p->lds_bytes + 7) / 8 : plain;
+    const int64_t a = (s.table_mode == 0 && s.ntile == 1 && s.ec_doubles == 0 ? (p->lds_bytes + 7) / 8 : plain) + more_carve;
     const int64_t b = (int64_t)mci::train_lds_doubles(maxn) + maxn + 256;
     const int64_t off = ((a > b ? a : b) + 1) & ~(int64_t)1;
     if (map_off) *map_off = (int)off;
@@ -149,6 +149,23 @@ void sweep_release(mci_ctx *c, void *base, size_t bytes) {
 // Workgroup size of the sweep kernel.  Measured on the 4-D Genz product peak at niter = 10, block = 16 (tools/sweep_bench.py,
 // profiles/r10_sweep.txt); csrc/mci_debug.h mci_debug_sweep_threads forces another one.
 const int kSweepThreads = 256;
+// The `until` units (mci_integrate_sweep_until) are compiled in the deterministic histogram layout (mci_device.h hslot, Cfg::DET): every
+// wave of the workgroup adds to a histogram and an observable copy of its own, and the copies are summed in a fixed order -- a point's
+// histogram, hence its map and every later iteration, does not depend on how the waves were scheduled, so its results are the same bytes
+// whichever workgroup runs it and whatever ran before.  What that takes of LDS beyond the plain carve, doubles (det_lds's count):
+int64_t sweep_until_carve(const mci_problem *p) { return ((int64_t)p->shape.htile + p->shape.nobs) * (kSweepThreads / 64 - 1); }
+int64_t sweep_until_lds(const mci_problem *p, int *map_off) {
+    return sweep_uses_leaves(p) ? sweep_leaves_lds(p, map_off, sweep_until_carve(p)) : persist_lds(p, map_off, sweep_until_carve(p));
+}
+// ... and what it refuses beyond sweep_refusal: the one-grid unit keeps within the 64 KiB every workgroup may ask for, the unit for several
+// leaves within kSweepLeavesMaxLds
+const char *sweep_until_lds_refusal(const mci_problem *p, std::string &buf) {
+    const int64_t lds = sweep_until_lds(p, nullptr), most = sweep_uses_leaves(p) ? kSweepLeavesMaxLds : 64 * 1024;
+    if (lds <= most) return nullptr;
+    buf = "the sample tables with one histogram copy per wave (a point's results must not depend on the waves' schedule), the refinement scratch and the point's map take " +
+          std::to_string((long long)lds) + " bytes of LDS (" + std::to_string((long long)most) + " at most)";
+    return buf.c_str();
+}
 } // namespace
 
 static bool sweep_leaves_unit(const mci_problem *p) { return sweep_uses_leaves(p); }
@@ -163,8 +180,9 @@ static int compile_sweep_unit(mci_problem *p, int which) {
     u.drop();
     Candidate c;
     mcijit::ProblemShape sh = p->shape;
-    sh.hcopy = 1;
-    sh.det = 0;
+    const bool until = which == mci_problem::Sweep::kUntil || which == mci_problem::Sweep::kLeavesUntil;
+    sh.hcopy = until ? T / 64 : 1; // (the `until` units: one histogram and observable copy per wave, sweep_until_carve)
+    sh.det = until ? 1 : 0;
     c.unit = k.jit_unit;
     c.src = mcijit::generate_source(sh, k.runs, k.jit_unit, k.alpha ? p->leaves[0].alpha : 0.0);
     c.threads = T;
@@ -174,8 +192,8 @@ static int compile_sweep_unit(mci_problem *p, int which) {
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
     // (the several-leaves and the chain solvers' units' LDS is the layout's; the two stratified units' is the call's: sweep_run)
-    const bool whole_map = which == mci_problem::Sweep::kLeaves || (which >= mci_problem::Sweep::kChains && which != mci_problem::Sweep::kStratLeaves);
-    return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kLeavesUntil || (which >= mci_problem::Sweep::kChains && which < mci_problem::Sweep::kStratLeaves);
+    return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, which == mci_problem::Sweep::kLeavesUntil ? sweep_until_lds(p, nullptr) : whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
 int mci_set_sweep_leaves(mci_problem *p, int32_t mode) {
@@ -260,9 +278,11 @@ int mci_debug_sweep_resample_lds(const mci_problem *p, int64_t *lds_w) {
 namespace {
 // The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
 // kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the chain solvers' units', kSegHolds the :mcmc unit's,
-// kSegCarry (the stored chains, the picks, the weights) and kSegBlk (the block means) the carried chain units' (none otherwise).  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
-// bytes per point), (the seeds: copied next), status words.
-enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegCarry, kSegBlk, kSegGhist, kSegD, kSegHolds, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+// kSegCarry (the stored chains, the picks, the weights) and kSegBlk (the block means) the carried chain units' (none otherwise), kSegSums
+// (every column's running W | sum w m) the `until` units'.  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
+// bytes per point), running sums, (the seeds: copied next), status words, and behind them in an `until` sweep the points' iteration
+// counts [npoint] and the cursor word.
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegCarry, kSegBlk, kSegGhist, kSegD, kSegHolds, kSegSums, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
 
 // What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
 struct SweepCall {
@@ -276,6 +296,9 @@ struct SweepCall {
     mci_result *results = nullptr;
     double *iter_mean = nullptr, *iter_std = nullptr;
     int32_t *status = nullptr;
+    // mci_integrate_sweep_until: the target (NULL: every point runs niter iterations) and where the points' iteration counts go (or NULL)
+    const mci_sweep_target *until = nullptr;
+    int32_t *niter_run = nullptr;
     // plan(): the unit's sizes for this call, made behind the results[] check; it may refuse
     std::function<int(SweepCall &)> plan;
     int64_t rows = 0;            // partial rows per point: the statistical blocks, or 1 (stratified)
@@ -313,10 +336,11 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((rc = c.plan(c))) return rc;
     const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
     const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, c.packed_doubles ? c.packed_doubles : (size_t)nstat,
-                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, c.carry_doubles, c.blk_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.seeds ? (size_t)1 : 0};
+                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, c.carry_doubles, c.blk_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.until ? 2 * (size_t)s.nobs : 0,
+                                         c.seeds ? (size_t)1 : 0};
     size_t o[kSegCount + 1] = {0};
     for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
-    const size_t ndbl = o[kSegStatus] + (P + 1) / 2;
+    const size_t ndbl = o[kSegStatus] + (c.until ? P + 1 : (P + 1) / 2); // status [P] ints; until: | iters [P] | cursor
     if ((int64_t)(ndbl * sizeof(double)) > kSweepMaxBytes)
         return fail(MCI_ERR_INVALID, c.too_big, (int)npoint, niter, c.too_big_count, (long long)(ndbl * sizeof(double)), (long long)kSweepMaxBytes);
     if ((rc = compile_sweep_unit(p, c.unit))) return rc;
@@ -328,7 +352,8 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((rc = sweep_alloc(p->ctx, ndbl * sizeof(double), &base, &got))) return rc;
     double *d = (double *)base;
     std::vector<double> hlog(P * (size_t)niter * nstat);
-    std::vector<int> hst(P);
+    std::vector<int> hst(P), hit(c.until ? P : 0);
+    mci::SweepUntilArgs fu{};
     auto run = [&]() -> int {
         auto t0 = std::chrono::steady_clock::now();
         if (nud > 0) HIPCHK(hipMemcpyAsync(d + o[kSegUd], c.userdata, P * nud * sizeof(double), hipMemcpyHostToDevice, st));
@@ -388,11 +413,17 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
         h.maps_in = c.maps_in ? d + o[kSegMapsIn] : nullptr;
         h.maps_out = d + o[kSegMapsOut];
         void *karg = c.args ? c.args(h, d, o) : (void *)&h;
+        if (c.until) { // (the `until` units: the head and the target behind it; the words behind the status words)
+            const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
+            fu.h = h;
+            fu.u = mci::SweepUntil{c.until->rtol, c.until->atol, c.until->min_niter, ignore, d + o[kSegSums], b.status + P, b.status + 2 * P};
+            karg = &fu;
+        }
         // workgroups: two per CU keep a CU's SIMDs busy while one of them sits in its refinement; any grid runs any npoint
         int cus = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->ctx->device));
         // (several leaves, stratified points: LDS that leaves no room for two workgroups in a CU's 160 KiB gets one)
-        const int per_cu = c.unit != mci_problem::Sweep::kOne && c.lds > 80 * 1024 ? 1 : 2;
+        const int per_cu = c.unit != mci_problem::Sweep::kOne && c.unit != mci_problem::Sweep::kUntil && c.lds > 80 * 1024 ? 1 : 2;
         int64_t grid = p->sweep.grid > 0 ? p->sweep.grid : per_cu * (int64_t)(cus > 0 ? cus : 256);
         if (grid > npoint) grid = npoint;
         if ((c.unit == mci_problem::Sweep::kStrat || c.unit == mci_problem::Sweep::kStratLeaves) && c.lds > 64 * 1024) // (the chunk is the call's: not known when the unit is compiled)
@@ -403,6 +434,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
         p->sweep.last_threads = u.threads;
         HIPCHK(hipMemcpyAsync(hlog.data(), d + o[kSegLog], hlog.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hst.data(), d + o[kSegStatus], P * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (c.until) HIPCHK(hipMemcpyAsync(hit.data(), b.status + P, P * sizeof(int), hipMemcpyDeviceToHost, st));
         if (c.maps_out) HIPCHK(hipMemcpyAsync(c.maps_out, d + o[kSegMapsOut], P * c.map_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
         if (c.copy_out && (rc = c.copy_out(d, o, st))) return rc;
         HIPCHK(hipStreamSynchronize(st));
@@ -415,6 +447,8 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     sweep_release(p->ctx, base, got);
     if (rc) return rc;
     if (c.finish) c.finish();
+    for (int q = 0; q < npoint && c.until; ++q) // (every point was run by some workgroup, for 1 to niter iterations)
+        if (hit[q] < 1 || hit[q] > niter) return fail(MCI_ERR_HIP, "sweep: point %d came back with %d iterations run (1 to %d)", q, hit[q], niter);
     // per point what mci_integrate makes of its log rows (main.jl:203, :211; stratified: strat_mean_std)
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
     std::vector<double> tm((size_t)niter * s.nobs), te((size_t)niter * s.nobs);
@@ -423,17 +457,21 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
         double *im = c.iter_mean ? c.iter_mean + (size_t)q * niter * s.nobs : res->iter_mean ? res->iter_mean : tm.data();
         double *ie = c.iter_std ? c.iter_std + (size_t)q * niter * s.nobs : res->iter_std ? res->iter_std : te.data();
         res->neval = 0;
-        for (int it = 0; it < niter; ++it) {
+        // (until: the point's own n_p rows -- the rows behind them were never written, and the log segment is not zeroed)
+        const int np = c.until ? hit[q] : niter;
+        for (int it = 0; it < np; ++it) {
             const double *row = hlog.data() + ((size_t)q * niter + it) * nstat;
             if (c.strat_stats) strat_mean_std(row, s.nobs, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
             else mci_mean_std(row, row + s.nobs, s.nobs, c.blocks, im + (size_t)it * s.nobs, ie + (size_t)it * s.nobs);
             res->neval += (int64_t)row[2 * s.nobs + 1];
-            if (res->visited && it == niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
+            if (res->visited && it == np - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
         }
+        for (size_t k = (size_t)np * s.nobs; k < (size_t)niter * s.nobs; ++k) im[k] = ie[k] = 0.0;
+        if (c.niter_run) c.niter_run[q] = np;
         if (c.iter_mean && res->iter_mean && res->iter_mean != im) memcpy(res->iter_mean, im, (size_t)niter * s.nobs * sizeof(double));
         if (c.iter_std && res->iter_std && res->iter_std != ie) memcpy(res->iter_std, ie, (size_t)niter * s.nobs * sizeof(double));
         for (int o2 = 0; o2 < s.nobs; ++o2) // main.jl:211 -> statistics.jl:24-55
-            mci_average(im + o2, ie + o2, s.nobs, ignore + 1, niter, &res->mean[o2], &res->stdev[o2], &res->chi2[o2]);
+            mci_average(im + o2, ie + o2, s.nobs, ignore + 1, np, &res->mean[o2], &res->stdev[o2], &res->chi2[o2]);
         res->correlated = 0;
         res->warmup = 0;
         // carried chains: the error from the scatter of the blocks' weighted averages over the run, as in mci_integrate (mci_host_integrate.h)
@@ -462,13 +500,15 @@ int sweep_check_args(const mci_problem *p, const mci_integrate_args *a, int32_t 
 }
 } // namespace
 
-// P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch
-int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
-                        double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
-    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_supported)) return rc;
+// P independent integrate() loops (main.jl:142-207), one workgroup each, in one launch; t: NULL (every point runs niter iterations) or the
+// target of mci_integrate_sweep_until (the `until` units)
+static int sweep_vegas_call(mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                            const double *maps_in, double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status, int32_t *niter_run) {
     if (!(a->neval > a->block)) return fail(MCI_ERR_INVALID, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block); // main.jl:222
     SweepCall c;
-    c.unit = sweep_uses_leaves(p) ? mci_problem::Sweep::kLeaves : mci_problem::Sweep::kOne; // (else one Continuous leaf: a row is its grid)
+    const bool leaves = sweep_uses_leaves(p); // (else one Continuous leaf: a row is its grid)
+    c.unit = leaves ? (t ? mci_problem::Sweep::kLeavesUntil : mci_problem::Sweep::kLeaves) : (t ? mci_problem::Sweep::kUntil : mci_problem::Sweep::kOne);
+    c.until = t, c.niter_run = niter_run;
     c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
     c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
     c.plan = [a](SweepCall &c) {
@@ -480,9 +520,39 @@ int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npo
     };
     c.map_doubles = (size_t)sweep_map_doubles(p);
     c.maxn = sweep_max_nbin(p);
-    c.lds = c.unit == mci_problem::Sweep::kLeaves ? sweep_leaves_lds(p, &c.map_off) : persist_lds(p, &c.map_off);
+    // (the `until` units' two LDS words are the last of the four flag slots both layouts count behind the map: nothing else uses it)
+    c.lds = t ? sweep_until_lds(p, &c.map_off) : leaves ? sweep_leaves_lds(p, &c.map_off) : persist_lds(p, &c.map_off);
     c.too_big = "a sweep of %d points x %d iterations x %lld blocks needs %lld bytes of device memory (limit %lld): split it";
     return sweep_run(p, a, c);
+}
+int mci_integrate_sweep(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                        double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_supported)) return rc;
+    return sweep_vegas_call(p, a, nullptr, npoint, userdata, seeds, maps_in, maps_out, results, iter_mean, iter_std, status, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// a target error per point: the same two kernels' `until` instantiations (mci_sweep.h vegas_sweep<Cfg, true>, mci_sweep_leaves.h
+// vegas_sweep_leaves<Cfg, true>), the stop rule of mci_sweep_common.h
+// ---------------------------------------------------------------------------------------------------
+int mci_sweep_until_supported(const mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, char *why, int32_t n) {
+    if (int rc = mci_sweep_supported(p, a, why, n)) return rc; // (whatever the fixed sweep refuses, with that reason)
+    std::string buf;
+    const char *r = !t ? "the target is NULL"
+                    : !(std::isfinite(t->rtol) && t->rtol >= 0.0) ? "rtol is negative or not finite"
+                    : !(std::isfinite(t->atol) && t->atol >= 0.0) ? "atol is negative or not finite"
+                    : t->min_niter < 0 ? "min_niter < 0" : sweep_until_lds_refusal(p, buf);
+    if (!r) return MCI_OK;
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
+    return fail(MCI_ERR_INVALID, "this sweep cannot run to a target error: %s", r);
+}
+
+static_assert(offsetof(mci::SweepUntilArgs, h) == 0, "the `until` units read the head where the fixed units do");
+int mci_integrate_sweep_until(mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, int32_t npoint, const double *userdata, const uint64_t *seeds,
+                              const double *maps_in, double *maps_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status, int32_t *niter_run) {
+    if (int rc = mci_sweep_until_supported(p, a, t, nullptr, 0)) return rc; // (first: a refusal is the same with and without a device)
+    if (int rc = sweep_check_args(p, a, npoint, userdata, results, mci_sweep_supported)) return rc;
+    return sweep_vegas_call(p, a, t, npoint, userdata, seeds, maps_in, maps_out, results, iter_mean, iter_std, status, niter_run);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -3,8 +3,12 @@
 // kUnits) and includes this header; the host (mci_host_sweep.h) compiles the same text, so the argument layout cannot drift.  Free of
 // host / std headers.
 //
-// In all four ONE workgroup owns a point and runs its whole loop, and no workgroup ever waits for another one: no grid-wide counters, no
-// spinning, no residency condition, and every loop's trip count is a kernel argument or a constant of the translation unit.
+// In all four ONE workgroup owns a point and runs its whole loop, and no workgroup ever waits for another one: no counter anybody waits for, no
+// spinning, no residency condition, and every loop's trip count is a kernel argument or a constant of the translation unit.  (The two
+// `until` units -- vegas_sweep<Cfg, true>, vegas_sweep_leaves<Cfg, true> -- hand out the points behind the first gridDim.x through one
+// word, SweepUntil::cursor: a workgroup that has finished a point adds 1 to it and takes what it gets.  Nothing ever waits on that word
+// or reads it back; a point's iteration loop stays bounded by the kernel argument niter, and it leaves the loop early only on numbers
+// its own workgroup holds.)
 //
 // The ordering argument.  What travels through global memory inside a point -- the partial rows, merge_stats' scratch and head, the
 // histogram row the sample loop adds to with f64 atomics, and whatever a unit adds of its own -- is written and read by the SAME
@@ -35,6 +39,49 @@ struct SweepHead {
     double *maps_out;      // [npoint][doubles of a map row]
 };
 
+// ---- a target error per point (mci_integrate_sweep_until): the `until` units' own argument behind the head, and the stop rule
+struct SweepUntil {
+    double rtol, atol;     // a column has converged when E <= max(atol, rtol |M|)
+    int min_niter, ignore; // ... and n >= max(ignore + 2, min_niter); ignore as mci_integrate resolved it
+    double *sums;          // [npoint][2 nobs], zeroed by the host: W_o | sum w m of column o, written and read by thread o % T alone
+    int *iters;            // [npoint]: n_p, the iterations point p ran
+    int *cursor;           // one word, zeroed by the host: points handed out behind the first gridDim.x
+};
+struct SweepUntilArgs {
+    SweepHead h;
+    SweepUntil u;
+};
+
+// The stop rule, in the reference's own arithmetic; tests/test_sweep_until_host.py compiles the lines between the markers for the host.
+// >>> sweep until rule
+// mci_mean_std of one column of a statistics head (main.jl:297-317): sum and sum of squares of the blocks' means
+__host__ __device__ inline void sweep_until_mean_std(double sum, double sq, int nblocks, double &m, double &s) {
+    m = sum / (double)nblocks; // main.jl:317
+    s = 0.0;                   // main.jl:311
+    if (nblocks > 1) {
+        const double v = (sq / (double)nblocks - m * m) / (double)(nblocks - 1); // main.jl:308
+        s = v < 0.0 ? 0.0 : sqrt(v);                                             // main.jl:297-299
+    }
+}
+// iteration n (1-based) of a column enters its running sums from n = ignore + 1 on: W += w, S += w m, w = 1 / (s + 1e-10)^2 (statistics.jl:186-204)
+__host__ __device__ inline void sweep_until_add(double m, double s, int n, int ignore, double &W, double &S) {
+    if (n <= ignore) return;
+    const double sd = s + 1.0e-10, w = 1.0 / (sd * sd);
+    W += w;
+    S += w * m;
+}
+// the column after its iteration n: M = S / W, E = 1 / sqrt(W) (mci_average) is an error estimate from two averaged iterations on
+// (below that mci_average returns iteration 1, statistics.jl:189-191); a column whose E or M is NaN or infinite never converges
+__host__ __device__ inline bool sweep_until_done(double W, double S, int n, int ignore, int min_niter, double rtol, double atol) {
+    const int first = ignore + 2 > min_niter ? ignore + 2 : min_niter;
+    if (n < first) return false;
+    const double M = S / W, E = 1.0 / sqrt(W);
+    if (!(isfinite(M) && isfinite(E))) return false;
+    const double rel = rtol * fabs(M), bound = atol > rel ? atol : rel;
+    return E <= bound;
+}
+// <<< sweep until rule
+
 // every wave has performed its global stores and atomics, then the workgroup meets
 __device__ __forceinline__ void sweep_round_trip() {
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
@@ -64,6 +111,40 @@ __device__ __forceinline__ TrainArgs sweep_log_row(const SweepHead &f, int p, in
     t.packed = f.m.packed + (size_t)p * f.t.nstat;
     t.iter_log_row = f.t.iter_log_row + ((size_t)p * f.niter + it) * f.t.nstat;
     return t;
+}
+
+// The rule on point p's statistics head after its iteration n (1-based), behind merge_stats and its barrier: column o is thread o % T's
+// -- it reads the head's sum and sum of squares, moves the column's running sums in the point's row of u.sums (written and read by this
+// thread alone, in program order: the header's ordering argument as it stands) and objects through *pending (LDS, reset by thread 0
+// before the iteration's sample loop) when the column has not converged.  The word is complete behind the workgroup's next barrier.
+__device__ __forceinline__ void sweep_until_columns(const SweepUntil &u, const double *packed, int nobs, int nblocks, int p, int n, int *pending) {
+    double *row = u.sums + (size_t)p * 2 * nobs;
+    int wait = 0;
+    for (int o = threadIdx.x; o < nobs; o += blockDim.x) {
+        double m, s, W = row[o], S = row[nobs + o];
+        sweep_until_mean_std(packed[o], packed[nobs + o], nblocks, m, s);
+        sweep_until_add(m, s, n, u.ignore, W, S);
+        row[o] = W;
+        row[nobs + o] = S;
+        if (!sweep_until_done(W, S, n, u.ignore, u.min_niter, u.rtol, u.atol)) wait = 1;
+    }
+    if (wait) atomicOr(pending, 1);
+}
+// The point a workgroup runs behind point p.  UNTIL: thread 0 leaves n_p in u.iters[p] and fetches the next point from the cursor --
+// gridDim.x + what the word held --, the others read it from words[1] (LDS) behind a barrier; the barrier that opens a point stands
+// between these reads and the next write.
+template <bool UNTIL> __device__ __forceinline__ int sweep_next_point(int p, const SweepUntil *u, int *words, int n_run) {
+    if constexpr (UNTIL) {
+        if (threadIdx.x == 0) {
+            u->iters[p] = n_run;
+            words[1] = (int)gridDim.x + atomicAdd(u->cursor, 1);
+        }
+        __syncthreads();
+        return words[1];
+    } else {
+        (void)u, (void)words, (void)n_run;
+        return p + (int)gridDim.x;
+    }
 }
 
 // merge_hist_bin for a slice of N bins at gh: hl <- the clearStatistics! offset + what the sample loop added; the slice is zero again for

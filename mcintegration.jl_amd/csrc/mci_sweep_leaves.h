@@ -20,13 +20,18 @@
 // stages the tables and zeroes its histogram and observable copies at every call, train_leaf fills its scratch before it reads it, the
 // merged slice is written before it is read, and the two verdict words are reset before the leaf that uses them (they alternate, so
 // that a reset never meets the atomicOr of the leaf before without a barrier in between).
+//
+// vegas_sweep_leaves<Cfg, true> (kernel mci_vegas_sweep_leaves_until, mci_integrate_sweep_until on a problem that opted in) is the same
+// body with a target error per point, everything new under `if constexpr (UNTIL)`: what mci_sweep.h says of vegas_sweep<Cfg, true>.  The
+// verdict and the next point are the two words of flags[3], which nothing else uses; the verdict is read behind a leaf's round trip
+// and held until the last leaf's train! and its closing barrier have passed.
 #pragma once
 #include "mci_sweep_common.h"
 
 namespace mci {
 
-template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const BatchArgs &a0, const SweepHead &f) {
-    static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0,
+template <class Cfg, bool UNTIL = false> __device__ __forceinline__ void vegas_sweep_leaves(const BatchArgs &a0, const SweepHead &f, const SweepUntil *u = nullptr) {
+    static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && (UNTIL ? Cfg::DET != 0 : Cfg::HCOPY == 1 && Cfg::DET == 0) && Cfg::EC_DOUBLES == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS (the host checks)");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -35,8 +40,10 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
     double *sm = smem, *hl = sm + train_lds_doubles(MAXN), *ps = hl + MAXN, *blk = smem + f.map_off;
     double *bedges = blk + B::E, *bdacc = blk + B::DA, *bddist = blk + B::DD, *flags = blk + B::FLAGS;
     int *bad = reinterpret_cast<int *>(flags); // bad[0], bad[1]: the verdicts of the even and the odd leaves; flags[2]: train_leaf's spare word
+    int *words = reinterpret_cast<int *>(flags + 3); // UNTIL's verdict | next point
     const int nblocks = f.m.nblocks;
-    for (int p = (int)blockIdx.x; p < f.npoint; p += (int)gridDim.x) {
+    int n_run = f.niter;
+    for (int p = (int)blockIdx.x; p < f.npoint; p = sweep_next_point<UNTIL>(p, u, words, n_run)) {
         __syncthreads(); // (the point before: its last LDS reads are through)
         if (f.maps_in) sweep_copy_row<Cfg, false>(blk, nullptr, f.maps_in + (size_t)p * NROW);
         else {
@@ -50,9 +57,12 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
         a.edges = bedges; // (LDS through the generic address space: stage_tables reads the three tables once per call)
         a.dacc = bdacc;
         a.ddist = bddist;
+        if constexpr (UNTIL) n_run = f.niter;
         for (int it = 0; it < f.niter; ++it) {
             a.iteration = a0.iteration + (u32)it;
             if (tid == 0) bad[0] = 0;
+            if constexpr (UNTIL)
+                if (tid == 0) words[0] = 0;
             for (int b = 0; b < nblocks; ++b) {
                 a.chunk_lo = b;  // work_item: row = block (wg_per_block = 1)
                 __syncthreads(); // (map and flag complete; whatever read this LDS before is through)
@@ -63,6 +73,8 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
             __syncthreads(); // the head of `packed` was written by this workgroup
             const TrainArgs t = sweep_log_row(f, p, it);
             iteration_bookkeeping(t);
+            [[maybe_unused]] bool done = false;
+            if constexpr (UNTIL) sweep_until_columns(*u, m.packed, f.m.nobs, nblocks, p, it + 1, words);
 #pragma unroll 1
             for (int l = 0; l < Cfg::NLEAF; ++l) {
                 const LeafDev L = f.t.leaves[l];
@@ -74,14 +86,22 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves(const Ba
                 // (this thread's first bin of the slice: (boff + first) % T == tid)
                 sweep_take_hist(m.ghist + L.boff, hl, N, (tid + T - L.boff % T) % T, (double)(nblocks + 1) * 1.0e-10, verdict);
                 sweep_round_trip(); // (hl, the verdict; the zeroed slice is out before the next iteration adds to it)
+                if constexpr (UNTIL) done = words[0] == 0;
                 // a bad histogram: this leaf's train! refuses (its map stays), the bits go to this point's status word; the other leaves
                 // and the other points never see it
                 if (train) train_leaf(L, hl, nullptr, sm, ps, *verdict, flags[2], bedges, bdacc, bddist, 0, m.status, false, nullptr, true);
                 __syncthreads();
             }
+            if constexpr (UNTIL)
+                if (done) { // (the whole workgroup read one verdict)
+                    n_run = it + 1;
+                    break;
+                }
         }
         sweep_copy_row<Cfg, true>(blk, f.maps_out + (size_t)p * NROW, nullptr);
     }
 }
+
+template <class Cfg> __device__ __forceinline__ void vegas_sweep_leaves_until(const BatchArgs &a0, const SweepUntilArgs &f) { vegas_sweep_leaves<Cfg, true>(a0, f.h, &f.u); }
 
 } // namespace mci

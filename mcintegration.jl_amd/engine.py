@@ -441,7 +441,7 @@ class Engine:
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
                 "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15,
-                "vegas_sweep_strat_leaves": 16}.get(solver) or _lib.SOLVERS[solver]
+                "vegas_sweep_strat_leaves": 16, "vegas_sweep_until": 17, "vegas_sweep_leaves_until": 18}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -455,7 +455,8 @@ class Engine:
         "mcmc_sweep_carry" (the same two kernels with chains carried from iteration to iteration: set_sweep_chain_carry) | "vegas_big" (the
         :vegas kernel with sixteen histogram copies in 1024-thread workgroups that big launches of eight-copy layouts run) |
         "vegas_sweep_strat_leaves" (the kernel of integrate_sweep_strat for a stratified problem with several Continuous leaves,
-        csrc/mci_sweep_strat_leaves.h; after set_sweep_strat_leaves("all"))"""
+        csrc/mci_sweep_strat_leaves.h; after set_sweep_strat_leaves("all")) | "vegas_sweep_until" | "vegas_sweep_leaves_until" (the kernels
+        of integrate_sweep_until: "vegas_sweep" and "vegas_sweep_leaves" with a target error per point)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -875,6 +876,56 @@ class Engine:
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
         return self._sweep_call(lib().mci_integrate_sweep, a, ud.shape[0], niter, (ud, sd, mi), lambda P: ((), {}))
 
+    @staticmethod
+    def _sweep_target(rtol, atol, min_niter):
+        return _lib.SweepTarget(float(0.0 if rtol is None else rtol), float(0.0 if atol is None else atol), int(0 if min_niter is None else min_niter))
+
+    def sweep_until_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, rtol=0.0, atol=0.0, min_niter=0, **kw):
+        """None when integrate_sweep_until takes this problem with these arguments and this target, else the reason
+        (mci_sweep_until_supported: whatever sweep_supported refuses, a negative or non-finite rtol / atol, min_niter < 0)"""
+        t = self._sweep_target(rtol, atol, min_niter)
+        return self._sweep_refusal(lambda p, a, why, n: lib().mci_sweep_until_supported(p, a, C.byref(t), why, n), solver, neval, niter, block, measurefreq)
+
+    def integrate_sweep_until(self, solver="vegas", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1,
+                              seed=1234, seeds=None, maps=None, first_iteration=0, rtol=0.0, atol=0.0, min_niter=0):
+        """integrate_sweep with a target error (mci_integrate_sweep_until): every point runs until each of its statistics columns has
+        E <= max(atol, rtol |M|) -- M, E the weighted average over its counted iterations and that average's error, as Result computes
+        them --, from iteration max(ignore + 2, min_niter) on, and at most `niter` iterations; still ONE launch: a workgroup that has
+        finished a point takes the next one nobody has begun.  Arguments and result dicts as integrate_sweep; every dict also carries
+        `niter_run` (the iterations the point ran) and `converged` (whether it met the target: False when it ran all `niter` without), and
+        its iter_mean / iter_std hold niter_run rows.  A point's results are those of integrate_sweep(..., niter=niter_run).  A column that
+        is NaN or infinite never converges.  rtol = atol = 0 stops nothing early.  Raises MCIError with the reason of
+        sweep_until_supported()."""
+        ud, sd, mi, _ = self._sweep_inputs("integrate_sweep_until", userdata, seeds, maps)
+        a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration)
+        t = self._sweep_target(rtol, atol, min_niter)
+        P = ud.shape[0]
+        nrun = np.zeros(P, dtype=np.int32)
+        fn = lambda p, a, P, ud, sd, mi, mo, res, im, ie, st: lib().mci_integrate_sweep_until(p, a, C.byref(t), P, ud, sd, mi, mo, res, im, ie, st,
+                                                                                                 nrun.ctypes.data_as(c_int32_p))
+        kept = {}
+        out = self._sweep_call(fn, a, P, niter, (ud, sd, mi), lambda P: ((), {}), keep=kept)
+        met = self._until_met(kept["iter_mean"], kept["iter_std"], nrun, ignore if ignore >= 0 else (1 if adapt else 0), t)
+        for q, r in enumerate(out):
+            n = int(nrun[q])
+            r["niter_run"], r["converged"] = n, bool(met[q])
+            r["iter_mean"], r["iter_std"] = r["iter_mean"][:n], r["iter_std"][:n]
+        return out
+
+    @staticmethod
+    def _until_met(im, ie, nrun, ignore, t):
+        """[P]: whether the rows each point came back with meet the target (the rule of csrc/mci_sweep_common.h on the host, all points
+        at once), for the points that ran all niter iterations: such a point may have met the target in its last one.  A point that
+        stopped below niter converged by definition -- the kernel's verdict, never second-guessed here.  im, ie: [P][niter][nobs], nrun [P]"""
+        rows = np.arange(im.shape[1])[None, :, None]
+        counted = (rows >= ignore) & (rows < nrun[:, None, None])
+        with np.errstate(all="ignore"):
+            w = np.where(counted, 1.0 / (ie + 1.0e-10) ** 2, 0.0)
+            W = w.sum(1)
+            M, E = np.where(counted, w * im, 0.0).sum(1) / W, 1.0 / np.sqrt(W)
+            ok = np.isfinite(M) & np.isfinite(E) & (E <= np.maximum(t.atol, t.rtol * np.abs(M)))
+        return (nrun < im.shape[1]) | (ok.all(1) & (nrun >= max(ignore + 2, t.min_niter)))
+
     def _sweep_inputs(self, name, userdata, seeds, maps, before_maps=None):
         """(userdata [P][nuserdata], seeds [P] | None, maps [P][sweep_map_doubles()] | None) as contiguous arrays, or the ValueError of
         entry point `name`; before_maps(): what the entry point checks between the seeds and the maps, its value the fourth of the tuple"""
@@ -901,9 +952,10 @@ class Engine:
                                  % (name, P, nmap, mi.shape))
         return ud, sd, mi, between
 
-    def _sweep_call(self, fn, a, P, niter, arrays, extra):
+    def _sweep_call(self, fn, a, P, niter, arrays, extra, keep=None):
         """fn (mci_integrate_sweep | mci_integrate_sweep_strat | mci_integrate_sweep_chains | mci_integrate_sweep_mcmc) on the arrays of _sweep_inputs -> the list of P result dicts.  extra(P): the
-        entry point's own arguments between maps_out and results, and the keys they add to every dict ({key: [P][...] array})"""
+        entry point's own arguments between maps_out and results, and the keys they add to every dict ({key: [P][...] array}); keep: a
+        dict that is given the [P][niter][nobs] arrays the dicts' iter_mean / iter_std are rows of"""
         ud, sd, mi = arrays
         n, nmap = self.nobs, self.sweep_map_doubles()
         im, ie = np.zeros((P, niter, n)), np.zeros((P, niter, n))
@@ -917,6 +969,8 @@ class Engine:
             res[q] = _lib.ResultC(niter, n, None, None, _dp(m[q]), _dp(s[q]), _dp(c2[q]), 0, 0.0, _dp(vis[q]), 0, 0)
         check(fn(self.p, C.byref(a), P, _dp(ud) if ud.size else None, sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None,
                  _dp(mi) if mi is not None else None, _dp(mo), *own, res, _dp(im), _dp(ie), st.ctypes.data_as(c_int32_p)))
+        if keep is not None:
+            keep.update(iter_mean=im, iter_std=ie)
         out = []
         for q in range(P):
             r = dict(mean=m[q], stdev=s[q], chi2=c2[q], iter_mean=im[q], iter_std=ie[q], neval=res[q].neval, seconds=res[q].seconds,

@@ -442,7 +442,7 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
                     measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, **kwargs):
+                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, rtol=None, atol=None, min_niter=None, **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -503,6 +503,16 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     reference's); report()'s hold note asks for 4 x hold_max instead of 16 x.  carry=True without chains= / mcmc_chains=, with
     stratify= or under "vegas" raises ValueError.  Where the sweep is refused, the looped integrate() calls carry by their own default.
 
+    rtol, atol: None (default) or a target error -- under solver="vegas" every point stops once each of its statistics columns has
+    stdev <= max(atol, rtol * |mean|) (the weighted average over its counted iterations and that average's error, as Result computes
+    them), from iteration max(ignore + 2, min_niter) on; `niter` becomes the maximum.  Still ONE launch (Engine.integrate_sweep_until):
+    a workgroup that has finished a point takes the next one.  Every Result then carries `niter_run` (the iterations it ran; its tables
+    hold that many rows) and `converged` (False when it ran all `niter` without meeting the target; report() says so); a point's
+    numbers are those of the fixed sweep with niter = niter_run.  leaves="all" works as before.  A column that is NaN or infinite never
+    converges.  The three keywords with another solver, with stratify=, chains= or mcmc_chains=, or min_niter without a tolerance,
+    raise ValueError; so does a tolerance on a problem that does not run as a sweep: the loop of integrate() calls below has no
+    such stop, and never runs in its place.
+
     A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
     measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
     a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
@@ -535,6 +545,18 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             raise ValueError('integrate_sweep: carry= belongs to a chain sweep (solver="vegasmc", chains=K or solver="mcmc", mcmc_chains=K); "vegas" has no chains')
         if chains is None and mcmc_chains is None:
             raise ValueError("integrate_sweep: carry= belongs to a chain sweep: give chains=K (solver=\"vegasmc\") or mcmc_chains=K (solver=\"mcmc\")")
+    until = rtol is not None or atol is not None
+    if min_niter is not None and not until:
+        raise ValueError("integrate_sweep: min_niter= belongs to a target error: give rtol= or atol=")
+    if until:
+        if solver != "vegas":
+            raise ValueError("integrate_sweep: rtol= / atol= / min_niter=: solver is not :vegas (chain solvers are not swept)")
+        for name, given in (("stratify", stratify is not None and stratify is not False), ("chains", chains is not None), ("mcmc_chains", mcmc_chains is not None)):
+            if given:
+                raise ValueError("integrate_sweep: rtol= / atol= / min_niter= and %s= do not go together (the stratified, :vegasmc and :mcmc "
+                                 "sweeps have no target error)" % name)
+        if min_niter is not None and (isinstance(min_niter, bool) or not isinstance(min_niter, (int, np.integer))):
+            raise ValueError("integrate_sweep: min_niter must be an int >= 0, got %r" % (min_niter,))
     if chains is not None and mcmc_chains is not None:
         raise ValueError('integrate_sweep: chains= (solver="vegasmc") and mcmc_chains= (solver="mcmc") do not go together')
     if chains is not None:
@@ -632,6 +654,13 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             why = (eng.sweep_mcmc_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=mcmc_chains,
                                             first_iteration=config.iterations_done, thermal_ratio=thermal_ratio)
                    if hasattr(eng, "sweep_mcmc_supported") else "this engine has no :mcmc sweep")
+        elif until:
+            why = (eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_until_supported")
+                   else "this engine has no sweep to a target error")
+            bad = why is None and eng.sweep_until_supported(solver, nevalperblock * block, niter, block, measurefreq, rtol=rtol or 0.0, atol=atol or 0.0,
+                                                            min_niter=min_niter or 0)
+            if bad:     # (the target itself: in the words of mci_sweep_until_supported)
+                raise ValueError("integrate_sweep: %s" % bad)
         else:
             why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
     if why is None and strat is not None:
@@ -682,9 +711,10 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             out.append(res)
         return out
     if why is None:
-        rs = eng.integrate_sweep(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
-                                 gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
-                                 first_iteration=config.iterations_done)
+        kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma, measurefreq=measurefreq,
+                  seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done)
+        rs = (eng.integrate_sweep_until(solver, rtol=rtol or 0.0, atol=atol or 0.0, min_niter=min_niter or 0, **kw) if until
+              else eng.integrate_sweep(solver, **kw))
         out = []
         for p, r in zip(params, rs):
             c = copy.copy(config)            # (the points share the engine; a sweep leaves its map and logs alone)
@@ -694,6 +724,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
             res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
             res.maps_by_leaf = r.get("maps_by_leaf")
             res.stratification, res.vegas_check, res.warmup, res.neval_discarded = None, None, 0, 0
+            if until:
+                res.niter_run, res.converged = r["niter_run"], r["converged"]
             if print >= 0:
                 report(res)
             out.append(res)
@@ -708,6 +740,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and alloc= needs the batched form" % why)
     if reweight is not None:
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and reweight= needs the batched form" % why)
+    if until:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and rtol= / atol= need the batched form" % why)
     warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),
                   RuntimeWarning, stacklevel=2)
     if eng is not None and hasattr(eng, "close"):

@@ -121,6 +121,8 @@ class Result:
         self.holds = self.hold_max = self.chain_steps = None
         # ... and whether the point's iterations continued each other's chains (integrate_sweep(..., carry=True)): hold_note's factor
         self.chains_carried = False
+        # set by integrate_sweep(..., rtol= | atol=): the iterations the point ran (the rows above) and whether it met the target, else None
+        self.niter_run = self.converged = None
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
         self.iterations = [(self._shape(self.iter_mean[i]), self._shape(self.iter_std[i]), config) for i in range(niter)]
 
@@ -149,6 +151,7 @@ class Result:
         r.stratification = self.stratification
         r.vegas_check = self.vegas_check
         r.holds, r.hold_max, r.chain_steps, r.chains_carried = self.holds, self.hold_max, self.chain_steps, self.chains_carried
+        r.niter_run, r.converged = self.niter_run, self.converged
         return r
 
     @property
@@ -342,3 +345,5 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
         print("  " + result.vegas_check_note, file=io)
     if getattr(result, "hold_note", None):   # (not in the reference)
         print("  " + result.hold_note, file=io)
+    if getattr(result, "converged", None) is False:   # (not in the reference: integrate_sweep(..., rtol= | atol=))
+        print("  note: this sweep point ran all %d iterations it was given without reaching its target error" % result.niter_run, file=io)

@@ -8,6 +8,7 @@
     python tools/sweep_bench.py strat --layout leaves [--nevals 10000,100000] [--points 1,16,256]   (profiles/r17_sweep_strat_leaves.txt)
     python tools/sweep_bench.py chains [--nevals 10000,100000,1000000] [--points 1,16,256] [--chains 1,16,64,256]   (profiles/r14_sweep_chains.txt)
     python tools/sweep_bench.py mcmc   [--nevals 10000,100000] [--points 1,16,256] [--chains 1,16,64,256]          (profiles/r15_sweep_mcmc.txt)
+    python tools/sweep_bench.py until  [--nevals 10000,100000] [--points 256,2048] [--rtol 2e-3] [--repeat 7]       (profiles/r18_sweep_until.txt)
 
 The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
 and of the same points as a loop of Engine.integrate calls with the persistent launch, in the same process.
@@ -32,6 +33,12 @@ deep per chain.  Both tables give the best and the worst of the timed runs of ev
 `chains --carry` | `mcmc --carry` (profiles/r16_sweep_carry.txt): the sweep with chains carried from iteration to iteration
 (set_sweep_chain_carry) against the uncarried sweep at the same nchain and against a loop of ordinary calls with the same nchain and
 carried chains (set_chain_carry(1)); the last columns give the dependent steps of a point-iteration without and with carrying.
+`until`: the Genz scan at niter = 20 with a target error (Engine.integrate_sweep_until) against the fixed sweep of the same points:
+(a) the cost of asking -- the `until` unit with rtol = atol = 0, which runs every iteration, over the fixed sweep; (b) the gain -- the
+`until` unit at --rtol over the fixed sweep, next to sum n_p / (20 P), the share of the iterations actually run, which is what a perfect
+schedule would reach.  The three calls alternate `--repeat` times after a warm-up of each.  Two clocks per call: `launch`, the library's
+own (result `seconds`: uploads, the one launch, read-back, up to the stream's synchronise -- what the kernel decides), and `call`, the
+wall time of the Engine method (with the host's statistics and P result dicts); best / median / worst of each.
 One GPU process; run each mode under its own time limit."""
 import argparse
 import os
@@ -410,9 +417,56 @@ def carry_table(Ps, nevals, chains, budget=3.0, solver="vegasmc"):
                       flush=True)
 
 
+# ---- until: a target error per point (csrc/mci_sweep.h vegas_sweep<Cfg, true>)
+def until_table(Ps, nevals, rtol, reps, niter=20):
+    from mcintegration_jl_amd import isa_mix
+    eng = sweep_engine()
+    for unit in ("vegas_sweep", "vegas_sweep_until"):
+        eng.compile(unit)
+        res = isa_mix.resources(eng.code_object(unit))["mci_" + unit]
+        print("# mci_%s: %d VGPRs, %d bytes of scratch" % (unit, res["vgpr"], res["scratch"]))
+    print("# 4-D Genz product peak, a from 2 to 8, niter = %d, block = %d, ignore = 1; %d alternating repetitions after one warm-up call of each"
+          % (niter, BLOCK, reps))
+    print("# fixed sweep | until, rtol = atol = 0 | until, rtol = %g: ms best / median / worst; launch = the library's clock up to the stream's synchronise, "
+          "call = the Engine method's wall time" % rtol)
+    for neval in nevals:
+        kw = dict(neval=neval, niter=niter, block=BLOCK, seed=SEED)
+        for P in Ps:
+            uds = np.array([point(k) for k in range(P)])
+            calls = (("fixed", lambda: eng.integrate_sweep("vegas", userdata=uds, **kw)),
+                     ("zero", lambda: eng.integrate_sweep_until("vegas", userdata=uds, rtol=0.0, atol=0.0, **kw)),
+                     ("until", lambda: eng.integrate_sweep_until("vegas", userdata=uds, rtol=rtol, **kw)))
+            out, times, secs = {}, {name: [] for name, _ in calls}, {name: [] for name, _ in calls}
+            for name, fn in calls:
+                fn()                                                   # (warm-up: code object loaded, buffer parked with the context)
+            for _ in range(reps):
+                for name, fn in calls:
+                    t0 = time.perf_counter()
+                    out[name] = fn()                                   # (ends in the stream's synchronise and the host's statistics)
+                    times[name].append(time.perf_counter() - t0)
+                    secs[name].append(out[name][0]["seconds"])
+            assert all(r["status"] == 0 for rs in out.values() for r in rs)
+            assert all(r["niter_run"] == niter for r in out["zero"])
+            same = all(a["iter_mean"].tobytes() == b["iter_mean"].tobytes() and a["maps"].tobytes() == b["maps"].tobytes() for a, b in zip(out["fixed"], out["zero"]))
+            nrun = np.array([r["niter_run"] for r in out["until"]])
+            share = nrun.sum() / float(niter * P)
+            col = lambda ts, name: "%8.3f / %8.3f / %8.3f" % tuple(1e3 * v for v in (min(ts[name]), float(np.median(ts[name])), max(ts[name])))
+            med, smed = {name: float(np.median(times[name])) for name in times}, {name: float(np.median(secs[name])) for name in secs}
+            print("neval %7d  P %5d  launch: fixed %s  zero target %s  rtol %s   zero / fixed %.3f   until / fixed %.3f   until / perfect schedule %.2f"
+                  % (neval, P, col(secs, "fixed"), col(secs, "zero"), col(secs, "until"), smed["zero"] / smed["fixed"], smed["until"] / smed["fixed"],
+                     smed["until"] / (share * smed["fixed"])))
+            print("                        call:   fixed %s  zero target %s  rtol %s   zero / fixed %.3f   until / fixed %.3f"
+                  % (col(times, "fixed"), col(times, "zero"), col(times, "until"), med["zero"] / med["fixed"], med["until"] / med["fixed"]))
+            one_each = P <= eng.last_sweep_launch()[0]         # (one point per workgroup: the launch lasts as long as its slowest point)
+            print("                        iterations run %.3f of %d P (converged %d of %d points, n_p min %d median %d max %d%s)   "
+                  "zero target == fixed bit for bit: %s   grid x threads = %s"
+                  % (share, niter, sum(1 for r in out["until"] if r["converged"]), P, nrun.min(), int(np.median(nrun)), nrun.max(),
+                     "; the slowest workgroup's share %.3f" % (nrun.max() / float(niter)) if one_each else "", same, eng.last_sweep_launch()), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["table", "threads", "once", "strat", "chains", "mcmc"])
+    ap.add_argument("mode", choices=["table", "threads", "once", "strat", "chains", "mcmc", "until"])
     ap.add_argument("--nevals", default="10000,100000,1000000")
     ap.add_argument("--chains", default="1,16,64,256")
     ap.add_argument("--neval", type=int, default=10000)
@@ -420,12 +474,17 @@ def main():
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--layout", choices=["genz", "bubble", "leaves"], default="genz")
+    ap.add_argument("--rtol", type=float, default=2e-3, help="until: the target error of the timed scan")
     ap.add_argument("--carry", action="store_true", help="chains | mcmc: the sweep with carried chains against the uncarried one and a loop of carried calls")
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
     if a.carry and a.mode not in ("chains", "mcmc"):
         ap.error("--carry goes with the chains and mcmc modes")
+    if a.mode == "until":
+        until_table([256, 2048] if a.points == "1,16,256,1024,4096" else Ps, [10000, 100000] if a.nevals == "10000,100000,1000000" else [int(v) for v in a.nevals.split(",")],
+                    a.rtol, a.repeat if a.repeat > 1 else 7)
+        return
     if a.mode in ("chains", "mcmc"):
         (carry_table if a.carry else chains_table)([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
                      [int(v) for v in a.chains.split(",")], solver="vegasmc" if a.mode == "chains" else "mcmc")
