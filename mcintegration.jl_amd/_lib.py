@@ -45,7 +45,9 @@ class DebugMergeIO(C.Structure):   # csrc/mci_debug.h mci_debug_merge_io
     _fields_ = [("nblocks", C.c_int32), ("wg_per_block", C.c_int32), ("nrows", C.c_int32), ("hist_rows", C.c_int32), ("use_ghist", C.c_int32),
                 ("hist_no_offset", C.c_int32), ("path", C.c_int32), ("part_cols", c_double_p), ("part_hist", c_double_p), ("ghist", c_double_p),
                 ("part_pa", c_double_p), ("hold", C.POINTER(C.c_uint64)), ("obs", c_double_p), ("packed", c_double_p), ("stage1", c_double_p),
-                ("scratch", c_double_p), ("block_means", c_double_p), ("status", c_int32_p), ("part_cols_out", c_double_p), ("ghist_out", c_double_p)]
+                ("scratch", c_double_p), ("block_means", c_double_p), ("status", c_int32_p), ("part_cols_out", c_double_p), ("ghist_out", c_double_p),
+                ("do_train", C.c_int32), ("train_walk", C.c_int32), ("grids", c_double_p), ("dists", c_double_p), ("accs", c_double_p),
+                ("grids_out", c_double_p), ("dists_out", c_double_p), ("accs_out", c_double_p), ("walk_counts", C.POINTER(C.c_int64))]
 
 
 HOST_INTEGRAND_FN = C.CFUNCTYPE(C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p)

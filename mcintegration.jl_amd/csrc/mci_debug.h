@@ -120,7 +120,7 @@ typedef struct mci_debug_merge_io {
     int32_t hist_rows;             /* rows of part_hist (k_hist_stage1 runs), or 0 */
     int32_t use_ghist;             /* or: the number of global histogram buffers in `ghist` (no first stage) */
     int32_t hist_no_offset;        /* MergeArgs::hist_no_offset */
-    int32_t path;                  /* 0: k_hist_stage1 -> k_finalize | 1: k_hist_stage1 -> k_finish (do_train = 0, no reweighting, no log row) */
+    int32_t path;                  /* 0: k_hist_stage1 -> k_finalize | 1: k_hist_stage1 -> k_finish (no reweighting, no log row; merge only unless do_train, below) */
     const double *part_cols;       /* [nrows][ncols] */
     const double *part_hist;       /* [hist_rows][nbin] */
     const double *ghist;           /* [use_ghist][nbin] */
@@ -135,6 +135,17 @@ typedef struct mci_debug_merge_io {
     int32_t *status;               /* the hook's own ST_* word */
     double *part_cols_out;         /* [nrows][ncols] as the kernels left them */
     double *ghist_out;             /* [use_ghist + 1][nbin]: the buffers as left behind, then a guard row the hook filled with NaN */
+    /* "and train" (path 1 only): k_finish goes on to refine every adapting leaf from the merged histogram in its LDS, as launch_train
+     * has it do behind a pending merge -- on tables of the HOOK's own, uploaded from here and read back to here, leaf after leaf in the
+     * problem's leaf order; the problem's grids and distributions stay as they are.  Refused: do_train on path 0, a walk outside
+     * 0 .. 3, a missing table. */
+    int32_t do_train;              /* 0: merge only (everything below is ignored) */
+    int32_t train_walk;            /* TrainArgs::serial_walk: 0 prefix scan | 1 serial | 2 serial, general form | 3 serial, one decision planted wrong */
+    const double *grids;           /* the Continuous leaves' old grids, npts doubles each (NULL only if there is none) */
+    const double *dists;           /* the Discrete leaves' distributions, K doubles each */
+    const double *accs;            /* ... and accumulations, K + 1 doubles each */
+    double *grids_out, *dists_out, *accs_out; /* the same tables as k_finish left them */
+    int64_t *walk_counts;          /* [2] or NULL: serial walks run as slots | in the general form (mci_debug_walk_counts, of the hook's own word) */
 } mci_debug_merge_io;
 int mci_debug_merge(mci_problem *prob, const mci_debug_merge_io *io);
 /* shape[8] = nobs, ni, ncols, nbin, npa, nstat, leaves, bins of the largest leaf; leaves[nleaf][2] (or NULL) = offset into the histogram

@@ -814,6 +814,19 @@ int mci_debug_merge(mci_problem *p, const mci_debug_merge_io *io) {
     if (nblocks > INT32_MAX / wpb || nrows > INT32_MAX / wide || nblocks > INT32_MAX / wide || hrows > INT32_MAX / nbin1 || (k + 1) > INT32_MAX / nbin1)
         return fail(MCI_ERR_INVALID, "merge: %lld blocks, %lld rows and %lld histogram rows are more than a test hook takes", (long long)nblocks, (long long)nrows, (long long)hrows);
     if (nrows < nblocks * wpb) return fail(MCI_ERR_INVALID, "merge: %lld rows for %lld blocks of %lld", (long long)nrows, (long long)nblocks, (long long)wpb);
+    // "and train": the caller's tables, leaf after leaf, in doubles
+    const bool train = io->do_train != 0;
+    size_t ngrid = 0, ndist = 0, nacc = 0;
+    for (auto &L : p->leaves) {
+        if (L.kind == MCI_CONTINUOUS) ngrid += (size_t)L.npts;
+        else if (L.kind == MCI_DISCRETE) ndist += (size_t)L.nbin, nacc += (size_t)L.nbin + 1;
+    }
+    if (train) {
+        if (io->path != 1) return fail(MCI_ERR_INVALID, "merge: do_train needs path 1 (k_finish)");
+        if (io->train_walk < 0 || io->train_walk > 3) return fail(MCI_ERR_INVALID, "merge: train walk %d (0 .. 3)", (int)io->train_walk);
+        if ((ngrid && (!io->grids || !io->grids_out)) || (ndist && (!io->dists || !io->accs || !io->dists_out || !io->accs_out)))
+            return fail(MCI_ERR_INVALID, "merge: do_train without its tables");
+    }
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
     HIPCHK(hipSetDevice(p->ctx->device));
     hipStream_t st = p->ctx->stream;
@@ -849,6 +862,31 @@ int mci_debug_merge(mci_problem *p, const mci_debug_merge_io *io) {
     if (io->obs && nbm) {
         if ((rc = d_obs.reserve((int64_t)nbm))) return rc;
         HIPCHK(hipMemcpyAsync(d_obs, io->obs, nbm * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    // the hook's own tables for "and train", laid out as the problem lays its own out (Leaf::eoff, doff)
+    DevBuf<double> d_tedges, d_tdacc, d_tddist;
+    std::vector<double> t_edges, t_dacc, t_ddist;
+    if (train) {
+        t_edges = p->h_edges;
+        t_dacc = p->h_dacc;
+        t_ddist = p->h_ddist;
+        size_t ig = 0, id = 0, ia = 0;
+        for (auto &L : p->leaves) {
+            if (L.kind == MCI_CONTINUOUS) {
+                memcpy(t_edges.data() + L.eoff, io->grids + ig, (size_t)L.npts * sizeof(double));
+                ig += (size_t)L.npts;
+            } else if (L.kind == MCI_DISCRETE) {
+                memcpy(t_ddist.data() + L.doff, io->dists + id, (size_t)L.nbin * sizeof(double));
+                memcpy(t_dacc.data() + L.eoff, io->accs + ia, ((size_t)L.nbin + 1) * sizeof(double));
+                id += (size_t)L.nbin;
+                ia += (size_t)L.nbin + 1;
+            }
+        }
+        if ((rc = d_tedges.reserve((int64_t)t_edges.size() + 1)) || (rc = d_tdacc.reserve((int64_t)t_dacc.size() + 1)) || (rc = d_tddist.reserve((int64_t)t_ddist.size() + 1)))
+            return rc;
+        if (!t_edges.empty()) HIPCHK(hipMemcpyAsync(d_tedges, t_edges.data(), t_edges.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        if (!t_dacc.empty()) HIPCHK(hipMemcpyAsync(d_tdacc, t_dacc.data(), t_dacc.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        if (!t_ddist.empty()) HIPCHK(hipMemcpyAsync(d_tddist, t_ddist.data(), t_ddist.size() * sizeof(double), hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipStreamSynchronize(st)); // (the uploads have read the caller's pageable memory)
     if (io->obs && nbm) { // finish_host_measure
@@ -892,11 +930,25 @@ int mci_debug_merge(mci_problem *p, const mci_debug_merge_io *io) {
         a.nd = s.ni + 1;
         a.status = d_stat;
         a.maxn = maxn;
+        if (train) { // ... or to refine as well, on the hook's tables
+            a.edges = d_tedges;
+            a.dacc = d_tdacc;
+            a.ddist = d_tddist;
+            a.do_train = 1;
+            a.serial_walk = io->train_walk;
+        }
         const size_t sm = train_lds_bytes(maxn, &a.spare);
         if (sm > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)mci::k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsMax));
         hipLaunchKernelGGL(mci::k_finish, finish_grid(s.nleaf, p->npa), dim3(train_threads(maxn)), sm, st, m, a);
     }
     HIPCHK(hipGetLastError());
+    int h_stat[4] = {0, 0, 0, 0};
+    if (train) {
+        if (!t_edges.empty()) HIPCHK(hipMemcpyAsync(t_edges.data(), d_tedges, t_edges.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (!t_dacc.empty()) HIPCHK(hipMemcpyAsync(t_dacc.data(), d_tdacc, t_dacc.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (!t_ddist.empty()) HIPCHK(hipMemcpyAsync(t_ddist.data(), d_tddist, t_ddist.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_stat, d_stat, sizeof(h_stat), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipMemcpyAsync(io->packed, d_packed, npacked * sizeof(double), hipMemcpyDeviceToHost, st));
     if (io->stage1) HIPCHK(hipMemcpyAsync(io->stage1, d_st1, (size_t)mci_problem::kGroups * s.nbin * sizeof(double), hipMemcpyDeviceToHost, st));
     if (io->scratch) HIPCHK(hipMemcpyAsync(io->scratch, d_scr, nscr * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -905,6 +957,21 @@ int mci_debug_merge(mci_problem *p, const mci_debug_merge_io *io) {
     if (io->part_cols_out) HIPCHK(hipMemcpyAsync(io->part_cols_out, d_cols, ncell * sizeof(double), hipMemcpyDeviceToHost, st));
     if (io->ghist_out) HIPCHK(hipMemcpyAsync(io->ghist_out, d_gh, (size_t)(k + 1) * s.nbin * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st)); // (the buffers are freed behind it)
+    if (train) {
+        size_t ig = 0, id = 0, ia = 0;
+        for (auto &L : p->leaves) {
+            if (L.kind == MCI_CONTINUOUS) {
+                memcpy(io->grids_out + ig, t_edges.data() + L.eoff, (size_t)L.npts * sizeof(double));
+                ig += (size_t)L.npts;
+            } else if (L.kind == MCI_DISCRETE) {
+                memcpy(io->dists_out + id, t_ddist.data() + L.doff, (size_t)L.nbin * sizeof(double));
+                memcpy(io->accs_out + ia, t_dacc.data() + L.eoff, ((size_t)L.nbin + 1) * sizeof(double));
+                id += (size_t)L.nbin;
+                ia += (size_t)L.nbin + 1;
+            }
+        }
+        if (io->walk_counts) io->walk_counts[0] = h_stat[1], io->walk_counts[1] = h_stat[2];
+    }
     return MCI_OK;
 }
 

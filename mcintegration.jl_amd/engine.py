@@ -575,13 +575,17 @@ class Engine:
         return out
 
     def merge_rows(self, nblocks, wg_per_block, part_cols, part_hist=None, ghist=None, part_pa=None, hold=None, obs=None, hist_no_offset=False,
-                   block_means=True, path="finalize"):
+                   block_means=True, path="finalize", train=None, grids=None, tables=None):
         """test hook (csrc/mci_debug.h mci_debug_merge): the merge kernels on their own over rows the caller made up -- part_cols [nrows,
         ncols], part_hist [hist_rows, nbin] (through k_hist_stage1) or ghist [k, nbin] (use_ghist = k), part_pa [nrows, 2 npa], hold [64]
         (uint64), obs [nblocks, nobs] (k_add_host_obs runs first); path "finalize" (k_finalize) | "finish" (k_finish, told to merge only).
         -> dict of packed [reduce_size], stage1 [32, nbin], scratch [nblocks, ncols], block_means [nblocks, nobs] (None if not wanted),
         status, part_cols [nrows, ncols] and ghist [k + 1, nbin] (the last row: the hook's NaN guard) as left behind.  This engine gives its
-        device and its shape only; nothing of its own state is read or written"""
+        device and its shape only; nothing of its own state is read or written.
+        train (path "finish" only): a walk as set_train_walk names them ("scan", "serial", "serial_general", "serial_wrong_decision") --
+        k_finish then refines every adapting leaf from the histogram it merged, on tables of the hook's own: grids = the old grid of every
+        Continuous leaf in leaf order, tables = (distribution, accumulation) of every Discrete leaf in leaf order.  The dict gains grids and
+        tables as k_finish left them (same order) and walk_counts (slots, general form)"""
         sh = self.merge_shape()
         pc = np.ascontiguousarray(part_cols, dtype=np.float64)
         ph = None if part_hist is None else np.ascontiguousarray(part_hist, dtype=np.float64)
@@ -607,8 +611,30 @@ class Engine:
                                None if ob is None else _dp(ob), _dp(out["packed"]), _dp(out["stage1"]), _dp(out["scratch"]),
                                None if out["block_means"] is None else _dp(out["block_means"]), C.pointer(status), _dp(out["part_cols"]),
                                _dp(out["ghist"]))
+        if train is not None:
+            if path != "finish" or train not in ("scan", "serial", "serial_general", "serial_wrong_decision"):
+                raise ValueError("train: path 'finish' and a walk of set_train_walk")
+            cont = [lf for lf in self.config.leaves if isinstance(lf, ContinuousVar)]
+            disc = [lf for lf in self.config.leaves if not isinstance(lf, (ContinuousVar, FermiK))]
+            gs = [np.ascontiguousarray(g, dtype=np.float64) for g in (grids or [])]
+            ts = [(np.ascontiguousarray(d, dtype=np.float64), np.ascontiguousarray(a, dtype=np.float64)) for d, a in (tables or [])]
+            if ([g.shape for g in gs] != [(lf.ninc,) for lf in cont]
+                    or [(d.shape, a.shape) for d, a in ts] != [((lf.upper - lf.lower + 1,), (lf.upper - lf.lower + 2,)) for lf in disc]):
+                raise ValueError("grids: one old grid per Continuous leaf; tables: (distribution [K], accumulation [K + 1]) per Discrete leaf")
+            cat = lambda xs: np.concatenate(xs) if xs else np.zeros(1)
+            gin, din, ain = cat(gs), cat([d for d, a in ts]), cat([a for d, a in ts])
+            gout, dout, aout = np.full(gin.shape, np.nan), np.full(din.shape, np.nan), np.full(ain.shape, np.nan)
+            counts = (C.c_int64 * 2)(-1, -1)
+            io.do_train, io.train_walk = 1, {"scan": 0, "serial": 1, "serial_general": 2, "serial_wrong_decision": 3}[train]
+            io.grids, io.dists, io.accs, io.grids_out, io.dists_out, io.accs_out = _dp(gin), _dp(din), _dp(ain), _dp(gout), _dp(dout), _dp(aout)
+            io.walk_counts = C.cast(counts, C.POINTER(C.c_int64))
         check(lib().mci_debug_merge(self.p, C.byref(io)))
         out["status"] = int(status.value)
+        if train is not None:
+            gsplit = np.split(gout, np.cumsum([g.size for g in gs])[:-1]) if gs else []
+            dsplit = np.split(dout, np.cumsum([d.size for d, a in ts])[:-1]) if ts else []
+            asplit = np.split(aout, np.cumsum([a.size for d, a in ts])[:-1]) if ts else []
+            out["grids"], out["tables"], out["walk_counts"] = gsplit, list(zip(dsplit, asplit)), (int(counts[0]), int(counts[1]))
         return out
 
     def sweep_resample_lds(self):

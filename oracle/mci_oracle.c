@@ -195,6 +195,8 @@ int mcio_train_continuous(double *grid, long npts, double *hist, double alpha) {
     double f_ninc = mcio_sum_julia(d, N) / (double)N; /* :226 */
     for (long i = 2; i <= npts - 1; ++i) { /* :227 (1-based i) */
         while (acc_f < f_ninc) {           /* :228 */
+            /* Julia throws a BoundsError where rounding lets the walk run past the last bin; here that would read past d[] */
+            if (j >= N) { free(d); free(newgrid); return 5; }
             j += 1;                        /* :229 */
             acc_f += d[j - 1];             /* :230 */
         }

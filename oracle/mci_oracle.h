@@ -178,7 +178,7 @@ double mcio_sum_julia(const double *v, long n);                    /* ... of any
 int mcio_rescale(double *dist, long n, double alpha);             /* :67-82, in place; !=0 on assert failure */
 
 /* ---- src/distribution/variable.jl ---- */
-int mcio_train_continuous(double *grid, long npts, double *hist, double alpha); /* :206-239 */
+int mcio_train_continuous(double *grid, long npts, double *hist, double alpha); /* :206-239; 1, 2: rescale's asserts, 3, 4: train!'s, 5: the walk left the grid (Julia: BoundsError) */
 int mcio_train_discrete(double *hist, long K, double alpha, double *distribution, double *accumulation); /* :369-382 */
 
 /* ---- config ---- */

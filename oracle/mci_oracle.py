@@ -86,6 +86,8 @@ def lib():
     L.mcio_locate.argtypes = [c_double_p, C.c_long, C.c_double]
     L.mcio_smooth.argtypes = [c_double_p, C.c_long, C.c_double, c_double_p]
     L.mcio_rescale.argtypes = [c_double_p, C.c_long, C.c_double]
+    L.mcio_sum_julia.restype = C.c_double
+    L.mcio_sum_julia.argtypes = [c_double_p, C.c_long]
     L.mcio_train_continuous.argtypes = [c_double_p, C.c_long, c_double_p, C.c_double]
     L.mcio_train_discrete.argtypes = [c_double_p, C.c_long, C.c_double, c_double_p, c_double_p]
     L.mcio_config_create.restype = C.POINTER(_Config)
@@ -207,6 +209,11 @@ def rescale(dist, alpha=1.5):
     if rc:
         raise AssertionError("rescale assertion %d" % rc)
     return d
+
+
+def sum_julia(v):
+    a = np.ascontiguousarray(v, dtype=np.float64)
+    return float(lib().mcio_sum_julia(_dp(a), len(a)))
 
 
 def train_continuous(grid, hist, alpha):

@@ -323,13 +323,14 @@ def check(c, out, who):
 MUTATIONS = ("drop_last_row", "short_row_loop", "per_floor")
 
 
-def mirror(c, mutate=None):
+def mirror(c, mutate=None, shape=None, x=None):
     """dict of packed [reduce size], stage1 [32, nbin] (NaN without a first stage), scratch [nblocks, ncols], block_means [nblocks, nobs]
     (None if the case does not want them), status, part_cols [nrows, ncols] as k_add_host_obs leaves them.
+    shape, x: a problem shape (Engine.merge_shape) and rows (as `inputs` returns them) of the caller's own instead of the table's.
     mutate: None | "drop_last_row" (the first stage loses the last row of its last non-empty group) | "short_row_loop" (merge_stats' row
     loop stops at wg_per_block - wg_per_block % 8) | "per_floor" (the first stage takes per = rows // 32)"""
     assert mutate is None or mutate in MUTATIONS
-    sh, x = SHAPES[c["problem"]], inputs(c)
+    sh, x = shape or SHAPES[c["problem"]], x or inputs(c)
     nobs, ni, ncols, nbin, npa = sh["nobs"], sh["ni"], sh["ncols"], sh["nbin"], sh["npa"]
     nblocks, wpb, nrows = c["nblocks"], c["wpb"], c["nrows"]
     nstat = 2 * nobs + 2 + ni + 1
