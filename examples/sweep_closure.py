@@ -17,7 +17,8 @@ every point starts from a map of its own -- its T grid spans its own (0, beta). 
 same scan under the reference's default solver: 64 fresh chains per block and point, still one launch.  `bubble_scan(solver="mcmc",
 mcmc_chains=64)` runs it under :mcmc, the solver the reference runs this example with: the closures are then called in that solver's
 form, integrand(idx, var, config) and measure(idx, var, obs, relative_weight, config), and every point reports its longest holding
-time."""
+time.  `bubble_train_then_produce()` is a training scan followed by a production scan that goes on from it: maps, reweight factors AND
+chains (carry=True, chain_state=), so the production scan's first iteration neither starts its chains afresh nor burns them in."""
 import math
 import os
 import sys
@@ -160,6 +161,28 @@ def bubble_scan(points=16, ninc=1000, solver="vegas", chains=None, mcmc_chains=N
     return scan, results
 
 
+def bubble_train_then_produce(points=16, ninc=1000, mcmc_chains=64):
+    """train, then production, under :mcmc with carried chains: the second scan takes every point's map, factors and chain state from the
+    first, keeps the maps (adapt=False) and measures more; its iterations are numbered on from the first scan's by themselves"""
+    scan = [bubble_para(float(rs)) for rs in np.linspace(1.0, 2.0, points)]
+    Qsize = scan[0].Qsize
+    var = lambda: (mci.Continuous(0.0, 1.0, alpha=3.0), mci.Continuous(0.0, PI, alpha=3.0), mci.Continuous(0.0, 2 * PI, alpha=3.0),
+                   mci.Continuous(0.0, scan[0].beta, alpha=3.0), mci.Discrete(1, Qsize, adapt=False))
+    uniform = np.full(Qsize, 1.0 / Qsize)
+    maps = [np.concatenate([np.linspace(0.0, hi, ninc) for hi in (1.0, PI, 2 * PI, p.beta)] + [np.concatenate([[0.0], np.cumsum(uniform)]), uniform])
+            for p in scan]
+    kw = lambda: dict(params=scan, leaves="all", measure=q_histogram_mcmc, var=var(), dof=[[1, 1, 1, 1, 1]], obs=[np.zeros(Qsize)], solver="mcmc",
+                      mcmc_chains=mcmc_chains, carry=True, seed=7)
+    head = mci.integrate_sweep(bubble_mcmc, maps=maps, neval=1e4, niter=5, **kw())
+    tail = mci.integrate_sweep(bubble_mcmc, maps=[r.map for r in head], reweight=[r.reweight for r in head], chain_state=[r.chain_state for r in head],
+                               adapt=False, neval=1e5, niter=10, **kw())
+    print("train, then production (:mcmc, %d carried chains per block): the production scan starts at iteration %d, its chains stored by iteration %d;"
+          " %d + %d evaluations at the first point" % (mcmc_chains, head[0].chain_state.iteration + 1, tail[0].chain_state.iteration, head[0].neval, tail[0].neval))
+    for p, r in list(zip(scan, tail))[::max(1, points // 8)]:
+        print("%6.3f  %s" % (p.rs, "  ".join("%12.6f +- %-10.6f" % (r.mean[0][i], r.stdev[0][i]) for i in range(Qsize))))
+    return scan, head, tail
+
+
 if __name__ == "__main__":
     main()
     stratified()
@@ -167,3 +190,4 @@ if __name__ == "__main__":
     bubble_scan()
     bubble_scan(solver="vegasmc", chains=64)
     bubble_scan(solver="mcmc", mcmc_chains=64)
+    bubble_train_then_produce()

@@ -62,6 +62,9 @@ enum { MCI_VEGAS_SWEEP_STRAT_LEAVES = 16 };
 /* ... and the two sweep kernels of mci_integrate_sweep with a target error per point (mci_integrate_sweep_until): the one-grid kernel
  * and the one for several variable leaves, code objects of their own */
 enum { MCI_VEGAS_SWEEP_UNTIL = 17, MCI_VEGAS_SWEEP_LEAVES_UNTIL = 18 };
+/* ... and the two carried chain sweep kernels with a first iteration that continues the chains of the call before
+ * (mci_integrate_sweep_chains_resume, mci_integrate_sweep_mcmc_resume): code objects of their own */
+enum { MCI_VEGASMC_SWEEP_RESUME = 19, MCI_MCMC_SWEEP_RESUME = 20 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes; mci_set_sweep_strat_leaves: which ones mci_integrate_sweep_strat takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -339,7 +342,8 @@ int mci_set_sweep_leaves(mci_problem *prob, int32_t mode);
  * the storing iteration's doReweight!) and run with nburn = 0; :vegasmc -- pi_new / pi_old is evaluated at every stored configuration on
  * the refined map and the moved factors, the block is resampled with these weights and runs with the burn-in mci_chain_burnin(steps,
  * 1, nslots).  The chain count is K in every iteration; with K = 1 nothing is ever carried.  The FIRST iteration of every call starts
- * afresh: chain state does not travel between calls (no chain state comes in or goes out).
+ * afresh: chain state does not travel between calls (no chain state comes in or goes out) -- of these two entry points; their
+ * siblings mci_integrate_sweep_chains_resume and mci_integrate_sweep_mcmc_resume hand every point's chain ends out and take them back in.
  * Results: when at least one iteration of a point was carried and niter > ignore + 1, the point's stdev is the block-lineage error
  * (the blocks' means of every iteration, mci_lineage_sums + mci_mean_std as in mci_integrate) and correlated = 1; mean and chi2 stay
  * the reference's.  Such calls run kernels of their own (MCI_VEGASMC_SWEEP_CARRY, MCI_MCMC_SWEEP_CARRY) and take, per point, two
@@ -450,6 +454,69 @@ int mci_integrate_sweep_mcmc(mci_problem *prob, const mci_integrate_args *args, 
  * variable (the sweep's map block holds Continuous and Discrete leaves only: a follow-up), tables that do not sit in LDS in one tile, or
  * more than 159 KiB of LDS for the chain loop's tables and counters or the refinement scratch plus the point's whole map (named). */
 int mci_sweep_mcmc_supported(const mci_problem *prob, const mci_integrate_args *args, char *why, int32_t n);
+/* What a carried chain sweep leaves behind for the next call: the record of the chains every point's last iteration stored, the same
+ * for all points of the call. */
+typedef struct {
+    int32_t solver;    /* MCI_VEGASMC | MCI_MCMC */
+    int32_t nd;        /* nintegrand + 1 */
+    int32_t ndraw;     /* draws of a configuration (mci_problem_info) */
+    int32_t iteration; /* the iteration that stored the chains: first_iteration + niter - 1 of the storing call */
+    int32_t ntrain;    /* train! calls of the point's lineage before that iteration, counted through the states it came in with */
+    int32_t adapted;   /* the storing call ran with adapt = 1: train! refined the map once more behind that iteration */
+    int64_t blocks;    /* statistical blocks (mci_standardize_block) */
+    int64_t nchain;    /* stored chains per block, K */
+} mci_sweep_chain_info;
+/* ... and the states themselves.  rows: [npoint][mci_sweep_chain_state_doubles] doubles, the caller's memory.  A row holds the end
+ * configurations x [ndraw][blocks * nchain], then the targets P [blocks * nchain] (:vegasmc) or the integrand indices curr
+ * [blocks * nchain] as 32-bit integers padded with zero to a whole double followed by reweight_used [nd], the factors the stored
+ * chains ran under (:mcmc).  Opaque to callers: a row goes back in as it came out. */
+typedef struct {
+    mci_sweep_chain_info info;
+    double *rows;
+} mci_sweep_chain_state;
+/* doubles of one point's state row after a call with these arguments (blocks from args->neval and args->block, K = args->nchain);
+ * info, if not NULL, receives the record such a call would write with no state coming in.  MCI_ERR_INVALID where the chain sweep of
+ * args->solver refuses the arguments or args->nchain < 2 (nothing is carried with one chain per block). */
+int mci_sweep_chain_state_doubles(const mci_problem *prob, const mci_integrate_args *args, int64_t *doubles, mci_sweep_chain_info *info);
+/* MCI_OK when the chain sweep of args->solver (MCI_VEGASMC | MCI_MCMC) takes these arguments together with a state of this record
+ * (state may be NULL: the arguments alone, with states going out); else MCI_ERR_INVALID with the reason in why[n] (and in
+ * mci_last_error).  Beyond the refusals of mci_sweep_chains_supported | mci_sweep_mcmc_supported: the sweep chain carry is off
+ * (mci_set_sweep_chain_carry), nchain = 1 (nothing is carried with one chain per block), and a state that does not fit -- another
+ * solver, another block count, another layout (nd, ndraw), fewer than two stored chains per block, or a gap in the iteration numbers
+ * (state->iteration + 1 != args->first_iteration).  A state that does not fit is never dropped silently.  *continues, if not NULL:
+ * 1 when iteration 0 of such a call continues the stored chains, 0 when it starts afresh -- without a state, or under :vegasmc when
+ * the stored chains ran on a map that had never been refined in their lineage and the storing call refined it behind them (ntrain = 0
+ * and adapted = 1: the rule of mci_set_chain_carry). */
+int mci_sweep_chain_state_supported(const mci_problem *prob, const mci_integrate_args *args, const mci_sweep_chain_info *state, char *why,
+                                    int32_t n, int32_t *continues);
+/* mci_integrate_sweep_chains with carried chains (mci_set_sweep_chain_carry(prob, 1) is required) that travel between calls.  A point
+ * of a call with state_in is what mci_integrate(..., nchain = K, first_iteration = n) is on a problem with mci_set_chain_carry(prob, 1)
+ * and one lane per chain that has just run the earlier call: where mci_sweep_chain_state_supported says so, iteration 0 continues the
+ * state's K_old chains per block (K_old and K may differ) -- pi_new / pi_old at every stored configuration, the block resampled from
+ * K_old to K chains, the burn-in mci_chain_burnin(steps, 1, nslots) --, otherwise it starts afresh; iteration `it` >= 1 continues
+ * iteration it - 1 iff adapt is 0, or the lineage's map was refined before iteration it - 1 (it >= 2 without a state, it >= 1 with
+ * one).  A run split in two calls joined through maps_out -> maps_in, reweight_out -> reweight_in, state_out -> state_in and
+ * first_iteration is, byte for byte, the unsplit run.
+ *   state_in   NULL (iteration 0 starts afresh: with state_out NULL too, mci_integrate_sweep_chains itself) or the state_out of the
+ *              call before: state_in->info as it was written, state_in->rows [npoint][its row length]
+ *   state_out  NULL or: rows [npoint][mci_sweep_chain_state_doubles(args)] to be filled with the chains the last iteration stored;
+ *              info is written by the call
+ * Results: correlated = 1 whenever iteration 0 continued; stdev is the block-lineage error when niter > ignore + 1, as under
+ * mci_set_sweep_chain_carry.  A call whose iteration 0 continues runs a kernel of its own (MCI_VEGASMC_SWEEP_RESUME); the input rows
+ * and max(K_old, K) running weights per block count towards the 4 GiB. */
+int mci_integrate_sweep_chains_resume(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata,
+                                      const uint64_t *seeds, const double *maps_in, double *maps_out, const double *reweight_in,
+                                      double *reweight_out, double *pa_out, const mci_sweep_chain_state *state_in,
+                                      mci_sweep_chain_state *state_out, mci_result *results, double *iter_mean, double *iter_std,
+                                      int32_t *status);
+/* mci_integrate_sweep_mcmc likewise (MCI_MCMC_SWEEP_RESUME).  Iteration 0 of a call with a state that fits always continues: the
+ * block's stored chains are resampled from K_old to K with probability ~ reweight_now[curr] / reweight_used[curr], reweight_used being
+ * the state's, and run with nburn = 0 -- no iteration of such a call holds a burn-in. */
+int mci_integrate_sweep_mcmc_resume(mci_problem *prob, const mci_integrate_args *args, int32_t npoint, const double *userdata,
+                                    const uint64_t *seeds, const double *maps_in, double *maps_out, const double *reweight_in,
+                                    double *reweight_out, double *pa_out, uint64_t *holds_out, const mci_sweep_chain_state *state_in,
+                                    mci_sweep_chain_state *state_out, mci_result *results, double *iter_mean, double *iter_std,
+                                    int32_t *status);
 
 /* ---- state access: res.config.var[i].grid etc. (docs/src/index.md:129) and external reducers ---- */
 /* :mcmc diagnostic of the last launch (summed over the ranks when a communicator is attached: every rank sizes its chains from

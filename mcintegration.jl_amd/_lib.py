@@ -12,6 +12,7 @@ CONTINUOUS, DISCRETE, FERMIK = 0, 1, 2
 VEGAS, VEGASMC, MCMC = 0, 1, 2
 ABI_VERSION = 5   # include/mci.h MCI_ABI_VERSION
 SOLVERS = {"vegas": VEGAS, "vegasmc": VEGASMC, "mcmc": MCMC, VEGAS: VEGAS, VEGASMC: VEGASMC, MCMC: MCMC}
+SOLVER_NAMES = {VEGAS: "vegas", VEGASMC: "vegasmc", MCMC: "mcmc"}
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)
@@ -59,6 +60,15 @@ HOST_MEASURE_IDX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int32), c_double_p, c_d
 
 class SweepTarget(C.Structure):   # include/mci.h mci_sweep_target
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("min_niter", C.c_int32)]
+
+
+class SweepChainInfo(C.Structure):   # include/mci.h mci_sweep_chain_info
+    _fields_ = [("solver", C.c_int32), ("nd", C.c_int32), ("ndraw", C.c_int32), ("iteration", C.c_int32), ("ntrain", C.c_int32), ("adapted", C.c_int32),
+                ("blocks", C.c_int64), ("nchain", C.c_int64)]
+
+
+class SweepChainState(C.Structure):  # include/mci.h mci_sweep_chain_state
+    _fields_ = [("info", SweepChainInfo), ("rows", c_double_p)]
 
 
 class ResultC(C.Structure):
@@ -120,6 +130,14 @@ SIGNATURES = [
     ("mci_integrate_sweep_mcmc", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
                                            c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint64), C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_sweep_mcmc_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_char_p, C.c_int32]),
+    ("mci_sweep_chain_state_doubles", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(C.c_int64), C.POINTER(SweepChainInfo)]),
+    ("mci_sweep_chain_state_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepChainInfo), C.c_char_p, C.c_int32, c_int32_p]),
+    ("mci_integrate_sweep_chains_resume", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
+                                                    c_double_p, c_double_p, c_double_p, C.POINTER(SweepChainState), C.POINTER(SweepChainState),
+                                                    C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
+    ("mci_integrate_sweep_mcmc_resume", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p, c_double_p,
+                                                  c_double_p, c_double_p, c_double_p, C.POINTER(C.c_uint64), C.POINTER(SweepChainState), C.POINTER(SweepChainState),
+                                                  C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p]),
     ("mci_get_iteration_log", C.c_int, [_VP, C.c_int32, c_double_p]),
     ("mci_reserve_iteration_log", C.c_int, [_VP, C.c_int32]),
     ("mci_get_packed", C.c_int, [_VP, c_double_p, C.c_int64]),

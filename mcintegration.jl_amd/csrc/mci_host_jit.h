@@ -699,13 +699,13 @@ int mci_compile_solver(mci_problem *p, int32_t solver) {
         a.solver = MCI_VEGAS;
         a.measurefreq = 1;
         a.niter = 1;
-        if (w == mci_problem::Sweep::kChains || w == mci_problem::Sweep::kChainsCarry) { // (the layout alone, as below: any chain count the call may bring)
+        if (w == mci_problem::Sweep::kChains || w == mci_problem::Sweep::kChainsCarry || w == mci_problem::Sweep::kChainsResume) { // (the layout alone, as below: any chain count the call may bring)
             a.solver = MCI_VEGASMC;
             a.nchain = 1;
             a.neval = (int64_t)1 << 40;
             a.block = 1;
             if (int rc = mci_sweep_chains_supported(p, &a, nullptr, 0)) return rc;
-        } else if (w == mci_problem::Sweep::kMcmc || w == mci_problem::Sweep::kMcmcCarry) { // (likewise)
+        } else if (w == mci_problem::Sweep::kMcmc || w == mci_problem::Sweep::kMcmcCarry || w == mci_problem::Sweep::kMcmcResume) { // (likewise)
             a.solver = MCI_MCMC;
             a.nchain = 1;
             a.neval = (int64_t)1 << 30; // (steps + nburn of the one chain stay below 2^31 - 1)

@@ -192,7 +192,8 @@ static int compile_sweep_unit(mci_problem *p, int which) {
                                      std::string("the sweep kernel") + k.for_what + " came out with static LDS or scratch at " + std::to_string(T) + " threads per workgroup",
                                      "the sweep code object" + (tag.empty() ? tag : " (" + tag + ")")};
     // (the several-leaves and the chain solvers' units' LDS is the layout's; the two stratified units' is the call's: sweep_run)
-    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kLeavesUntil || (which >= mci_problem::Sweep::kChains && which < mci_problem::Sweep::kStratLeaves);
+    const bool whole_map = which == mci_problem::Sweep::kLeaves || which == mci_problem::Sweep::kLeavesUntil || (which >= mci_problem::Sweep::kChains && which < mci_problem::Sweep::kStratLeaves) ||
+                           which == mci_problem::Sweep::kChainsResume || which == mci_problem::Sweep::kMcmcResume;
     return u.load(p->ctx, c, mcijit::kUnits[k.jit_unit].kernel, which == mci_problem::Sweep::kLeavesUntil ? sweep_until_lds(p, nullptr) : whole_map ? sweep_leaves_lds(p, nullptr) : 0, rules);
 }
 
@@ -278,11 +279,12 @@ int mci_debug_sweep_resample_lds(const mci_problem *p, int64_t *lds_w) {
 namespace {
 // The sweep's one device buffer: doubles, segment by segment, every segment [npoint][doubles per point]; behind them the status words.
 // kSegOff, kSegTbase and kSegD are the stratified unit's, kSegRw and kSegPa the chain solvers' units', kSegHolds the :mcmc unit's,
-// kSegCarry (the stored chains, the picks, the weights) and kSegBlk (the block means) the carried chain units' (none otherwise), kSegSums
+// kSegCarry (the stored chains, the picks, the weights) and kSegBlk (the block means) the carried chain units' (none otherwise), kSegState
+// (the state rows a call came in with: read only) the units' that continue the chains of the call before, kSegSums
 // (every column's running W | sum w m) the `until` units'.  Everything from kSegGhist on is zeroed before the launch: histogram rows, d rows, holding-time histograms (64 words of 8
 // bytes per point), running sums, (the seeds: copied next), status words, and behind them in an `until` sweep the points' iteration
 // counts [npoint] and the cursor word.
-enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegCarry, kSegBlk, kSegGhist, kSegD, kSegHolds, kSegSums, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
+enum { kSegUd, kSegMapsIn, kSegMapsOut, kSegLog, kSegPart, kSegScratch, kSegPacked, kSegOff, kSegTbase, kSegRw, kSegPa, kSegCarry, kSegBlk, kSegState, kSegGhist, kSegD, kSegHolds, kSegSums, kSegSeeds, kSegStatus, kSegCount = kSegStatus };
 
 // What an entry point hands to sweep_run: the call's arguments as they came, and what its unit makes of them
 struct SweepCall {
@@ -309,6 +311,8 @@ struct SweepCall {
     size_t packed_doubles = 0;   // a point's packed row; 0: the statistics head alone
     size_t holds_doubles = 0;    // per point: kSegHolds (64 or none)
     size_t carry_doubles = 0, blk_doubles = 0; // per point: kSegCarry, kSegBlk (carried chains)
+    size_t state_doubles = 0;    // per point: kSegState (the state row iteration 0 continues)
+    bool first_continued = false; // iteration 0 continued the chains of the call before: every result is correlated
     const double *block_means = nullptr; // carried chains, set by finish(): [npoint][niter][blocks][nobs] on the host -- the points' errors come from their blocks' lineages
     int maxn = 0;                // bins of the largest leaf
     int64_t lds = 0;             // bytes of LDS of a workgroup
@@ -336,7 +340,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
     if ((rc = c.plan(c))) return rc;
     const size_t P = (size_t)npoint, rows = (size_t)c.rows * s.ncols;
     const size_t per_point[kSegCount] = {(size_t)nud, c.maps_in ? c.map_doubles : 0, c.map_doubles, (size_t)niter * nstat, rows, rows, c.packed_doubles ? c.packed_doubles : (size_t)nstat,
-                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, c.carry_doubles, c.blk_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.until ? 2 * (size_t)s.nobs : 0,
+                                         c.off_doubles,  c.tbase_doubles, c.rw_doubles, c.pa_doubles, c.carry_doubles, c.blk_doubles, c.state_doubles, (size_t)s.nbin, c.d_doubles, c.holds_doubles, c.until ? 2 * (size_t)s.nobs : 0,
                                          c.seeds ? (size_t)1 : 0};
     size_t o[kSegCount + 1] = {0};
     for (int k = 0; k < kSegCount; ++k) o[k + 1] = o[k] + P * per_point[k];
@@ -482,6 +486,7 @@ int sweep_run(mci_problem *p, const mci_integrate_args *a, SweepCall &c) {
             for (int o2 = 0; o2 < s.nobs; ++o2) res->stdev[o2] = le[o2] > 0.0 ? le[o2] : res->stdev[o2];
             res->correlated = 1;
         }
+        if (c.first_continued) res->correlated = 1; // (even where the call is too short for a lineage error)
         if (c.status) c.status[q] = hst[q];
     }
     return MCI_OK;
@@ -870,30 +875,105 @@ int sweep_chains_query(const mci_problem *p, const mci_integrate_args *a, char *
     return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep of %s points: %s", solver == MCI_MCMC ? ":mcmc" : ":vegasmc", r);
 }
 
+// doubles of one point's chain state row (include/mci.h mci_sweep_chain_state; mci_sweep_chains.h SweepResumeArgs): x [ndraw][cap] | P [cap]
+// (:vegasmc) or curr [cap] ints on whole doubles | reweight_used [nd] (:mcmc)
+size_t sweep_state_doubles(int ndraw, int nd, int64_t blocks, int64_t nchain, bool mcmc) {
+    const size_t cap = (size_t)blocks * (size_t)nchain;
+    return (size_t)ndraw * cap + (mcmc ? (cap + 1) / 2 + (size_t)nd : cap);
+}
+// what the *_resume entry points refuse beyond sweep_chains_refusal, and whether iteration 0 continues the state's chains: plan_may_carry
+// (mci_host_plan.h) with the state's record in place of launch.chain_*
+const char *sweep_state_refusal(const mci_problem *p, const mci_integrate_args *a, const mci_sweep_chain_info *st, std::string &buf, bool *continues) {
+    const bool mcmc = a->solver == MCI_MCMC;
+    *continues = false;
+    if (const char *r = sweep_chains_refusal(p, a, buf, mcmc ? MCI_MCMC : MCI_VEGASMC)) return r;
+    if (!p->sweep.chain_carry) return "the sweep chain carry is off (mci_set_sweep_chain_carry(prob, 1) first: only carried chains travel between calls)";
+    if (a->nchain == 1) return "nchain = 1 together with a chain state (nothing is carried with one chain per block)";
+    if (!st) return nullptr;
+    int64_t npb, blocks;
+    mci_standardize_block(a->neval, a->block, 1, &npb, &blocks);
+    if (st->solver != a->solver) {
+        buf = std::string("the state is another solver's (stored under ") + (st->solver == MCI_MCMC ? ":mcmc" : st->solver == MCI_VEGASMC ? ":vegasmc" : "an unknown solver") +
+              ", the call runs " + (mcmc ? ":mcmc" : ":vegasmc") + ")";
+        return buf.c_str();
+    }
+    if (st->blocks != blocks) {
+        buf = "the state holds another block count (" + std::to_string((long long)st->blocks) + " blocks stored, the call runs " + std::to_string((long long)blocks) + ")";
+        return buf.c_str();
+    }
+    if (st->nd != p->ni + 1 || st->ndraw != p->shape.ndraw) {
+        buf = "the state is another layout's (nd = " + std::to_string(st->nd) + ", ndraw = " + std::to_string(st->ndraw) + " stored, the problem has nd = " +
+              std::to_string(p->ni + 1) + ", ndraw = " + std::to_string(p->shape.ndraw) + ")";
+        return buf.c_str();
+    }
+    if (st->nchain < 2) {
+        buf = "the state holds " + std::to_string((long long)st->nchain) + " chains per block (nothing is carried with fewer than two)";
+        return buf.c_str();
+    }
+    if (st->nchain > ((int64_t)1 << 31) / blocks) { // (blocks >= 1: sweep_chains_refusal took neval > block)
+        buf = "the state holds " + std::to_string((long long)st->nchain) + " chains per block (blocks x chains is addressed in 32 bits)";
+        return buf.c_str();
+    }
+    if (st->ntrain < 0 || st->iteration < 0) return "the state's record is damaged (a negative iteration or train! count)";
+    if ((int64_t)st->iteration + 1 != (int64_t)a->first_iteration) {
+        buf = "a gap in the iteration numbers (the state was stored by iteration " + std::to_string(st->iteration) + ", the call starts at first_iteration = " +
+              std::to_string((long long)a->first_iteration) + ": " + std::to_string(st->iteration + 1) + " continues it)";
+        return buf.c_str();
+    }
+    // (:vegasmc: not out of an iteration on the never-refined map onto a refined one -- chain_ntrain >= 1 || chain_ntrain == ntrain)
+    *continues = mcmc || st->ntrain >= 1 || !st->adapted;
+    return nullptr;
+}
+
 // P independent chain-solver integrate() loops (main.jl:142-207 around vegas_mc/montecarlo.jl:112-241 | mcmc/montecarlo.jl:72-187), one
 // workgroup each, in one launch.  What the two entry points share; solver: MCI_VEGASMC | MCI_MCMC (holds_out: the latter's)
 static_assert(offsetof(mci::SweepChainArgs, h) == 0, "sweep_run fills the chain units' argument through its head");
 static_assert(offsetof(mci::SweepChainCarryArgs, c) == 0, "one object serves the four chain units: the uncarried ones read its first member");
 int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solver, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
                       double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, uint64_t *holds_out, mci_result *results,
-                      double *iter_mean, double *iter_std, int32_t *status) {
+                      double *iter_mean, double *iter_std, int32_t *status, const mci_sweep_chain_state *state_in = nullptr, mci_sweep_chain_state *state_out = nullptr) {
     const bool mcmc = solver == MCI_MCMC;
+    // chains that travel between calls (the *_resume entry points): the state's record against the call's, first -- a refusal is the same
+    // with and without a device
+    bool first_cont = false; // iteration 0 continues the state's chains
+    int ntrain0 = 0;         // train! calls of the points' lineage before iteration 0
+    int64_t k_old = 0;
+    size_t state_row_in = 0;
+    if (state_in || state_out) {
+        if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+        if ((state_in && !state_in->rows) || (state_out && !state_out->rows)) return fail(MCI_ERR_INVALID, "a chain state without rows");
+        if (a->solver != solver) return fail(MCI_ERR_INVALID, "this problem cannot run as a sweep of %s points: %s", mcmc ? ":mcmc" : ":vegasmc", mcmc ? "solver is not :mcmc" : "solver is not :vegasmc");
+        int32_t cont = 0;
+        if (int rc = mci_sweep_chain_state_supported(p, a, state_in ? &state_in->info : nullptr, nullptr, 0, &cont)) return rc;
+        first_cont = cont != 0;
+        if (state_in) {
+            ntrain0 = state_in->info.ntrain + (state_in->info.adapted ? 1 : 0);
+            k_old = state_in->info.nchain;
+            state_row_in = sweep_state_doubles(state_in->info.ndraw, state_in->info.nd, state_in->info.blocks, k_old, mcmc);
+        }
+    }
     if (int rc = sweep_check_args(p, a, npoint, userdata, results, mcmc ? mci_sweep_mcmc_supported : mci_sweep_chains_supported)) return rc;
     const size_t P = (size_t)npoint, nd = (size_t)p->ni + 1, npa2 = 2 * (size_t)p->npa;
     const size_t tables = (size_t)p->nstat + p->shape.nbin; // where merge_pa leaves them in a packed row (mci_train.h)
-    mci::SweepChainCarryArgs fa{}; // (the uncarried units' argument is its first member)
+    mci::SweepChainResumeArgs fa{}; // (the uncarried units' argument is its first member, the carried units' its first two)
     mci::SweepChainArgs &f = fa.c;
     mci::SweepCarryArgs &fk = fa.k;
+    mci::SweepResumeArgs &fr = fa.r;
     std::vector<double> hrw, hbm;
     SweepCall c;
     // mci_set_sweep_chain_carry: the units with carried chains.  What a point keeps between its iterations, per point, in doubles of
     // kSegCarry (cap = blocks * nchain stored chains a buffer): x [2][ndraw][cap] | P [2][cap] (:vegasmc) or curr [2][cap] ints (:mcmc) |
     // W [cap] | w [cap] (:vegasmc) or reweight_used [nd] (:mcmc) | src [cap] ints
     const bool carry = p->sweep.chain_carry != 0;
-    const int carry_first = (mcmc || !a->adapt) ? 1 : 2; // (plan_may_carry: :vegasmc not out of the iteration on the map before its first refinement)
-    const bool carried = carry && a->nchain > 1 && a->niter > carry_first; // some iteration of every point continues the one before
-    size_t cx = 0, cp = 0, cw = 0, cw2 = 0, csrc = 0; // offsets of the parts behind x, doubles
+    // (... nor, with a state, where the lineage's map was refined before iteration 0 already: ntrain0 >= 1)
+    const int carry_first = (mcmc || !a->adapt || ntrain0 >= 1) ? 1 : 2; // (plan_may_carry: :vegasmc not out of the iteration on the map before its first refinement)
+    const bool carried = carry && a->nchain > 1 && (a->niter > carry_first || first_cont); // some iteration of every point continues the one before
+    size_t cx = 0, cp = 0, cw = 0, cw2 = 0, csrc = 0, wcap = 0; // offsets of the parts behind x, doubles; a point's running weights
     c.unit = carry ? (mcmc ? mci_problem::Sweep::kMcmcCarry : mci_problem::Sweep::kChainsCarry) : (mcmc ? mci_problem::Sweep::kMcmc : mci_problem::Sweep::kChains);
+    if (first_cont) c.unit = mcmc ? mci_problem::Sweep::kMcmcResume : mci_problem::Sweep::kChainsResume; // (the carry setting is on: the query)
+    c.first_continued = first_cont;
+    c.state_doubles = first_cont ? state_row_in : 0;
+    size_t state_row_out = 0;
     c.npoint = npoint, c.userdata = userdata, c.seeds = seeds, c.maps_in = maps_in, c.maps_out = maps_out;
     c.results = results, c.iter_mean = iter_mean, c.iter_std = iter_std, c.status = status;
     c.plan = [&, a, npa2](SweepCall &c) {
@@ -903,11 +983,13 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
         c.too_big_count = (long long)c.blocks;
         if (carry) {
             const size_t cap = (size_t)c.blocks * (size_t)a->nchain, half = (cap + 1) / 2;
+            wcap = first_cont && k_old > a->nchain ? (size_t)c.blocks * (size_t)k_old : cap; // (iteration 0 weighs the state's K_old chains a block)
             cx = 2 * (size_t)p->shape.ndraw * cap;
             cp = cx;                            // P [2][cap] | curr [2][cap] ints
             cw = cp + (mcmc ? 2 * half : 2 * cap);
-            cw2 = cw + cap;                     // w [cap] | reweight_used [nd]
-            csrc = cw2 + (mcmc ? nd : cap);
+            cw2 = cw + wcap;                    // w [wcap] | reweight_used [nd]
+            csrc = cw2 + (mcmc ? nd : wcap);
+            state_row_out = sweep_state_doubles(p->shape.ndraw, (int)nd, c.blocks, a->nchain, mcmc);
             c.carry_doubles = csrc + half;
             c.blk_doubles = (size_t)a->niter * (size_t)c.blocks * (size_t)p->shape.nobs;
             hbm.resize(carried ? P * c.blk_doubles : 0);
@@ -935,6 +1017,7 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
             for (size_t q = 1; q < P; ++q) memcpy(hrw.data() + q * nd, hrw.data(), nd * sizeof(double));
         }
         HIPCHK(hipMemcpyAsync(d + o[kSegRw], reweight_in ? reweight_in : hrw.data(), P * nd * sizeof(double), hipMemcpyHostToDevice, st));
+        if (first_cont) HIPCHK(hipMemcpyAsync(d + o[kSegState], state_in->rows, P * state_row_in * sizeof(double), hipMemcpyHostToDevice, st));
         return (int)MCI_OK;
     };
     c.args = [&, p, a](const mci::SweepHead &h, double *d, const size_t *o) -> void * {
@@ -956,9 +1039,9 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
             if (mcmc) fk.chain_curr = reinterpret_cast<int *>(g), g += P * 2 * half;
             else fk.chain_P = g, g += P * 2 * cap;
             fk.carry_W = g;
-            g += P * cap;
+            g += P * wcap;
             if (mcmc) fk.rw_used = g, g += P * nd;
-            else fk.carry_w = g, g += P * cap;
+            else fk.carry_w = g, g += P * wcap;
             fk.carry_src = reinterpret_cast<int *>(g);
             fk.block_means = d + o[kSegBlk];
             const int64_t steps = c.neval_per_block / a->nchain;
@@ -966,6 +1049,12 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
             fk.burnin_carried = mci_chain_burnin(steps, 1, sweep_nslots(p)); // plan_vegasmc_chains: the reference's own neval / 100
             fk.carry_first = carry_first;
             fk.lds_w = sweep_resample_lds(c.map_off);
+            if (first_cont) {
+                fr.state_in = d + o[kSegState];
+                fr.state_stride = (mci::i64)state_row_in;
+                fr.nchain_old = k_old;
+                fr.wcap = (mci::i64)wcap;
+            }
         }
         return &fa;
     };
@@ -976,10 +1065,33 @@ int sweep_chains_call(mci_problem *p, const mci_integrate_args *a, int32_t solve
                                     hipMemcpyDeviceToHost, st));
         if (mcmc && holds_out) HIPCHK(hipMemcpyAsync(holds_out, d + o[kSegHolds], P * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         if (!hbm.empty()) HIPCHK(hipMemcpyAsync(hbm.data(), d + o[kSegBlk], hbm.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (state_out) { // the buffer the last iteration wrote, part by part into every point's row (the padding behind an odd count of indices: zero)
+            const size_t cap = (size_t)c.blocks * (size_t)a->nchain, half = (cap + 1) / 2, nx = (size_t)p->shape.ndraw * cap, wb = (size_t)(a->niter - 1) & 1;
+            const size_t row = state_row_out * sizeof(double);
+            memset(state_out->rows, 0, P * row);
+            HIPCHK(hipMemcpy2DAsync(state_out->rows, row, fk.chain_x + wb * nx, 2 * nx * sizeof(double), nx * sizeof(double), P, hipMemcpyDeviceToHost, st));
+            if (mcmc) {
+                HIPCHK(hipMemcpy2DAsync(state_out->rows + nx, row, fk.chain_curr + wb * cap, 2 * cap * sizeof(int), cap * sizeof(int), P, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpy2DAsync(state_out->rows + nx + half, row, fk.rw_used, nd * sizeof(double), nd * sizeof(double), P, hipMemcpyDeviceToHost, st));
+            } else
+                HIPCHK(hipMemcpy2DAsync(state_out->rows + nx, row, fk.chain_P + wb * cap, 2 * cap * sizeof(double), cap * sizeof(double), P, hipMemcpyDeviceToHost, st));
+        }
         return (int)MCI_OK;
     };
     c.finish = [&] { c.block_means = hbm.empty() ? nullptr : hbm.data(); };
-    return sweep_run(p, a, c);
+    if (int rc = sweep_run(p, a, c)) return rc;
+    if (state_out) { // the record of what the rows hold: plan_may_carry's fields for the next call
+        mci_sweep_chain_info &si = state_out->info;
+        si.solver = solver;
+        si.nd = (int32_t)nd;
+        si.ndraw = p->shape.ndraw;
+        si.iteration = a->first_iteration + a->niter - 1;
+        si.ntrain = ntrain0 + (a->adapt ? a->niter - 1 : 0);
+        si.adapted = a->adapt ? 1 : 0;
+        si.blocks = c.blocks;
+        si.nchain = a->nchain;
+    }
+    return MCI_OK;
 }
 } // namespace
 
@@ -990,6 +1102,42 @@ int mci_integrate_sweep_chains(mci_problem *p, const mci_integrate_args *a, int3
                                double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, mci_result *results, double *iter_mean,
                                double *iter_std, int32_t *status) {
     return sweep_chains_call(p, a, MCI_VEGASMC, npoint, userdata, seeds, maps_in, maps_out, reweight_in, reweight_out, pa_out, nullptr, results, iter_mean, iter_std, status);
+}
+int mci_sweep_chain_state_supported(const mci_problem *p, const mci_integrate_args *a, const mci_sweep_chain_info *state, char *why, int32_t n, int32_t *continues) {
+    if (why && n > 0) why[0] = 0;
+    if (continues) *continues = 0;
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    std::string buf;
+    bool cont = false;
+    const char *r = sweep_state_refusal(p, a, state, buf, &cont);
+    if (!r) {
+        if (continues) *continues = cont ? 1 : 0;
+        return MCI_OK;
+    }
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
+    return fail(MCI_ERR_INVALID, "this chain sweep cannot go on from a chain state: %s", r);
+}
+int mci_sweep_chain_state_doubles(const mci_problem *p, const mci_integrate_args *a, int64_t *doubles, mci_sweep_chain_info *info) {
+    if (!p || !a || !doubles) return fail(MCI_ERR_INVALID, "NULL argument");
+    const bool mcmc = a->solver == MCI_MCMC;
+    if (int rc = sweep_chains_query(p, a, nullptr, 0, mcmc ? MCI_MCMC : MCI_VEGASMC)) return rc;
+    if (a->nchain < 2) return fail(MCI_ERR_INVALID, "this chain sweep cannot go on from a chain state: nchain = 1 together with a chain state (nothing is carried with one chain per block)");
+    int64_t npb, blocks;
+    mci_standardize_block(a->neval, a->block, 1, &npb, &blocks);
+    *doubles = (int64_t)sweep_state_doubles(p->shape.ndraw, p->ni + 1, blocks, a->nchain, mcmc);
+    if (info) *info = mci_sweep_chain_info{a->solver, p->ni + 1, p->shape.ndraw, a->first_iteration + a->niter - 1, a->adapt ? a->niter - 1 : 0, a->adapt ? 1 : 0, blocks, a->nchain};
+    return MCI_OK;
+}
+int mci_integrate_sweep_chains_resume(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                                      double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, const mci_sweep_chain_state *state_in,
+                                      mci_sweep_chain_state *state_out, mci_result *results, double *iter_mean, double *iter_std, int32_t *status) {
+    return sweep_chains_call(p, a, MCI_VEGASMC, npoint, userdata, seeds, maps_in, maps_out, reweight_in, reweight_out, pa_out, nullptr, results, iter_mean, iter_std, status, state_in, state_out);
+}
+int mci_integrate_sweep_mcmc_resume(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,
+                                    double *maps_out, const double *reweight_in, double *reweight_out, double *pa_out, uint64_t *holds_out,
+                                    const mci_sweep_chain_state *state_in, mci_sweep_chain_state *state_out, mci_result *results, double *iter_mean, double *iter_std,
+                                    int32_t *status) {
+    return sweep_chains_call(p, a, MCI_MCMC, npoint, userdata, seeds, maps_in, maps_out, reweight_in, reweight_out, pa_out, holds_out, results, iter_mean, iter_std, status, state_in, state_out);
 }
 // mcmc/montecarlo.jl:72-187, mcmc/updates.jl, main.jl:183, :322-346
 int mci_integrate_sweep_mcmc(mci_problem *p, const mci_integrate_args *a, int32_t npoint, const double *userdata, const uint64_t *seeds, const double *maps_in,

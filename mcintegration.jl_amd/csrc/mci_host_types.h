@@ -169,9 +169,9 @@ struct mci_problem {
     // one code object per unit, JIT-compiled (or loaded from the kernel cache) the first time it is needed
     // kernel slots (kslot): :vegas for measurefreq == 1 | :vegasmc | :mcmc | :vegas for any measurefreq | sample dump
     //                      | :vegasmc with several lanes per chain | :mcmc with several lanes per chain (mci_spec.h)
-    // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the ten sweep units (Sweep)
+    // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the twelve sweep units (Sweep)
     // ... and the big :vegas unit (sixteen histogram copies, 1024 threads: mci_host_vegas_plan.h VegasBigUnit)
-    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kVegasBig = kSweep + 10, kKernels = kVegasBig + 1 };
+    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kVegasBig = kSweep + 12, kKernels = kVegasBig + 1 };
     KernelUnit kernel[kKernels];
     VegasKernelPlan vegas; // which :vegas code object the launches run (mci_host_vegas_plan.h)
     VegasBigUnit vegas_big; // ... and whether big launches have a third one to run (kernel[kVegasBig])
@@ -419,14 +419,15 @@ struct mci_problem {
         double *hstart = nullptr;
         int64_t hstart_n = 0;
     } strat;
-    // Batched parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat, mci_integrate_sweep_chains, mci_integrate_sweep_mcmc, mci_integrate_sweep_until; mci_host_sweep.h): the ten sweep units are
+    // Batched parameter sweeps (mci_integrate_sweep, mci_integrate_sweep_strat, mci_integrate_sweep_chains, mci_integrate_sweep_mcmc, mci_integrate_sweep_until; mci_host_sweep.h): the twelve sweep units are
     // kernel[kSweep + which].  A sweep keeps nothing else here: its maps, logs and status words come in and go out through the call's arguments.
     struct Sweep {
         // mci_sweep.h (one Continuous grid) | mci_sweep_leaves.h (any mix of Continuous and Discrete leaves) | mci_sweep_strat.h
         // (stratified points) | mci_sweep_chains.h (:vegasmc points | :mcmc points, fresh | carried chains) | mci_sweep_strat_leaves.h
         // (stratified points, several Continuous leaves) | mci_sweep.h, mci_sweep_leaves.h again (a target error per point:
-        // mci_integrate_sweep_until): mci_host_sweep.h kSweepUnits describes them in this order
-        enum { kOne = 0, kLeaves = 1, kStrat = 2, kChains = 3, kMcmc = 4, kChainsCarry = 5, kMcmcCarry = 6, kStratLeaves = 7, kUntil = 8, kLeavesUntil = 9, kUnits = 10 };
+        // mci_integrate_sweep_until) | mci_sweep_chains.h again (carried chains that go on from the call before:
+        // mci_integrate_sweep_chains_resume | mci_integrate_sweep_mcmc_resume): mci_host_sweep.h kSweepUnits describes them in this order
+        enum { kOne = 0, kLeaves = 1, kStrat = 2, kChains = 3, kMcmc = 4, kChainsCarry = 5, kMcmcCarry = 6, kStratLeaves = 7, kUntil = 8, kLeavesUntil = 9, kChainsResume = 10, kMcmcResume = 11, kUnits = 12 };
         int grid = 0;                 // csrc/mci_debug.h mci_debug_sweep_workgroups: workgroups of the next sweeps, 0 = the default
         int want_threads = 0;         // ... mci_debug_sweep_threads: 256 | 512 | 1024, 0 = the default (the one-grid unit only)
         int last_grid = 0, last_threads = 0;
@@ -444,7 +445,7 @@ struct mci_problem {
     static_assert(kVegasBig == kSweep + Sweep::kUnits, "one handle per sweep unit");
 };
 
-// The ten sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
+// The twelve sweep units, in the order of mci_problem::Sweep::unit: everything that tells them apart when they are compiled, loaded and
 // named (mci_host_sweep.h compile_sweep_unit; mci_host_jit.h mci_compile_solver, mci_kernel_code_object).  The headers, the kernel symbol
 // and the #defines are the JIT unit's row (mci_jit.h kUnits).
 struct SweepUnitDesc {
@@ -467,6 +468,8 @@ static const SweepUnitDesc kSweepUnits[mci_problem::Sweep::kUnits] = {
     {mcijit::kUnitSweepStratLeaves, MCI_VEGAS_SWEEP_STRAT_LEAVES, MCI_VEGAS, "stratified points, several leaves", " for stratified points with several leaves", false, false},
     {mcijit::kUnitSweepUntil, MCI_VEGAS_SWEEP_UNTIL, MCI_VEGAS, "a target error per point", " with a target error per point", true, false},
     {mcijit::kUnitSweepLeavesUntil, MCI_VEGAS_SWEEP_LEAVES_UNTIL, MCI_VEGAS, "several leaves, a target error per point", " for several leaves with a target error per point", false, false},
+    {mcijit::kUnitSweepChainsResume, MCI_VEGASMC_SWEEP_RESUME, MCI_VEGASMC, ":vegasmc points, chains of the call before", " for :vegasmc points that continue the chains of the call before", false, false},
+    {mcijit::kUnitSweepMcmcResume, MCI_MCMC_SWEEP_RESUME, MCI_MCMC, ":mcmc points, chains of the call before", " for :mcmc points that continue the chains of the call before", false, false},
 };
 static int sweep_unit_of(int32_t solver) {
     for (int w = 0; w < mci_problem::Sweep::kUnits; ++w)

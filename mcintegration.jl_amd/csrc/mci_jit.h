@@ -124,8 +124,11 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // (mci_set_sweep_strat_leaves); compiled like kUnitSweepLeaves (scan walk, every leaf's own learning rate) without MCI_WORK_ITEM_FROM_CALLER
 // kUnitSweepUntil, kUnitSweepLeavesUntil: kUnitSweep and kUnitSweepLeaves with a target error per point (mci_sweep.h vegas_sweep<Cfg, true>,
 // mci_sweep_leaves.h vegas_sweep_leaves<Cfg, true>; mci_integrate_sweep_until): kernels and code objects of their own, compiled like them
-// The ten sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitSweepStratLeaves = 13, kUnitSweepUntil = 14, kUnitSweepLeavesUntil = 15, kUnitCount = 16 };
+// kUnitSweepChainsResume, kUnitSweepMcmcResume: the two carried units with a first iteration that continues the chains of the call before
+// (mci_sweep_chains.h chain_sweep<Cfg, MCMC, true, true>; mci_integrate_sweep_chains_resume | mci_integrate_sweep_mcmc_resume): kernels and
+// code objects of their own, compiled like them
+// The twelve sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitSweepStratLeaves = 13, kUnitSweepUntil = 14, kUnitSweepLeavesUntil = 15, kUnitSweepChainsResume = 16, kUnitSweepMcmcResume = 17, kUnitCount = 18 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -163,6 +166,8 @@ constexpr UnitRow kUnits[] = {
     /* kUnitSweepStratLeaves */ {"mci_sweep_strat_leaves.h", {{"mci_strat.h", &kStratHeader}, MCI_HDR_SWEEP, {"mci_sweep_strat.h", &kSweepStratHeader}, {"mci_sweep_strat_leaves.h", &kSweepStratLeavesHeader}}, "mci_vegas_sweep_strat_leaves", "SweepStratArgs", "f", "vegas_sweep_strat_leaves", 1, false, 2, true, false, false},
     /* kUnitSweepUntil       */ {"mci_sweep.h", {MCI_HDR_SWEEP, {"mci_sweep.h", &kSweepHeader}}, "mci_vegas_sweep_until", "SweepUntilArgs", "f", "vegas_sweep_until", 1, true, 1, true, true, true},
     /* kUnitSweepLeavesUntil */ {"mci_sweep_leaves.h", {MCI_HDR_SWEEP, {"mci_sweep_leaves.h", &kSweepLeavesHeader}}, "mci_vegas_sweep_leaves_until", "SweepUntilArgs", "f", "vegas_sweep_leaves_until", 1, false, 2, true, false, true},
+    /* kUnitSweepChainsResume */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep_resume", "SweepChainResumeArgs", "f", "vegasmc_sweep_resume", -1, false, 2, true, false, true},
+    /* kUnitSweepMcmcResume   */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep_resume", "SweepChainResumeArgs", "f", "mcmc_sweep_resume", -1, false, 2, true, false, true},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN

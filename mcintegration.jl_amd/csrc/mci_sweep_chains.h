@@ -55,6 +55,17 @@
 // resampling, carry_src -> chain starts, reweight_used -> resampling (the round trips of the leaves' histogram slices).  merge_stats writes
 // the blocks' means of every iteration (MergeArgs::block_means) for the host's block-lineage error (mci_lineage_sums).
 //
+// Chains that go on from the call before (chain_sweep<Cfg, MCMC, true, true>: the units kUnitSweepChainsResume | kUnitSweepMcmcResume, the
+// entry points mci_integrate_sweep_chains_resume | mci_integrate_sweep_mcmc_resume; the four units above keep their instructions --
+// everything below stands under `if constexpr (RESUME)` and reads an argument of its own, SweepResumeArgs).  What is said above remains
+// true of mci_integrate_sweep_chains | mci_integrate_sweep_mcmc; through the new entry points a point's chain ends go out behind the launch
+// (the host copies the buffer the last iteration wrote, (niter - 1) & 1) and come in again as a read-only input segment.  Iteration 0 of a
+// point then continues the K_old stored chains per block of its state row where the host found the state to fit (plan_may_carry with the
+// state's record in place of the problem's): carry_x | carry_curr | carry_P | carry_nchain | carry_cap | carry_total and ResampleArgs::n_old
+// are the state's (K_old, stride blocks * K_old), store_* and n_new the call's K, reweight_used (:mcmc) the state's factors, and the
+// resampler's LDS limit (lds_w) is held against K_old.  From iteration 1 on the body is the carried unit's.  The input segment is only
+// read, so the ordering argument of mci_sweep_common.h holds as written; carry_W and carry_w have room for max(K_old, K) chains a block.
+//
 // LDS: the chain loop's carve Lds<Cfg> (tables | histogram | observables | reduction scratch | propose / accept counters) and the
 // refinement's scratch share the front of the segment -- each is dead while the other runs --, the point's map block lies behind both
 // (SweepHead::map_off; the host's sweep_leaves_lds counts the carve including the counters).
@@ -91,6 +102,20 @@ struct SweepChainCarryArgs {
     SweepChainArgs c; // (first: the host fills one object for all four units)
     SweepCarryArgs k;
 };
+// the third part of the argument of the two units whose first iteration continues the chains of the call before: the two above, then
+// the states the points come in with.  A point's row: x [ndraw][blocks * nchain_old] | P [blocks * nchain_old] (:vegasmc) or curr
+// [blocks * nchain_old] ints, padded to a double, and reweight_used [nd] (:mcmc)
+struct SweepResumeArgs {
+    const double *state_in; // [npoint][state_stride]  read only
+    i64 state_stride;       // doubles of a row
+    i64 nchain_old;         // stored chains per block, > 1
+    i64 wcap;               // doubles of a point's carry_W | carry_w row: blocks * max(nchain_old, nchain)
+};
+struct SweepChainResumeArgs {
+    SweepChainArgs c; // (the layout of SweepChainCarryArgs, then the states)
+    SweepCarryArgs k;
+    SweepResumeArgs r;
+};
 
 // pi_new / pi_old of block lb's stored chains: the workgroup's lanes stride over them (vegasmc_carry_weights for one block)
 template <class Cfg> __device__ __forceinline__ void carry_weights_block(const BatchArgs &a, const i64 lb) {
@@ -110,7 +135,9 @@ template <class Cfg> __device__ __forceinline__ void carry_weights_block(const B
     for (i64 from = tid; from < a.carry_nchain; from += T) vegasmc_carry_weight<Cfg>(a, t, rw, lb * a.carry_nchain + from);
 }
 
-template <class Cfg, bool MCMC, bool CARRY = false> __device__ __forceinline__ void chain_sweep(const BatchArgs &a0, const SweepChainArgs &fc, const SweepCarryArgs *kp = nullptr) {
+template <class Cfg, bool MCMC, bool CARRY = false, bool RESUME = false>
+__device__ __forceinline__ void chain_sweep(const BatchArgs &a0, const SweepChainArgs &fc, const SweepCarryArgs *kp = nullptr, const SweepResumeArgs *rp = nullptr) {
+    static_assert(CARRY || !RESUME, "only carried chains go on from a state");
     static_assert(Cfg::NLEAF >= 1 && sweep_kinds_ok<Cfg>() && Cfg::NTILE == 1 && Cfg::TABLE_MODE == 0 && Cfg::HCOPY == 1 && Cfg::DET == 0 && Cfg::EC_DOUBLES == 0 &&
                       Cfg::HOST_MEASURE == 0 && Cfg::HOST_INTEGRAND == 0,
                   "a sweep point keeps Continuous and Discrete leaves, their tables and one histogram tile in LDS, and measures on the device (the host checks)");
@@ -152,9 +179,14 @@ template <class Cfg, bool MCMC, bool CARRY = false> __device__ __forceinline__ v
             a.iteration = a0.iteration + (u32)it;
             if (tid == 0) bad[0] = 0;
             bool cont = false; // this iteration's chains continue those of the one before
+            bool first = false; // ... those of the call before: the point's state row
             if constexpr (CARRY) {
                 const SweepCarryArgs &fk = *kp;
                 cont = keep && it >= fk.carry_first;
+                if constexpr (RESUME) {
+                    first = keep && it == 0;
+                    cont = cont || first;
+                }
                 if (keep) {
                     const int wb = it & 1;
                     double *x2 = fk.chain_x + (size_t)p * 2 * Cfg::NDRAW * cap;
@@ -175,6 +207,22 @@ template <class Cfg, bool MCMC, bool CARRY = false> __device__ __forceinline__ v
                         a.carry_total = cap;
                         a.burnin = cont ? fk.burnin_carried : a0.burnin;
                     }
+                    if constexpr (RESUME) {
+                        const SweepResumeArgs &fr = *rp;
+                        if constexpr (!MCMC) a.carry_w = fk.carry_w + (size_t)p * fr.wcap;
+                        if (first) { // the stored side is the state's: nchain_old chains a block, a row of its own
+                            const i64 cap_old = (i64)nblocks * fr.nchain_old;
+                            const double *row = fr.state_in + (size_t)p * fr.state_stride;
+                            a.carry_x = row;
+                            a.carry_nchain = fr.nchain_old;
+                            a.carry_cap = cap_old;
+                            if constexpr (MCMC) a.carry_curr = reinterpret_cast<const int *>(row + (size_t)Cfg::NDRAW * cap_old);
+                            else {
+                                a.carry_P = row + (size_t)Cfg::NDRAW * cap_old;
+                                a.carry_total = cap_old;
+                            }
+                        }
+                    }
                 }
                 m.block_means = fk.block_means + ((size_t)p * f.niter + it) * nblocks * f.m.nobs;
             }
@@ -192,6 +240,15 @@ template <class Cfg, bool MCMC, bool CARRY = false> __device__ __forceinline__ v
                         ra.src = fk.carry_src + (size_t)p * cap;
                         ra.W = fk.carry_W + (size_t)p * cap;
                         ra.w_chain = nullptr;
+                        if constexpr (RESUME) {
+                            const SweepResumeArgs &fr = *rp;
+                            ra.W = fk.carry_W + (size_t)p * fr.wcap;
+                            if (first) {
+                                ra.n_old = fr.nchain_old;
+                                if constexpr (MCMC) // (behind the integrand indices, which end on a double)
+                                    ra.rw_used = fr.state_in + (size_t)p * fr.state_stride + (size_t)Cfg::NDRAW * nblocks * fr.nchain_old + ((size_t)nblocks * fr.nchain_old + 1) / 2;
+                            }
+                        }
                         __syncthreads(); // (whatever read the front of the LDS segment before is through)
                         if constexpr (!MCMC) {
                             carry_weights_block<Cfg>(a, b);
@@ -240,5 +297,8 @@ template <class Cfg> __device__ __forceinline__ void mcmc_sweep(const BatchArgs 
 // ... and with chains carried from iteration to iteration (mci_set_sweep_chain_carry): two more units, the same body
 template <class Cfg> __device__ __forceinline__ void vegasmc_sweep_carry(const BatchArgs &a0, const SweepChainCarryArgs &f) { chain_sweep<Cfg, false, true>(a0, f.c, &f.k); }
 template <class Cfg> __device__ __forceinline__ void mcmc_sweep_carry(const BatchArgs &a0, const SweepChainCarryArgs &f) { chain_sweep<Cfg, true, true>(a0, f.c, &f.k); }
+// ... and with a first iteration that continues the chains of the call before (mci_integrate_sweep_chains_resume | mci_integrate_sweep_mcmc_resume)
+template <class Cfg> __device__ __forceinline__ void vegasmc_sweep_resume(const BatchArgs &a0, const SweepChainResumeArgs &f) { chain_sweep<Cfg, false, true, true>(a0, f.c, &f.k, &f.r); }
+template <class Cfg> __device__ __forceinline__ void mcmc_sweep_resume(const BatchArgs &a0, const SweepChainResumeArgs &f) { chain_sweep<Cfg, true, true, true>(a0, f.c, &f.k, &f.r); }
 
 } // namespace mci

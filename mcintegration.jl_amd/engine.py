@@ -441,7 +441,7 @@ class Engine:
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
                 "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15,
-                "vegas_sweep_strat_leaves": 16, "vegas_sweep_until": 17, "vegas_sweep_leaves_until": 18}.get(solver) or _lib.SOLVERS[solver]
+                "vegas_sweep_strat_leaves": 16, "vegas_sweep_until": 17, "vegas_sweep_leaves_until": 18, "vegasmc_sweep_resume": 19, "mcmc_sweep_resume": 20}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -456,7 +456,8 @@ class Engine:
         :vegas kernel with sixteen histogram copies in 1024-thread workgroups that big launches of eight-copy layouts run) |
         "vegas_sweep_strat_leaves" (the kernel of integrate_sweep_strat for a stratified problem with several Continuous leaves,
         csrc/mci_sweep_strat_leaves.h; after set_sweep_strat_leaves("all")) | "vegas_sweep_until" | "vegas_sweep_leaves_until" (the kernels
-        of integrate_sweep_until: "vegas_sweep" and "vegas_sweep_leaves" with a target error per point)"""
+        of integrate_sweep_until: "vegas_sweep" and "vegas_sweep_leaves" with a target error per point) | "vegasmc_sweep_resume" |
+        "mcmc_sweep_resume" (the two carried kernels with a first iteration that continues the chains of the call before: state=)"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -1073,7 +1074,7 @@ class Engine:
         return self._sweep_refusal(lib().mci_sweep_chains_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration)
 
     def integrate_sweep_chains(self, solver="vegasmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
-                               measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, carry=False):
+                               measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, carry=False, state=None, keep_state=True):
         """A parameter sweep under the default solver in one launch (mci_integrate_sweep_chains): P independent :vegasmc loops -- what
         integrate("vegasmc", nchain=nchain) runs on this engine with set_chain_carry(0) and one lane per chain -- one workgroup per
         point, the blocks of a point one after another.  Arguments and result dicts as integrate_sweep (any mix of Continuous and
@@ -1083,17 +1084,48 @@ class Engine:
         packed buffer, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_chains_supported().
         carry=True: this call runs with set_sweep_chain_carry(True) -- what integrate("vegasmc", nchain=nchain) runs with
         set_chain_carry(1); `correlated` and `stdev` are then integrate()'s (the block-lineage error); False: whatever
-        set_sweep_chain_carry says (off by default)."""
+        set_sweep_chain_carry says (off by default).
+        state: None or one ChainState per point, the `chain_state` of the dicts of the call before (mci_integrate_sweep_chains_resume):
+        with maps=, reweight= and first_iteration = the states' iteration + 1 the points are what integrate("vegasmc", nchain=nchain,
+        first_iteration=...) is on an engine with set_chain_carry(1) that has just run that call -- iteration 0 continues the stored
+        chains (their count may differ from nchain) unless they ran on a never-refined map that has been refined since.  A state that
+        does not fit (solver, blocks, layout, a gap in the iteration numbers), carry off or nchain = 1 raise MCIError by name.  With
+        carried chains and nchain > 1 every dict has `chain_state` (else None) and `continued` (iteration 0 continued a state).
+        keep_state=False: no states are copied out (`chain_state` None): block x nchain x (ndraw + 1) doubles per point less to read back."""
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain)
-        return self._sweep_chain_solver("integrate_sweep_chains", lib().mci_integrate_sweep_chains, a, niter, userdata, seeds, maps, reweight, False, carry)
+        return self._sweep_chain_solver("integrate_sweep_chains", lib().mci_integrate_sweep_chains, a, niter, userdata, seeds, maps, reweight, False, carry,
+                                        state, lib().mci_integrate_sweep_chains_resume, keep_state)
 
-    def _sweep_chain_solver(self, name, fn, a, niter, userdata, seeds, maps, reweight, holds, carry=False):
+    def sweep_chain_state_doubles(self, solver="vegasmc", neval=10000, niter=10, block=16, measurefreq=1, nchain=2, first_iteration=0, adapt=True, thermal_ratio=0.1):
+        """(doubles of one point's chain state row, the record a call with these arguments and no state writes: a dict)
+        (mci_sweep_chain_state_doubles); MCIError where the chain sweep refuses the arguments or nchain < 2"""
+        a = self._integrate_args(solver, neval, niter, block, -1, adapt, 1.0, measurefreq, 1234, first_iteration, nchain, thermal_ratio)
+        n, info = C.c_int64(), _lib.SweepChainInfo()
+        check(lib().mci_sweep_chain_state_doubles(self.p, C.byref(a), C.byref(n), C.byref(info)))
+        return n.value, {k: getattr(info, k) for k, _ in _lib.SweepChainInfo._fields_}
+
+    def sweep_chain_state_supported(self, state=None, solver="vegasmc", neval=10000, niter=10, block=16, measurefreq=1, nchain=2, first_iteration=0,
+                                    adapt=True, thermal_ratio=0.1):
+        """(None, continues) when the chain sweep of `solver` takes these arguments together with `state` (a ChainState, or None: states
+        only go out) -- continues: iteration 0 goes on from the stored chains --, else (the reason, False) (mci_sweep_chain_state_supported)"""
+        a = self._integrate_args(solver, neval, niter, block, -1, adapt, 1.0, measurefreq, 1234, first_iteration, nchain, thermal_ratio)
+        why, cont = C.create_string_buffer(512), C.c_int32()
+        info = self._chain_info(state) if state is not None else None
+        rc = lib().mci_sweep_chain_state_supported(self.p, C.byref(a), C.byref(info) if info is not None else None, why, len(why), C.byref(cont))
+        return (None, bool(cont.value)) if rc == 0 else (why.value.decode(), False)
+
+    @staticmethod
+    def _chain_info(st):
+        return _lib.SweepChainInfo(_lib.SOLVERS[st.solver], st.nd, st.ndraw, st.iteration, st.ntrain, 1 if st.adapted else 0, st.blocks, st.nchain)
+
+    def _sweep_chain_solver(self, name, fn, a, niter, userdata, seeds, maps, reweight, holds, carry=False, state=None, fn_resume=None, keep_state=True):
         """what integrate_sweep_chains and integrate_sweep_mcmc share: the arrays, the reweight check, the per-point factors and tables;
-        holds: the entry point also returns every point's holding-time histogram; carry: set_sweep_chain_carry(True) for this call"""
+        holds: the entry point also returns every point's holding-time histogram; carry: set_sweep_chain_carry(True) for this call;
+        state, fn_resume: the points' chain states and the entry point that takes them and hands them out"""
         if carry and not self.sweep_chain_carry():
             self.set_sweep_chain_carry(True)
             try:
-                return self._sweep_chain_solver(name, fn, a, niter, userdata, seeds, maps, reweight, holds)
+                return self._sweep_chain_solver(name, fn, a, niter, userdata, seeds, maps, reweight, holds, False, state, fn_resume, keep_state)
             finally:
                 self.set_sweep_chain_carry(False)
         ud, sd, mi, _ = self._sweep_inputs(name, userdata, seeds, maps)
@@ -1105,6 +1137,29 @@ class Engine:
             if ri.shape != (P, nd):
                 raise ValueError("%s: reweight must be [points = %d][integrands + 1 = %d], got shape %s" % (name, P, nd, ri.shape))
 
+        # chains that travel between calls: states go out of every carried call with more than one chain per block; a state that comes
+        # in is the library's to accept or to refuse by name
+        from .statistics import ChainState
+        keeps = fn_resume is not None and keep_state and self.sweep_chain_carry() and a.nchain > 1
+        s_in = s_out = rows_in = rows_out = None
+        if state is not None:
+            state = list(state)
+            if len(state) != P or not all(isinstance(s, ChainState) for s in state):
+                raise ValueError("%s: state must hold one ChainState per point (%d), the chain_state of an earlier call's results" % (name, P))
+            if any(s.record() != state[0].record() for s in state):
+                raise ValueError("%s: the points' chain states disagree with each other (%s)"
+                                 % (name, ", ".join(sorted({str(s.record()) for s in state}))))
+            if any(s.data.shape != (state[0].row_doubles(),) for s in state):
+                raise ValueError("%s: a chain state's array does not hold the %d doubles of its record" % (name, state[0].row_doubles()))
+            rows_in = np.ascontiguousarray(np.stack([s.data for s in state]), dtype=np.float64)
+            s_in = _lib.SweepChainState(self._chain_info(state[0]), _dp(rows_in))
+        if keeps:
+            n = C.c_int64()
+            check(lib().mci_sweep_chain_state_doubles(self.p, C.byref(a), C.byref(n), None))
+            rows_out = np.zeros((P, n.value))
+            s_out = _lib.SweepChainState(_lib.SweepChainInfo(), _dp(rows_out))
+        resume = s_in is not None or s_out is not None
+
         def extra(P):
             ro, pa = np.zeros((P, nd)), np.zeros((P, 2, 3, nd, m))
             own, keys = (_dp(ri) if ri is not None else None, _dp(ro), _dp(pa)), dict(reweight=ro, propose=pa[:, 0], accept=pa[:, 1])
@@ -1112,8 +1167,21 @@ class Engine:
                 ho = np.zeros((P, 64), dtype=np.uint64)
                 own += (ho.ctypes.data_as(C.POINTER(C.c_uint64)),)
                 keys["holds"] = ho
+            if resume:
+                own += (C.byref(s_in) if s_in is not None else None, C.byref(s_out) if s_out is not None else None)
             return own, keys
-        out = self._sweep_call(fn, a, P, niter, (ud, sd, mi), extra)
+        continued = False
+        if s_in is not None:   # (asked before the call: the refusal by name, and whether iteration 0 goes on from the states)
+            cont = C.c_int32()
+            check(lib().mci_sweep_chain_state_supported(self.p, C.byref(a), C.byref(s_in.info), None, 0, C.byref(cont)))
+            continued = bool(cont.value)
+        out = self._sweep_call(fn_resume if resume else fn, a, P, niter, (ud, sd, mi), extra)
+        for q, r in enumerate(out):
+            r["continued"] = continued
+            r["chain_state"] = None
+            if s_out is not None:
+                i = s_out.info
+                r["chain_state"] = ChainState(_lib.SOLVER_NAMES[i.solver], i.blocks, i.nchain, i.ndraw, i.nd, i.iteration, i.ntrain, bool(i.adapted), rows_out[q].copy())
         if holds:
             for r in out:
                 r["hold_max"] = self.hold_max_of(r["holds"])
@@ -1130,7 +1198,8 @@ class Engine:
         return self._sweep_refusal(lib().mci_sweep_mcmc_supported, solver, neval, niter, block, measurefreq, nchain, first_iteration, thermal_ratio)
 
     def integrate_sweep_mcmc(self, solver="mcmc", userdata=None, neval=10000, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0,
-                             measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, thermal_ratio=0.1, carry=False):
+                             measurefreq=1, seed=1234, seeds=None, maps=None, first_iteration=0, nchain=1, reweight=None, thermal_ratio=0.1, carry=False,
+                             state=None, keep_state=True):
         """A parameter sweep under :mcmc in one launch (mci_integrate_sweep_mcmc): P independent :mcmc loops -- what
         integrate("mcmc", nchain=nchain, thermal_ratio=thermal_ratio) runs on this engine with set_chain_carry(0) and one lane per
         chain -- one workgroup per point, the blocks of a point one after another.  Arguments and result dicts as
@@ -1139,11 +1208,14 @@ class Engine:
         none).  There is no warm-up repetition and no automatic chain count: nchain >= 1 is explicit.  The engine's own map, factors,
         packed buffer, hold histogram, logs and carried chains are not touched.  Raises MCIError with the reason of sweep_mcmc_supported().
         carry=True: as in integrate_sweep_chains -- every iteration after a point's first continues the stored chains, resampled to the
-        moved reweight factors, with no burn-in; every dict's `carried` says whether the point's later iterations were."""
+        moved reweight factors, with no burn-in; every dict's `carried` says whether the point's later iterations were.
+        state: as in integrate_sweep_chains (mci_integrate_sweep_mcmc_resume) -- iteration 0 of a call with states that fit always
+        continues the stored chains, so no iteration of the call holds a burn-in; `chain_state`, `continued` and keep_state as there."""
         a = self._integrate_args(solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain, thermal_ratio)
-        out = self._sweep_chain_solver("integrate_sweep_mcmc", lib().mci_integrate_sweep_mcmc, a, niter, userdata, seeds, maps, reweight, True, carry)
+        out = self._sweep_chain_solver("integrate_sweep_mcmc", lib().mci_integrate_sweep_mcmc, a, niter, userdata, seeds, maps, reweight, True, carry,
+                                       state, lib().mci_integrate_sweep_mcmc_resume, keep_state)
         for r in out:
-            r["carried"] = bool((carry or self.sweep_chain_carry()) and nchain > 1 and niter > 1)
+            r["carried"] = bool((carry or self.sweep_chain_carry()) and nchain > 1 and (niter > 1 or r["continued"]))
         return out
 
     def sweep_workgroups(self, g=0):

@@ -442,7 +442,7 @@ def _trace_sweep_measure(measure, traced_on, params, solver):
 
 def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
                     measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, rtol=None, atol=None, min_niter=None, **kwargs):
+                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, rtol=None, atol=None, min_niter=None, chain_state=None, **kwargs):
     """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
     mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
     integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
@@ -502,6 +502,17 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     Results of carried points have correlated = True and the block-lineage error as `stdev` (with_ignore() falls back to the
     reference's); report()'s hold note asks for 4 x hold_max instead of 16 x.  carry=True without chains= / mcmc_chains=, with
     stratify= or under "vegas" raises ValueError.  Where the sweep is refused, the looped integrate() calls carry by their own default.
+
+    chain_state: None (default) or [r.chain_state for r in head] -- with carry=True and more than one chain per block every Result
+    carries `chain_state` (a ChainState: the record of its chains and one array), and a later call that takes the list next to maps= and
+    reweight= goes on from those chains instead of starting afresh: a point is then what integrate(..., nchain=K) is on the engine that
+    has just run the earlier call (Engine.integrate_sweep_chains / integrate_sweep_mcmc, state=).  Its first iteration continues the
+    stored chains -- :mcmc without any burn-in; :vegasmc unless they ran on a never-refined map that was refined since -- and the call's
+    chain count may differ from the stored one.  On a fresh configuration (no config=) the call takes first_iteration from the states;
+    states that disagree with each other or with config.iterations_done raise ValueError, and so does chain_state= without carry=True,
+    with the wrong length, or where the sweep is refused and the points would loop over ordinary calls.  A state of another solver,
+    block count or layout is refused by name (MCIError).  Results of a call whose first iteration continued have correlated = True and
+    the block-lineage error, as in integrate().
 
     rtol, atol: None (default) or a target error -- under solver="vegas" every point stops once each of its statistics columns has
     stdev <= max(atol, rtol * |mean|) (the weighted average over its counted iterations and that average's error, as Result computes
@@ -581,6 +592,23 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError('integrate_sweep: reweight= belongs to a chain sweep (solver="vegasmc", chains=K)')
     if reweight is not None and len(reweight) != P:
         raise ValueError("integrate_sweep: reweight must hold one vector per point (%d), got %d" % (P, len(reweight)))
+    if chain_state is not None:
+        from .statistics import ChainState
+        if not carry:
+            raise ValueError("integrate_sweep: chain_state= belongs to a chain sweep with carried chains: give carry=True (and chains=K or mcmc_chains=K)")
+        try:
+            chain_state = list(chain_state)
+        except TypeError:
+            raise ValueError("integrate_sweep: chain_state must be a list with one ChainState per point")
+        if len(chain_state) != P:
+            raise ValueError("integrate_sweep: chain_state must hold one ChainState per point (%d), got %d" % (P, len(chain_state)))
+        if not all(isinstance(s, ChainState) for s in chain_state):
+            raise ValueError("integrate_sweep: chain_state must hold ChainState objects (the chain_state of an earlier sweep's results; None: that "
+                             "call kept no chains -- carry=True and more than one chain per block)")
+        nexts = sorted({s.iteration + 1 for s in chain_state})
+        if len(nexts) != 1:
+            raise ValueError("integrate_sweep: the chain states disagree with each other: they were stored by iterations %s"
+                             % ", ".join(str(n - 1) for n in nexts))
     if alloc is not None and (stratify is None or stratify is False):
         raise ValueError("integrate_sweep: alloc= belongs to a stratified sweep (stratify=True or mci.Stratify(...))")
     if alloc is not None:
@@ -594,6 +622,12 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     pristine = copy.deepcopy(kwargs) if fresh else None
     if fresh:
         config = Configuration(**kwargs)
+    if chain_state is not None:
+        if fresh:
+            config.iterations_done = nexts[0]    # (a fresh configuration goes on where the states' call stopped)
+        elif config.iterations_done != nexts[0]:
+            raise ValueError("integrate_sweep: the chain states were stored by iteration %d, and config.iterations_done = %d: the call would "
+                             "not start at the iteration that continues them (%d)" % (nexts[0] - 1, config.iterations_done, nexts[0]))
     if ignore is None:
         ignore = 1 if adapt else 0
     strat = _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, LocalComm())
@@ -688,6 +722,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
     if why is None and (chains is not None or mcmc_chains is not None):
         kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma,
                   measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done, reweight=reweight)
+        if chain_state is not None:
+            kw["state"] = chain_state
         rs = (eng.integrate_sweep_chains(solver, nchain=chains, carry=carry, **kw) if chains is not None
               else eng.integrate_sweep_mcmc(solver, nchain=mcmc_chains, thermal_ratio=thermal_ratio, carry=carry, **kw))
         out = []
@@ -702,6 +738,7 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
                 res.stdev = res._shape(res._flat_std)
             res.sweep_batched, res.map, res.status, res.reweight = True, r["maps"], r["status"], r["reweight"]
             res.maps_by_leaf = r.get("maps_by_leaf")
+            res.chain_state = r.get("chain_state")
             res.stratification, res.vegas_check, res.warmup, res.neval_discarded, res.chain_bias = None, None, 0, 0, None
             if mcmc_chains is not None:
                 res.holds, res.hold_max, res.chain_steps = r["holds"], r["hold_max"], nevalperblock // mcmc_chains
@@ -740,6 +777,8 @@ def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and alloc= needs the batched form" % why)
     if reweight is not None:
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and reweight= needs the batched form" % why)
+    if chain_state is not None:
+        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and chain_state= needs the batched form" % why)
     if until:
         raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and rtol= / atol= need the batched form" % why)
     warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),

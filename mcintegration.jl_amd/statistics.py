@@ -70,6 +70,32 @@ def chain_estimator_bias(solver, steps_per_block, chains_per_block, nblocks, nco
     return dict(z=z, tau=tau, times=float(steps_per_block) / tau, acceptance=a, steps_per_block=int(steps_per_block), nblocks=int(nblocks), solver=solver)
 
 
+class ChainState:
+    """What a carried chain sweep leaves behind for the next call, one per point (Result.chain_state; mci_sweep_chain_state): the record
+    the next call is held against -- solver, blocks, nchain (stored chains per block), ndraw, nd (integrands + 1), iteration (the one
+    that stored the chains), ntrain (train! calls of the point's lineage before that iteration), adapted (the storing call refined its
+    map) -- and `data`, the chains' end configurations with their targets (:vegasmc) or integrand indices and factors (:mcmc) as one
+    float64 array.  Opaque: it goes back in as integrate_sweep(..., chain_state=[r.chain_state for r in head]) next to maps= and
+    reweight=."""
+    FIELDS = ("solver", "blocks", "nchain", "ndraw", "nd", "iteration", "ntrain", "adapted")
+
+    def __init__(self, solver, blocks, nchain, ndraw, nd, iteration, ntrain, adapted, data):
+        self.solver, self.blocks, self.nchain, self.ndraw, self.nd = str(solver), int(blocks), int(nchain), int(ndraw), int(nd)
+        self.iteration, self.ntrain, self.adapted = int(iteration), int(ntrain), bool(adapted)
+        self.data = np.ascontiguousarray(data, dtype=np.float64)
+
+    def record(self):
+        return tuple(getattr(self, k) for k in self.FIELDS)
+
+    def row_doubles(self):
+        """doubles `data` holds for this record (mci_sweep_chain_state_doubles)"""
+        cap = self.blocks * self.nchain
+        return self.ndraw * cap + ((cap + 1) // 2 + self.nd if self.solver == "mcmc" else cap)
+
+    def __repr__(self):
+        return "ChainState(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.FIELDS)
+
+
 class Result:
     """statistics.jl:16-63.  mean/stdev/chi2 are lists with one entry per integrand: a float for scalar
     observables, an ndarray for array observables (like `obs=[zeros(4)]`).
@@ -121,6 +147,9 @@ class Result:
         self.holds = self.hold_max = self.chain_steps = None
         # ... and whether the point's iterations continued each other's chains (integrate_sweep(..., carry=True)): hold_note's factor
         self.chains_carried = False
+        # set by integrate_sweep(..., carry=True) with more than one chain per block: the point's ChainState, what a later call takes as
+        # chain_state= to go on from these chains; else None
+        self.chain_state = None
         # set by integrate_sweep(..., rtol= | atol=): the iterations the point ran (the rows above) and whether it met the target, else None
         self.niter_run = self.converged = None
         self.mean, self.stdev, self.chi2 = self._shape(self._flat_mean), self._shape(self._flat_std), self._shape(self._flat_chi2)
@@ -152,6 +181,7 @@ class Result:
         r.vegas_check = self.vegas_check
         r.holds, r.hold_max, r.chain_steps, r.chains_carried = self.holds, self.hold_max, self.chain_steps, self.chains_carried
         r.niter_run, r.converged = self.niter_run, self.converged
+        r.chain_state = self.chain_state
         return r
 
     @property

@@ -8,6 +8,7 @@
     python tools/sweep_bench.py strat --layout leaves [--nevals 10000,100000] [--points 1,16,256]   (profiles/r17_sweep_strat_leaves.txt)
     python tools/sweep_bench.py chains [--nevals 10000,100000,1000000] [--points 1,16,256] [--chains 1,16,64,256]   (profiles/r14_sweep_chains.txt)
     python tools/sweep_bench.py mcmc   [--nevals 10000,100000] [--points 1,16,256] [--chains 1,16,64,256]          (profiles/r15_sweep_mcmc.txt)
+    python tools/sweep_bench.py chains --resume | mcmc --resume [--nevals 10000,100000] [--points 16,256] [--chains 16,64,256] [--repeat 5]   (profiles/r20_sweep_resume.txt)
     python tools/sweep_bench.py until  [--nevals 10000,100000] [--points 256,2048] [--rtol 2e-3] [--repeat 7]       (profiles/r18_sweep_until.txt)
 
 The 4-D Genz product peak, niter = 10, block = 16.  `table`: wall time and us per point-iteration of Engine.integrate_sweep at every P,
@@ -33,6 +34,11 @@ deep per chain.  Both tables give the best and the worst of the timed runs of ev
 `chains --carry` | `mcmc --carry` (profiles/r16_sweep_carry.txt): the sweep with chains carried from iteration to iteration
 (set_sweep_chain_carry) against the uncarried sweep at the same nchain and against a loop of ordinary calls with the same nchain and
 carried chains (set_chain_carry(1)); the last columns give the dependent steps of a point-iteration without and with carrying.
+`chains --resume` | `mcmc --resume`: the continuation call -- a carried sweep of niter = 10 that follows a training call of niter = 10
+through maps=, reweight= and first_iteration = 10 -- with the points' chain states (state=: its first iteration continues the stored chains)
+and without them (its first iteration starts afresh and, under :mcmc, burns in), the two calls alternating `--repeat` times after a warm-up
+of each; `launch` is the library's clock, `call` the wall time of the Engine method, best / median / worst of each, and the last columns
+give the dependent steps of the call without and with the states.  On a library whose sweeps take no state= only the side without is timed.
 `until`: the Genz scan at niter = 20 with a target error (Engine.integrate_sweep_until) against the fixed sweep of the same points:
 (a) the cost of asking -- the `until` unit with rtol = atol = 0, which runs every iteration, over the fixed sweep; (b) the gain -- the
 `until` unit at --rtol over the fixed sweep, next to sum n_p / (20 P), the share of the iterations actually run, which is what a perfect
@@ -417,6 +423,54 @@ def carry_table(Ps, nevals, chains, budget=3.0, solver="vegasmc"):
                       flush=True)
 
 
+def resume_table(Ps, nevals, chains, reps, solver="vegasmc"):
+    """the continuation call with | without the chain states of the call before"""
+    import inspect
+    from mcintegration_jl_amd._lib import lib
+    eng = bubble_engine(bubble_point(0))
+    sweep = eng.integrate_sweep_chains if solver == "vegasmc" else eng.integrate_sweep_mcmc
+    has_state = "state" in inspect.signature(sweep).parameters
+    print("# bubble (4 Continuous leaves of 999 increments + Discrete(1, 4), q histogram), solver :%s, block = %d: a carried sweep of niter = %d, then the"
+          " timed continuation call of niter = %d (maps, reweight, first_iteration = %d)" % (solver, BLOCK, NITER, NITER, NITER))
+    print("# without the chain states | with them%s: ms best / median / worst over %d alternating repetitions after one warm-up call of each"
+          % ("" if has_state else " (this library's sweeps take no state=: not timed)", reps))
+    for neval in nevals:
+        for nchain in chains:
+            if nchain < 2 or nchain > neval // BLOCK:
+                continue
+            steps, trips = neval // BLOCK // nchain, -(-nchain // 256)
+            burn = int(lib().mci_mcmc_burnin(steps, nchain, 5, 2, 5, 0.1)) if solver == "mcmc" else 0
+            deep = (BLOCK * trips * (NITER * steps + burn), BLOCK * trips * NITER * steps)
+            for P in Ps:
+                uds = np.array([bubble_point(k) for k in range(P)])
+                kw = dict(userdata=uds, neval=neval, niter=NITER, block=BLOCK, seed=SEED, nchain=nchain, carry=True)
+                head = sweep(solver, **kw)
+                on = dict(kw, maps=[r["maps"] for r in head], reweight=[r["reweight"] for r in head], first_iteration=NITER)
+                calls = [("without", lambda: sweep(solver, **on))]
+                if has_state:
+                    calls.append(("with", lambda: sweep(solver, state=[r["chain_state"] for r in head], **on)))
+                out, times, secs = {}, {name: [] for name, _ in calls}, {name: [] for name, _ in calls}
+                for name, fn in calls:
+                    fn()                                               # (warm-up: code object loaded, buffer parked with the context)
+                for _ in range(reps):
+                    for name, fn in calls:
+                        t0 = time.perf_counter()
+                        out[name] = fn()
+                        times[name].append(time.perf_counter() - t0)
+                        secs[name].append(out[name][0]["seconds"])
+                assert all(r["status"] == 0 for rs in out.values() for r in rs)
+                col = lambda ts, name: "%9.3f / %9.3f / %9.3f" % tuple(1e3 * v for v in (min(ts[name]), float(np.median(ts[name])), max(ts[name])))
+                line = "neval %7d  nchain %4d  P %4d  launch: without %s" % (neval, nchain, P, col(secs, "without"))
+                if has_state:
+                    assert all(r["continued"] for r in out["with"]) and not any(r["continued"] for r in out["without"])
+                    line += "  with %s  without / with %.3f   call: without %s  with %s  without / with %.3f   neval of point 0: %d -> %d" % (
+                        col(secs, "with"), np.median(secs["without"]) / np.median(secs["with"]), col(times, "without"), col(times, "with"),
+                        np.median(times["without"]) / np.median(times["with"]), out["without"][0]["neval"], out["with"][0]["neval"])
+                else:
+                    line += "   call: without %s" % col(times, "without")
+                print(line + "   steps deep %d -> %d (derived ratio %.2f)   grid x threads = %s" % (deep[0], deep[1], deep[0] / deep[1], eng.last_sweep_launch()), flush=True)
+
+
 # ---- until: a target error per point (csrc/mci_sweep.h vegas_sweep<Cfg, true>)
 def until_table(Ps, nevals, rtol, reps, niter=20):
     from mcintegration_jl_amd import isa_mix
@@ -476,6 +530,7 @@ def main():
     ap.add_argument("--layout", choices=["genz", "bubble", "leaves"], default="genz")
     ap.add_argument("--rtol", type=float, default=2e-3, help="until: the target error of the timed scan")
     ap.add_argument("--carry", action="store_true", help="chains | mcmc: the sweep with carried chains against the uncarried one and a loop of carried calls")
+    ap.add_argument("--resume", action="store_true", help="chains | mcmc: the continuation call of a carried sweep with and without the chain states of the call before")
     a = ap.parse_args()
     Ps = [int(v) for v in a.points.split(",")]
     mci.use_rocm_compiler()
@@ -484,6 +539,13 @@ def main():
     if a.mode == "until":
         until_table([256, 2048] if a.points == "1,16,256,1024,4096" else Ps, [10000, 100000] if a.nevals == "10000,100000,1000000" else [int(v) for v in a.nevals.split(",")],
                     a.rtol, a.repeat if a.repeat > 1 else 7)
+        return
+    if a.resume and a.mode not in ("chains", "mcmc"):
+        ap.error("--resume goes with the chains and mcmc modes")
+    if a.resume:
+        resume_table([16, 256] if a.points == "1,16,256,1024,4096" else Ps, [10000, 100000] if a.nevals == "10000,100000,1000000" else [int(v) for v in a.nevals.split(",")],
+                     [16, 64, 256] if a.chains == "1,16,64,256" else [int(v) for v in a.chains.split(",")], a.repeat if a.repeat > 1 else 5,
+                     solver="vegasmc" if a.mode == "chains" else "mcmc")
         return
     if a.mode in ("chains", "mcmc"):
         (carry_table if a.carry else chains_table)([P for P in Ps if P <= 256] if a.points == "1,16,256,1024,4096" else Ps, [int(v) for v in a.nevals.split(",")],
