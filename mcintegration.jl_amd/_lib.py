@@ -51,6 +51,12 @@ class DebugMergeIO(C.Structure):   # csrc/mci_debug.h mci_debug_merge_io
                 ("grids_out", c_double_p), ("dists_out", c_double_p), ("accs_out", c_double_p), ("walk_counts", C.POINTER(C.c_int64))]
 
 
+class DebugStratReduceIO(C.Structure):   # csrc/mci_debug.h mci_debug_strat_reduce_io
+    _fields_ = [("ncube", C.c_int64), ("nchunk", C.c_int64), ("nw", C.c_int32), ("beta", C.c_double), ("off", C.POINTER(C.c_int64)),
+                ("part", c_double_p), ("rec_h", C.POINTER(C.c_int64)), ("rec_s", c_double_p), ("dnext", c_double_p), ("out", c_double_p),
+                ("log_row", c_double_p)]
+
+
 HOST_INTEGRAND_FN = C.CFUNCTYPE(C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p)
 HOST_INTEGRAND_IDX_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p)
 HOST_MEASURE_FN = C.CFUNCTYPE(C.c_int, c_double_p, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, c_double_p, C.c_int32, C.c_void_p)
@@ -226,6 +232,9 @@ DEBUG_SIGNATURES = [
     ("mci_debug_sweep_resample_lds", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("mci_debug_merge", C.c_int, [_VP, C.POINTER(DebugMergeIO)]),
     ("mci_debug_merge_shape", C.c_int, [_VP, c_int32_p, c_int32_p]),
+    ("mci_debug_strat_alloc", C.c_int, [_VP, c_double_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64), c_double_p]),
+    ("mci_debug_strat_reduce", C.c_int, [_VP, C.POINTER(DebugStratReduceIO)]),
+    ("mci_debug_strat_remap", C.c_int, [_VP, C.c_int32, c_int32_p, c_int32_p, C.c_double, c_double_p, c_double_p]),
     ("mci_debug_sweep_strat_geometry", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_int32)]),
 ]

@@ -148,6 +148,35 @@ typedef struct mci_debug_merge_io {
     int64_t *walk_counts;          /* [2] or NULL: serial walks run as slots | in the general form (mci_debug_walk_counts, of the hook's own word) */
 } mci_debug_merge_io;
 int mci_debug_merge(mci_problem *prob, const mci_debug_merge_io *io);
+/* test hooks: the three static kernels of stratified :vegas (mci_static_kernels.h k_strat_alloc, k_strat_reduce, k_strat_remap) on their
+ * own over inputs the caller made up, launched by the helpers the product launches them with (mci_host_strat.h strat_alloc_launches,
+ * strat_reduce_launch, strat_remap_launch: phases, grids and thread counts are written down once).  The problem gives its device and its
+ * stream only and need not be stratified: every buffer is the hook's own, the problem's plan, offsets, d_h and carried allocation stay as
+ * they are.  Every output is filled with 0xFF bytes before the launch: what a kernel leaves unwritten comes back as -1 | NaN.  Each hook
+ * synchronises.  An offline context: MCI_ERR_NO_DEVICE.
+ * mci_debug_strat_alloc: d[ncube] -> off_out[ncube + 1] and the scratch tsum_out[2 ntile + 2] = tile sums | tile bases | total | uniform
+ * flag, ntile = min(ceil(ncube / 256), 1024); uniform = 1: d_h = 1 whatever d holds.  Refused (MCI_ERR_INVALID): ncube outside
+ * 1 .. 2^31 - 1, nsamp < 2 ncube or > 2^52, uniform other than 0 | 1. */
+int mci_debug_strat_alloc(mci_problem *prob, const double *d, int64_t ncube, int64_t nsamp, int32_t uniform, int64_t *off_out, double *tsum_out);
+/* mci_debug_strat_reduce: the chunks' partial rows and boundary records as the sample kernel leaves them (mci_strat.h StratArgs) -> out,
+ * log_row and the d_h of the cut hypercubes.  Refused: ncube outside 1 .. 2^31 - 1, nchunk outside 1 .. 2^24, nw outside 1 .. 8, a beta
+ * that is negative or not finite, a rec_h entry outside -1 .. ncube - 1 (the kernel indexes off and dnext with it). */
+typedef struct mci_debug_strat_reduce_io {
+    int64_t ncube, nchunk;
+    int32_t nw;            /* weight columns, 1 .. 8 */
+    double beta;
+    const int64_t *off;    /* [ncube + 1] */
+    const double *part;    /* [nchunk][2 nw] */
+    const int64_t *rec_h;  /* [nchunk][2], -1 = none */
+    const double *rec_s;   /* [nchunk][2][2 nw] */
+    double *dnext;         /* [ncube] in and out: the caller's fill goes up, what the kernel left comes back */
+    double *out;           /* [2 nw] out: mean | var */
+    double *log_row;       /* [2 nw] out, or NULL: the kernel is given no log row */
+} mci_debug_strat_reduce_io;
+int mci_debug_strat_reduce(mci_problem *prob, const mci_debug_strat_reduce_io *io);
+/* mci_debug_strat_remap: d_old[prod n_old] on the plan n_old[ndim] -> d_new_out[prod n_new] on the plan n_new[ndim], raised to e.
+ * Refused: ndim outside 1 .. 32, a cell count < 1, more than 2^31 - 1 hypercubes on either side, an e that is not finite. */
+int mci_debug_strat_remap(mci_problem *prob, int32_t ndim, const int32_t *n_old, const int32_t *n_new, double e, const double *d_old, double *d_new_out);
 /* shape[8] = nobs, ni, ncols, nbin, npa, nstat, leaves, bins of the largest leaf; leaves[nleaf][2] (or NULL) = offset into the histogram
  * section, bins.  No device needed. */
 int mci_debug_merge_shape(const mci_problem *prob, int32_t *shape, int32_t *leaves);

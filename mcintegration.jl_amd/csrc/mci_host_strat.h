@@ -93,6 +93,23 @@ void strat_geometry(int64_t N, int64_t nblocks, const int64_t (&need)[4], StratG
 
 int strat_alloc_tiles(int64_t ncube) { return mci::strat_alloc_ntile(ncube); }
 
+// The launches of the three stratified static kernels, for the product (below) and for the test hooks of csrc/mci_debug.h alike, so that
+// grids, thread counts and phases are written down once.
+// k_strat_alloc: tile sums (ntile workgroups), tile bases + total + the uniform verdict (one), offsets (ntile)
+hipError_t strat_alloc_launches(const mci::StratAllocArgs &a, hipStream_t stream) {
+    for (int phase = 0; phase < 3; ++phase) {
+        hipLaunchKernelGGL(mci::k_strat_alloc, dim3(phase == 1 ? 1 : (unsigned)a.ntile), dim3(256), 0, stream, a, phase);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// k_strat_reduce: one workgroup
+hipError_t strat_reduce_launch(const mci::StratReduceArgs &r, hipStream_t stream) {
+    hipLaunchKernelGGL(mci::k_strat_reduce, dim3(1), dim3(mci::kStratReduceThreads), 0, stream, r);
+    return hipGetLastError();
+}
+
 // the allocation of the run about to start, over the offsets the last run used: from d_h, or uniform
 int strat_launch_alloc(mci_problem *p, bool uniform) {
     auto &st = p->strat;
@@ -104,10 +121,7 @@ int strat_launch_alloc(mci_problem *p, bool uniform) {
     a.nsamp = st.nsamp;
     a.ntile = strat_alloc_tiles(st.ncube);
     a.uniform = uniform ? 1 : 0;
-    for (int phase = 0; phase < 3; ++phase) {
-        hipLaunchKernelGGL(mci::k_strat_alloc, dim3(phase == 1 ? 1 : (unsigned)a.ntile), dim3(256), 0, p->ctx->stream, a, phase);
-        HIPCHK(hipGetLastError());
-    }
+    HIPCHK(strat_alloc_launches(a, p->ctx->stream));
     st.alloc_valid = true;
     st.alloc_pending = false;
     return MCI_OK;
@@ -115,6 +129,7 @@ int strat_launch_alloc(mci_problem *p, bool uniform) {
 
 // h / n = (h * magic) >> shift, exact for h < 2^31 (Granlund-Montgomery, N = 31): the reciprocals the sample kernel decodes a hypercube
 // into its cells with (StratArgs) and k_strat_remap a new hypercube into its
+// >>> strat magic (compiled for the host by tests/test_strat_kernels_host.py)
 void strat_magic(uint32_t n, uint32_t *magic, int *shift) {
     int l = 0;
     while (((uint64_t)1 << l) < n) ++l;
@@ -127,6 +142,21 @@ void strat_magic(uint32_t n, uint32_t *magic, int *shift) {
         *magic = 0x80000000u;
         *shift = 31;
     }
+}
+// <<< strat magic
+
+// k_strat_remap over a.ncube = prod n_new new hypercubes: the plans and their reciprocals into the arguments, one thread per new hypercube
+// up to 4096 workgroups of 256 (the kernel strides beyond)
+hipError_t strat_remap_launch(mci::StratRemapArgs &a, const int *n_old, const int *n_new, int D, hipStream_t stream) {
+    a.ndim = D;
+    for (int d = 0; d < D; ++d) {
+        strat_magic((uint32_t)n_new[d], &a.magic[d], &a.shift[d]);
+        a.n_new[d] = n_new[d];
+        a.n_old[d] = n_old[d];
+    }
+    const unsigned grid = (unsigned)((a.ncube + 255) / 256 < 4096 ? (a.ncube + 255) / 256 : 4096);
+    hipLaunchKernelGGL(mci::k_strat_remap, dim3(grid), dim3(256), 0, stream, a);
+    return hipGetLastError();
 }
 
 // d_off / d_d with room for ncube hypercubes (what they held is gone when they grow)
@@ -185,16 +215,8 @@ int strat_start_alloc(mci_problem *p, const std::vector<int> &ns, int64_t ncube,
         a.d_old = src;
         a.d_new = d_new;
         a.ncube = ncube;
-        a.ndim = D;
         a.e = st.beta / st.c_beta;
-        for (int d = 0; d < D; ++d) {
-            strat_magic((uint32_t)ns[d], &a.magic[d], &a.shift[d]);
-            a.n_new[d] = ns[d];
-            a.n_old[d] = st.c_nstrat[d];
-        }
-        const unsigned grid = (unsigned)((ncube + 255) / 256 < 4096 ? (ncube + 255) / 256 : 4096);
-        hipLaunchKernelGGL(mci::k_strat_remap, dim3(grid), dim3(256), 0, p->ctx->stream, a);
-        const hipError_t launched = hipGetLastError();
+        const hipError_t launched = strat_remap_launch(a, st.c_nstrat.data(), ns.data(), D, p->ctx->stream);
         if (upload) (void)hipFree(upload);
         st.d_off.adopt(off_new, ncube + 1);
         st.d_d.adopt(d_new, ncube);
@@ -398,6 +420,122 @@ int mci_debug_strat_start_d(mci_problem *p, double *d, int64_t n) {
     return MCI_OK;
 }
 
+// csrc/mci_debug.h: k_strat_alloc, k_strat_reduce and k_strat_remap alone over inputs the caller made up, launched by the helpers the
+// product launches them with (strat_alloc_launches, strat_reduce_launch, strat_remap_launch); buffers of the hooks' own, nothing of the
+// problem's but the device and the stream -- p->strat is neither read nor written
+int mci_debug_strat_alloc(mci_problem *p, const double *d, int64_t ncube, int64_t nsamp, int32_t uniform, int64_t *off_out, double *tsum_out) {
+    if (!p || !d || !off_out || !tsum_out) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (ncube < 1 || ncube > (((int64_t)1 << 31) - 1)) return fail(MCI_ERR_INVALID, "strat alloc: %lld hypercubes (1 .. 2^31 - 1)", (long long)ncube);
+    if (nsamp < 2 * ncube || nsamp > ((int64_t)1 << 52))
+        return fail(MCI_ERR_INVALID, "strat alloc: %lld samples for %lld hypercubes (two each at least, 2^52 at most)", (long long)nsamp, (long long)ncube);
+    if (uniform != 0 && uniform != 1) return fail(MCI_ERR_INVALID, "strat alloc: uniform must be 0 or 1");
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t hs = p->ctx->stream;
+    const int ntile = strat_alloc_tiles(ncube);
+    DevBuf<double> d_d, d_tsum;
+    DevBuf<long long> d_off;
+    int rc;
+    if ((rc = d_d.reserve(ncube)) || (rc = d_off.reserve(ncube + 1)) || (rc = d_tsum.reserve(2 * ntile + 2))) return rc;
+    HIPCHK(hipMemcpyAsync(d_d, d, (size_t)ncube * sizeof(double), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemsetAsync(d_off, 0xFF, (size_t)(ncube + 1) * sizeof(long long), hs)); // (an offset the kernel leaves unwritten comes back as
+    HIPCHK(hipMemsetAsync(d_tsum, 0xFF, (size_t)(2 * ntile + 2) * sizeof(double), hs)); // -1, a scratch entry as NaN)
+    HIPCHK(hipStreamSynchronize(hs)); // (the upload has read the caller's pageable memory)
+    mci::StratAllocArgs a{};
+    a.d = d_d;
+    a.off = d_off;
+    a.tsum = d_tsum;
+    a.ncube = ncube;
+    a.nsamp = nsamp;
+    a.ntile = ntile;
+    a.uniform = uniform;
+    HIPCHK(strat_alloc_launches(a, hs));
+    HIPCHK(hipMemcpyAsync(off_out, d_off, (size_t)(ncube + 1) * sizeof(long long), hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(tsum_out, d_tsum, (size_t)(2 * ntile + 2) * sizeof(double), hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipStreamSynchronize(hs)); // (the buffers are freed behind it)
+    return MCI_OK;
+}
+
+int mci_debug_strat_reduce(mci_problem *p, const mci_debug_strat_reduce_io *io) {
+    if (!p || !io || !io->off || !io->part || !io->rec_h || !io->rec_s || !io->dnext || !io->out) return fail(MCI_ERR_INVALID, "NULL argument");
+    const int64_t ncube = io->ncube, nchunk = io->nchunk;
+    const int nw = io->nw;
+    if (ncube < 1 || ncube > (((int64_t)1 << 31) - 1)) return fail(MCI_ERR_INVALID, "strat reduce: %lld hypercubes (1 .. 2^31 - 1)", (long long)ncube);
+    if (nchunk < 1 || nchunk > ((int64_t)1 << 24)) return fail(MCI_ERR_INVALID, "strat reduce: %lld chunks (1 .. 2^24)", (long long)nchunk);
+    if (nw < 1 || nw > mci::kStratReduceCols) return fail(MCI_ERR_INVALID, "strat reduce: %d weight columns (1 .. %d)", nw, (int)mci::kStratReduceCols);
+    if (!std::isfinite(io->beta) || io->beta < 0.0) return fail(MCI_ERR_INVALID, "strat reduce: beta must be finite and >= 0");
+    for (int64_t i = 0; i < 2 * nchunk; ++i) // (the kernel reads off[h], off[h + 1] and writes dnext[h] of every record's h)
+        if (io->rec_h[i] < -1 || io->rec_h[i] >= ncube)
+            return fail(MCI_ERR_INVALID, "strat reduce: rec_h[%lld] = %lld, outside -1 .. %lld", (long long)i, (long long)io->rec_h[i], (long long)(ncube - 1));
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t hs = p->ctx->stream;
+    DevBuf<long long> d_off, d_rec_h;
+    DevBuf<double> d_part, d_rec_s, d_dnext, d_out, d_row;
+    int rc;
+    if ((rc = d_off.reserve(ncube + 1)) || (rc = d_rec_h.reserve(2 * nchunk)) || (rc = d_part.reserve(nchunk * 2 * nw)) || (rc = d_rec_s.reserve(nchunk * 4 * nw)) ||
+        (rc = d_dnext.reserve(ncube)) || (rc = d_out.reserve(2 * nw)) || (rc = d_row.reserve(2 * nw)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(d_off, io->off, (size_t)(ncube + 1) * sizeof(long long), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemcpyAsync(d_rec_h, io->rec_h, (size_t)(2 * nchunk) * sizeof(long long), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemcpyAsync(d_part, io->part, (size_t)(nchunk * 2 * nw) * sizeof(double), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemcpyAsync(d_rec_s, io->rec_s, (size_t)(nchunk * 4 * nw) * sizeof(double), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemcpyAsync(d_dnext, io->dnext, (size_t)ncube * sizeof(double), hipMemcpyHostToDevice, hs)); // (the caller's fill: the sample kernel's part)
+    HIPCHK(hipMemsetAsync(d_out, 0xFF, (size_t)(2 * nw) * sizeof(double), hs));
+    HIPCHK(hipMemsetAsync(d_row, 0xFF, (size_t)(2 * nw) * sizeof(double), hs));
+    HIPCHK(hipStreamSynchronize(hs));
+    mci::StratReduceArgs r{};
+    r.off = d_off;
+    r.part = d_part;
+    r.rec_h = d_rec_h;
+    r.rec_s = d_rec_s;
+    r.ncube = ncube;
+    r.nchunk = nchunk;
+    r.nw = nw;
+    r.beta = io->beta;
+    r.dnext = d_dnext;
+    r.out = d_out;
+    r.log_row = io->log_row ? d_row.get() : nullptr;
+    HIPCHK(strat_reduce_launch(r, hs));
+    HIPCHK(hipMemcpyAsync(io->dnext, d_dnext, (size_t)ncube * sizeof(double), hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(io->out, d_out, (size_t)(2 * nw) * sizeof(double), hipMemcpyDeviceToHost, hs));
+    if (io->log_row) HIPCHK(hipMemcpyAsync(io->log_row, d_row, (size_t)(2 * nw) * sizeof(double), hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipStreamSynchronize(hs));
+    return MCI_OK;
+}
+
+int mci_debug_strat_remap(mci_problem *p, int32_t ndim, const int32_t *n_old, const int32_t *n_new, double e, const double *d_old, double *d_new_out) {
+    if (!p || !n_old || !n_new || !d_old || !d_new_out) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (ndim < 1 || ndim > mci::kStratRemapMaxDraw) return fail(MCI_ERR_INVALID, "strat remap: %d draws (1 .. %d)", (int)ndim, (int)mci::kStratRemapMaxDraw);
+    if (!std::isfinite(e)) return fail(MCI_ERR_INVALID, "strat remap: the exponent must be finite");
+    int64_t c_old = 1, c_new = 1;
+    for (int d = 0; d < ndim; ++d) {
+        if (n_old[d] < 1 || n_new[d] < 1) return fail(MCI_ERR_INVALID, "strat remap: draw %d is cut into %d -> %d cells (each >= 1)", d, (int)n_old[d], (int)n_new[d]);
+        c_old *= n_old[d];
+        c_new *= n_new[d];
+        if (c_old > (((int64_t)1 << 31) - 1) || c_new > (((int64_t)1 << 31) - 1)) return fail(MCI_ERR_INVALID, "strat remap: more than 2^31 - 1 hypercubes");
+    }
+    if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    hipStream_t hs = p->ctx->stream;
+    DevBuf<double> d_src, d_dst;
+    int rc;
+    if ((rc = d_src.reserve(c_old)) || (rc = d_dst.reserve(c_new))) return rc;
+    HIPCHK(hipMemcpyAsync(d_src, d_old, (size_t)c_old * sizeof(double), hipMemcpyHostToDevice, hs));
+    HIPCHK(hipMemsetAsync(d_dst, 0xFF, (size_t)c_new * sizeof(double), hs));
+    HIPCHK(hipStreamSynchronize(hs));
+    mci::StratRemapArgs a{};
+    a.d_old = d_src;
+    a.d_new = d_dst;
+    a.ncube = c_new;
+    a.e = e;
+    std::vector<int> o(n_old, n_old + ndim), n(n_new, n_new + ndim);
+    HIPCHK(strat_remap_launch(a, o.data(), n.data(), ndim, hs));
+    HIPCHK(hipMemcpyAsync(d_new_out, d_dst, (size_t)c_new * sizeof(double), hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipStreamSynchronize(hs));
+    return MCI_OK;
+}
+
 // every stratified allocation of a call starts afresh (mci_integrate): uniform, or from the carried d_h (strat_start_alloc)
 static void strat_call_start(mci_problem *p) { p->strat.alloc_valid = p->strat.alloc_pending = false; }
 
@@ -525,8 +663,7 @@ static int strat_finish(mci_problem *p, double *row, int32_t adapt) {
     r.dnext = st.d_d;
     r.out = st.d_stat;
     r.log_row = row;
-    hipLaunchKernelGGL(mci::k_strat_reduce, dim3(1), dim3(mci::kStratReduceThreads), 0, p->ctx->stream, r);
-    HIPCHK(hipGetLastError());
+    HIPCHK(strat_reduce_launch(r, p->ctx->stream));
     st.alloc_pending = adapt != 0; // (adapt = false: the allocation the call started with stays)
     // d_d is now the d_h of a finished iteration of this plan: what a carrying problem starts its next call from
     st.c_valid = true;

@@ -125,7 +125,8 @@ __global__ void __launch_bounds__(512) k_finish(MergeArgs m, TrainArgs a) {
 // P_h = tile base + (stretch base + run), which is monotone in h (the addends are non-negative and every base is the exact sum the
 // stretch or tile before it ends on), so n_h >= 2 holds in floating point.  Three launches: phase 0 (ntile workgroups) tile sums, phase 1
 // (one workgroup) tile bases, total and the decision "uniform" (first iteration of a call, or a total that is 0 or not finite: d_h = 1),
-// phase 2 (ntile workgroups) the offsets.
+// phase 2 (ntile workgroups) the offsets.  d_h is not range-checked: a total that is finite allocates in proportion however large the
+// d_h are (M P_h overflowing is recomputed as M (P_h / P), strat_alloc_offsets), one that is 0, inf or NaN allocates uniformly.
 struct StratAllocArgs {
     const double *d;        // [ncube]
     long long *off;         // [ncube + 1] out
@@ -266,7 +267,7 @@ __global__ void __launch_bounds__(kStratReduceThreads) k_strat_reduce(StratReduc
                 acc[nw + q] += V * V * v2 / n;
                 ssum += v2;
             }
-            a.dnext[h] = pow(ssum, 0.5 * a.beta);
+            a.dnext[h] = strat_damp(ssum, a.beta);
         }
     }
     for (int q = 0; q < 2 * nw; ++q) {

@@ -41,6 +41,8 @@ struct StratArgs {
 // The allocation rule of k_strat_alloc (mci_static_kernels.h) and of the stratified sweep (mci_sweep_strat.h), per tile and thread: the
 // hypercubes are cut into ntile tiles, a tile into 256 stretches; P_h = tile base + (stretch base + running sum), every base the
 // sequential sum of what lies before it; C_h = M P_h / P (M = N - 2 ncube), off[h + 1] = 2 (h + 1) + floor(C_h), the last C_h := M.
+// C_h is rounded as (M P_h) / P; only where that product leaves the double range it is M (P_h / P), so that a finite total always gives
+// an allocation in proportion and every input whose product is finite keeps its bits.
 // k_strat_alloc takes the tile from blockIdx.x, the sweep's one workgroup walks the tiles in order.
 // >>> strat alloc rule (compiled for the host by tests/test_sweep_strat_host.py)
 __host__ __device__ inline int strat_alloc_ntile(long long ncube) { return (int)((ncube + 255) / 256 < 1024 ? (ncube + 255) / 256 : 1024); }
@@ -80,7 +82,9 @@ __host__ __device__ inline void strat_alloc_offsets(const double *d, long long *
     double run = 0.0;
     for (long long h = lo; h < hi; ++h) {
         run += d[h];
-        double C = (double)M * (tbase + (sbase + run)) / total;
+        const double P = tbase + (sbase + run);
+        double C = (double)M * P / total;
+        if (!(C - C == 0.0)) C = (double)M * (P / total); // M P_h beyond the double range (d_h near 1e305): the quotient first, P_h / P <= 1
         if (h == ncube - 1 || C > (double)M) C = (double)M;
         off[h + 1] = 2 * (h + 1) + (long long)floor(C);
     }
@@ -138,6 +142,13 @@ template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_samp
 __device__ __forceinline__ double strat_s2(double s1, double s2, double n) {
     const double v = (s2 - s1 * s1 / n) / (n - 1.0);
     return v > 0.0 ? v : 0.0;
+}
+
+// d_h = (sum_k s^2_{h,k})^(beta / 2) of the next allocation, for every kernel that writes one (the sample kernel's interior hypercubes,
+// k_strat_reduce's cut ones, the stratified sweep).  beta = 2 hands the sum through: the device's pow(x, 1.0) is within an ulp of x, not x.
+__device__ __forceinline__ double strat_damp(double ssum, double beta) {
+    const double a = 0.5 * beta;
+    return a == 1.0 ? ssum : pow(ssum, a);
 }
 
 // LDS behind the sample kernel's own carve (doubles): offsets [nloc + 1] (int64) | sums [nloc][2 NW] | lane hypercubes [T] (int) |
@@ -299,7 +310,7 @@ template <class Cfg> __device__ __forceinline__ void vegas_strat(const BatchArgs
                     pm[NW + qq] += V * V * v2 / n;
                     ssum += v2;
                 });
-                st.dnext[hfirst + j] = pow(ssum, 0.5 * st.beta);
+                st.dnext[hfirst + j] = strat_damp(ssum, st.beta);
             } else {
                 const int rr = (j == 0) ? 0 : 1; // cut at the chunk's start (or both ends) | at its end
                 double *rs = st.rec_s + (2 * chunk + rr) * 2 * NW;

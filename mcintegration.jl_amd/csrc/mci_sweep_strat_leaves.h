@@ -141,7 +141,7 @@ template <class Cfg> __device__ __forceinline__ void vegas_sweep_strat_leaves(co
                             pm[NW + qq] += V * V * v2 / n;
                             ssum += v2;
                         });
-                        d[hfirst + j] = pow(ssum, 0.5 * st.beta);
+                        d[hfirst + j] = strat_damp(ssum, st.beta);
                     } else if (j == nl - 1) {
                         static_for<0, 2 * NW>([&](auto Q) { cut[decltype(Q)::value] = sj[decltype(Q)::value]; });
                     }

@@ -638,6 +638,55 @@ class Engine:
             out["grids"], out["tables"], out["walk_counts"] = gsplit, list(zip(dsplit, asplit)), (int(counts[0]), int(counts[1]))
         return out
 
+    def strat_alloc_rows(self, d, nsamp, uniform=False):
+        """test hook (csrc/mci_debug.h mci_debug_strat_alloc): k_strat_alloc's three launches on their own over d [ncube] made up by the
+        caller -> (off [ncube + 1] int64, tsum [2 ntile + 2] = tile sums | tile bases | total | uniform flag).  This engine gives its
+        device only and need not be stratified; its own plan and allocation stay as they are"""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.ndim != 1:
+            raise ValueError("d [ncube]")
+        ntile = max(min(-(-d.size // 256), 1024), 0)
+        off = np.full(d.size + 1, -1, dtype=np.int64)
+        tsum = np.full(2 * ntile + 2, np.nan)
+        check(lib().mci_debug_strat_alloc(self.p, _dp(d), d.size, int(nsamp), 1 if uniform else 0, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(tsum)))
+        return off, tsum
+
+    def strat_reduce_rows(self, off, part, rec_h, rec_s, dnext, beta, log_row=True):
+        """test hook (csrc/mci_debug.h mci_debug_strat_reduce): k_strat_reduce on its own over off [ncube + 1], part [nchunk, 2 nw], rec_h
+        [nchunk, 2], rec_s [nchunk, 2, 2 nw] and dnext [ncube] (the fill the cut hypercubes' d_h are written into) -> dict of out [2 nw],
+        log_row [2 nw] (None if not asked for: the kernel is then given no log row) and dnext [ncube] as the kernel left it"""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        part = np.ascontiguousarray(part, dtype=np.float64)
+        rec_h = np.ascontiguousarray(rec_h, dtype=np.int64)
+        rec_s = np.ascontiguousarray(rec_s, dtype=np.float64)
+        dn = np.array(dnext, dtype=np.float64, order="C")
+        if (off.ndim != 1 or part.ndim != 2 or part.shape[1] % 2 or rec_h.shape != (part.shape[0], 2) or rec_s.shape != (part.shape[0], 2, part.shape[1])
+                or dn.shape != (off.size - 1,)):
+            raise ValueError("off [ncube + 1], part [nchunk, 2 nw], rec_h [nchunk, 2], rec_s [nchunk, 2, 2 nw], dnext [ncube]")
+        nchunk, nw = part.shape[0], part.shape[1] // 2
+        out = np.full(2 * nw, np.nan)
+        row = np.full(2 * nw, np.nan) if log_row else None
+        i64 = C.POINTER(C.c_int64)
+        io = _lib.DebugStratReduceIO(off.size - 1, nchunk, nw, float(beta), off.ctypes.data_as(i64), _dp(part), rec_h.ctypes.data_as(i64), _dp(rec_s),
+                                     _dp(dn), _dp(out), None if row is None else _dp(row))
+        check(lib().mci_debug_strat_reduce(self.p, C.byref(io)))
+        return dict(out=out, log_row=row, dnext=dn)
+
+    def strat_remap_rows(self, n_old, n_new, e, d_old):
+        """test hook (csrc/mci_debug.h mci_debug_strat_remap): k_strat_remap on its own: d_old [prod n_old] on the plan n_old -> d_new
+        [prod n_new] on the plan n_new, raised to e (e == 1 copies the bits)"""
+        no, nn = np.ascontiguousarray(n_old, dtype=np.int32), np.ascontiguousarray(n_new, dtype=np.int32)
+        d = np.ascontiguousarray(d_old, dtype=np.float64)
+        if no.ndim != 1 or no.shape != nn.shape or d.ndim != 1:
+            raise ValueError("n_old and n_new [ndim], d_old [prod n_old]")
+        # (a plan the hook refuses is refused before anything is read or written)
+        ok = 1 <= no.size <= 32 and min(no.min(), nn.min()) >= 1 and max(np.prod(no, dtype=np.float64), np.prod(nn, dtype=np.float64)) < 2 ** 31
+        if ok and d.size != int(np.prod(no, dtype=np.int64)):
+            raise ValueError("n_old and n_new [ndim], d_old [prod n_old]")
+        out = np.full(int(np.prod(nn, dtype=np.int64)) if ok else 1, np.nan)
+        check(lib().mci_debug_strat_remap(self.p, no.size, no.ctypes.data_as(c_int32_p), nn.ctypes.data_as(c_int32_p), float(e), _dp(d), _dp(out)))
+        return out
+
     def sweep_resample_lds(self):
         """stored chains per block up to which a carried sweep point's resampler keeps its running weights in LDS (csrc/mci_debug.h
         mci_debug_sweep_resample_lds)"""

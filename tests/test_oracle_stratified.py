@@ -6,6 +6,8 @@ import math
 import numpy as np
 import pytest
 
+from strat_cases import kernel_order_alloc
+
 SEED = 20240229
 
 
@@ -129,41 +131,6 @@ def test_cell_decode(oracle, nstrat):
     cell = np.stack(np.unravel_index(h, nstrat, order="F"), axis=1)
     np.testing.assert_array_equal(np.floor(r["y"] * np.array(nstrat, dtype=np.float64)).astype(np.int64), cell)
     assert np.all(r["y"] < 1.0)
-
-
-def kernel_order_alloc(d, N):
-    """k_strat_alloc's documented order of the prefix sum in double: tiles of ceil(ncube / min(ceil(ncube / 256),
-    1024)) hypercubes, 256 stretches each; P_h = tile base + (stretch base + running sum), every base the sequential sum of what lies
-    before it; then C_h = M P_h / P, floor, the last one M."""
-    d = np.asarray(d, dtype=np.float64)
-    nc = d.size
-    M = N - 2 * nc
-    ntile = min(-(-nc // 256), 1024)
-    tl = -(-nc // ntile)
-    Ppre = np.zeros(nc)
-    tsum = np.zeros(ntile)
-    inner = []
-    for g in range(ntile):
-        t0, t1 = min(g * tl, nc), min(g * tl + tl, nc)
-        if t1 <= t0:
-            inner.append(None)
-            continue
-        per = -(-(t1 - t0) // 256)
-        pad = np.zeros(256 * per)
-        pad[:t1 - t0] = d[t0:t1]
-        run = np.cumsum(pad.reshape(256, per), axis=1)          # sequential along a stretch
-        sbase = np.concatenate([[0.0], np.cumsum(run[:, -1])])  # sequential over the stretches
-        tsum[g] = sbase[256]
-        inner.append((t0, t1, (sbase[:256, None] + run).reshape(-1)[:t1 - t0]))
-    tbase = np.concatenate([[0.0], np.cumsum(tsum)])
-    total = tbase[ntile]
-    for g, it in enumerate(inner):
-        if it is not None:
-            Ppre[it[0]:it[1]] = tbase[g] + it[2]
-    C = np.minimum(float(M) * Ppre / total, float(M))
-    C[-1] = M
-    fl = np.floor(C).astype(np.int64)
-    return np.concatenate([[0], 2 * np.arange(1, nc + 1) + fl])
 
 
 CAP_CASES = [(64, 8192), (24389, 200000), (528529, 2 ** 22 + 5)]

@@ -133,3 +133,6 @@ def test_entry_points_are_bound():
     L = mci.lib()
     assert hasattr(L, "mci_set_stratification_carry") and hasattr(L, "mci_get_strat_carry")
     assert L.mci_abi_version() == _lib.ABI_VERSION   # (two functions more, no structure changed)
+    hooks = {name: args for name, _, args in _lib.DEBUG_SIGNATURES}
+    for name in ("mci_debug_strat_alloc", "mci_debug_strat_reduce", "mci_debug_strat_remap"):     # (tests/test_strat_kernels_host.py holds their signatures)
+        assert name in hooks and hasattr(L, name)

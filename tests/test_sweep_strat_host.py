@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import mcintegration_jl_amd as mci
-from test_oracle_stratified import kernel_order_alloc
+from strat_cases import kernel_order_alloc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "mcintegration.jl_amd", "csrc", "mci_strat.h")

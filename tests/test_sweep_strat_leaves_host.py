@@ -12,7 +12,7 @@ import pytest
 
 import mcintegration_jl_amd as mci
 from test_hip_sweep_strat_leaves import CHAIN_CASES, CHAIN_IDS, LAYOUTS
-from test_oracle_stratified import kernel_order_alloc
+from strat_cases import kernel_order_alloc
 from test_sweep_strat_host import uniform_offsets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
