@@ -1867,42 +1867,243 @@ template <class Cfg> __device__ __forceinline__ void store_carried(const BatchAr
     static_for<0, Cfg::NDRAW>([&](auto K) { constexpr int k = decltype(K)::value; a.store_x[(i64)k * a.store_cap + slot] = c.x[k]; });
 }
 
-template <class Cfg> __device__ __forceinline__ void vegasmc_chains(const BatchArgs &a) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+// ---------------------------------------------------------------------------------------------
+// What the four chain kernels (vegasmc_chains | mcmc_chains and their host-closure forms vegasmc_host_step | mcmc_host_step), the
+// carry-weight kernel and a sweep point's workgroup (mci_sweep_chains.h) share around the Markov step.
+// ---------------------------------------------------------------------------------------------
+// The prologue: the three tables into LDS, with ZERO the workgroup's histogram, observable and propose | accept areas cleared, the
+// barrier, and where the draws read their tables.
+template <class Cfg, bool ZERO> __device__ __forceinline__ Tables<Cfg> chain_setup(const BatchArgs &a, double *smem) {
     const int tid = threadIdx.x, T = blockDim.x;
     double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
-    double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
     stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    if constexpr (Mode<Cfg>::HIST_LDS)
-        for (int i = tid; i < Cfg::HTILE * Cfg::HCOPY; i += T) sH[i] = 0.0;
-    for (int i = tid; i < Cfg::NOBS * ocopy<Cfg>(); i += T) sO[i] = 0.0;
-    u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
-    for (int i = tid; i < 2 * PaTable<Cfg>::N; i += T) sPA[i] = 0ull;
+    if constexpr (ZERO) {
+        double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
+        if constexpr (Mode<Cfg>::HIST_LDS)
+            for (int i = tid; i < Cfg::HTILE * Cfg::HCOPY; i += T) sH[i] = 0.0;
+        for (int i = tid; i < Cfg::NOBS * ocopy<Cfg>(); i += T) sO[i] = 0.0;
+        u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
+        for (int i = tid; i < 2 * PaTable<Cfg>::N; i += T) sPA[i] = 0ull;
+    }
     __syncthreads();
     Tables<Cfg> t;
     if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
     else t.E = a.edges;
     t.DA = sDA;
     t.DD = sDD;
+    return t;
+}
+// The stream words of block B's chains and the Philox key.  chain identity = (block, chain within the block): the block index rides in
+// the top 12 bits of the stream word, so the streams of a block do not depend on how many chains any other block (or rank) runs
+struct ChainStreams { u32 init, step, group, k0, k1; };
+template <int INIT, int STEP, int GROUP> __device__ __forceinline__ ChainStreams chain_streams(const BatchArgs &a, const i64 B) {
+    const u32 bs = (u32)B << 20;
+    ChainStreams S;
+    S.init = a.iteration * 8u + INIT + bs;
+    S.step = a.iteration * 8u + STEP + bs;
+    S.group = a.iteration * 8u + GROUP + bs;
+    S.k0 = (u32)a.seed;
+    S.k1 = (u32)(a.seed >> 32);
+    return S;
+}
+template <class Cfg> __device__ __forceinline__ void load_reweight(const BatchArgs &a, double (&rw)[Cfg::NI + 1]) {
+    static_for<0, Cfg::NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
+}
+// the lane's partial statistics row: the observable sums and the columns behind them
+template <class Cfg> __device__ __forceinline__ void zero_partials(double (&acc)[Cfg::NW], double (&extra)[Cfg::NCOLS - Cfg::NOBS]) {
+    static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
+    static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
+}
+// rand(1:n) of step `s` (0-based) from the chain's own uniform or, shared, from the one the 64 chains ch & ~63 .. ch | 63 of ONE block
+// have in common.  The sequence does not depend on the chain states, so every chain is still a valid Markov chain and blocks stay
+// independent; the dispatch on the picked index becomes a scalar branch (the lane-per-chain kernels read it through readfirstlane).
+__device__ __forceinline__ int group_pick(const ChainStreams &S, const bool shared, const double uown, const i64 ch, const u64 s, const int n) {
+    double u = uown;
+    if (shared) {
+        const u64 gidx = ((u64)(ch & ~(i64)63) << 32) | s;
+        const u32x4 rg = philox4x32_10((u32)gidx, (u32)(gidx >> 32), 0u, S.group, S.k0, S.k1);
+        u = u01(rg.x, rg.y);
+    }
+    int k = (int)(u * (double)n);
+    if (k >= n) k = n - 1;
+    return k;
+}
+// create! on every live slot as one sample of the map draws it: x, bin, prob = 1/pj  (sampler.jl:303 / :20)
+template <class Cfg> __device__ __forceinline__ void chain_from_sample(const Sample<Cfg> &s, Chain<Cfg> &c) {
+    static_for<0, Cfg::NDRAW>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        c.x[k] = s.x[k];
+        c.bin[k] = s.bin[k];
+        c.prob[k] = 1.0 / s.pj[k];
+    });
+}
+template <class Cfg> __device__ __forceinline__ void pad_probs(const Chain<Cfg> &c, double (&pad)[Cfg::NI + 1]) {
+    static_for<0, Cfg::NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); });
+}
+
+// ---- BatchArgs::HostStep: chain cid's column of the state arrays (SoA, stride nc) ----
+// PROPOSED: the proposal the host evaluated (hx, pprob, pbin), else the chain's configuration (cx, cprob, cbin)
+template <class Cfg, bool PROPOSED> __device__ __forceinline__ void hs_load_chain(const BatchArgs::HostStep &h, const i64 cid, Chain<Cfg> &c) {
+    const i64 nc = h.nc;
+    static_for<0, Cfg::NDRAW>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        c.x[k] = (PROPOSED ? h.hx : h.cx)[k * nc + cid];
+        c.prob[k] = (PROPOSED ? h.pprob : h.cprob)[k * nc + cid];
+        c.bin[k] = (PROPOSED ? h.pbin : h.cbin)[k * nc + cid];
+    });
+}
+template <class Cfg, bool PROPOSED> __device__ __forceinline__ void hs_store_chain(const BatchArgs::HostStep &h, const i64 cid, const Chain<Cfg> &c) {
+    const i64 nc = h.nc;
+    static_for<0, Cfg::NDRAW>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        (PROPOSED ? h.hx : h.cx)[k * nc + cid] = c.x[k];
+        (PROPOSED ? h.pprob : h.cprob)[k * nc + cid] = c.prob[k];
+        (PROPOSED ? h.pbin : h.cbin)[k * nc + cid] = c.bin[k];
+    });
+}
+// a start configuration: the chain's state and what the host evaluates first
+template <class Cfg> __device__ __forceinline__ void hs_store_start(const BatchArgs::HostStep &h, const i64 cid, const Chain<Cfg> &c) {
+    const i64 nc = h.nc;
+    static_for<0, Cfg::NDRAW>([&](auto K) {
+        constexpr int k = decltype(K)::value;
+        h.cx[k * nc + cid] = c.x[k];
+        h.hx[k * nc + cid] = c.x[k];
+        h.cbin[k * nc + cid] = c.bin[k];
+        h.cprob[k * nc + cid] = c.prob[k];
+    });
+}
+
+// ---- the :vegasmc step (vegas_mc/updates.jl:45-106, vegas_mc/montecarlo.jl:151-232), shared by vegasmc_chains and vegasmc_host_step ----
+// config.probability  montecarlo.jl:162-166, updates.jl:84-87:  reweight[N+1] pad[N+1] + sum_i |w_i| reweight[i] pad[i]
+template <class Cfg> __device__ __forceinline__ double vegasmc_target(const double *w /*[NW]*/, const double (&rw)[Cfg::NI + 1], const double (&pad)[Cfg::NI + 1]) {
+    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    double p = rw[NORMI] * pad[NORMI];
+    static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; p += absw<Cfg, i>(w) * rw[i] * pad[i]; });
+    return p;
+}
+// changeVariable up to the integrand call (updates.jl:52-66): pool vi's slot picked by uslot is drawn again.  n: the proposed
+// configuration (unchanged draws are copy-propagated); active: there was something to sample
+template <class Cfg> struct VegasmcProposal {
+    Chain<Cfg> n;
+    double prop;
+    bool active;
+};
+template <class Cfg> __device__ __forceinline__ VegasmcProposal<Cfg> vegasmc_propose(const Tables<Cfg> &t, const Chain<Cfg> &c, const int vi, const double uslot, const u64 sidx,
+                                                                                    const u32 st_step, const u32 k0, const u32 k1, const u32x4 &r1) {
+    Chain<Cfg> n = c;
+    double prop = 1.0;
+    bool active = false;
+    static_for<0, Cfg::NPOOL>([&](auto V) {
+        constexpr int v = decltype(V)::value;
+        constexpr int md = Cfg::pool_maxdof(v), nl = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
+        // :52-57  a lone single-valued Discrete, or a pool nobody uses, has nothing to sample
+        constexpr bool skip = (md <= 0) || (nl == 1 && Cfg::leaf_kind(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1 &&
+                                            Cfg::leaf_nbin(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1);
+        if constexpr (!skip) {
+            if (vi == v) {
+                active = true;
+                int slot = (int)(uslot * (double)md); // :58
+                if (slot >= md) slot = md - 1;
+                static_for<0, nl>([&](auto Lf) {
+                    constexpr int l = decltype(Lf)::value;
+                    constexpr int kk = 3 + l; // RNG draw index within the step
+                    double y;
+                    if constexpr (kk == 3) y = u01(r1.z, r1.w);
+                    else {
+                        const u32x4 rr = philox4x32_10((u32)sidx, (u32)(sidx >> 32), (u32)(kk >> 1), st_step, k0, k1);
+                        y = (kk & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
+                    }
+                    double xo, po, xn, pn;
+                    int bo, bn;
+                    get_slot<Cfg, v, l>(c, slot, xo, po, bo);
+                    draw_pool_leaf<Cfg, v, l>(t, y, xn, pn, bn); // shift!  sampler.jl:336-386, :57-71
+                    put_slot<Cfg, v, l>(n, slot, xn, pn, bn);
+                    prop *= po / pn;                              // 1/prob_ratio  sampler.jl:385, :70
+                });
+            }
+        }
+    });
+    VegasmcProposal<Cfg> out;
+    out.n = n;
+    out.prop = prop;
+    out.active = active;
+    return out;
+}
+// changeVariable from the proposal's weights wn on (updates.jl:77-102).  count(ok) books propose | accept (:90, :92) where the
+// kernel keeps them, between the decision and the commit.
+template <class Cfg, class Count> __device__ __forceinline__ void vegasmc_accept(const VegasmcProposal<Cfg> &pr, const double *wn /*[NW]*/, const double uacc, const double (&rw)[Cfg::NI + 1],
+                                                                                Chain<Cfg> &c, double (&w)[Cfg::NW], double (&pad)[Cfg::NI + 1], double &probability,
+                                                                                double (&extra)[Cfg::NCOLS - Cfg::NOBS], Count &&count) {
+    constexpr int NI = Cfg::NI, XE = Cols<Cfg>::NEVAL - Cfg::NOBS;
+    double padn[NI + 1];
+    extra[XE] += 1.0;                                 // config.neval += 1   :77
+    pad_probs<Cfg>(pr.n, padn);                       // :79-81
+    const double newp = vegasmc_target<Cfg>(wn, rw, padn); // :84-87
+    const double R = pr.prop * newp / probability;    // :88
+    const bool ok = uacc < R;                         // :91
+    count(ok);
+    if (ok) {
+        c = pr.n;
+        static_for<0, Cfg::NW>([&](auto I) { w[decltype(I)::value] = wn[decltype(I)::value]; }); // :93-95
+        static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = padn[decltype(I)::value]; }); // :96-98
+        probability = newp;                           // :100
+    } // else shiftRollback!  :102  (the proposal copy is dropped)
+}
+// histogram  montecarlo.jl:198-211
+template <class Cfg> __device__ __forceinline__ void vegasmc_hist_weights(const Chain<Cfg> &c, const double (&w)[Cfg::NW], const double (&pad)[Cfg::NI + 1], const double probability,
+                                                                         double *sH, double *gH, const int tile) {
+    constexpr int NI = Cfg::NI;
+    double wh[NI];
+    static_for<0, NI>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        const double aw = absw<Cfg, i>(w);
+        const double f2 = aw * aw / own_prob<Cfg, i>(c);                   // :203
+        wh[i] = f2 * pad[i] / probability;                                 // :204
+    });
+    Sample<Cfg> sb;
+    static_for<0, Cfg::NDRAW>([&](auto K) { sb.bin[decltype(K)::value] = c.bin[decltype(K)::value]; });
+    hist_update<Cfg>(sb, wh, sH, gH, tile);
+}
+// measurement  montecarlo.jl:213-232, the mj-th of chain ch of local block lb
+template <class Cfg> __device__ __forceinline__ void vegasmc_measure(const BatchArgs &a, const i64 lb, const i64 ch, const i64 mj, const int tile, const Chain<Cfg> &c,
+                                                                    const double (&w)[Cfg::NW], const double (&pad)[Cfg::NI + 1], const double (&rw)[Cfg::NI + 1],
+                                                                    const double probability, double (&acc)[Cfg::NW], double (&extra)[Cfg::NCOLS - Cfg::NOBS], double *sO) {
+    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
+    double relw[Cfg::NW];
+    static_for<0, NI>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        extra[XV + i] += absw<Cfg, i>(w) * fabs(pad[i] * rw[i]) / probability; // :216
+        static_for<0, Cfg::NCOMP>([&](auto Q) {
+            constexpr int q = i * Cfg::NCOMP + decltype(Q)::value;
+            relw[q] = w[q] * pad[i] / probability;                             // :218/:220
+        });
+    });
+    if constexpr (Cfg::HOST_MEASURE != 0) { // :224-227 on the host, after the launch
+        if (tile == 0) host_measure_record<Cfg, Cfg::NW>(a, lb, ch, mj, c.x, relw, -1);
+    } else
+    measure<Cfg>(c.x, c.bin, relw, a.ud, acc, obs_wave<Cfg>(sO));
+    extra[XN] += pad[NORMI] / probability;                // :229
+    extra[XV + NORMI] += rw[NORMI] * pad[NORMI] / probability; // :230
+}
+
+template <class Cfg> __device__ __forceinline__ void vegasmc_chains(const BatchArgs &a) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NI = Cfg::NI;
+    const int tid = threadIdx.x, T = blockDim.x;
+    double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
+    u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
+    const Tables<Cfg> t = chain_setup<Cfg, true>(a, smem);
 
     const WorkItem wi = work_item<Cfg>(a);
     const int slice = wi.slice, tile = wi.tile;
-    const i64 B = a.block_lo + wi.lb;
     const i64 steps = a.neval_per_block / a.nchain;
-    // chain identity = (block, chain within the block): the block index rides in the top 12 bits of the stream word, so the
-    // streams of a block do not depend on how many chains any other block (or rank) runs
-    const u32 bs = (u32)B << 20;
-    const u32 st_init = a.iteration * 8u + STREAM_MC_INIT + bs, st_step = a.iteration * 8u + STREAM_MC_STEP + bs;
-    const u32 k0 = (u32)a.seed, k1 = (u32)(a.seed >> 32);
+    const ChainStreams S = chain_streams<STREAM_MC_INIT, STREAM_MC_STEP, STREAM_MC_GROUP>(a, a.block_lo + wi.lb);
     double rw[NI + 1];
-    static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
+    load_reweight<Cfg>(a, rw);
 
-    double acc[Cfg::NW];
-    static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
-    double extra[Cfg::NCOLS - Cfg::NOBS];
-    static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
-    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XE = Cols<Cfg>::NEVAL - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
+    double acc[Cfg::NW], extra[Cfg::NCOLS - Cfg::NOBS];
+    zero_partials<Cfg>(acc, extra);
     u32 npr[Cfg::NPOOL], nac[Cfg::NPOOL]; // propose[2, 1, vi], accept[2, 1, vi] of the lane's current chain (vegas_mc/updates.jl:90-92)
     static_for<0, Cfg::NPOOL>([&](auto V) { npr[decltype(V)::value] = 0u; nac[decltype(V)::value] = 0u; });
     auto flush_pa = [&]() { // lane counters -> the workgroup's 64-bit table in LDS (once per chain: off the step loop)
@@ -1921,130 +2122,47 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_chains(const BatchA
         if (a.carry_x) load_carried<Cfg>(a, t, wi.lb, carried_from(a, wi.lb, ch), c); // continues the previous iteration's chain (BatchArgs::carry_x)
         else {   // initialize!  (montecarlo.jl:151-153): create! on every live slot
             Sample<Cfg> s;
-            draw_sample<Cfg>(t, a.seed, st_init, g, s);
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                c.x[k] = s.x[k];
-                c.bin[k] = s.bin[k];
-                c.prob[k] = 1.0 / s.pj[k]; // sampler.jl:303 / :20
-            });
+            draw_sample<Cfg>(t, a.seed, S.init, g, s);
+            chain_from_sample<Cfg>(s, c);
         }
         double w[Cfg::NW], pad[NI + 1];
         Cfg::integrand(c.x, w, a.ud, -1); // :155-159
-        static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); }); // :161
-        double probability = rw[NORMI] * pad[NORMI]; // :162
-        static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; probability += absw<Cfg, i>(w) * rw[i] * pad[i]; }); // :163-166
+        pad_probs<Cfg>(c, pad);           // :161
+        double probability = vegasmc_target<Cfg>(w, rw, pad);
 
         i64 mcnt = 0, mj = 0; // ne % measurefreq and ne / measurefreq, carried (no 64-bit division per step)
         for (i64 ne = 1; ne <= steps; ++ne) { // :184
             const u64 sidx = (g << 32) | (u64)(ne - 1);
-            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, st_step, k0, k1);
-            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, st_step, k0, k1);
+            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, S.step, S.k0, S.k1);
+            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, S.step, S.k0, S.k1);
             // ---- changeVariable  updates.jl:45-106 ----
-            // :50 rand(1:Nv).  With many chains per block the 64 chains of a wave share the pool-pick sequence (it does
-            // not depend on the chain states): the pool dispatch below becomes a scalar branch
-            double upool = u01(r0.x, r0.y);
-            if (Cfg::NPOOL > 1 && a.nchain > 1) {
-                const u64 gidx = ((u64)(ch & ~(i64)63) << 32) | (u64)(ne - 1);
-                const u32x4 rg = philox4x32_10((u32)gidx, (u32)(gidx >> 32), 0u, a.iteration * 8u + STREAM_MC_GROUP + bs, k0, k1);
-                upool = u01(rg.x, rg.y);
-            }
-            int vi = (int)(upool * (double)Cfg::NPOOL);
-            if (vi >= Cfg::NPOOL) vi = Cfg::NPOOL - 1;
-            if (Cfg::NPOOL > 1 && a.nchain > 1) vi = __builtin_amdgcn_readfirstlane(vi);
+            // :50 rand(1:Nv).  With many chains per block the 64 chains of a wave share the pool-pick sequence: the pool
+            // dispatch becomes a scalar branch
+            const bool shared = Cfg::NPOOL > 1 && a.nchain > 1;
+            int vi = group_pick(S, shared, u01(r0.x, r0.y), ch, (u64)(ne - 1), Cfg::NPOOL);
+            if (shared) vi = __builtin_amdgcn_readfirstlane(vi);
             const double uslot = u01(r0.z, r0.w);
             const double uacc = u01(r1.x, r1.y);
-            Chain<Cfg> n = c; // proposal; unchanged draws are copy-propagated
-            double prop = 1.0;
-            bool active = false;
-            static_for<0, Cfg::NPOOL>([&](auto V) {
-                constexpr int v = decltype(V)::value;
-                constexpr int md = Cfg::pool_maxdof(v), nl = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
-                // :52-57  a lone single-valued Discrete, or a pool nobody uses, has nothing to sample
-                constexpr bool skip = (md <= 0) || (nl == 1 && Cfg::leaf_kind(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1 &&
-                                                    Cfg::leaf_nbin(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1);
-                if constexpr (!skip) {
-                    if (vi == v) {
-                        active = true;
-                        int slot = (int)(uslot * (double)md); // :58
-                        if (slot >= md) slot = md - 1;
-                        static_for<0, nl>([&](auto Lf) {
-                            constexpr int l = decltype(Lf)::value;
-                            constexpr int kk = 3 + l; // RNG draw index within the step
-                            double y;
-                            if constexpr (kk == 3) y = u01(r1.z, r1.w);
-                            else {
-                                const u32x4 rr = philox4x32_10((u32)sidx, (u32)(sidx >> 32), (u32)(kk >> 1), st_step, k0, k1);
-                                y = (kk & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
-                            }
-                            double xo, po, xn, pn;
-                            int bo, bn;
-                            get_slot<Cfg, v, l>(c, slot, xo, po, bo);
-                            draw_pool_leaf<Cfg, v, l>(t, y, xn, pn, bn); // shift!  sampler.jl:336-386, :57-71
-                            put_slot<Cfg, v, l>(n, slot, xn, pn, bn);
-                            prop *= po / pn;                              // 1/prob_ratio  sampler.jl:385, :70
-                        });
-                    }
-                }
-            });
-            if (active && prop > 4.9406564584124654e-324) { // :63-65
-                double wn[Cfg::NW], padn[NI + 1];
-                Cfg::integrand(n.x, wn, a.ud, -1);             // :67-75
-                extra[XE] += 1.0;                              // config.neval += 1   :77
-                static_for<0, NI + 1>([&](auto I) { padn[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(n); }); // :79-81
-                double newp = rw[NORMI] * padn[NORMI];         // :84
-                static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; newp += absw<Cfg, i>(wn) * rw[i] * padn[i]; }); // :85-87
-                const double R = prop * newp / probability;    // :88
-                const bool ok = uacc < R;                      // :91
-                static_for<0, Cfg::NPOOL>([&](auto V) { // (vi is wave-uniform with many chains per block: one scalar branch is taken)
-                    constexpr int v = decltype(V)::value;
-                    if (vi == v) {
-                        npr[v] += 1u;                          // :90
-                        nac[v] += ok ? 1u : 0u;                // :92
-                    }
+            const VegasmcProposal<Cfg> pr = vegasmc_propose<Cfg>(t, c, vi, uslot, sidx, S.step, S.k0, S.k1, r1);
+            if (pr.active && pr.prop > 4.9406564584124654e-324) { // :63-65
+                double wn[Cfg::NW];
+                Cfg::integrand(pr.n.x, wn, a.ud, -1);              // :67-75
+                vegasmc_accept<Cfg>(pr, wn, uacc, rw, c, w, pad, probability, extra, [&](const bool ok) {
+                    static_for<0, Cfg::NPOOL>([&](auto V) { // (vi is wave-uniform with many chains per block: one scalar branch is taken)
+                        constexpr int v = decltype(V)::value;
+                        if (vi == v) {
+                            npr[v] += 1u;                          // :90
+                            nac[v] += ok ? 1u : 0u;                // :92
+                        }
+                    });
                 });
-                if (ok) {
-                    c = n;
-                    static_for<0, Cfg::NW>([&](auto I) { w[decltype(I)::value] = wn[decltype(I)::value]; }); // :93-95
-                    static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = padn[decltype(I)::value]; }); // :96-98
-                    probability = newp;                        // :100
-                } // else shiftRollback!  :102  (the proposal copy is dropped)
             }
-            // ---- histogram  montecarlo.jl:198-211 ----
-            {
-                double wh[NI];
-                static_for<0, NI>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    const double aw = absw<Cfg, i>(w);
-                    const double f2 = aw * aw / own_prob<Cfg, i>(c);                   // :203
-                    wh[i] = f2 * pad[i] / probability;                                 // :204
-                });
-                Sample<Cfg> sb;
-                static_for<0, Cfg::NDRAW>([&](auto K) { sb.bin[decltype(K)::value] = c.bin[decltype(K)::value]; });
-                hist_update<Cfg>(sb, wh, sH, a.ghist, tile);
-            }
+            vegasmc_hist_weights<Cfg>(c, w, pad, probability, sH, a.ghist, tile);
             if ((ne & 0x3FFFFFFF) == 0) flush_pa(); // (32-bit lane counters: hand over long before they wrap)
-            // ---- measurement  montecarlo.jl:213-232 ----
             mcnt = mcnt + 1 == a.measurefreq ? 0 : mcnt + 1;
             const bool mf = mcnt == 0;
             mj += mf ? 1 : 0;
-            if (mf && (double)ne >= a.burnin) { // :213
-                double relw[Cfg::NW];
-                static_for<0, NI>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    extra[XV + i] += absw<Cfg, i>(w) * fabs(pad[i] * rw[i]) / probability; // :216
-                    static_for<0, Cfg::NCOMP>([&](auto Q) {
-                        constexpr int q = i * Cfg::NCOMP + decltype(Q)::value;
-                        relw[q] = w[q] * pad[i] / probability;                             // :218/:220
-                    });
-                });
-                if constexpr (Cfg::HOST_MEASURE != 0) { // :224-227 on the host, after the launch
-                    if (tile == 0) host_measure_record<Cfg, Cfg::NW>(a, wi.lb, ch, mj, c.x, relw, -1);
-                } else
-                measure<Cfg>(c.x, c.bin, relw, a.ud, acc, obs_wave<Cfg>(sO));
-                extra[XN] += pad[NORMI] / probability;                // :229
-                extra[XV + NORMI] += rw[NORMI] * pad[NORMI] / probability; // :230
-            }
+            if (mf && (double)ne >= a.burnin) vegasmc_measure<Cfg>(a, wi.lb, ch, mj, tile, c, w, pad, rw, probability, acc, extra, sO); // :213
         }
         flush_pa();
         if (a.store_x && tile == 0) {
@@ -2061,7 +2179,7 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_chains(const BatchA
 // One stored chain: j = local block * carry_nchain + stored chain.  Shared by the grid-strided launch below and by a sweep point's
 // workgroup, which strides over one block's stored chains between two of its iterations (mci_sweep_chains.h).
 template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weight(const BatchArgs &a, const Tables<Cfg> &t, const double (&rw)[Cfg::NI + 1], const i64 j) {
-    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    constexpr int NI = Cfg::NI;
     const i64 lb = j / a.carry_nchain, from = j % a.carry_nchain;
     Chain<Cfg> c;
     load_carried<Cfg>(a, t, lb, from, c);
@@ -2070,26 +2188,17 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weight(const 
         static_for<0, Cfg::NW>([&](auto Q) { w[decltype(Q)::value] = a.host_w[decltype(Q)::value * a.carry_total + j]; });
     else
     Cfg::integrand(c.x, w, a.ud, -1);
-    static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); });
-    double probability = rw[NORMI] * pad[NORMI];
-    static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; probability += absw<Cfg, i>(w) * rw[i] * pad[i]; });
+    pad_probs<Cfg>(c, pad);
+    const double probability = vegasmc_target<Cfg>(w, rw, pad);
     const double r = probability / a.carry_P[lb * a.carry_nchain + from];
     a.carry_w[j] = (r == r && r < 1.7976931348623157e308 && r > 0.0) ? r : 0.0; // (a configuration neither target can have produced continues nothing)
 }
 template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weights(const BatchArgs &a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI;
     const int tid = threadIdx.x, T = blockDim.x;
-    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
-    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    __syncthreads();
-    Tables<Cfg> t;
-    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
-    else t.E = a.edges;
-    t.DA = sDA;
-    t.DD = sDD;
-    double rw[NI + 1];
-    static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
+    const Tables<Cfg> t = chain_setup<Cfg, false>(a, smem);
+    double rw[Cfg::NI + 1];
+    load_reweight<Cfg>(a, rw);
     for (i64 j = (i64)blockIdx.x * T + tid; j < a.carry_total; j += (i64)gridDim.x * T) vegasmc_carry_weight<Cfg>(a, t, rw, j);
 }
 
@@ -2102,36 +2211,19 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_carry_weights(const
 template <class Cfg> __device__ __forceinline__ void vegasmc_host_step(const BatchArgs &a) {
     static_assert(Cfg::NTILE == 1, "host-closure chains keep one histogram tile");
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI, NORMI = Cfg::NI;
+    constexpr int NI = Cfg::NI;
     const int tid = threadIdx.x, T = blockDim.x;
-    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
     double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
-    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    if constexpr (Mode<Cfg>::HIST_LDS)
-        for (int i = tid; i < Cfg::HTILE * Cfg::HCOPY; i += T) sH[i] = 0.0;
-    for (int i = tid; i < Cfg::NOBS * ocopy<Cfg>(); i += T) sO[i] = 0.0;
     u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
-    for (int i = tid; i < 2 * PaTable<Cfg>::N; i += T) sPA[i] = 0ull;
-    __syncthreads();
-    Tables<Cfg> t;
-    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
-    else t.E = a.edges;
-    t.DA = sDA;
-    t.DD = sDD;
+    const Tables<Cfg> t = chain_setup<Cfg, true>(a, smem);
 
     const WorkItem wi = work_item<Cfg>(a);
     const BatchArgs::HostStep &h = a.hs;
-    const i64 B = a.block_lo + wi.lb;
-    const u32 bs = (u32)B << 20;
-    const u32 st_init = a.iteration * 8u + STREAM_MC_INIT + bs, st_step = a.iteration * 8u + STREAM_MC_STEP + bs;
-    const u32 k0 = (u32)a.seed, k1 = (u32)(a.seed >> 32);
+    const ChainStreams S = chain_streams<STREAM_MC_INIT, STREAM_MC_STEP, STREAM_MC_GROUP>(a, a.block_lo + wi.lb);
     double rw[NI + 1];
-    static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
-    double acc[Cfg::NW];
-    static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
-    double extra[Cfg::NCOLS - Cfg::NOBS];
-    static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
-    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XE = Cols<Cfg>::NEVAL - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
+    load_reweight<Cfg>(a, rw);
+    double acc[Cfg::NW], extra[Cfg::NCOLS - Cfg::NOBS];
+    zero_partials<Cfg>(acc, extra);
     const i64 nc = h.nc;
 
     for (i64 ch = (i64)wi.slice * T + tid; ch < a.nchain; ch += (i64)a.wg_per_block * T) {
@@ -2142,35 +2234,18 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_host_step(const Bat
             if (a.carry_x) load_carried<Cfg>(a, t, wi.lb, carried_from(a, wi.lb, ch), c); // ... or the previous iteration's chain goes on (BatchArgs::carry_x)
             else {
                 Sample<Cfg> s;
-                draw_sample<Cfg>(t, a.seed, st_init, g, s);
-                static_for<0, Cfg::NDRAW>([&](auto K) {
-                    constexpr int k = decltype(K)::value;
-                    c.x[k] = s.x[k];
-                    c.bin[k] = s.bin[k];
-                    c.prob[k] = 1.0 / s.pj[k]; // sampler.jl:303 / :20
-                });
+                draw_sample<Cfg>(t, a.seed, S.init, g, s);
+                chain_from_sample<Cfg>(s, c);
             }
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                h.cx[k * nc + cid] = c.x[k];
-                h.hx[k * nc + cid] = c.x[k];
-                h.cbin[k * nc + cid] = c.bin[k];
-                h.cprob[k * nc + cid] = c.prob[k];
-            });
+            hs_store_start<Cfg>(h, cid, c);
             continue;
         }
-        static_for<0, Cfg::NDRAW>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            c.x[k] = h.cx[k * nc + cid];
-            c.prob[k] = h.cprob[k * nc + cid];
-            c.bin[k] = h.cbin[k * nc + cid];
-        });
+        hs_load_chain<Cfg, false>(h, cid, c);
         double w[Cfg::NW], pad[NI + 1], probability;
-        static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(c); }); // :161
+        pad_probs<Cfg>(c, pad); // :161
         if (h.ne == 1) { // the weights of the initial configuration: config.probability  (:162-166)
             static_for<0, Cfg::NW>([&](auto Q) { w[decltype(Q)::value] = a.host_w[decltype(Q)::value * nc + cid]; });
-            probability = rw[NORMI] * pad[NORMI];
-            static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; probability += absw<Cfg, i>(w) * rw[i] * pad[i]; });
+            probability = vegasmc_target<Cfg>(w, rw, pad);
         } else {
             static_for<0, Cfg::NW>([&](auto Q) { w[decltype(Q)::value] = h.cw[decltype(Q)::value * nc + cid]; });
             probability = h.cprobability[cid];
@@ -2178,120 +2253,35 @@ template <class Cfg> __device__ __forceinline__ void vegasmc_host_step(const Bat
             const int vi = h.pvi[cid];
             const double prop = h.pprop[cid];
             if (vi >= 0 && prop > 4.9406564584124654e-324) { // :63-65
-                Chain<Cfg> n;
-                static_for<0, Cfg::NDRAW>([&](auto K) {
-                    constexpr int k = decltype(K)::value;
-                    n.x[k] = h.hx[k * nc + cid];
-                    n.prob[k] = h.pprob[k * nc + cid];
-                    n.bin[k] = h.pbin[k * nc + cid];
-                });
-                double wn[Cfg::NW], padn[NI + 1];
+                VegasmcProposal<Cfg> pr; // as the launch before this one left it
+                hs_load_chain<Cfg, true>(h, cid, pr.n);
+                pr.prop = prop;
+                pr.active = true;
+                double wn[Cfg::NW];
                 static_for<0, Cfg::NW>([&](auto Q) { wn[decltype(Q)::value] = a.host_w[decltype(Q)::value * nc + cid]; }); // :67-75, on the host
-                extra[XE] += 1.0;                              // config.neval += 1   :77
-                static_for<0, NI + 1>([&](auto I) { padn[decltype(I)::value] = pad_prob<Cfg, decltype(I)::value>(n); }); // :79-81
-                double newp = rw[NORMI] * padn[NORMI];         // :84
-                static_for<0, NI>([&](auto I) { constexpr int i = decltype(I)::value; newp += absw<Cfg, i>(wn) * rw[i] * padn[i]; }); // :85-87
-                const double R = prop * newp / probability;    // :88
-                const bool ok = h.puacc[cid] < R;              // :91
-                lds_count(&sPA[PaTable<Cfg>::idx(1, 0, vi)], 1ull);                              // :90
-                if (ok) lds_count(&sPA[PaTable<Cfg>::N + PaTable<Cfg>::idx(1, 0, vi)], 1ull);    // :92
-                if (ok) {
-                    c = n;
-                    static_for<0, Cfg::NW>([&](auto I) { w[decltype(I)::value] = wn[decltype(I)::value]; }); // :93-95
-                    static_for<0, NI + 1>([&](auto I) { pad[decltype(I)::value] = padn[decltype(I)::value]; }); // :96-98
-                    probability = newp;                        // :100
-                } // else shiftRollback!  :102
-            }
-            {   // histogram  montecarlo.jl:198-211
-                double wh[NI];
-                static_for<0, NI>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    const double aw = absw<Cfg, i>(w);
-                    const double f2 = aw * aw / own_prob<Cfg, i>(c);                   // :203
-                    wh[i] = f2 * pad[i] / probability;                                 // :204
+                vegasmc_accept<Cfg>(pr, wn, h.puacc[cid], rw, c, w, pad, probability, extra, [&](const bool ok) {
+                    lds_count(&sPA[PaTable<Cfg>::idx(1, 0, vi)], 1ull);                              // :90
+                    if (ok) lds_count(&sPA[PaTable<Cfg>::N + PaTable<Cfg>::idx(1, 0, vi)], 1ull);    // :92
                 });
-                Sample<Cfg> sb;
-                static_for<0, Cfg::NDRAW>([&](auto K) { sb.bin[decltype(K)::value] = c.bin[decltype(K)::value]; });
-                hist_update<Cfg>(sb, wh, sH, a.ghist, 0);
             }
-            if (ne % a.measurefreq == 0 && (double)ne >= a.burnin) { // measurement  :213-232
-                double relw[Cfg::NW];
-                static_for<0, NI>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    extra[XV + i] += absw<Cfg, i>(w) * fabs(pad[i] * rw[i]) / probability; // :216
-                    static_for<0, Cfg::NCOMP>([&](auto Q) {
-                        constexpr int q = i * Cfg::NCOMP + decltype(Q)::value;
-                        relw[q] = w[q] * pad[i] / probability;                             // :218/:220
-                    });
-                });
-                if constexpr (Cfg::HOST_MEASURE != 0) host_measure_record<Cfg, Cfg::NW>(a, wi.lb, ch, ne / a.measurefreq, c.x, relw, -1);
-                else measure<Cfg>(c.x, c.bin, relw, a.ud, acc, obs_wave<Cfg>(sO));
-                extra[XN] += pad[NORMI] / probability;                // :229
-                extra[XV + NORMI] += rw[NORMI] * pad[NORMI] / probability; // :230
-            }
+            vegasmc_hist_weights<Cfg>(c, w, pad, probability, sH, a.ghist, 0);
+            if (ne % a.measurefreq == 0 && (double)ne >= a.burnin) // :213
+                vegasmc_measure<Cfg>(a, wi.lb, ch, ne / a.measurefreq, 0, c, w, pad, rw, probability, acc, extra, sO);
         }
         if (h.ne <= h.steps) { // ---- changeVariable, up to the integrand call  updates.jl:45-66 ----
             const i64 ne = h.ne;
             const u64 sidx = (g << 32) | (u64)(ne - 1);
-            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, st_step, k0, k1);
-            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, st_step, k0, k1);
-            double upool = u01(r0.x, r0.y);
-            if (Cfg::NPOOL > 1 && a.nchain > 1) { // (the 64 chains of a wave share the pool pick, as in vegasmc_chains)
-                const u64 gidx = ((u64)(ch & ~(i64)63) << 32) | (u64)(ne - 1);
-                const u32x4 rg = philox4x32_10((u32)gidx, (u32)(gidx >> 32), 0u, a.iteration * 8u + STREAM_MC_GROUP + bs, k0, k1);
-                upool = u01(rg.x, rg.y);
-            }
-            int vi = (int)(upool * (double)Cfg::NPOOL);
-            if (vi >= Cfg::NPOOL) vi = Cfg::NPOOL - 1;
+            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, S.step, S.k0, S.k1);
+            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, S.step, S.k0, S.k1);
+            const int vi = group_pick(S, Cfg::NPOOL > 1 && a.nchain > 1, u01(r0.x, r0.y), ch, (u64)(ne - 1), Cfg::NPOOL); // :50
             const double uslot = u01(r0.z, r0.w);
-            Chain<Cfg> n = c;
-            double prop = 1.0;
-            bool active = false;
-            static_for<0, Cfg::NPOOL>([&](auto V) {
-                constexpr int v = decltype(V)::value;
-                constexpr int md = Cfg::pool_maxdof(v), nl = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
-                constexpr bool skip = (md <= 0) || (nl == 1 && Cfg::leaf_kind(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1 &&
-                                                    Cfg::leaf_nbin(Cfg::draw_leaf(md > 0 ? k00 : 0)) == 1);
-                if constexpr (!skip) {
-                    if (vi == v) {
-                        active = true;
-                        int slot = (int)(uslot * (double)md); // :58
-                        if (slot >= md) slot = md - 1;
-                        static_for<0, nl>([&](auto Lf) {
-                            constexpr int l = decltype(Lf)::value;
-                            constexpr int kk = 3 + l;
-                            double y;
-                            if constexpr (kk == 3) y = u01(r1.z, r1.w);
-                            else {
-                                const u32x4 rr = philox4x32_10((u32)sidx, (u32)(sidx >> 32), (u32)(kk >> 1), st_step, k0, k1);
-                                y = (kk & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
-                            }
-                            double xo, po, xn, pn;
-                            int bo, bn;
-                            get_slot<Cfg, v, l>(c, slot, xo, po, bo);
-                            draw_pool_leaf<Cfg, v, l>(t, y, xn, pn, bn); // shift!  sampler.jl:336-386, :57-71
-                            put_slot<Cfg, v, l>(n, slot, xn, pn, bn);
-                            prop *= po / pn;                              // 1/prob_ratio  sampler.jl:385, :70
-                        });
-                    }
-                }
-            });
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                h.hx[k * nc + cid] = n.x[k];
-                h.pprob[k * nc + cid] = n.prob[k];
-                h.pbin[k * nc + cid] = n.bin[k];
-            });
-            h.pprop[cid] = prop;
+            const VegasmcProposal<Cfg> pr = vegasmc_propose<Cfg>(t, c, vi, uslot, sidx, S.step, S.k0, S.k1, r1);
+            hs_store_chain<Cfg, true>(h, cid, pr.n);
+            h.pprop[cid] = pr.prop;
             h.puacc[cid] = u01(r1.x, r1.y);
-            h.pvi[cid] = active ? vi : -1;
+            h.pvi[cid] = pr.active ? vi : -1;
         }
-        static_for<0, Cfg::NDRAW>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            h.cx[k * nc + cid] = c.x[k];
-            h.cprob[k * nc + cid] = c.prob[k];
-            h.cbin[k * nc + cid] = c.bin[k];
-        });
+        hs_store_chain<Cfg, false>(h, cid, c);
         static_for<0, Cfg::NW>([&](auto Q) { h.cw[decltype(Q)::value * nc + cid] = w[decltype(Q)::value]; });
         h.cprobability[cid] = probability;
         if (a.store_x && h.ne == h.steps + 1) { // the chain's last step is through
@@ -2602,54 +2592,134 @@ template <class Cfg> __device__ __forceinline__ McmcProposal<Cfg> mcmc_propose(c
     return out;
 }
 
+// ---- the rest of the :mcmc step (mcmc/montecarlo.jl:118-172, mcmc/updates.jl:35-53), shared by mcmc_chains and mcmc_host_step ----
+template <class Cfg> __device__ __forceinline__ Weight<Cfg> zero_weight() {
+    Weight<Cfg> r;
+    static_for<0, Cfg::NCOMP>([&](auto Q) { r.v[decltype(Q)::value] = 0.0; });
+    r.abs = 0.0;
+    return r;
+}
+// the weight the host evaluated for chain cid's handed-over configuration
+template <class Cfg> __device__ __forceinline__ Weight<Cfg> host_weight(const BatchArgs &a, const i64 cid) {
+    const i64 nc = a.hs.nc;
+    Weight<Cfg> r;
+    static_for<0, Cfg::NCOMP>([&](auto Q) { r.v[decltype(Q)::value] = a.host_w[decltype(Q)::value * nc + cid]; });
+    if constexpr (Cfg::NCOMP == 1) r.abs = fabs(r.v[0]);
+    else r.abs = hypot(r.v[0], r.v[Cfg::NCOMP - 1]);
+    return r;
+}
+// reweight[i] of a run-time integrand index
+template <class Cfg> __device__ __forceinline__ double rw_sel(const double (&rw)[Cfg::NI + 1], const int i) {
+    double r = rw[Cfg::NI];
+    static_for<0, Cfg::NI>([&](auto I) { if (i == decltype(I)::value) r = rw[decltype(I)::value]; });
+    return r;
+}
+// initialize!  montecarlo.jl:190-193: try `tr` of chain g's start configuration
+template <class Cfg> __device__ __forceinline__ void mcmc_draw_start(const BatchArgs &a, const Tables<Cfg> &t, const ChainStreams &S, const u64 g, const int tr, Chain<Cfg> &c) {
+    Sample<Cfg> s;
+    draw_sample<Cfg>(t, a.seed, S.init, g * 16384ull + (u64)tr, s);
+    chain_from_sample<Cfg>(s, c);
+    static_for<0, Cfg::NPOOL>([&](auto V) { // FermiK slots are created jointly from their D uniforms (same stream, k = flat draw)
+        constexpr int v = decltype(V)::value;
+        if constexpr (pool_is_fermik<Cfg>(v)) {
+            constexpr int D = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
+            constexpr double kF = Cfg::leaf_lower(Cfg::draw_leaf(k00));
+            static_for<0, Cfg::pool_maxdof(v)>([&](auto Sl) {
+                constexpr int kb = k00 + decltype(Sl)::value * D;
+                double u[D], kk[D];
+                const u64 iidx = g * 16384ull + (u64)tr;
+                static_for<0, D>([&](auto J) {
+                    constexpr int kq = kb + decltype(J)::value;
+                    const u32x4 rr = philox4x32_10((u32)iidx, (u32)(iidx >> 32), (u32)(kq >> 1), S.init, S.k0, S.k1);
+                    u[decltype(J)::value] = (kq & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
+                    kk[decltype(J)::value] = kF / sqrt((double)D); // variable.jl:13: the pool's initial content
+                });
+                (void)fermik_create<Cfg, v>(u, kk);
+                static_for<0, D>([&](auto J) { c.x[kb + decltype(J)::value] = kk[decltype(J)::value]; });
+            });
+        }
+    });
+}
+// The evaluate-and-accept tail of all three updates from the proposal's weight wn on (updates.jl:40-53, :94-105, :135-145).
+// decided(ok) runs between the bookkeeping and the commit, while the chain still holds its old state.
+template <class Cfg, class Decided> __device__ __forceinline__ void mcmc_accept(const McmcProposal<Cfg> &pr, const Weight<Cfg> &wn, const double uacc, const double (&rw)[Cfg::NI + 1], u64 *sPA,
+                                                                               Chain<Cfg> &c, int &curr, Weight<Cfg> &weight, double &probability,
+                                                                               double (&extra)[Cfg::NCOLS - Cfg::NOBS], Decided &&decided) {
+    constexpr int NORMI = Cfg::NI, XE = Cols<Cfg>::NEVAL - Cfg::NOBS;
+    extra[XE] += 1.0;                                                                         // :40, :94, :135
+    const double newp = pr.newcurr == NORMI ? rw[NORMI] : wn.abs * rw_sel<Cfg>(rw, pr.newcurr); // :42-44, :96, :137
+    const double R = pr.prop * newp / probability;                                            // :46, :97, :138
+    const bool ok = uacc < R;                                                                 // :49, :100, :141
+    // propose[1, curr, new] :48,:50 | propose[2, curr, vi] :99,:101 | propose[3, curr, vi] :140,:142
+    pa_count<Cfg, false>(sPA, PaTable<Cfg>::idx(pr.ut, curr, pr.ut == 0 ? pr.newcurr : pr.pvi), true, ok);
+    decided(ok);
+    if (ok) {
+        c = pr.n;
+        curr = pr.newcurr;                                                                    // :51-53
+        weight = wn;
+        probability = newp;
+    } // else the proposal copy is dropped: createRollback!/removeRollback! are no-ops (sampler.jl:306, :324),
+      // shiftRollback!/swapRollback! restore the slot (:105, :145)
+}
+// measurement  montecarlo.jl:144-172 of a chain that sits on an integrand (curr != N+1), the mj-th of chain ch of local block lb.  The
+// normalisation's one line (:158) stays in the kernels, the other arm of their branch: inside a helper the two arms' adds are sunk into one
+// add through a select of the two arrays' addresses (see get_slot), and the lane's partial row moves into scratch memory.
+template <class Cfg> __device__ __forceinline__ void mcmc_measure(const BatchArgs &a, const i64 lb, const i64 ch, const i64 mj, const int tile, const int curr, const Chain<Cfg> &c,
+                                                                 const Weight<Cfg> &weight, const double probability, double (&acc)[Cfg::NW], double *sH, double *sO) {
+    constexpr int NI = Cfg::NI;
+    double relw[Cfg::NCOMP]; // :162
+    static_for<0, Cfg::NCOMP>([&](auto Q) { relw[decltype(Q)::value] = weight.v[decltype(Q)::value] / probability; });
+    if constexpr (Cfg::HOST_MEASURE != 0) { // measure(idx, var, obs, relative_weight, config) on the host, after the launch  :166-169
+        if (tile == 0) host_measure_record<Cfg, Cfg::NCOMP>(a, lb, ch, mj, c.x, relw, curr);
+    }
+    static_for<0, NI>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        if (curr == i) {
+            static_for<0, Cfg::NDRAW>([&](auto K) { // :147-154  accumulate!(var, pos + offset, 1.0)
+                constexpr int k = decltype(K)::value;
+                if constexpr ((Cfg::own_mask(i) >> k) & 1ull) hist_add<Cfg, k>(c.bin[k], 1.0, sH, a.ghist, tile);
+            });
+            if constexpr (Cfg::HOST_MEASURE != 0) {
+            } else if constexpr (Cfg::CUSTOM_MEASURE != 0) { // measure(idx, var, obs, relative_weight, config)  :166-169
+                double rwv[Cfg::NW];
+                static_for<0, Cfg::NW>([&](auto Q) { rwv[decltype(Q)::value] = 0.0; });
+                static_for<0, Cfg::NCOMP>([&](auto Q) { rwv[i * Cfg::NCOMP + decltype(Q)::value] = relw[decltype(Q)::value]; });
+                Cfg::measure(c.x, rwv, a.ud, i, obs_wave<Cfg>(sO));
+            } else if constexpr (Cfg::obs_bin_draw(i) >= 0) {
+                const int b = c.bin[Cfg::obs_bin_draw(i)];
+                if (b >= 0 && b < Cfg::obs_nbin(i)) lds_add(&obs_wave<Cfg>(sO)[Cfg::obs_off(i) + b], relw[0]);
+            }
+        }
+        if constexpr (Cfg::CUSTOM_MEASURE == 0 && Cfg::obs_bin_draw(i) < 0) // :164
+            static_for<0, Cfg::NCOMP>([&](auto Q) { acc[i * Cfg::NCOMP + decltype(Q)::value] += curr == i ? relw[decltype(Q)::value] : 0.0; });
+    });
+}
+
 template <class Cfg> __device__ __forceinline__ void mcmc_chains(const BatchArgs &a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NI = Cfg::NI, NORMI = Cfg::NI, ND = Cfg::NI + 1, NPOOL = Cfg::NPOOL;
     constexpr int NUPD = 2 * NPOOL + 2; // [changeIntegrand, swapVariable, changeVariable x 2*Nv]  montecarlo.jl:127-130
     const int tid = threadIdx.x, T = blockDim.x;
-    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
     double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
-    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    if constexpr (Mode<Cfg>::HIST_LDS)
-        for (int i = tid; i < Cfg::HTILE * Cfg::HCOPY; i += T) sH[i] = 0.0;
-    for (int i = tid; i < Cfg::NOBS * ocopy<Cfg>(); i += T) sO[i] = 0.0;
     u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
-    for (int i = tid; i < 2 * PaTable<Cfg>::N; i += T) sPA[i] = 0ull;
-    __syncthreads();
-    Tables<Cfg> t;
-    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
-    else t.E = a.edges;
-    t.DA = sDA;
-    t.DD = sDD;
+    const Tables<Cfg> t = chain_setup<Cfg, true>(a, smem);
 
     const WorkItem wi = work_item<Cfg>(a);
     const int slice = wi.slice, tile = wi.tile;
-    const i64 B = a.block_lo + wi.lb;
     const i64 steps = a.neval_per_block / a.nchain, nburn = a.nburn;
-    const u32 bs = (u32)B << 20; // (block, chain within the block) identify a chain: see vegasmc_chains
-    const u32 st_init = a.iteration * 8u + STREAM_MCMC_INIT + bs, st_step = a.iteration * 8u + STREAM_MCMC_STEP + bs;
-    const u32 k0 = (u32)a.seed, k1 = (u32)(a.seed >> 32);
+    const ChainStreams S = chain_streams<STREAM_MCMC_INIT, STREAM_MCMC_STEP, STREAM_MCMC_GROUP>(a, a.block_lo + wi.lb);
     double rw[ND];
-    static_for<0, ND>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
-    auto rw_sel = [&](int i) {
-        double r = rw[NORMI];
-        static_for<0, NI>([&](auto I) { if (i == decltype(I)::value) r = rw[decltype(I)::value]; });
-        return r;
-    };
+    load_reweight<Cfg>(a, rw);
 
-    double acc[Cfg::NW];
-    static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
-    double extra[Cfg::NCOLS - Cfg::NOBS];
-    static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
-    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XE = Cols<Cfg>::NEVAL - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
+    double acc[Cfg::NW], extra[Cfg::NCOLS - Cfg::NOBS];
+    zero_partials<Cfg>(acc, extra);
+    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
 
     for (i64 ch = (i64)slice * T + tid; ch < a.nchain; ch += (i64)a.wg_per_block * T) {
         const u64 g = (u64)ch;
         int curr = a.nchain == 1 ? 0 : (int)(g % (u64)ND); // montecarlo.jl:76 idx = 1; many chains start stratified
         Chain<Cfg> c;
-        Weight<Cfg> weight; // :116 _State(curr, zero(T), 1.0)
-        static_for<0, Cfg::NCOMP>([&](auto Q) { weight.v[decltype(Q)::value] = 0.0; });
-        weight.abs = 0.0;
+        Weight<Cfg> weight = zero_weight<Cfg>(); // :116 _State(curr, zero(T), 1.0)
         double probability = 1.0;
         bool fresh = a.carry_x == nullptr;
         if (!fresh) { // continues the previous iteration's chain: its configuration and the integrand it sat on (BatchArgs::carry_x)
@@ -2658,7 +2728,7 @@ template <class Cfg> __device__ __forceinline__ void mcmc_chains(const BatchArgs
             curr = a.carry_curr[wi.lb * a.carry_nchain + from];
             if (curr != NORMI) {
                 weight = eval_sel<Cfg>(curr, c.x, a.ud);        // :197 on the carried configuration
-                probability = weight.abs * rw_sel(curr);        // :199
+                probability = weight.abs * rw_sel<Cfg>(rw, curr); // :199
                 if (!(probability > 4.940656458412465e-274)) {  // (cannot happen while the integrand is the one that left it there)
                     fresh = true;
                     curr = (int)(g % (u64)ND);
@@ -2666,40 +2736,12 @@ template <class Cfg> __device__ __forceinline__ void mcmc_chains(const BatchArgs
             } else probability = rw[NORMI];                     // :201-202
         }
         for (int tr = 0; fresh && tr < 10000; ++tr) {    // :118-124
-            Sample<Cfg> s;
-            draw_sample<Cfg>(t, a.seed, st_init, g * 16384ull + (u64)tr, s); // initialize!  :190-193
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                c.x[k] = s.x[k];
-                c.bin[k] = s.bin[k];
-                c.prob[k] = 1.0 / s.pj[k];
-            });
-            static_for<0, NPOOL>([&](auto V) { // FermiK slots are created jointly from their D uniforms (same stream, k = flat draw)
-                constexpr int v = decltype(V)::value;
-                if constexpr (pool_is_fermik<Cfg>(v)) {
-                    constexpr int D = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
-                    constexpr double kF = Cfg::leaf_lower(Cfg::draw_leaf(k00));
-                    static_for<0, Cfg::pool_maxdof(v)>([&](auto S) {
-                        constexpr int kb = k00 + decltype(S)::value * D;
-                        double u[D], kk[D];
-                        const u64 iidx = g * 16384ull + (u64)tr;
-                        static_for<0, D>([&](auto J) {
-                            constexpr int kq = kb + decltype(J)::value;
-                            const u32x4 rr = philox4x32_10((u32)iidx, (u32)(iidx >> 32), (u32)(kq >> 1), st_init, k0, k1);
-                            u[decltype(J)::value] = (kq & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
-                            kk[decltype(J)::value] = kF / sqrt((double)D); // variable.jl:13: the pool's initial content
-                        });
-                        (void)fermik_create<Cfg, v>(u, kk);
-                        static_for<0, D>([&](auto J) { c.x[kb + decltype(J)::value] = kk[decltype(J)::value]; });
-                    });
-                }
-            });
+            mcmc_draw_start<Cfg>(a, t, S, g, tr, c);
             if (curr != NORMI) {
                 weight = eval_sel<Cfg>(curr, c.x, a.ud);        // :197
-                probability = weight.abs * rw_sel(curr);        // :199
+                probability = weight.abs * rw_sel<Cfg>(rw, curr); // :199
             } else {
-                static_for<0, Cfg::NCOMP>([&](auto Q) { weight.v[decltype(Q)::value] = 0.0; });
-                weight.abs = 0.0;
+                weight = zero_weight<Cfg>();
                 probability = rw[NORMI];                        // :201-202
             }
             if (curr == NORMI || probability > 4.940656458412465e-274) break; // :120-122 (TINY)
@@ -2714,108 +2756,54 @@ template <class Cfg> __device__ __forceinline__ void mcmc_chains(const BatchArgs
         for (i64 it = 1; it <= steps + nburn; ++it) { // :134
             const u64 sidx = (g << 32) | (u64)(it - 1);
             static_for<0, ND>([&](auto I) { extra[XV + decltype(I)::value] += curr == decltype(I)::value ? 1.0 : 0.0; }); // :136
-            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, st_step, k0, k1);
-            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, st_step, k0, k1);
-            const u32x4 r2 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 2u, st_step, k0, k1);
-            // :137 rand(rng, updates).  With many chains per block the 64 chains of a wave (chains ch & ~63 .. | 63 of ONE
-            // block) share the update-type sequence: it is independent of the chain states, so every chain is still a
-            // valid Markov chain, blocks stay independent, and the wave no longer walks through all three update bodies
-            // at every step.  nchain = 1 (the reference's chain) draws its own.
-            double uupd = u01(r0.x, r0.y);
-            if (a.nchain > 1) {
-                const u64 gidx = ((u64)(ch & ~(i64)63) << 32) | (u64)(it - 1);
-                const u32x4 rg = philox4x32_10((u32)gidx, (u32)(gidx >> 32), 0u, a.iteration * 8u + STREAM_MCMC_GROUP + bs, k0, k1);
-                uupd = u01(rg.x, rg.y);
-            }
-            int upd = (int)(uupd * (double)NUPD);
-            if (upd >= NUPD) upd = NUPD - 1;
+            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, S.step, S.k0, S.k1);
+            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, S.step, S.k0, S.k1);
+            const u32x4 r2 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 2u, S.step, S.k0, S.k1);
+            // :137 rand(rng, updates).  With many chains per block the 64 chains of a wave share the update-type sequence: the
+            // wave no longer walks through all three update bodies at every step.  nchain = 1 (the reference's chain) draws its own.
+            int upd = group_pick(S, a.nchain > 1, u01(r0.x, r0.y), ch, (u64)(it - 1), NUPD);
             if (a.nchain > 1) upd = __builtin_amdgcn_readfirstlane(upd); // wave-uniform by construction: a scalar branch
             const double upick = u01(r0.z, r0.w), us1 = u01(r1.x, r1.y), us2 = u01(r1.z, r1.w), uacc = u01(r2.x, r2.y);
             // ---- build the proposal (n, prop, newcurr); ONE evaluate-and-accept tail serves all three updates, so
             // lanes that diverged on the update type reconverge before the expensive part ----
-            const McmcProposal<Cfg> pr = mcmc_propose<Cfg>(t, c, curr, upd, upick, us1, us2, sidx, st_step, k0, k1, r2);
-            const Chain<Cfg> &n = pr.n;
-            const double prop = pr.prop;
-            const bool active = pr.active;
-            const int newcurr = pr.newcurr, ut = pr.ut, pvi = pr.pvi;
-            const u64 touched = pr.touched;
-            if (active && prop > 4.9406564584124654e-324) { // updates.jl:29-31, :88-90, :129-131
-                Weight<Cfg> wn;
-                static_for<0, Cfg::NCOMP>([&](auto Q) { wn.v[decltype(Q)::value] = 0.0; });
-                wn.abs = 0.0;
-                if (newcurr != NORMI) wn = eval_sel<Cfg>(newcurr, n.x, a.ud);                  // :35-38, :92, :133
-                extra[XE] += 1.0;                                                               // :40, :94, :135
-                const double newp = newcurr == NORMI ? rw[NORMI] : wn.abs * rw_sel(newcurr);    // :42-44, :96, :137
-                const double R = prop * newp / probability;                                     // :46, :97, :138
-                const bool ok = uacc < R;                                                       // :49, :100, :141
-                // propose[1, curr, new] :48,:50 | propose[2, curr, vi] :99,:101 | propose[3, curr, vi] :140,:142
-                pa_count<Cfg, false>(sPA, PaTable<Cfg>::idx(ut, curr, ut == 0 ? newcurr : pvi), true, ok);
-                if (a.hold_hist) {
-                    const int now = (int)it;
-                    u64 mo = 0ull, mn = 0ull; // live draws of the old and of the proposed integrand
-                    static_for<0, NI>([&](auto I) {
-                        constexpr int i = decltype(I)::value;
-                        mo = curr == i ? Cfg::own_mask(i) : mo;
-                        mn = newcurr == i ? Cfg::own_mask(i) : mn;
-                    });
-                    static_for<0, Cfg::NDRAW>([&](auto K) {
-                        constexpr int k = decltype(K)::value;
-                        // changeIntegrand: the slots it creates start their first hold (they held nothing before);
-                        // changeVariable / swapVariable: an accepted move of the slot ends its hold (also when a Discrete
-                        // redraw lands on the same value: the chain was free to move)
-                        const bool chg = ok && (((ut == 0 ? (mn & ~mo) : touched) >> k) & 1ull) != 0ull;
-                        const int hold = now - last[k];
-                        hmax = (chg && ut != 0 && hold > hmax) ? hold : hmax;
-                        last[k] = chg ? now : last[k];
-                    });
-                    const bool chg = ok && newcurr != curr;
-                    const int hold = now - lastc;
-                    hmax = (chg && hold > hmax) ? hold : hmax;
-                    lastc = chg ? now : lastc;
-                }
-                if (ok) {
-                    c = n;
-                    curr = newcurr;                                                             // :51-53
-                    weight = wn;
-                    probability = newp;
-                } // else the proposal copy is dropped: createRollback!/removeRollback! are no-ops (sampler.jl:306, :324),
-                  // shiftRollback!/swapRollback! restore the slot (:105, :145)
+            const McmcProposal<Cfg> pr = mcmc_propose<Cfg>(t, c, curr, upd, upick, us1, us2, sidx, S.step, S.k0, S.k1, r2);
+            if (pr.active && pr.prop > 4.9406564584124654e-324) { // updates.jl:29-31, :88-90, :129-131
+                Weight<Cfg> wn = zero_weight<Cfg>();
+                if (pr.newcurr != NORMI) wn = eval_sel<Cfg>(pr.newcurr, pr.n.x, a.ud);         // :35-38, :92, :133
+                mcmc_accept<Cfg>(pr, wn, uacc, rw, sPA, c, curr, weight, probability, extra, [&](const bool ok) {
+                    if (a.hold_hist) {
+                        const int newcurr = pr.newcurr, ut = pr.ut;
+                        const u64 touched = pr.touched;
+                        const int now = (int)it;
+                        u64 mo = 0ull, mn = 0ull; // live draws of the old and of the proposed integrand
+                        static_for<0, NI>([&](auto I) {
+                            constexpr int i = decltype(I)::value;
+                            mo = curr == i ? Cfg::own_mask(i) : mo;
+                            mn = newcurr == i ? Cfg::own_mask(i) : mn;
+                        });
+                        static_for<0, Cfg::NDRAW>([&](auto K) {
+                            constexpr int k = decltype(K)::value;
+                            // changeIntegrand: the slots it creates start their first hold (they held nothing before);
+                            // changeVariable / swapVariable: an accepted move of the slot ends its hold (also when a Discrete
+                            // redraw lands on the same value: the chain was free to move)
+                            const bool chg = ok && (((ut == 0 ? (mn & ~mo) : touched) >> k) & 1ull) != 0ull;
+                            const int hold = now - last[k];
+                            hmax = (chg && ut != 0 && hold > hmax) ? hold : hmax;
+                            last[k] = chg ? now : last[k];
+                        });
+                        const bool chg = ok && newcurr != curr;
+                        const int hold = now - lastc;
+                        hmax = (chg && hold > hmax) ? hold : hmax;
+                        lastc = chg ? now : lastc;
+                    }
+                });
             }
-            // ---- measurement  montecarlo.jl:144-172 ----
             mcnt = mcnt + 1 == a.measurefreq ? 0 : mcnt + 1;
             const bool mf = mcnt == 0;
             mj += mf ? 1 : 0;
             if (mf && it >= nburn) {
-                if (curr != NORMI) {
-                    double relw[Cfg::NCOMP]; // :162
-                    static_for<0, Cfg::NCOMP>([&](auto Q) { relw[decltype(Q)::value] = weight.v[decltype(Q)::value] / probability; });
-                    if constexpr (Cfg::HOST_MEASURE != 0) { // measure(idx, var, obs, relative_weight, config) on the host, after the launch  :166-169
-                        if (tile == 0) host_measure_record<Cfg, Cfg::NCOMP>(a, wi.lb, ch, mj, c.x, relw, curr);
-                    }
-                    static_for<0, NI>([&](auto I) {
-                        constexpr int i = decltype(I)::value;
-                        if (curr == i) {
-                            static_for<0, Cfg::NDRAW>([&](auto K) { // :147-154  accumulate!(var, pos + offset, 1.0)
-                                constexpr int k = decltype(K)::value;
-                                if constexpr ((Cfg::own_mask(i) >> k) & 1ull) hist_add<Cfg, k>(c.bin[k], 1.0, sH, a.ghist, tile);
-                            });
-                            if constexpr (Cfg::HOST_MEASURE != 0) {
-                            } else if constexpr (Cfg::CUSTOM_MEASURE != 0) { // measure(idx, var, obs, relative_weight, config)  :166-169
-                                double rwv[Cfg::NW];
-                                static_for<0, Cfg::NW>([&](auto Q) { rwv[decltype(Q)::value] = 0.0; });
-                                static_for<0, Cfg::NCOMP>([&](auto Q) { rwv[i * Cfg::NCOMP + decltype(Q)::value] = relw[decltype(Q)::value]; });
-                                Cfg::measure(c.x, rwv, a.ud, i, obs_wave<Cfg>(sO));
-                            } else if constexpr (Cfg::obs_bin_draw(i) >= 0) {
-                                const int b = c.bin[Cfg::obs_bin_draw(i)];
-                                if (b >= 0 && b < Cfg::obs_nbin(i)) lds_add(&obs_wave<Cfg>(sO)[Cfg::obs_off(i) + b], relw[0]);
-                            }
-                        }
-                        if constexpr (Cfg::CUSTOM_MEASURE == 0 && Cfg::obs_bin_draw(i) < 0) // :164
-                            static_for<0, Cfg::NCOMP>([&](auto Q) { acc[i * Cfg::NCOMP + decltype(Q)::value] += curr == i ? relw[decltype(Q)::value] : 0.0; });
-                    });
-                } else {
-                    extra[XN] += 1.0 / rw[NORMI]; // :158
-                }
+                if (curr != NORMI) mcmc_measure<Cfg>(a, wi.lb, ch, mj, tile, curr, c, weight, probability, acc, sH, sO);
+                else extra[XN] += 1.0 / rw[NORMI]; // :158
             }
         }
         if (a.hold_hist) { // holds still running when the chain ends count with their length so far
@@ -2851,100 +2839,36 @@ template <class Cfg> __device__ __forceinline__ void mcmc_chains(const BatchArgs
 template <class Cfg> __device__ __forceinline__ void mcmc_host_step(const BatchArgs &a) {
     static_assert(Cfg::NTILE == 1, "host-closure chains keep one histogram tile");
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI, NORMI = Cfg::NI, ND = Cfg::NI + 1, NPOOL = Cfg::NPOOL;
+    constexpr int NORMI = Cfg::NI, ND = Cfg::NI + 1, NPOOL = Cfg::NPOOL;
     constexpr int NUPD = 2 * NPOOL + 2;
     const int tid = threadIdx.x, T = blockDim.x;
-    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
     double *sH = smem + Lds<Cfg>::H, *sO = smem + Lds<Cfg>::O;
-    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    if constexpr (Mode<Cfg>::HIST_LDS)
-        for (int i = tid; i < Cfg::HTILE * Cfg::HCOPY; i += T) sH[i] = 0.0;
-    for (int i = tid; i < Cfg::NOBS * ocopy<Cfg>(); i += T) sO[i] = 0.0;
     u64 *sPA = reinterpret_cast<u64 *>(smem + Lds<Cfg>::PA);
-    for (int i = tid; i < 2 * PaTable<Cfg>::N; i += T) sPA[i] = 0ull;
-    __syncthreads();
-    Tables<Cfg> t;
-    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
-    else t.E = a.edges;
-    t.DA = sDA;
-    t.DD = sDD;
+    const Tables<Cfg> t = chain_setup<Cfg, true>(a, smem);
 
     const WorkItem wi = work_item<Cfg>(a);
     const BatchArgs::HostStep &h = a.hs;
-    const i64 B = a.block_lo + wi.lb;
     const i64 total = a.neval_per_block / a.nchain + a.nburn, nburn = a.nburn, nc = h.nc;
-    const u32 bs = (u32)B << 20;
-    const u32 st_init = a.iteration * 8u + STREAM_MCMC_INIT + bs, st_step = a.iteration * 8u + STREAM_MCMC_STEP + bs;
-    const u32 k0 = (u32)a.seed, k1 = (u32)(a.seed >> 32);
+    const ChainStreams S = chain_streams<STREAM_MCMC_INIT, STREAM_MCMC_STEP, STREAM_MCMC_GROUP>(a, a.block_lo + wi.lb);
     double rw[ND];
-    static_for<0, ND>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
-    auto rw_sel = [&](int i) {
-        double r = rw[NORMI];
-        static_for<0, NI>([&](auto I) { if (i == decltype(I)::value) r = rw[decltype(I)::value]; });
-        return r;
-    };
-    double acc[Cfg::NW];
-    static_for<0, Cfg::NW>([&](auto I) { acc[decltype(I)::value] = 0.0; });
-    double extra[Cfg::NCOLS - Cfg::NOBS];
-    static_for<0, Cfg::NCOLS - Cfg::NOBS>([&](auto I) { extra[decltype(I)::value] = 0.0; });
-    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XE = Cols<Cfg>::NEVAL - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
+    load_reweight<Cfg>(a, rw);
+    double acc[Cfg::NW], extra[Cfg::NCOLS - Cfg::NOBS];
+    zero_partials<Cfg>(acc, extra);
+    constexpr int XN = Cols<Cfg>::NORM - Cfg::NOBS, XV = Cols<Cfg>::VISITED - Cfg::NOBS;
 
     for (i64 ch = (i64)wi.slice * T + tid; ch < a.nchain; ch += (i64)a.wg_per_block * T) {
         const u64 g = (u64)ch;
         const i64 cid = wi.lb * a.nchain + ch;
         Chain<Cfg> c;
-        auto draw_start = [&](const int tr) { // initialize!  :190-193: try `tr` of the start configuration -> state + what the host evaluates
-            Sample<Cfg> s;
-            draw_sample<Cfg>(t, a.seed, st_init, g * 16384ull + (u64)tr, s);
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                c.x[k] = s.x[k];
-                c.bin[k] = s.bin[k];
-                c.prob[k] = 1.0 / s.pj[k];
-            });
-            static_for<0, NPOOL>([&](auto V) { // FermiK slots are created jointly from their D uniforms (same stream, k = flat draw)
-                constexpr int v = decltype(V)::value;
-                if constexpr (pool_is_fermik<Cfg>(v)) {
-                    constexpr int D = Cfg::pool_nleaf(v), k00 = Cfg::pool_first_draw(v);
-                    constexpr double kF = Cfg::leaf_lower(Cfg::draw_leaf(k00));
-                    static_for<0, Cfg::pool_maxdof(v)>([&](auto S) {
-                        constexpr int kb = k00 + decltype(S)::value * D;
-                        double u[D], kk[D];
-                        const u64 iidx = g * 16384ull + (u64)tr;
-                        static_for<0, D>([&](auto J) {
-                            constexpr int kq = kb + decltype(J)::value;
-                            const u32x4 rr = philox4x32_10((u32)iidx, (u32)(iidx >> 32), (u32)(kq >> 1), st_init, k0, k1);
-                            u[decltype(J)::value] = (kq & 1) ? u01(rr.z, rr.w) : u01(rr.x, rr.y);
-                            kk[decltype(J)::value] = kF / sqrt((double)D);
-                        });
-                        (void)fermik_create<Cfg, v>(u, kk);
-                        static_for<0, D>([&](auto J) { c.x[kb + decltype(J)::value] = kk[decltype(J)::value]; });
-                    });
-                }
-            });
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                h.cx[k * nc + cid] = c.x[k];
-                h.hx[k * nc + cid] = c.x[k];
-                h.cbin[k * nc + cid] = c.bin[k];
-                h.cprob[k * nc + cid] = c.prob[k];
-            });
-        };
         if (h.ne == 0) {
             int curr0 = a.nchain == 1 ? 0 : (int)(g % (u64)ND); // montecarlo.jl:76 idx = 1; many chains start stratified
             if (a.carry_x) { // the previous iteration's chain goes on: its configuration and the integrand it sat on (BatchArgs::carry_x)
                 const i64 from = carried_from(a, wi.lb, ch);
                 load_carried<Cfg>(a, t, wi.lb, from, c);
                 curr0 = a.carry_curr[wi.lb * a.carry_nchain + from];
-                static_for<0, Cfg::NDRAW>([&](auto K) {
-                    constexpr int k = decltype(K)::value;
-                    h.cx[k * nc + cid] = c.x[k];
-                    h.hx[k * nc + cid] = c.x[k];
-                    h.cbin[k * nc + cid] = c.bin[k];
-                    h.cprob[k * nc + cid] = c.prob[k];
-                });
             } else
-            draw_start(0);
+            mcmc_draw_start<Cfg>(a, t, S, g, 0, c);
+            hs_store_start<Cfg>(h, cid, c);
             h.ccurr[cid] = curr0;
             h.cit[cid] = -1;
             h.ctr[cid] = 0;
@@ -2954,22 +2878,14 @@ template <class Cfg> __device__ __forceinline__ void mcmc_host_step(const BatchA
         int it = h.cit[cid];
         if (it >= total) continue; // this chain is through
         int curr = h.ccurr[cid];
-        static_for<0, Cfg::NDRAW>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            c.x[k] = h.cx[k * nc + cid];
-            c.prob[k] = h.cprob[k * nc + cid];
-            c.bin[k] = h.cbin[k * nc + cid];
-        });
+        hs_load_chain<Cfg, false>(h, cid, c);
         Weight<Cfg> weight;
         double probability;
         if (it < 0) { // ---- the start configuration was evaluated  :118-126, :195-203 ----
-            static_for<0, Cfg::NCOMP>([&](auto Q) { weight.v[decltype(Q)::value] = 0.0; });
-            weight.abs = 0.0;
+            weight = zero_weight<Cfg>();
             if (curr != NORMI) {
-                static_for<0, Cfg::NCOMP>([&](auto Q) { weight.v[decltype(Q)::value] = a.host_w[decltype(Q)::value * nc + cid]; });
-                if constexpr (Cfg::NCOMP == 1) weight.abs = fabs(weight.v[0]);
-                else weight.abs = hypot(weight.v[0], weight.v[Cfg::NCOMP - 1]);
-                probability = weight.abs * rw_sel(curr);        // :199
+                weight = host_weight<Cfg>(a, cid);
+                probability = weight.abs * rw_sel<Cfg>(rw, curr); // :199
             } else {
                 probability = rw[NORMI];                        // :201-202
             }
@@ -2979,7 +2895,8 @@ template <class Cfg> __device__ __forceinline__ void mcmc_host_step(const BatchA
                     if (probability == 0.0) atomicOr(a.status, ST_MCMC_INIT); // :125-126 error(...)
                 } else {
                     h.ctr[cid] = tr;
-                    draw_start(tr);
+                    mcmc_draw_start<Cfg>(a, t, S, g, tr, c);
+                    hs_store_start<Cfg>(h, cid, c);
                     h.hidx[cid] = curr;
                     continue;
                 }
@@ -2993,87 +2910,34 @@ template <class Cfg> __device__ __forceinline__ void mcmc_host_step(const BatchA
             const double prop = h.pprop[cid];
             const int newcurr = h.pnew[cid], ut = h.put[cid], pvi = h.pvi[cid];
             if (ut >= 0 && prop > 4.9406564584124654e-324) { // updates.jl:29-31, :88-90, :129-131  (ut < 0: nothing was proposed)
-                Chain<Cfg> n;
-                static_for<0, Cfg::NDRAW>([&](auto K) {
-                    constexpr int k = decltype(K)::value;
-                    n.x[k] = h.hx[k * nc + cid];
-                    n.prob[k] = h.pprob[k * nc + cid];
-                    n.bin[k] = h.pbin[k * nc + cid];
-                });
-                Weight<Cfg> wn;
-                static_for<0, Cfg::NCOMP>([&](auto Q) { wn.v[decltype(Q)::value] = 0.0; });
-                wn.abs = 0.0;
-                if (newcurr != NORMI) {                                                        // :35-38, :92, :133 -- on the host
-                    static_for<0, Cfg::NCOMP>([&](auto Q) { wn.v[decltype(Q)::value] = a.host_w[decltype(Q)::value * nc + cid]; });
-                    if constexpr (Cfg::NCOMP == 1) wn.abs = fabs(wn.v[0]);
-                    else wn.abs = hypot(wn.v[0], wn.v[Cfg::NCOMP - 1]);
-                }
-                extra[XE] += 1.0;                                                               // :40, :94, :135
-                const double newp = newcurr == NORMI ? rw[NORMI] : wn.abs * rw_sel(newcurr);    // :42-44, :96, :137
-                const double R = prop * newp / probability;                                     // :46, :97, :138
-                const bool ok = h.puacc[cid] < R;                                               // :49, :100, :141
-                pa_count<Cfg, false>(sPA, PaTable<Cfg>::idx(ut, curr, ut == 0 ? newcurr : pvi), true, ok);
-                if (ok) {
-                    c = n;
-                    curr = newcurr;                                                             // :51-53
-                    weight = wn;
-                    probability = newp;
-                }
+                McmcProposal<Cfg> pr; // as the launch before this one left it
+                hs_load_chain<Cfg, true>(h, cid, pr.n);
+                pr.prop = prop;
+                pr.active = true;
+                pr.newcurr = newcurr;
+                pr.ut = ut;
+                pr.pvi = pvi;
+                pr.touched = 0ull; // (the holding-time diagnostic's)
+                Weight<Cfg> wn = zero_weight<Cfg>();
+                if (newcurr != NORMI) wn = host_weight<Cfg>(a, cid);                           // :35-38, :92, :133 -- on the host
+                mcmc_accept<Cfg>(pr, wn, h.puacc[cid], rw, sPA, c, curr, weight, probability, extra, [](const bool) {});
             }
-            if (step % a.measurefreq == 0 && step >= nburn) { // ---- measurement  montecarlo.jl:144-172 ----
-                if (curr != NORMI) {
-                    double relw[Cfg::NCOMP]; // :162
-                    static_for<0, Cfg::NCOMP>([&](auto Q) { relw[decltype(Q)::value] = weight.v[decltype(Q)::value] / probability; });
-                    if constexpr (Cfg::HOST_MEASURE != 0) host_measure_record<Cfg, Cfg::NCOMP>(a, wi.lb, ch, step / a.measurefreq, c.x, relw, curr);
-                    static_for<0, NI>([&](auto I) {
-                        constexpr int i = decltype(I)::value;
-                        if (curr == i) {
-                            static_for<0, Cfg::NDRAW>([&](auto K) { // :147-154  accumulate!(var, pos + offset, 1.0)
-                                constexpr int k = decltype(K)::value;
-                                if constexpr ((Cfg::own_mask(i) >> k) & 1ull) hist_add<Cfg, k>(c.bin[k], 1.0, sH, a.ghist, 0);
-                            });
-                            if constexpr (Cfg::HOST_MEASURE != 0) {
-                            } else if constexpr (Cfg::CUSTOM_MEASURE != 0) { // measure(idx, var, obs, relative_weight, config)  :166-169
-                                double rwv[Cfg::NW];
-                                static_for<0, Cfg::NW>([&](auto Q) { rwv[decltype(Q)::value] = 0.0; });
-                                static_for<0, Cfg::NCOMP>([&](auto Q) { rwv[i * Cfg::NCOMP + decltype(Q)::value] = relw[decltype(Q)::value]; });
-                                Cfg::measure(c.x, rwv, a.ud, i, obs_wave<Cfg>(sO));
-                            } else if constexpr (Cfg::obs_bin_draw(i) >= 0) {
-                                const int b = c.bin[Cfg::obs_bin_draw(i)];
-                                if (b >= 0 && b < Cfg::obs_nbin(i)) lds_add(&obs_wave<Cfg>(sO)[Cfg::obs_off(i) + b], relw[0]);
-                            }
-                        }
-                        if constexpr (Cfg::CUSTOM_MEASURE == 0 && Cfg::obs_bin_draw(i) < 0) // :164
-                            static_for<0, Cfg::NCOMP>([&](auto Q) { acc[i * Cfg::NCOMP + decltype(Q)::value] += curr == i ? relw[decltype(Q)::value] : 0.0; });
-                    });
-                } else {
-                    extra[XN] += 1.0 / rw[NORMI]; // :158
-                }
+            if (step % a.measurefreq == 0 && step >= nburn) {
+                if (curr != NORMI) mcmc_measure<Cfg>(a, wi.lb, ch, step / a.measurefreq, 0, curr, c, weight, probability, acc, sH, sO);
+                else extra[XN] += 1.0 / rw[NORMI]; // :158
             }
             it = step;
         }
         if (it < total) { // ---- propose step it + 1 ----
             const u64 sidx = (g << 32) | (u64)it;
             static_for<0, ND>([&](auto I) { extra[XV + decltype(I)::value] += curr == decltype(I)::value ? 1.0 : 0.0; }); // :136
-            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, st_step, k0, k1);
-            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, st_step, k0, k1);
-            const u32x4 r2 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 2u, st_step, k0, k1);
-            double uupd = u01(r0.x, r0.y);
-            if (a.nchain > 1) { // (the 64 chains of a wave share the update-type sequence, as in mcmc_chains)
-                const u64 gidx = ((u64)(ch & ~(i64)63) << 32) | (u64)it;
-                const u32x4 rg = philox4x32_10((u32)gidx, (u32)(gidx >> 32), 0u, a.iteration * 8u + STREAM_MCMC_GROUP + bs, k0, k1);
-                uupd = u01(rg.x, rg.y);
-            }
-            int upd = (int)(uupd * (double)NUPD);
-            if (upd >= NUPD) upd = NUPD - 1;
+            const u32x4 r0 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 0u, S.step, S.k0, S.k1);
+            const u32x4 r1 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 1u, S.step, S.k0, S.k1);
+            const u32x4 r2 = philox4x32_10((u32)sidx, (u32)(sidx >> 32), 2u, S.step, S.k0, S.k1);
+            const int upd = group_pick(S, a.nchain > 1, u01(r0.x, r0.y), ch, (u64)it, NUPD); // :137
             const double upick = u01(r0.z, r0.w), us1 = u01(r1.x, r1.y), us2 = u01(r1.z, r1.w);
-            const McmcProposal<Cfg> pr = mcmc_propose<Cfg>(t, c, curr, upd, upick, us1, us2, sidx, st_step, k0, k1, r2);
-            static_for<0, Cfg::NDRAW>([&](auto K) {
-                constexpr int k = decltype(K)::value;
-                h.hx[k * nc + cid] = pr.n.x[k];
-                h.pprob[k * nc + cid] = pr.n.prob[k];
-                h.pbin[k * nc + cid] = pr.n.bin[k];
-            });
+            const McmcProposal<Cfg> pr = mcmc_propose<Cfg>(t, c, curr, upd, upick, us1, us2, sidx, S.step, S.k0, S.k1, r2);
+            hs_store_chain<Cfg, true>(h, cid, pr.n);
             h.pprop[cid] = pr.prop;
             h.puacc[cid] = u01(r2.x, r2.y);
             h.pnew[cid] = pr.newcurr;
@@ -3088,12 +2952,7 @@ template <class Cfg> __device__ __forceinline__ void mcmc_host_step(const BatchA
                 a.store_curr[wi.lb * a.nchain + ch] = curr;
             }
         }
-        static_for<0, Cfg::NDRAW>([&](auto K) {
-            constexpr int k = decltype(K)::value;
-            h.cx[k * nc + cid] = c.x[k];
-            h.cprob[k * nc + cid] = c.prob[k];
-            h.cbin[k * nc + cid] = c.bin[k];
-        });
+        hs_store_chain<Cfg, false>(h, cid, c);
         static_for<0, Cfg::NCOMP>([&](auto Q) { h.cw[decltype(Q)::value * nc + cid] = weight.v[decltype(Q)::value]; });
         h.cwabs[cid] = weight.abs;
         h.cprobability[cid] = probability;

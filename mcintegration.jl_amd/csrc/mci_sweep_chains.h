@@ -120,18 +120,10 @@ struct SweepChainResumeArgs {
 // pi_new / pi_old of block lb's stored chains: the workgroup's lanes stride over them (vegasmc_carry_weights for one block)
 template <class Cfg> __device__ __forceinline__ void carry_weights_block(const BatchArgs &a, const i64 lb) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NI = Cfg::NI;
     const int tid = threadIdx.x, T = blockDim.x;
-    double *sE = smem + Lds<Cfg>::E, *sDA = smem + Lds<Cfg>::DA, *sDD = smem + Lds<Cfg>::DD;
-    stage_tables<Cfg>(a.edges, a.dacc, a.ddist, sE, sDA, sDD);
-    __syncthreads();
-    Tables<Cfg> t;
-    if constexpr (Mode<Cfg>::EDGE_LDS) t.E = sE;
-    else t.E = a.edges;
-    t.DA = sDA;
-    t.DD = sDD;
-    double rw[NI + 1];
-    static_for<0, NI + 1>([&](auto I) { rw[decltype(I)::value] = a.reweight[decltype(I)::value]; });
+    const Tables<Cfg> t = chain_setup<Cfg, false>(a, smem);
+    double rw[Cfg::NI + 1];
+    load_reweight<Cfg>(a, rw);
     for (i64 from = tid; from < a.carry_nchain; from += T) vegasmc_carry_weight<Cfg>(a, t, rw, lb * a.carry_nchain + from);
 }
 

@@ -75,6 +75,20 @@ def test_kernels_with_several_lanes_per_chain_do_not_spill(name, solver):
     assert k["scratch"] == 0 and k["vgpr_spill"] <= 8 and k["vgpr"] <= 512 and k.get("lds", 0) == 0, k
 
 
+@pytest.mark.parametrize("solver", ["vegasmc", "mcmc"])
+def test_host_closure_chain_kernels_do_not_spill(solver):
+    """csrc/mci_device.h vegasmc_host_step | mcmc_host_step: the chain kernels of a Python closure (the Markov step cut at the integrand
+    call; one launch per step, the chain state in global memory between launches) on the 12-D nested-Gaussian layout.  They share the
+    step's pieces with the device-source kernels, and like the kernels with several lanes per chain they may use the whole unified
+    register file (one wave per SIMD: 328 and 298 VGPRs) -- but nothing parked in AGPRs and no scratch memory, in the step kernel and in
+    the carry-weight kernel next to it"""
+    c5 = [b for b in BASELINE if b[0] == "c5"][0]
+    res = isa_mix.resources(_code_object(c5[1], lambda: (lambda x: 1.0), None, solver))
+    assert "mci_%s_chains" % solver in res, res
+    for k, r in res.items():
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["vgpr"] <= 512, (solver, k, r)
+
+
 @pytest.mark.parametrize("name", ["c1", "c2"])
 def test_persistent_vegas_kernel_neither_spills_nor_declares_static_lds(name):
     """the persistent :vegas kernel (mci_set_persistent; sample loop + block merge + train! of one Continuous grid, 256 threads, plain
