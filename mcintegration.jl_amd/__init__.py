@@ -11,7 +11,8 @@ from ._lib import MCIError, compiler_id, lib, library_path, use_rocm_compiler  #
 from .configuration import Configuration  # noqa: F401
 from .engine import Engine, shutdown  # noqa: F401
 from .integrand import HostIntegrand, HostMeasure, Integrand, Measure, bin_by  # noqa: F401
-from .integrate import Stratify, integrate, integrate_sweep, prefill_kernel_cache, standardize_block  # noqa: F401
+from .integrate import Stratify, integrate, prefill_kernel_cache, standardize_block  # noqa: F401
+from .sweep import integrate_sweep  # noqa: F401
 from .solvers import MCMC, Vegas, VegasMC  # noqa: F401  (reference: modules Vegas, VegasMC, MCMC -- `Solver.montecarlo`, the seam of main.jl:253-264)
 from .statistics import ChainState, Result, average, mean_std, report  # noqa: F401
 from . import trace  # noqa: F401

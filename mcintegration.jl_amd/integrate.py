@@ -50,21 +50,6 @@ class StratD(np.ndarray):
         self.nstrat, self.beta = getattr(obj, "nstrat", None), getattr(obj, "beta", None)
 
 
-def _sweep_alloc_rows(alloc, P, plan):
-    """alloc= of a stratified sweep -> [P][ncube] d_h, checked against the call's plan {nstrat, ncube, beta}"""
-    rows = np.zeros((P, plan["ncube"]))
-    for k, v in enumerate(alloc):
-        ns, beta = getattr(v, "nstrat", None), getattr(v, "beta", None)
-        if ns is not None and (list(ns) != list(plan["nstrat"]) or beta != plan["beta"]):
-            raise ValueError("integrate_sweep: alloc[%d] was measured on nstrat = %s under beta = %r, this call runs nstrat = %s under beta = %r "
-                             "(there is no remap in a sweep)" % (k, list(ns), beta, list(plan["nstrat"]), plan["beta"]))
-        v = np.asarray(v, dtype=np.float64)
-        if v.shape != (plan["ncube"],):
-            raise ValueError("integrate_sweep: alloc[%d] has shape %s, the plan nstrat = %s has %d hypercubes" % (k, v.shape, list(plan["nstrat"]), plan["ncube"]))
-        rows[k] = v
-    return rows
-
-
 def _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm):
     """the Stratify an integrate() call asks for (None: plain), refused -- before any engine exists -- where this mode does not reach"""
     if stratify is None or stratify is False:
@@ -383,424 +368,6 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     if print >= 0:
         report(res, io=printio)                                                       # main.jl:212-213
     return res
-
-
-class _MeasureConfig:
-    """the configuration a sweep's measure closure is traced on: point 0's, with every read off config.userdata on record"""
-
-    def __init__(self, config, userdata, rec):
-        from . import trace as tr
-        self._config, self._rec, self._touched = config, rec, False
-        self._plain = userdata
-        self._view = tr._userdata_view(userdata, rec, False, ())
-        self._lazy = isinstance(self._view, tr._UserdataView)   # (anything else -- a number, an array -- is read the moment it is touched)
-        if not self._lazy:
-            del rec.literals[:]
-
-    def __getattr__(self, name):
-        return getattr(self._config, name)
-
-    @property
-    def userdata(self):
-        self._touched = True
-        return self._view if self._lazy else self._plain
-
-    def reads(self):
-        if self._lazy:
-            return list(self._rec.literals)
-        return [((), self._plain)] if self._touched and self._plain is not None else []
-
-
-def _trace_sweep_measure(measure, traced_on, params, solver):
-    """The measure closure of a sweep, traced on the configuration the integrand was traced on (point 0).  A sweep has ONE ud row per
-    point and that row is the integrand's: a measure whose body would hold a value read off config.userdata -- a float, an array -- is
-    refused with a ValueError naming it, and so is one that reads anything else (an int, a string) in which the points differ.
-    Returns the traced Measure, or None when the closure does not trace (it is then bound like any other closure)."""
-    from . import trace as tr
-    rec = tr._Trace()
-    mcfg = _MeasureConfig(traced_on, params[0], rec)
-    mindexed = callback_form(measure, solver, what="measure") == "indexed"
-    try:
-        traced = tr.trace_measure(measure, mcfg, indexed=mindexed)
-    except tr.TraceError:
-        traced = None
-    for path, was in mcfg.reads():
-        name = tr._path_name(path)
-        if isinstance(was, (float, np.floating, np.ndarray, list, tuple)) and not isinstance(was, bool):
-            raise ValueError("integrate_sweep: the measure reads %s off config.userdata, and its value would be written into the measure's "
-                             "body: a sweep has one ud row per point, and that row is the integrand's" % name)
-        for q in params[1:]:
-            try:
-                now = tr._reach(q, path)
-            except Exception as e:
-                raise ValueError("integrate_sweep: the measure reads %s, which cannot be read at every point (%s: %s)" % (name, type(e).__name__, e))
-            if not tr._same_leaf(was, now):
-                raise ValueError("integrate_sweep: the measure reads %s, which is %r at the traced point and %r at another: the points "
-                                 "would trace to different measure bodies" % (name, was, now))
-    return traced
-
-
-def integrate_sweep(integrand, params, *, solver="vegas", config=None, neval=1e4, niter=10, block=16, gamma=1.0, adapt=True, ignore=None,
-                    measure=None, measurefreq=1, seeds=None, maps=None, device=None, trace=None, print=-1, leaves="one", stratify=None, alloc=None,
-                    chains=None, reweight=None, mcmc_chains=None, thermal_ratio=0.1, carry=False, rtol=None, atol=None, min_niter=None, chain_state=None, **kwargs):
-    """A parameter sweep: the integral at every entry of `params`, as ONE launch where the layout allows (Engine.integrate_sweep,
-    mci_integrate_sweep: one workgroup runs a point's whole loop).  Returns a list of Result, one per point; result p is what
-    integrate() returns for point p on a fresh copy of the configuration -- every point starts from the configuration's current
-    map, and by default all points share the seed (common random numbers: a smooth curve over the scan); seeds = one per point.
-
-    params: what the integrand reads its parameters from.  For a Python closure these are the `config.userdata` objects (a struct of
-    floats, a dict, a number: examples/bubble_closure.py) -- the closure is traced ONCE, on params[0], and every point's ud row is
-    evaluated from its object by the trace's parameter evaluation (trace.py "Captured parameters").  Only FLOATS are parameters:
-    ints, bools, strings, non-finite floats and array shapes the closure reads off userdata are written into the body, so points that
-    differ in one of them (`Para(a=2)` next to `Para(a=3)`: write 2.0, 3.0), and a closure whose body depends on the values, are
-    refused with a ValueError naming the field -- never run on the body of point 0.  For a device-source string or an Integrand (mci.catalog) they are the
-    userdata rows.  A float array the closure indexes with a Discrete draw (`para.extQ[Ext[0] - 1]`) is a table of the body: every
-    point's row carries its own values, and its shape must be the same at every point.  maps: None or [P][Engine.sweep_map_doubles()]
-    starting maps; every Result carries `map` (the point's map after its last iteration, the flat row), `maps_by_leaf` (leaf by leaf: a
-    Continuous leaf's grid, a Discrete leaf's distribution), `status` (device flags of that point, 0 = none) and `sweep_batched`.
-
-    leaves: "one" (default) sweeps problems with ONE Continuous variable leaf; "all" opts in to sweeps of any mix of Continuous and
-    Discrete leaves that fits a workgroup's LDS (Engine.set_sweep_leaves) -- composites, histograms over a Discrete draw.  A `measure`
-    closure is traced on the same point as the integrand; one that reads a value off config.userdata is refused (ValueError).
-
-    stratify: True or Stratify(beta, nstrat, max_nhcube) -- every point runs VEGAS+ adaptive stratified sampling, what
-    integrate(..., stratify=...) runs, still in ONE launch (Engine.integrate_sweep_strat; one Continuous variable leaf, or with
-    leaves="all" several of them: variable types with ranges of their own, a composite with one grid per axis --
-    Engine.set_sweep_strat_leaves; `map` is then the flat row of every leaf's grid, `maps_by_leaf` the grids one by one).  Every Result
-    then carries `stratification` (nstrat, ncube, beta, carried = "uniform" | "same plan"), `strat_d` (the d_h its last iteration
-    measured) and `strat_counts` (the allocation that iteration used).  alloc: a list of P strat_d arrays, e.g. [r.strat_d for r in
-    trained] -- every point's first allocation is made from its entry, which must have been measured on this call's plan and beta
-    (there is no remap in a sweep: a strat_d remembers the plan and beta it was measured under, and another one raises ValueError);
-    with adapt=False the whole scan keeps it: train, then freeze.  A sweep carries through alloc, never through Stratify(carry=True).
-    Where the stratified sweep is refused (Engine.sweep_strat_supported: several Continuous leaves without leaves="all", a map that does
-    not fit a workgroup's LDS, ...) the points run as integrate(..., stratify=...) calls, as below; alloc= then raises.
-
-    chains: None (default) or an int >= 1 -- with solver="vegasmc", the reference's default solver, every point runs its :vegasmc loop
-    with that many chains per block, fresh in every iteration, still in ONE launch (Engine.integrate_sweep_chains: one workgroup per
-    point, a lane per chain; any mix of Continuous and Discrete leaves, whatever `leaves` says).  Every Result then also carries
-    `reweight` (the point's factors after its last doReweight!), and its config.visited / config.propose / config.accept are the
-    point's own; correlated = False.  reweight = [r.reweight for r in head] together with maps = [r.map for r in head] goes on with a
-    scan.  Without chains= a chain solver is not swept (the loop below, as ever); chains= with solver="vegas", with stratify= or under
-    "mcmc" raises ValueError.  Where the chain sweep is refused (Engine.sweep_chains_supported) the points run as
-    integrate(..., nchain=chains) calls, as below; reweight= then raises.
-
-    mcmc_chains: None (default) or an int >= 1 -- with solver="mcmc" every point runs its :mcmc loop with that many chains per block
-    and burn-in floor(steps * thermal_ratio) (mci_mcmc_burnin), fresh in every iteration, still in ONE launch
-    (Engine.integrate_sweep_mcmc; no warm-up repetition, no automatic chain count).  Closures are called in the solver's form,
-    integrand(idx, var, config) and measure(idx, var, obs, relative_weight, config).  Every Result carries what a chains= sweep's
-    does (`reweight`, own visited / propose / accept, correlated = False) and `holds` (the point's holding-time histogram, 64 counts
-    over the call) and `hold_max` (the upper bound 2^b - 1 of its highest occupied bin b, 0 if none); report() adds a note where
-    16 * hold_max exceeds the measured steps of a chain.  reweight= goes with it as with chains=.  mcmc_chains= with another solver,
-    together with chains= or with stratify= raises ValueError; without it an :mcmc scan loops as below.  Where the sweep is refused
-    (Engine.sweep_mcmc_supported) the points run as integrate(..., solver="mcmc", nchain=mcmc_chains, thermal_ratio=...) calls;
-    reweight= then raises.
-
-    carry: False (default) or True -- with chains= or mcmc_chains= every iteration of a point after its first continues the chains of
-    the one before, resampled to the target train! and doReweight! have moved (Engine.set_sweep_chain_carry: what integrate() does by
-    default; :vegasmc with adapt=True from the third iteration on; one chain per block carries nothing).  :mcmc chains then burn in
-    only in a point's first iteration.  The first iteration of every call starts afresh -- chain state does not travel between calls.
-    Results of carried points have correlated = True and the block-lineage error as `stdev` (with_ignore() falls back to the
-    reference's); report()'s hold note asks for 4 x hold_max instead of 16 x.  carry=True without chains= / mcmc_chains=, with
-    stratify= or under "vegas" raises ValueError.  Where the sweep is refused, the looped integrate() calls carry by their own default.
-
-    chain_state: None (default) or [r.chain_state for r in head] -- with carry=True and more than one chain per block every Result
-    carries `chain_state` (a ChainState: the record of its chains and one array), and a later call that takes the list next to maps= and
-    reweight= goes on from those chains instead of starting afresh: a point is then what integrate(..., nchain=K) is on the engine that
-    has just run the earlier call (Engine.integrate_sweep_chains / integrate_sweep_mcmc, state=).  Its first iteration continues the
-    stored chains -- :mcmc without any burn-in; :vegasmc unless they ran on a never-refined map that was refined since -- and the call's
-    chain count may differ from the stored one.  On a fresh configuration (no config=) the call takes first_iteration from the states;
-    states that disagree with each other or with config.iterations_done raise ValueError, and so does chain_state= without carry=True,
-    with the wrong length, or where the sweep is refused and the points would loop over ordinary calls.  A state of another solver,
-    block count or layout is refused by name (MCIError).  Results of a call whose first iteration continued have correlated = True and
-    the block-lineage error, as in integrate().
-
-    rtol, atol: None (default) or a target error -- under solver="vegas" every point stops once each of its statistics columns has
-    stdev <= max(atol, rtol * |mean|) (the weighted average over its counted iterations and that average's error, as Result computes
-    them), from iteration max(ignore + 2, min_niter) on; `niter` becomes the maximum.  Still ONE launch (Engine.integrate_sweep_until):
-    a workgroup that has finished a point takes the next one.  Every Result then carries `niter_run` (the iterations it ran; its tables
-    hold that many rows) and `converged` (False when it ran all `niter` without meeting the target; report() says so); a point's
-    numbers are those of the fixed sweep with niter = niter_run.  leaves="all" works as before.  A column that is NaN or infinite never
-    converges.  The three keywords with another solver, with stratify=, chains= or mcmc_chains=, or min_niter without a tolerance,
-    raise ValueError; so does a tolerance on a problem that does not run as a sweep: the loop of integrate() calls below has no
-    such stop, and never runs in its place.
-
-    A problem that cannot run as a sweep (Engine.sweep_supported: several variable leaves or a Discrete variable without leaves = "all",
-    measurefreq != 1, a host integrand, ...) runs the points as ordinary integrate() calls, one after another, each on a fresh Configuration(**kwargs);
-    a RuntimeWarning says so once, with the reason, and the results have sweep_batched = False.  Keywords as integrate()."""
-    import copy
-    import warnings
-    if trace is None:
-        trace = TRACE_DEFAULT
-    if solver in (":vegas", ":vegasmc", ":mcmc"):
-        solver = solver[1:]
-    if solver not in SOLVERS:
-        raise ValueError("Solver %s is not supported!" % solver)
-    if leaves not in ("one", "all"):
-        raise ValueError('integrate_sweep: leaves must be "one" or "all", got %r' % (leaves,))
-    try:
-        P = len(params)
-    except TypeError:
-        raise ValueError("integrate_sweep: params must be a sequence with one entry per point")
-    if not 1 <= P <= Engine.SWEEP_MAX_POINTS:
-        raise ValueError("integrate_sweep: %d points; a sweep takes 1 to %d" % (P, Engine.SWEEP_MAX_POINTS))
-    if seeds is not None and len(seeds) != P:
-        raise ValueError("integrate_sweep: seeds must hold one seed per point (%d), got %d" % (P, len(seeds)))
-    if maps is not None and len(maps) != P:
-        raise ValueError("integrate_sweep: maps must hold one map per point (%d), got %d" % (P, len(maps)))
-    if carry not in (False, True):
-        raise ValueError("integrate_sweep: carry must be True or False, got %r" % (carry,))
-    if carry:
-        if stratify is not None and stratify is not False:
-            raise ValueError("integrate_sweep: carry= and stratify= do not go together (stratification is :vegas's)")
-        if solver == "vegas":
-            raise ValueError('integrate_sweep: carry= belongs to a chain sweep (solver="vegasmc", chains=K or solver="mcmc", mcmc_chains=K); "vegas" has no chains')
-        if chains is None and mcmc_chains is None:
-            raise ValueError("integrate_sweep: carry= belongs to a chain sweep: give chains=K (solver=\"vegasmc\") or mcmc_chains=K (solver=\"mcmc\")")
-    until = rtol is not None or atol is not None
-    if min_niter is not None and not until:
-        raise ValueError("integrate_sweep: min_niter= belongs to a target error: give rtol= or atol=")
-    if until:
-        if solver != "vegas":
-            raise ValueError("integrate_sweep: rtol= / atol= / min_niter=: solver is not :vegas (chain solvers are not swept)")
-        for name, given in (("stratify", stratify is not None and stratify is not False), ("chains", chains is not None), ("mcmc_chains", mcmc_chains is not None)):
-            if given:
-                raise ValueError("integrate_sweep: rtol= / atol= / min_niter= and %s= do not go together (the stratified, :vegasmc and :mcmc "
-                                 "sweeps have no target error)" % name)
-        if min_niter is not None and (isinstance(min_niter, bool) or not isinstance(min_niter, (int, np.integer))):
-            raise ValueError("integrate_sweep: min_niter must be an int >= 0, got %r" % (min_niter,))
-    if chains is not None and mcmc_chains is not None:
-        raise ValueError('integrate_sweep: chains= (solver="vegasmc") and mcmc_chains= (solver="mcmc") do not go together')
-    if chains is not None:
-        if isinstance(chains, bool) or not isinstance(chains, (int, np.integer)) or chains < 1:
-            raise ValueError("integrate_sweep: chains must be an int >= 1 (chains per block), got %r" % (chains,))
-        if solver != "vegasmc":
-            raise ValueError('integrate_sweep: chains= belongs to solver="vegasmc" (%s)'
-                             % ('"vegas" is swept without it' if solver == "vegas" else 'a sweep of "mcmc" points is a follow-up'))
-        if stratify is not None and stratify is not False:
-            raise ValueError("integrate_sweep: chains= and stratify= do not go together (stratification is :vegas's)")
-        chains = int(chains)
-    if mcmc_chains is not None:
-        if isinstance(mcmc_chains, bool) or not isinstance(mcmc_chains, (int, np.integer)) or mcmc_chains < 1:
-            raise ValueError("integrate_sweep: mcmc_chains must be an int >= 1 (chains per block), got %r" % (mcmc_chains,))
-        if solver != "mcmc":
-            raise ValueError('integrate_sweep: mcmc_chains= belongs to solver="mcmc" (%s)'
-                             % ('"vegas" is swept without it' if solver == "vegas" else '"vegasmc" takes chains='))
-        if stratify is not None and stratify is not False:
-            raise ValueError("integrate_sweep: mcmc_chains= and stratify= do not go together (stratification is :vegas's)")
-        mcmc_chains = int(mcmc_chains)
-    if reweight is not None and chains is None and mcmc_chains is None:
-        raise ValueError('integrate_sweep: reweight= belongs to a chain sweep (solver="vegasmc", chains=K)')
-    if reweight is not None and len(reweight) != P:
-        raise ValueError("integrate_sweep: reweight must hold one vector per point (%d), got %d" % (P, len(reweight)))
-    if chain_state is not None:
-        from .statistics import ChainState
-        if not carry:
-            raise ValueError("integrate_sweep: chain_state= belongs to a chain sweep with carried chains: give carry=True (and chains=K or mcmc_chains=K)")
-        try:
-            chain_state = list(chain_state)
-        except TypeError:
-            raise ValueError("integrate_sweep: chain_state must be a list with one ChainState per point")
-        if len(chain_state) != P:
-            raise ValueError("integrate_sweep: chain_state must hold one ChainState per point (%d), got %d" % (P, len(chain_state)))
-        if not all(isinstance(s, ChainState) for s in chain_state):
-            raise ValueError("integrate_sweep: chain_state must hold ChainState objects (the chain_state of an earlier sweep's results; None: that "
-                             "call kept no chains -- carry=True and more than one chain per block)")
-        nexts = sorted({s.iteration + 1 for s in chain_state})
-        if len(nexts) != 1:
-            raise ValueError("integrate_sweep: the chain states disagree with each other: they were stored by iterations %s"
-                             % ", ".join(str(n - 1) for n in nexts))
-    if alloc is not None and (stratify is None or stratify is False):
-        raise ValueError("integrate_sweep: alloc= belongs to a stratified sweep (stratify=True or mci.Stratify(...))")
-    if alloc is not None:
-        try:
-            nalloc = len(alloc)
-        except TypeError:
-            raise ValueError("integrate_sweep: alloc must be a list with one strat_d array per point")
-        if nalloc != P:
-            raise ValueError("integrate_sweep: alloc must hold one strat_d array per point (%d), got %d" % (P, nalloc))
-    fresh = config is None
-    pristine = copy.deepcopy(kwargs) if fresh else None
-    if fresh:
-        config = Configuration(**kwargs)
-    if chain_state is not None:
-        if fresh:
-            config.iterations_done = nexts[0]    # (a fresh configuration goes on where the states' call stopped)
-        elif config.iterations_done != nexts[0]:
-            raise ValueError("integrate_sweep: the chain states were stored by iteration %d, and config.iterations_done = %d: the call would "
-                             "not start at the iteration that continues them (%d)" % (nexts[0] - 1, config.iterations_done, nexts[0]))
-    if ignore is None:
-        ignore = 1 if adapt else 0
-    strat = _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, LocalComm())
-    if strat is not None and strat.carry:
-        raise ValueError("integrate_sweep: Stratify(carry=True) is the ordinary call's way to carry an allocation; a sweep takes alloc=")
-    closure = callable(integrand) and not isinstance(integrand, (Integrand, HostIntegrand))
-    why = rows = bound = None
-    if closure:
-        from . import trace as tr
-        traced_on = copy.copy(config)      # (the caller's Configuration keeps its userdata)
-        traced_on.userdata = params[0]
-        form = callback_form(integrand, solver, False)
-        try:
-            if trace is False:
-                raise tr.TraceError("trace = False")
-            bound = tr.trace_integrand(integrand, traced_on, indexed=form == "indexed", inplace=form == "inplace")
-            if getattr(bound, "userdata_for", None) is None:
-                raise ValueError("integrate_sweep: the closure's body depends on the values of its parameters (a Python branch on a captured "
-                                 "float, a table indexed with a draw): the points would trace to different bodies")
-            rows = np.array([bound.userdata_for(p) for p in params], dtype=np.float64).reshape(P, len(bound.userdata))
-        except tr.TraceError as e:
-            why = "the closure was not traced (%s): a host integrand" % e
-        bound_measure = measure
-        if why is None and trace is not False and callable(measure) and not isinstance(measure, (Measure, HostMeasure)) and not hasattr(measure, "pool"):
-            bound_measure = _trace_sweep_measure(measure, traced_on, params, solver) or measure
-    else:
-        if isinstance(integrand, str):
-            integrand = Integrand(integrand, None)
-        if isinstance(integrand, HostIntegrand):
-            why = "a host integrand (device source or a traced closure only)"
-        else:
-            rows = np.asarray(params, dtype=np.float64)
-            if rows.ndim != 2 or (len(integrand.userdata) and rows.shape[1] != len(integrand.userdata)):
-                raise ValueError("integrate_sweep: params must be userdata rows [points][%d] for this integrand, got shape %s"
-                                 % (len(integrand.userdata), rows.shape))
-            bound = Integrand(integrand.body, rows[0], integrand.name)
-    if device is None:
-        device = 0
-    nevalperblock, block = standardize_block(int(neval), block, 1)
-    eng = None
-    if why is None:
-        eng = _bind(config, bound, bound_measure if closure else measure, solver, trace=trace, print=print, device=device)
-        if hasattr(eng, "set_sweep_leaves"):
-            eng.set_sweep_leaves(leaves)
-        if strat is not None and hasattr(eng, "set_sweep_strat_leaves"):
-            eng.set_sweep_strat_leaves(leaves)      # (leaves="all" opts in to both leaf modes)
-        if strat is not None:
-            if not hasattr(eng, "integrate_sweep_strat"):
-                why = "this engine has no stratified sweep"
-            else:
-                eng.set_stratification(strat.nstrat, strat.beta, strat.max_nhcube)
-                why = eng.sweep_strat_supported(solver, nevalperblock * block, niter, block, measurefreq)
-        elif chains is not None:
-            why = (eng.sweep_chains_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=chains,
-                                              first_iteration=config.iterations_done)
-                   if hasattr(eng, "sweep_chains_supported") else "this engine has no chain sweep")
-        elif mcmc_chains is not None:
-            why = (eng.sweep_mcmc_supported(solver, nevalperblock * block, niter, block, measurefreq, nchain=mcmc_chains,
-                                            first_iteration=config.iterations_done, thermal_ratio=thermal_ratio)
-                   if hasattr(eng, "sweep_mcmc_supported") else "this engine has no :mcmc sweep")
-        elif until:
-            why = (eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_until_supported")
-                   else "this engine has no sweep to a target error")
-            bad = why is None and eng.sweep_until_supported(solver, nevalperblock * block, niter, block, measurefreq, rtol=rtol or 0.0, atol=atol or 0.0,
-                                                            min_niter=min_niter or 0)
-            if bad:     # (the target itself: in the words of mci_sweep_until_supported)
-                raise ValueError("integrate_sweep: %s" % bad)
-        else:
-            why = eng.sweep_supported(solver, nevalperblock * block, niter, block, measurefreq) if hasattr(eng, "sweep_supported") else "this engine has no sweep"
-    if why is None and strat is not None:
-        plan = eng.sweep_strat_plan(nevalperblock * block, block)
-        d_rows = _sweep_alloc_rows(alloc, P, plan) if alloc is not None else None
-        rs = eng.integrate_sweep_strat(solver, userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt,
-                                       gamma=gamma, measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps,
-                                       first_iteration=config.iterations_done, d=d_rows)
-        out = []
-        for p, r in zip(params, rs):
-            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, logs and allocation alone)
-            c.userdata = p if closure else None
-            c.visited = r["visited"]
-            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block)
-            res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
-            res.maps_by_leaf = r.get("maps_by_leaf")
-            res.stratification = dict(nstrat=list(plan["nstrat"]), ncube=plan["ncube"], beta=plan["beta"], carry=False,
-                                      carried="same plan" if alloc is not None else "uniform")
-            res.strat_d, res.strat_counts = StratD(r["strat_d"], plan["nstrat"], plan["beta"]), r["strat_counts"]
-            res.vegas_check, res.warmup, res.neval_discarded = None, 0, 0
-            if print >= 0:
-                report(res)
-            out.append(res)
-        return out
-    if why is None and (chains is not None or mcmc_chains is not None):
-        kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma,
-                  measurefreq=measurefreq, seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done, reweight=reweight)
-        if chain_state is not None:
-            kw["state"] = chain_state
-        rs = (eng.integrate_sweep_chains(solver, nchain=chains, carry=carry, **kw) if chains is not None
-              else eng.integrate_sweep_mcmc(solver, nchain=mcmc_chains, thermal_ratio=thermal_ratio, carry=carry, **kw))
-        out = []
-        for p, r in zip(params, rs):
-            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map, factors and logs alone)
-            c.userdata = p if closure else None
-            c.visited = r["visited"]
-            c._sweep_tables = (r["propose"], r["accept"])   # config.propose / config.accept: this point's, not the engine's
-            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block, correlated=r["correlated"])
-            if r["correlated"]:              # (carried chains: the block-lineage error, made by the library from the point's block means)
-                res._flat_std = np.asarray(r["stdev"], dtype=np.float64)
-                res.stdev = res._shape(res._flat_std)
-            res.sweep_batched, res.map, res.status, res.reweight = True, r["maps"], r["status"], r["reweight"]
-            res.maps_by_leaf = r.get("maps_by_leaf")
-            res.chain_state = r.get("chain_state")
-            res.stratification, res.vegas_check, res.warmup, res.neval_discarded, res.chain_bias = None, None, 0, 0, None
-            if mcmc_chains is not None:
-                res.holds, res.hold_max, res.chain_steps = r["holds"], r["hold_max"], nevalperblock // mcmc_chains
-                res.chains_carried = bool(r.get("carried"))
-            if print >= 0:
-                report(res)
-            out.append(res)
-        return out
-    if why is None:
-        kw = dict(userdata=rows, neval=nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma, measurefreq=measurefreq,
-                  seed=config.seed, seeds=seeds, maps=maps, first_iteration=config.iterations_done)
-        rs = (eng.integrate_sweep_until(solver, rtol=rtol or 0.0, atol=atol or 0.0, min_niter=min_niter or 0, **kw) if until
-              else eng.integrate_sweep(solver, **kw))
-        out = []
-        for p, r in zip(params, rs):
-            c = copy.copy(config)            # (the points share the engine; a sweep leaves its map and logs alone)
-            c.userdata = p if closure else None
-            c.visited = r["visited"]
-            res = Result(r["iter_mean"], r["iter_std"], c, ignore, neval=r["neval"], seconds=r["seconds"], block=block)
-            res.sweep_batched, res.map, res.status = True, r["maps"], r["status"]
-            res.maps_by_leaf = r.get("maps_by_leaf")
-            res.stratification, res.vegas_check, res.warmup, res.neval_discarded = None, None, 0, 0
-            if until:
-                res.niter_run, res.converged = r["niter_run"], r["converged"]
-            if print >= 0:
-                report(res)
-            out.append(res)
-        return out
-    # not a sweep layout: the points one after another, each an ordinary call on a configuration of its own
-    if not fresh:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and the looped form builds one Configuration per "
-                         "point from keywords (var=..., dof=...), not from config=" % why)
-    if maps is not None:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and maps= needs the batched form" % why)
-    if alloc is not None:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and alloc= needs the batched form" % why)
-    if reweight is not None:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and reweight= needs the batched form" % why)
-    if chain_state is not None:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and chain_state= needs the batched form" % why)
-    if until:
-        raise ValueError("integrate_sweep: this problem does not run as a sweep (%s), and rtol= / atol= need the batched form" % why)
-    warnings.warn("integrate_sweep: this problem does not run as a sweep (%s): %d ordinary integrate() calls, one after another" % (why, P),
-                  RuntimeWarning, stacklevel=2)
-    if eng is not None and hasattr(eng, "close"):
-        eng.close()
-    out = []
-    for k, p in enumerate(params):
-        kw = copy.deepcopy(pristine)
-        if closure:
-            kw["userdata"], f = p, integrand
-        else:
-            f = integrand if isinstance(integrand, HostIntegrand) else Integrand(integrand.body, rows[k], integrand.name)
-        c = Configuration(**kw)
-        if seeds is not None:
-            c.seed = int(seeds[k])
-        res = integrate(f, solver=solver, config=c, neval=neval, niter=niter, block=block, gamma=gamma, adapt=adapt, ignore=ignore, measure=measure,
-                        measurefreq=measurefreq, device=device, trace=trace, print=print, **({"stratify": strat} if strat is not None else {}), **({"nchain": chains} if chains is not None else {}),
-                        **({"nchain": mcmc_chains, "thermal_ratio": thermal_ratio} if mcmc_chains is not None else {}))
-        res.sweep_batched, res.map, res.maps_by_leaf, res.status = False, None, None, 0
-        out.append(res)
-    return out
 
 
 def prefill_kernel_cache():
