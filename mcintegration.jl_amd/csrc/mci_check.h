@@ -78,20 +78,12 @@ __device__ inline double check_uniform(const CheckArgs &a, unsigned long long in
     return __longlong_as_double((long long)bits) - 1.0; // [1, 2) - 1: exact
 }
 
-// product of 1/prob over the draws of `mask`: the bare increments of eight draws, then their N factors (the bare product of 48 narrow
-// increments underflows, DESIGN.md "Jacobian")
+// product of 1/prob over the draws of `mask`, draw by draw as the reference forms it (vegas/montecarlo.jl:126): no bare product of
+// increments, which leaves the doubles where the Jacobian itself does not (DESIGN.md "Jacobian")
 __device__ inline double check_jacobian(const CheckArgs &a, const double *raw, unsigned long long mask) {
-    double j = 1.0, sc = 1.0;
-    for (int k = 0; k < a.ndraw; ++k) {
-        if ((mask >> k) & 1ull) {
-            j *= raw[k];
-            sc *= a.draw[k].scale;
-        }
-        if ((k + 1) % 8 == 0 || k + 1 == a.ndraw) {
-            j *= sc;
-            sc = 1.0;
-        }
-    }
+    double j = 1.0;
+    for (int k = 0; k < a.ndraw; ++k)
+        if ((mask >> k) & 1ull) j *= raw[k] * a.draw[k].scale;
     return j;
 }
 

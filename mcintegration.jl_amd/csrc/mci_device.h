@@ -501,8 +501,11 @@ template <class Cfg> constexpr double jac_scale(int k) {
     return Cfg::leaf_kind(Cfg::draw_leaf(k)) == 0 ? (double)Cfg::leaf_nbin(Cfg::draw_leaf(k)) : 1.0;
 }
 // product of jac_scale over the draws lo <= k < hi of `mask` (compile-time).  The N factors are applied once per group of
-// 8 draws, not once per sample: the bare product of 8 increments cannot underflow, the bare product of 48 narrow ones does
-// (D = 48 sharply peaked dimensions with increments ~1e-7 gave weights of exactly 0 when the scale was applied at the end)
+// 8 draws, not once per sample (D = 48 sharply peaked dimensions with increments ~1e-7 gave weights of exactly 0 when the scale was
+// applied at the end), and a group's factors go in BEFORE its increments: every intermediate value is then the reference's partial
+// product (vegas/montecarlo.jl:126, draw by draw) times the N factors of the group's draws still to come -- never smaller than a
+// value the reference itself forms.  Applied behind the increments, eight increments of 2^-125 / 999 gave (2^-125 / 999)^8 ~ 2^-1080 = 0
+// for a Jacobian of 2^-1000, and lost bits in the denormals from 2^-118 down (tests/test_hip_map.py, the small ranges).
 template <class Cfg> constexpr double jac_scale_product(unsigned long long mask, int lo = 0, int hi = 64) {
     double p = 1.0;
     for (int k = lo; k < Cfg::NDRAW && k < hi; ++k)
@@ -620,6 +623,16 @@ template <class Cfg, bool ECACHE = false, bool KV = false, int DPC = 2> __device
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        if constexpr ((DPC * c) % kJacGroup == 0) { // open a group of draws: its N factors
+            constexpr int lo = DPC * c, hi = lo + kJacGroup;
+            constexpr double sc = jac_scale_product<Cfg>(ALL, lo, hi);
+            if constexpr (sc != 1.0) s.jac *= sc;
+            static_for<0, Cfg::NI>([&](auto I) {
+                constexpr int i = decltype(I)::value;
+                constexpr double si = jac_scale_product<Cfg>(Cfg::own_mask(i), lo, hi);
+                if constexpr (Cfg::own_mask(i) != ALL && si != 1.0) s.jaci[i] *= si;
+            });
+        }
         static_for<0, DPC>([&](auto H) {
             constexpr int k = DPC * c + decltype(H)::value;
             if constexpr (k < Cfg::NDRAW) {
@@ -633,23 +646,13 @@ template <class Cfg, bool ECACHE = false, bool KV = false, int DPC = 2> __device
                 draw_leaf<Cfg, k, true, ECACHE>(t, y1, s.x[k], raw, s.bin[k]);
                 pack_bin<Cfg, k>(s);
                 s.pj[k] = raw * jac_scale<Cfg>(k);
-                s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied below)
+                s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied above)
                 static_for<0, Cfg::NI>([&](auto I) {
                     constexpr int i = decltype(I)::value;
                     if constexpr (((Cfg::own_mask(i) >> k) & 1ull) && Cfg::own_mask(i) != ALL) s.jaci[i] *= raw;
                 });
             }
         });
-        if constexpr (((DPC * c + DPC) % kJacGroup == 0 || DPC * c + DPC >= Cfg::NDRAW)) { // close a group of draws: apply its N factors
-            constexpr int hi = DPC * c + DPC, lo = ((hi - 1) / kJacGroup) * kJacGroup;
-            constexpr double sc = jac_scale_product<Cfg>(ALL, lo, hi);
-            if constexpr (sc != 1.0) s.jac *= sc;
-            static_for<0, Cfg::NI>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                constexpr double si = jac_scale_product<Cfg>(Cfg::own_mask(i), lo, hi);
-                if constexpr (Cfg::own_mask(i) != ALL && si != 1.0) s.jaci[i] *= si;
-            });
-        }
     });
     static_for<0, Cfg::NI>([&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -1031,22 +1034,8 @@ template <class Cfg, bool KV, int DPC, bool UNI> __device__ __forceinline__ void
         }
         if constexpr (c >= LAG) { // the draws whose pairs were asked for LAG blocks ago: x = g[iy] + dy * (g[iy+1] - g[iy])  sampler.jl:299
             constexpr int cc = c - LAG;
-            static_for<0, DPC>([&](auto H) {
-                constexpr int k = DPC * cc + decltype(H)::value;
-                if constexpr (k < Cfg::NDRAW) {
-                    s.x[k] = pe[k].x + pdy[k] * pe[k].y;
-                    const double raw = pe[k].y;
-                    pack_bin<Cfg, k>(s);
-                    s.pj[k] = raw * jac_scale<Cfg>(k);
-                    s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied below)
-                    static_for<0, Cfg::NI>([&](auto I) {
-                        constexpr int i = decltype(I)::value;
-                        if constexpr (((Cfg::own_mask(i) >> k) & 1ull) && Cfg::own_mask(i) != ALL) s.jaci[i] *= raw;
-                    });
-                }
-            });
-            if constexpr (((DPC * cc + DPC) % kJacGroup == 0 || DPC * cc + DPC >= Cfg::NDRAW)) { // close a group of draws: apply its N factors
-                constexpr int hi = DPC * cc + DPC, lo = ((hi - 1) / kJacGroup) * kJacGroup;
+            if constexpr ((DPC * cc) % kJacGroup == 0) { // open a group of draws: its N factors
+                constexpr int lo = DPC * cc, hi = lo + kJacGroup;
                 constexpr double sc = jac_scale_product<Cfg>(ALL, lo, hi);
                 if constexpr (sc != 1.0) s.jac *= sc;
                 static_for<0, Cfg::NI>([&](auto I) {
@@ -1055,6 +1044,20 @@ template <class Cfg, bool KV, int DPC, bool UNI> __device__ __forceinline__ void
                     if constexpr (Cfg::own_mask(i) != ALL && si != 1.0) s.jaci[i] *= si;
                 });
             }
+            static_for<0, DPC>([&](auto H) {
+                constexpr int k = DPC * cc + decltype(H)::value;
+                if constexpr (k < Cfg::NDRAW) {
+                    s.x[k] = pe[k].x + pdy[k] * pe[k].y;
+                    const double raw = pe[k].y;
+                    pack_bin<Cfg, k>(s);
+                    s.pj[k] = raw * jac_scale<Cfg>(k);
+                    s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied above)
+                    static_for<0, Cfg::NI>([&](auto I) {
+                        constexpr int i = decltype(I)::value;
+                        if constexpr (((Cfg::own_mask(i) >> k) & 1ull) && Cfg::own_mask(i) != ALL) s.jaci[i] *= raw;
+                    });
+                }
+            });
             if constexpr (c < NCH) __builtin_amdgcn_sched_barrier(0);
         }
     });

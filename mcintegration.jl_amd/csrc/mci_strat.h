@@ -105,6 +105,16 @@ template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_samp
     static_for<0, NCH>([&](auto C) {
         constexpr int c = decltype(C)::value;
         const u32x4 r = philox4x32_10<KV>(ilo, ihi, (u32)c, stream, keys);
+        if constexpr ((DPC * c) % kJacGroup == 0) { // open a group of draws: its N factors, as draw_sample applies them
+            constexpr int lo = DPC * c, hi = lo + kJacGroup;
+            constexpr double sc = jac_scale_product<Cfg>(ALL, lo, hi);
+            if constexpr (sc != 1.0) s.jac *= sc;
+            static_for<0, Cfg::NI>([&](auto I) {
+                constexpr int i = decltype(I)::value;
+                constexpr double si = jac_scale_product<Cfg>(Cfg::own_mask(i), lo, hi);
+                if constexpr (Cfg::own_mask(i) != ALL && si != 1.0) s.jaci[i] *= si;
+            });
+        }
         static_for<0, DPC>([&](auto H) {
             constexpr int k = DPC * c + decltype(H)::value;
             if constexpr (k < Cfg::NDRAW) {
@@ -114,23 +124,13 @@ template <class Cfg, bool KV, int DPC> __device__ __forceinline__ void draw_samp
                 double raw;
                 draw_leaf<Cfg, k, false>(t, y, s.x[k], raw, s.bin[k]);
                 s.pj[k] = raw * jac_scale<Cfg>(k);
-                s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied below, in the groups draw_sample applies it in)
+                s.jac *= raw; // jac /= prob   vegas/montecarlo.jl:126 (scale applied above, in the groups draw_sample applies it in)
                 static_for<0, Cfg::NI>([&](auto I) {
                     constexpr int i = decltype(I)::value;
                     if constexpr (((Cfg::own_mask(i) >> k) & 1ull) && Cfg::own_mask(i) != ALL) s.jaci[i] *= raw;
                 });
             }
         });
-        if constexpr (((DPC * c + DPC) % kJacGroup == 0 || DPC * c + DPC >= Cfg::NDRAW)) {
-            constexpr int hi = DPC * c + DPC, lo = ((hi - 1) / kJacGroup) * kJacGroup;
-            constexpr double sc = jac_scale_product<Cfg>(ALL, lo, hi);
-            if constexpr (sc != 1.0) s.jac *= sc;
-            static_for<0, Cfg::NI>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                constexpr double si = jac_scale_product<Cfg>(Cfg::own_mask(i), lo, hi);
-                if constexpr (Cfg::own_mask(i) != ALL && si != 1.0) s.jaci[i] *= si;
-            });
-        }
     });
     static_for<0, Cfg::NI>([&](auto I) {
         constexpr int i = decltype(I)::value;
