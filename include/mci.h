@@ -65,6 +65,9 @@ enum { MCI_VEGAS_SWEEP_UNTIL = 17, MCI_VEGAS_SWEEP_LEAVES_UNTIL = 18 };
 /* ... and the two carried chain sweep kernels with a first iteration that continues the chains of the call before
  * (mci_integrate_sweep_chains_resume, mci_integrate_sweep_mcmc_resume): code objects of their own */
 enum { MCI_VEGASMC_SWEEP_RESUME = 19, MCI_MCMC_SWEEP_RESUME = 20 };
+/* ... and the persistent :vegas kernel with a target error (mci_integrate_until on a call the persistent launch takes): a code object
+ * of its own, for the layouts MCI_VEGAS_PERSISTENT has one for */
+enum { MCI_VEGAS_PERSISTENT_UNTIL = 21 };
 /* mci_set_sweep_leaves: which problems mci_integrate_sweep takes; mci_set_sweep_strat_leaves: which ones mci_integrate_sweep_strat takes */
 enum { MCI_SWEEP_ONE_GRID = 0, MCI_SWEEP_ALL_LEAVES = 1 };
 
@@ -324,6 +327,36 @@ int mci_integrate_sweep_until(mci_problem *prob, const mci_integrate_args *args,
  * take more than 64 KiB of LDS (one Continuous leaf) or 159 KiB (several leaves), with the byte count.  rtol = atol = 0 is legal and
  * never stops a point early. */
 int mci_sweep_until_supported(const mci_problem *prob, const mci_integrate_args *args, const mci_sweep_target *target, char *why, int32_t n);
+/* mci_integrate with a target error: args->niter is the most the call runs.  After counted iteration n (1-based; the repeated warm-up
+ * launches of automatic :mcmc chain lengths are not counted) the call forms, per statistics column o, (M_o, E_o) = what mci_integrate
+ * would leave in result->mean / stdev had it been called with niter = n: while no iteration so far continued the chains of the one
+ * before (:vegas always; the chain solvers with carry off or one chain per block) mci_average over rows ignore + 1 .. n -- each row
+ * (mean, std) from mci_mean_std, on a stratified problem the stratified (mean, std) --; once the call is correlated the same M and the
+ * block-lineage error (mci_lineage_sums(..., init = ignore + 1, max = n) -> mci_mean_std; a column that is identically zero keeps the
+ * 1e-10-regularised error, as at the end of mci_integrate).  The call stops at the first n >= max(ignore + 2, min_niter) at which
+ * E_o <= max(atol, rtol |M_o|) holds in every column.  A column whose M or E is not finite never converges; rtol = atol = 0 never stops
+ * a call early.  *niter_run = n (args->niter when the call never stopped).  The first n rows of result->iter_mean / iter_std are valid;
+ * mean, stdev, chi2, correlated, neval and visited are those of mci_integrate with niter = n, and the problem is left as that call would
+ * leave it: map, reweight factors, chain state, stratification allocation, iteration log and block log.  result->niter stays the
+ * caller's capacity (>= args->niter).
+ * A :vegas call that mci_integrate runs as ONE persistent launch (mci_set_persistent) stays one launch: a kernel and code object of its
+ * own (MCI_VEGAS_PERSISTENT_UNTIL, csrc/mci_persist_until.h) applies the rule in its statistics workgroup after every turn and stops the
+ * grid.  The sampling workgroups run one turn ahead of the verdict, so a launch that stops at n < args->niter has drawn the samples of
+ * turn n + 1 and throws them away: they are in neither result->neval nor the estimate (mci_last_integrate_discarded counts them), the
+ * map has seen n refinements, the log holds n rows.  That is the price of a stop, at most one iteration of a launch-bound call.  A
+ * launch that stalls falls back to the launch chain like mci_integrate's, target and all.
+ * Everything else -- the three solvers, stratified :vegas, :vegas layouts and sizes the persistent launch does not take -- runs on the
+ * launch chain of mci_integrate: up to iteration max(ignore + 2, min_niter) - 1 the launches are queued back to back, from there on
+ * every finished iteration's log row (and, once a chain solver's call is correlated, its block-log row) comes back behind one
+ * synchronisation and the host applies the rule -- the host side of the rule text the kernels compile (csrc/mci_sweep_common.h).
+ * Nothing is discarded there.  mci_integrate itself is the same call without a target: same launches, same code objects.
+ * Refused (MCI_ERR_INVALID, the reason also through mci_integrate_until_supported): a NULL target; an rtol or atol that is negative or
+ * not finite; min_niter < 0; more than one rank (the lineage sums would need a collective per iteration); everything mci_integrate
+ * refuses.  An offline context answers MCI_ERR_NO_DEVICE behind those. */
+int mci_integrate_until(mci_problem *prob, const mci_integrate_args *args, const mci_sweep_target *target, mci_result *result, int32_t *niter_run);
+/* MCI_OK when mci_integrate_until takes this problem with these arguments and this target; else MCI_ERR_INVALID with the reason in
+ * why[n] (and in mci_last_error).  Needs no device. */
+int mci_integrate_until_supported(const mci_problem *prob, const mci_integrate_args *args, const mci_sweep_target *target, char *why, int32_t n);
 /* Which problems run as a sweep.  MCI_SWEEP_ONE_GRID (default): one Continuous leaf, as described above.  MCI_SWEEP_ALL_LEAVES: also
  * any :vegas problem whose leaves are all Continuous or Discrete (FermiK: "vegas doesn't work with FermiK"), with the tables and the
  * histograms in LDS in one tile and at most 159 KiB of LDS for the sample tables or the refinement scratch of the largest leaf plus the

@@ -121,6 +121,8 @@ SIGNATURES = [
     ("mci_integrate_sweep_until", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.c_int32, c_double_p, C.POINTER(C.c_uint64), c_double_p,
                                             c_double_p, C.POINTER(ResultC), c_double_p, c_double_p, c_int32_p, c_int32_p]),
     ("mci_sweep_until_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.c_char_p, C.c_int32]),
+    ("mci_integrate_until", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.POINTER(ResultC), c_int32_p]),
+    ("mci_integrate_until_supported", C.c_int, [_VP, C.POINTER(IntegrateArgs), C.POINTER(SweepTarget), C.c_char_p, C.c_int32]),
     ("mci_set_sweep_leaves", C.c_int, [_VP, C.c_int32]),
     ("mci_set_sweep_chain_carry", C.c_int, [_VP, C.c_int32]),
     ("mci_set_sweep_strat_leaves", C.c_int, [_VP, C.c_int32]),

@@ -38,6 +38,7 @@
 #include "mci_sweep_strat.h" // SweepStratArgs (likewise)
 #include "mci_sweep_strat_leaves.h"
 #include "mci_sweep_chains.h" // SweepChainArgs (likewise)
+#include "mci_persist_until.h" // PersistUntilArgs (likewise)
 
 namespace {
 

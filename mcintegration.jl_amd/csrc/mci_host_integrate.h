@@ -78,40 +78,44 @@ void persist_orphans_join() {
 }
 } // namespace
 static void persist_job_drop(mci_problem *p) {
-    if (!p->persist_job) return;
-    mci_problem::PersistJob *j = p->persist_job;
-    p->persist_job = nullptr;
-    if (j->done.load(std::memory_order_acquire)) {
-        if (j->th.joinable()) j->th.join();
-        delete j;
-        return;
+    for (mci_problem::PersistJob *&slot : p->persist_job) {
+        if (!slot) continue;
+        mci_problem::PersistJob *j = slot;
+        slot = nullptr;
+        if (j->done.load(std::memory_order_acquire)) {
+            if (j->th.joinable()) j->th.join();
+            delete j;
+            continue;
+        }
+        static std::once_flag once;
+        std::call_once(once, [] { atexit(persist_orphans_join); });
+        std::lock_guard<std::mutex> g(g_orphan_mu);
+        g_orphans.push_back(j);
     }
-    static std::once_flag once;
-    std::call_once(once, [] { atexit(persist_orphans_join); });
-    std::lock_guard<std::mutex> g(g_orphan_mu);
-    g_orphans.push_back(j);
 }
 // MCI_OK with the unit's `compiled` set: the kernel is loaded.  MCI_OK without: not yet (background == true and the code object is
-// still being compiled) -- the caller takes the launch chain this time.
-static int compile_persist(mci_problem *p, bool background) {
-    KernelUnit &u = p->kernel[mci_problem::kPersist];
+// still being compiled) -- the caller takes the launch chain this time.  until: the unit with a target error (mci_persist_until.h,
+// kernel[kPersistUntil]; chosen for mci_integrate_until alone) instead of the fixed one.
+static int compile_persist(mci_problem *p, bool background, bool until) {
+    KernelUnit &u = p->kernel[until ? mci_problem::kPersistUntil : mci_problem::kPersist];
     if (u.compiled) return MCI_OK;
     Candidate local, *c = &local;
-    if (p->persist_job) {
-        if (!p->persist_job->done.load(std::memory_order_acquire)) {
+    mci_problem::PersistJob *&job = p->persist_job[until ? 1 : 0];
+    if (job) {
+        if (!job->done.load(std::memory_order_acquire)) {
             if (background) return MCI_OK;
-            p->persist_job->th.join(); // (a caller that insists)
+            job->th.join(); // (a caller that insists)
         }
-        if (p->persist_job->th.joinable()) p->persist_job->th.join();
-        local = std::move(p->persist_job->c);
-        delete p->persist_job;
-        p->persist_job = nullptr;
+        if (job->th.joinable()) job->th.join();
+        local = std::move(job->c);
+        delete job;
+        job = nullptr;
     } else {
         mcijit::ProblemShape sh = p->shape;
         sh.hcopy = 1;
         sh.det = 0;
-        c->unit = mcijit::kUnitVegasPersist;
-        c->src = mcijit::generate_source(sh, MCI_VEGAS, mcijit::kUnitVegasPersist, p->leaves[0].alpha);
+        c->unit = until ? mcijit::kUnitVegasPersistUntil : mcijit::kUnitVegasPersist;
+        c->src = mcijit::generate_source(sh, MCI_VEGAS, c->unit, p->leaves[0].alpha);
         // (512 threads for the hand-pipelined loops of 8..16 draws -- what the launch chain runs them at -- was tried: 22.5 instead of 18.3 us
         // per iteration of the 16-D Gaussian at neval = 1e4, against 15.8 as a launch chain; the automatic rule stops at 7 draws)
         c->threads = p->threads;
@@ -128,9 +132,9 @@ static int compile_persist(mci_problem *p, bool background) {
                 std::lock_guard<std::mutex> g(mu);
                 if (++asked[mcijit::fnv1a(c->src)] < kPersistAfterCalls) return MCI_OK;
             }
-            p->persist_job = new mci_problem::PersistJob;
-            p->persist_job->c = std::move(local);
-            mci_problem::PersistJob *j = p->persist_job;
+            job = new mci_problem::PersistJob;
+            job->c = std::move(local);
+            mci_problem::PersistJob *j = job;
             j->th = std::thread([j] {
                 j->c.build();
                 j->done.store(true, std::memory_order_release);
@@ -151,13 +155,17 @@ static int compile_persist(mci_problem *p, bool background) {
     // (a refusal is not an error of the call: it takes the launch chain; its LDS stays below the limit that needs raising)
     static const KernelUnit::Rules rules = {KernelUnit::kUnlinkAndFail, true, "the persistent :vegas kernel came out with static LDS or scratch",
                                             "the persistent :vegas code object"};
+    if (until && !p->ctx->offline)
+        if (int rc = p->d_persist_sums.reserve(2 * (int64_t)p->shape.nobs)) return rc;
     const int rc = u.load(p->ctx, *c, mcijit::kUnits[c->unit].kernel, 0, rules);
     if (rc) p->persist_failed = true;
     return rc;
 }
 
-// queue the one launch that runs iterations first_iteration .. first_iteration + niter - 1 over blocks [lo, hi)
-static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t nevalperblock, int64_t lo, int64_t hi, int wpb) {
+// queue the one launch that runs iterations first_iteration .. first_iteration + niter - 1 over blocks [lo, hi); until: NULL, or the target
+// of mci_integrate_until (the unit of mci_persist_until.h: the same launch, which may stop early -- persist_stopped() tells)
+static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t nevalperblock, int64_t lo, int64_t hi, int wpb, const mci_sweep_target *until,
+                          int ignore) {
     const auto &s = p->shape;
     const int64_t nblocks = hi - lo, nrows = nblocks * wpb;
     int rc;
@@ -165,7 +173,8 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     HIPCHK(hipSetDevice(p->ctx->device));
     if ((rc = ensure_capacity(p, 2 * nrows, nblocks))) return rc; // (the partial rows are double-buffered by the turn's parity)
     if ((rc = grow_iteration_log(p, (int64_t)p->log_row + ia->niter))) return rc;
-    const int T = p->kernel[mci_problem::kPersist].threads;
+    const KernelUnit &unit = p->kernel[until ? mci_problem::kPersistUntil : mci_problem::kPersist];
+    const int T = unit.threads;
     mci::BatchArgs a{};
     fill_batch(p, a);
     a.seed = ia->seed;
@@ -179,7 +188,8 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     a.status = p->d_status;
     a.tile_stride = nblocks * nevalperblock;
     a.nrows = nrows;
-    mci::PersistArgs f{};
+    mci::PersistUntilArgs fu{}; // (the fixed unit is given its head alone)
+    mci::PersistArgs &f = fu.p;
     mci::MergeArgs &m = f.m;
     m = merge_args(p, nblocks, wpb, nrows);
     m.use_ghist = 1;
@@ -195,20 +205,21 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     const int64_t lds = persist_lds(p, &f.map_off);
     f.ctr = p->d_persist;
     if (p->persist_arrive > (1ull << 39)) { // (the arrive count owns 40 bits of the counter word: start over long before it spills)
-        HIPCHK(hipMemsetAsync(p->d_persist, 0, 3 * sizeof(unsigned long long), p->ctx->stream));
+        HIPCHK(hipMemsetAsync(p->d_persist, 0, kPersistCtrWords * sizeof(unsigned long long), p->ctx->stream));
         p->persist_arrive = p->persist_done = 0;
     }
     f.arrive0 = p->persist_arrive;
     f.done0 = p->persist_done;
     f.spin_ticks = p->persist_spin_ticks; // 2 s of the 100 MHz wall clock per wait
-    void *args[] = {&a, &f};
+    if (until) fu.u = mci::SweepUntil{until->rtol, until->atol, until->min_niter, ignore, p->d_persist_sums, nullptr, nullptr};
+    void *args[] = {&a, until ? (void *)&fu : (void *)&f};
     // The map the call starts from, kept aside: workgroup 0 writes the refined map back as soon as ITS last turn is through, and another
     // workgroup can still run out of time after that -- the fall-back to the launch chain (mci_integrate) restores this copy instead
     // of trusting that `edges` was not touched (8 KB, device to device, behind nothing: ~2 us of a 0.17 ms call)
     if ((rc = p->d_edges_backup.reserve(p->h_edges.size() ? (int64_t)p->h_edges.size() : 1))) return rc;
     if (p->h_edges.size()) HIPCHK(hipMemcpyAsync(p->d_edges_backup, p->d_edges, p->h_edges.size() * sizeof(double), hipMemcpyDeviceToDevice, p->ctx->stream));
     // nrows sampling workgroups + the statistics workgroup
-    HIPCHK(hipModuleLaunchKernel(p->kernel[mci_problem::kPersist].f, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
+    HIPCHK(hipModuleLaunchKernel(unit.f, (unsigned)nrows + 1, 1, 1, (unsigned)T, 1, 1, (unsigned)lds, p->ctx->stream, args, nullptr));
     p->persist_arrive += (unsigned long long)(ia->niter + 1) * (unsigned long long)nrows; // (+ one "finished reading" per workgroup at the end)
     p->persist_done += (unsigned long long)ia->niter;
     p->launch.time_this_launch = false;
@@ -218,6 +229,19 @@ static int persist_launch(mci_problem *p, const mci_integrate_args *ia, int64_t 
     record_launch(p, nblocks * nevalperblock, nrows, T, nblocks);
     p->log_row += ia->niter;
     return MCI_OK;
+}
+// Behind a launch with a target that stopped at turn n < niter (the stop word of mci_persist_until.h, read in the call's own
+// synchronisation): the record persist_launch made for niter turns, put right.  Such a launch has added (n + 2) G arrivals -- turns
+// 0 .. n once each and the final signal -- and n turns done, not (niter + 1) G and niter; its log holds n rows; the partial rows that
+// `packed` was merged from are turn n - 1's.
+static void persist_stopped(mci_problem *p, const mci_integrate_args *ia, int n) {
+    const unsigned long long G = (unsigned long long)p->merge.nrows;
+    p->persist_arrive -= (unsigned long long)(ia->niter + 1) * G;
+    p->persist_arrive += (unsigned long long)(n + 2) * G;
+    p->persist_done -= (unsigned long long)(ia->niter - n);
+    p->log_row -= ia->niter - n;
+    const size_t rows = (size_t)G * p->shape.ncols;
+    p->merge.part_cols = p->d_part_cols + (size_t)((n - 1) & 1) * rows;
 }
 
 // sum over the ranks of a few host doubles (the lineage sums of a run): through a device scratch word of the communicator's stream
@@ -238,8 +262,87 @@ static int comm_sum_host(mci_problem *p, double *v, int n) {
     return MCI_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the tail of a call: log rows -> mci_result, for mci_integrate (everything at once, n = niter) and for mci_integrate_until (after
+// every iteration the rule looks at, n = that iteration): ONE text, so "the numbers mci_integrate would report with niter = n" is what
+// the rule reads
+// ---------------------------------------------------------------------------------------------------
+namespace {
+struct IntegrateRows {
+    int rows = 0;           // log rows already turned into res->iter_mean / iter_std
+    int64_t blk = 0;        // rows of the block log already in `bm`
+    std::vector<double> bm; // [blk][local blocks][nobs]
+};
+} // namespace
+// h: the call's log rows [n][nstat] (host).  Fills res->iter_mean / iter_std rows [st.rows, n), neval, visited, mean / stdev / chi2 and
+// correlated as mci_integrate with niter = n does; fetches the block-log rows it has not seen yet when the call is correlated.
+static int integrate_result(mci_problem *p, const mci_integrate_args *a, int n, int64_t block, int64_t nb, int ignore, bool strat, int64_t blk_row0,
+                            const double *h, IntegrateRows &st, mci_result *res) {
+    const auto &s = p->shape;
+    int rc;
+    for (int it = st.rows; it < n; ++it) { // main.jl:203
+        const double *row = h + (size_t)it * p->nstat;
+        if (strat) strat_mean_std(row, s.nobs, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
+        else
+        mci_mean_std(row, row + s.nobs, s.nobs, block, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
+    }
+    if (n > st.rows) st.rows = n;
+    res->neval = 0;
+    for (int it = 0; it < n; ++it) res->neval += (int64_t)h[(size_t)it * p->nstat + 2 * s.nobs + 1];
+    if (res->visited && n > 0) memcpy(res->visited, h + (size_t)(n - 1) * p->nstat + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
+    for (int o = 0; o < s.nobs; ++o) // main.jl:211 -> statistics.jl:24-55
+        mci_average(res->iter_mean + o, res->iter_std + o, s.nobs, ignore + 1, n, &res->mean[o], &res->stdev[o], &res->chi2[o]);
+    // Carried chains: consecutive iterations are not independent, which statistics.jl:186-220 assumes -- but the blocks are (a block's
+    // chains descend from that block's chains only), so the error comes from the scatter of the blocks' weighted averages over the run
+    // (mci_lineage_sums + the reference's own _mean_std over them); same weights, same mean.
+    res->correlated = 0;
+    if (a->solver != MCI_VEGAS && blk_row0 >= 0 && p->launch.blk_rows - blk_row0 == n && p->launch.blk_carried > 0 && n > ignore + 1) {
+        const size_t stride = (size_t)nb * s.nobs;
+        st.bm.resize((size_t)n * stride);
+        if (st.blk < n) {
+            HIPCHK(hipMemcpyAsync(st.bm.data() + (size_t)st.blk * stride, p->d_blocklog + (size_t)(blk_row0 + st.blk) * p->launch.blk_stride,
+                                  (size_t)(n - st.blk) * stride * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+            HIPCHK(hipStreamSynchronize(p->ctx->stream));
+            st.blk = n;
+        }
+        std::vector<double> sums(2 * (size_t)s.nobs);
+        mci_lineage_sums(st.bm.data(), n, nb, s.nobs, res->iter_std, ignore + 1, n, sums.data(), sums.data() + s.nobs);
+        if ((rc = comm_sum_host(p, sums.data(), (int)sums.size()))) return rc;
+        std::vector<double> lm(s.nobs), le(s.nobs);
+        mci_mean_std(sums.data(), sums.data() + s.nobs, s.nobs, block, lm.data(), le.data());
+        // (a column that is identically zero -- the imaginary part of a real integrand -- keeps the reference's 1e-10-regularised error,
+        // statistics.jl:192-198, instead of an exact 0)
+        for (int o = 0; o < s.nobs; ++o) res->stdev[o] = le[o] > 0.0 ? le[o] : res->stdev[o];
+        res->correlated = 1;
+    }
+    return MCI_OK;
+}
+
+// (tests/test_integrate_until_host.py compiles the lines between the markers for the host, next to the rule text of mci_sweep_common.h)
+// >>> integrate until rule
+// The stop rule of mci_integrate_until after counted iteration n (mci_sweep_common.h, the host side of the same text).  Uncorrelated
+// call: the columns' running sums W | S in `ws` [2 nobs] (sweep_until_add over rows [*added, n)), M = S / W, E = 1 / sqrt(W) as
+// sweep_until_done forms them.  Correlated call: res->mean / res->stdev as integrate_result has just left them (the block-lineage error).
+static bool integrate_until_met(const mci_sweep_target *t, const mci_result *res, int nobs, int n, int ignore, double *ws, int *added) {
+    for (; *added < n; ++*added)
+        for (int o = 0; o < nobs; ++o)
+            mci::sweep_until_add(res->iter_mean[(size_t)*added * nobs + o], res->iter_std[(size_t)*added * nobs + o], *added + 1, ignore, ws[o], ws[nobs + o]);
+    const int first = ignore + 2 > t->min_niter ? ignore + 2 : t->min_niter;
+    if (n < first) return false;
+    for (int o = 0; o < nobs; ++o) {
+        // (sweep_until_done's own lines from M, E on: its unqualified isfinite() is the device's overload in this translation unit's host pass)
+        const double M = res->correlated ? res->mean[o] : ws[nobs + o] / ws[o], E = res->correlated ? res->stdev[o] : 1.0 / sqrt(ws[o]);
+        if (!(std::isfinite(M) && std::isfinite(E))) return false;
+        const double rel = t->rtol * fabs(M);
+        if (!(E <= (t->atol > rel ? t->atol : rel))) return false;
+    }
+    return true;
+}
+// <<< integrate until rule
+
 // integrate  (reference src/main.jl:71-218)
-int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) {
+// t: NULL (mci_integrate: all a->niter iterations) or the target of mci_integrate_until, which then leaves the iterations it ran in *niter_run
+static int integrate_call(mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, mci_result *res, int32_t *niter_run) {
     if (!p || !a || !res) return fail(MCI_ERR_INVALID, "NULL argument");
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context: no device to run on");
     const auto &s = p->shape;
@@ -261,15 +364,16 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     bool persist = !strat && persist_plan(p, a, nevalperblock, hi - lo, &wpb_persist);
     // (automatic mode: a code object that is not in the kernel cache yet is compiled on a thread of its own, and until it is there the
     // calls go through the launch chain -- a new integrand's first call costs what it did, 0.2 s, not the 0.8 s of the larger unit)
-    if (persist) (void)compile_persist(p, p->persistent < 0);
-    persist = persist && p->kernel[mci_problem::kPersist].compiled;
+    // (a call with a target: the unit of mci_persist_until.h, by the same rules)
+    if (persist) (void)compile_persist(p, p->persistent < 0, t != nullptr);
+    persist = persist && p->kernel[t ? mci_problem::kPersistUntil : mci_problem::kPersist].compiled;
     if (!persist && !strat && (rc = compile_solver(p, kslot(a->solver, a->measurefreq)))) return rc;
     if ((rc = mci_set_reweight_goal(p, a->reweight_goal, a->reweight_goal ? p->ni + 1 : 0))) return rc;
     const int ignore = a->ignore >= 0 ? a->ignore : (a->adapt ? 1 : 0);
     const size_t nlog = (size_t)a->niter * p->nstat; // the pinned landing place of the statistics (+ the status word), sized outside the timed loop
-    if ((int64_t)nlog + 1 > p->h_log.capacity()) {
-        int64_t ncap = p->h_log.capacity() ? p->h_log.capacity() : (int64_t)64 * p->nstat + 1;
-        while (ncap < (int64_t)nlog + 1) ncap *= 2;
+    if ((int64_t)nlog + 2 > p->h_log.capacity()) { // (+ the stop word of a persistent launch with a target)
+        int64_t ncap = p->h_log.capacity() ? p->h_log.capacity() : (int64_t)64 * p->nstat + 2;
+        while (ncap < (int64_t)nlog + 2) ncap *= 2;
         if ((rc = p->h_log.reserve(ncap))) return rc;
     }
     int64_t blk_row0 = -1; // this call's first row of the block log (chain solvers): the log starts over with every call
@@ -290,9 +394,15 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
     int res_warmup = 0;
     p->last_discarded_neval = 0;
     p->last_discarded_launches = 0;
+    // mci_integrate_until: n, the iterations the call runs (the rule below shortens it); what has come back so far
+    int n = a->niter, copied = 0, added = 0;
+    IntegrateRows rows;
+    std::vector<double> ws(t ? 2 * (size_t)s.nobs : 0, 0.0);
+    const int first = t ? (ignore + 2 > t->min_niter ? ignore + 2 : t->min_niter) : 0;
     for (int attempt = 0;; ++attempt) {
         p->last_persistent = persist;
-        if (persist && (rc = persist_launch(p, a, nevalperblock, lo, hi, wpb_persist))) return rc;
+        if (persist && (rc = persist_launch(p, a, nevalperblock, lo, hi, wpb_persist, t, ignore))) return rc;
+        const unsigned long long persist_done0 = p->persist_done - (unsigned long long)a->niter; // (the launch's done0: what its stop word is counted from)
         // (a hipGraph replay of this chain was measured and dropped: 37.6 against 34.8 us per launch-bound iteration for the eager
         // asynchronous launches on ROCm 7.0 / MI355X, profiles/r02_ablation.txt)
         for (int it = 0; it < a->niter && !persist; ++it) { // main.jl:142
@@ -318,12 +428,32 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
                 p->last_discarded_neval += nevalperblock * (hi - lo);
                 p->last_discarded_launches += 1;
             }
+            // mci_integrate_until: up to iteration first - 1 the launches are queued back to back as ever; from there on the rows that
+            // have not come back yet do, behind one synchronisation per iteration, and the rule reads what mci_integrate would report
+            // with niter = it + 1 (an iteration is looked at only once it has been accepted: behind the warm-up repeats above)
+            if (t && it + 1 >= first) {
+                HIPCHK(hipMemcpyAsync(h + (size_t)copied * p->nstat, p->d_iterlog + (size_t)(row0 + copied) * p->nstat, (size_t)(it + 1 - copied) * p->nstat * sizeof(double),
+                                      hipMemcpyDeviceToHost, p->ctx->stream));
+                HIPCHK(hipStreamSynchronize(p->ctx->stream));
+                copied = it + 1;
+                if ((rc = integrate_result(p, a, it + 1, block, hi - lo, ignore, strat, blk_row0, h, rows, res))) return rc;
+                if (integrate_until_met(t, res, s.nobs, it + 1, ignore, ws.data(), &added)) {
+                    n = it + 1;
+                    break;
+                }
+            }
         }
         p->launch_counted = false;
         // the statistics of all iterations and the status word come back behind the last kernel in ONE synchronisation, into pinned memory (a
         // pageable destination goes through a staging copy: ~15 us of a 0.2 ms default-size call)
-        HIPCHK(hipMemcpyAsync(h, p->d_iterlog + (size_t)row0 * p->nstat, nlog * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+        // (mci_integrate_until's launch chain: the rows the rule has not fetched already)
+        if (n > copied)
+            HIPCHK(hipMemcpyAsync(h + (size_t)copied * p->nstat, p->d_iterlog + (size_t)(row0 + copied) * p->nstat, (size_t)(n - copied) * p->nstat * sizeof(double),
+                                  hipMemcpyDeviceToHost, p->ctx->stream));
         HIPCHK(hipMemcpyAsync(hstatus, p->d_status, sizeof(int), hipMemcpyDeviceToHost, p->ctx->stream));
+        // (a persistent launch with a target: where it stopped comes back in the same synchronisation, behind the status word)
+        unsigned long long *hstop = reinterpret_cast<unsigned long long *>(p->h_log + nlog + 1);
+        if (persist && t) HIPCHK(hipMemcpyAsync(hstop, p->d_persist + mci::kPersistStopWord, sizeof(unsigned long long), hipMemcpyDeviceToHost, p->ctx->stream));
         HIPCHK(hipStreamSynchronize(p->ctx->stream));
         if (persist && attempt == 0 && (*hstatus & mci::ST_PERSIST_STALL)) {
             // A grid-wide wait of the persistent launch ran out of time (its workgroups were not all resident: a device shared with another
@@ -339,41 +469,50 @@ int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) 
             if ((rc = compile_solver(p, kslot(a->solver, a->measurefreq)))) return rc;
             continue;
         }
+        if (persist && t && *hstop > persist_done0 && *hstop - persist_done0 < (unsigned long long)a->niter) {
+            // the launch stopped at turn n: its turn n + 1 of samples was drawn and thrown away (neither in res->neval nor in the estimate)
+            n = (int)(*hstop - persist_done0);
+            persist_stopped(p, a, n);
+            p->last_discarded_neval += nevalperblock * (hi - lo);
+        }
         break;
     }
     if (*hstatus && (rc = check_status(p))) return rc; // (reads it again, clears it, names the failure)
     auto t1 = std::chrono::steady_clock::now();
     res->seconds = std::chrono::duration<double>(t1 - t0).count();
-    res->neval = 0;
-    for (int it = 0; it < a->niter; ++it) { // main.jl:203
-        const double *row = h + (size_t)it * p->nstat;
-        if (strat) strat_mean_std(row, s.nobs, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
-        else
-        mci_mean_std(row, row + s.nobs, s.nobs, block, res->iter_mean + (size_t)it * s.nobs, res->iter_std + (size_t)it * s.nobs);
-        res->neval += (int64_t)row[2 * s.nobs + 1];
-        if (res->visited && it == a->niter - 1) memcpy(res->visited, row + 2 * s.nobs + 2, (size_t)(s.ni + 1) * sizeof(double));
-    }
-    for (int o = 0; o < s.nobs; ++o) // main.jl:211 -> statistics.jl:24-55
-        mci_average(res->iter_mean + o, res->iter_std + o, s.nobs, ignore + 1, a->niter, &res->mean[o], &res->stdev[o], &res->chi2[o]);
-    // Carried chains: consecutive iterations are not independent, which statistics.jl:186-220 assumes -- but the blocks are (a block's
-    // chains descend from that block's chains only), so the error comes from the scatter of the blocks' weighted averages over the run
-    // (mci_lineage_sums + the reference's own _mean_std over them); same weights, same mean.
-    res->correlated = 0;
     res->warmup = res_warmup;
-    if (a->solver != MCI_VEGAS && blk_row0 >= 0 && p->launch.blk_rows - blk_row0 == a->niter && p->launch.blk_carried > 0 && a->niter > ignore + 1) {
-        const int64_t nb = hi - lo;
-        std::vector<double> bm((size_t)a->niter * nb * s.nobs), sums(2 * (size_t)s.nobs);
-        HIPCHK(hipMemcpyAsync(bm.data(), p->d_blocklog + (size_t)blk_row0 * p->launch.blk_stride, bm.size() * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
-        HIPCHK(hipStreamSynchronize(p->ctx->stream));
-        mci_lineage_sums(bm.data(), a->niter, nb, s.nobs, res->iter_std, ignore + 1, a->niter, sums.data(), sums.data() + s.nobs);
-        if ((rc = comm_sum_host(p, sums.data(), (int)sums.size()))) return rc;
-        std::vector<double> lm(s.nobs), le(s.nobs);
-        mci_mean_std(sums.data(), sums.data() + s.nobs, s.nobs, block, lm.data(), le.data());
-        // (a column that is identically zero -- the imaginary part of a real integrand -- keeps the reference's 1e-10-regularised error,
-        // statistics.jl:192-198, instead of an exact 0)
-        for (int o = 0; o < s.nobs; ++o) res->stdev[o] = le[o] > 0.0 ? le[o] : res->stdev[o];
-        res->correlated = 1;
-    }
+    if ((rc = integrate_result(p, a, n, block, hi - lo, ignore, strat, blk_row0, h, rows, res))) return rc;
+    if (niter_run) *niter_run = n;
     return MCI_OK;
+}
+
+int mci_integrate(mci_problem *p, const mci_integrate_args *a, mci_result *res) { return integrate_call(p, a, nullptr, res, nullptr); }
+
+// ---------------------------------------------------------------------------------------------------
+// mci_integrate with a target error: the same call, stopped by the rule of mci_sweep_common.h
+// ---------------------------------------------------------------------------------------------------
+int mci_integrate_until_supported(const mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, char *why, int32_t n) {
+    if (!p || !a) return fail(MCI_ERR_INVALID, "NULL argument");
+    char buf[160];
+    const char *r = nullptr;
+    if (!t) r = "the target is NULL";
+    else if (!(std::isfinite(t->rtol) && t->rtol >= 0.0)) r = "rtol is negative or not finite";
+    else if (!(std::isfinite(t->atol) && t->atol >= 0.0)) r = "atol is negative or not finite";
+    else if (t->min_niter < 0) r = "min_niter < 0";
+    else if (p->ctx->nranks != 1) r = "more than one rank (the block-lineage sums would need a collective per iteration)";
+    // ... and what mci_integrate refuses
+    else if (!(a->neval > a->block)) snprintf(buf, sizeof buf, "neval=%lld should be larger than nblock = %lld", (long long)a->neval, (long long)a->block), r = buf;
+    else if (a->solver != MCI_VEGAS && a->solver != MCI_VEGASMC && a->solver != MCI_MCMC) snprintf(buf, sizeof buf, "Solver %d is not supported!", a->solver), r = buf;
+    else if (p->strat.on && a->solver != MCI_VEGAS) r = "stratification works with solver = :vegas only (mci_set_stratification_off first)";
+    else if (p->strat.on && a->measurefreq != 1) r = "stratification: measurefreq != 1 is refused (every sample is measured)";
+    if (!r) return MCI_OK;
+    if (why && n > 0) snprintf(why, (size_t)n, "%s", r);
+    return fail(MCI_ERR_INVALID, "this call cannot run to a target error: %s", r);
+}
+
+int mci_integrate_until(mci_problem *p, const mci_integrate_args *a, const mci_sweep_target *t, mci_result *res, int32_t *niter_run) {
+    if (!p || !a || !res || !niter_run) return fail(MCI_ERR_INVALID, "NULL argument");
+    if (int rc = mci_integrate_until_supported(p, a, t, nullptr, 0)) return rc; // (first: a refusal is the same with and without a device)
+    return integrate_call(p, a, t, res, niter_run);
 }
 

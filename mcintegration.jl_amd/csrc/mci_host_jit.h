@@ -520,6 +520,7 @@ int mci_kernel_code_object(mci_problem *p, int32_t solver, char *buf, int32_t n)
     int k = -1;
     std::string what = "solver " + std::to_string(solver);
     if (solver == MCI_VEGAS_PERSISTENT) k = mci_problem::kPersist, what = "the persistent :vegas kernel";
+    else if (solver == MCI_VEGAS_PERSISTENT_UNTIL) k = mci_problem::kPersistUntil, what = "the persistent :vegas kernel with a target error";
     else if (solver == MCI_VEGASMC_LANES || solver == MCI_MCMC_LANES) k = solver == MCI_VEGASMC_LANES ? kSlotVegasmcSpec : kSlotMcmcSpec, what = "the several-lanes-per-chain kernel";
     else if (solver == MCI_VEGAS_STRAT) k = mci_problem::kStrat, what = "the stratified :vegas kernel";
     else if (const int w = sweep_unit_of(solver); w >= 0) k = mci_problem::kSweep + w, what = std::string("the sweep kernel") + kSweepUnits[w].for_what;
@@ -678,7 +679,7 @@ int mci_check_status(mci_problem *p) {
     if (p->ctx->offline) return fail(MCI_ERR_NO_DEVICE, "offline context");
     return check_status(p);
 }
-static int compile_persist(mci_problem *p, bool background);
+static int compile_persist(mci_problem *p, bool background, bool until);
 static bool persist_layout_ok(const mci_problem *p);
 static int compile_strat(mci_problem *p); // (mci_host_strat.h)
 static int compile_sweep_unit(mci_problem *p, int which); // (mci_host_sweep.h)
@@ -687,7 +688,11 @@ static bool sweep_strat_leaves_unit(const mci_problem *p);
 int mci_compile_solver(mci_problem *p, int32_t solver) {
     if (solver == MCI_VEGAS_PERSISTENT) { // the persistent :vegas kernel (mci_set_persistent), for layouts that allow it
         if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
-        return compile_persist(p, false);
+        return compile_persist(p, false, false);
+    }
+    if (solver == MCI_VEGAS_PERSISTENT_UNTIL) { // ... and the one mci_integrate_until launches
+        if (!persist_layout_ok(p)) return fail(MCI_ERR_INVALID, "this layout has no persistent :vegas kernel (mci_set_persistent)");
+        return compile_persist(p, false, true);
     }
     if (solver == MCI_VEGASMC_LANES || solver == MCI_MCMC_LANES) return mci_compile_chain_speculation(p, solver == MCI_VEGASMC_LANES ? MCI_VEGASMC : MCI_MCMC);
     if (solver == MCI_VEGAS_STRAT) { // (mci_host_strat.h)

@@ -171,7 +171,8 @@ struct mci_problem {
     //                      | :vegasmc with several lanes per chain | :mcmc with several lanes per chain (mci_spec.h)
     // behind them: the persistent :vegas unit (mci_set_persistent), the stratified one (mci_host_strat.h), the twelve sweep units (Sweep)
     // ... and the big :vegas unit (sixteen histogram copies, 1024 threads: mci_host_vegas_plan.h VegasBigUnit)
-    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kVegasBig = kSweep + 12, kKernels = kVegasBig + 1 };
+    // ... and the persistent :vegas unit with a target error (mci_persist_until.h; mci_integrate_until)
+    enum { kSlots = 7, kPersist = kSlots, kStrat, kSweep, kVegasBig = kSweep + 12, kPersistUntil, kKernels };
     KernelUnit kernel[kKernels];
     VegasKernelPlan vegas; // which :vegas code object the launches run (mci_host_vegas_plan.h)
     VegasBigUnit vegas_big; // ... and whether big launches have a third one to run (kernel[kVegasBig])
@@ -305,8 +306,9 @@ struct mci_problem {
     // its translation unit takes twice as long to compile as the plain sample kernel (train! comes with it): in automatic mode a code
     // object that is not in the kernel cache is compiled on a thread of its own while the calls go through the launch chain
     struct PersistJob;
-    PersistJob *persist_job = nullptr;
-    DevBuf<unsigned long long> d_persist;    // [0] arrived | done << 40, [2] gave up
+    PersistJob *persist_job[2] = {nullptr, nullptr}; // [0] the fixed unit's, [1] the one with a target error
+    DevBuf<unsigned long long> d_persist;    // [0] arrived | done << 40, [2] gave up, [3] the turn count a launch with a target stopped at (mci_persist_until.h)
+    DevBuf<double> d_persist_sums;           // [2 nobs]: the running sums of that launch's rule
     DevBuf<double> d_edges_backup;           // the map a persistent launch started from (restored when it stalls)
     unsigned long long persist_arrive = 0, persist_done = 0;
     unsigned long long persist_spin_ticks = 200000000ull; // ticks of the 100 MHz wall clock a grid-wide wait may take: 2 s (mci_debug_persist_spin_ticks)
@@ -518,6 +520,7 @@ static void persist_job_drop(mci_problem *p);
 namespace { void persist_orphans_join(); }
 // counters [0..2] of the persistent :vegas kernel + (MCI_PERSIST_TRACE builds) the phase stamps of three workgroups over eight turns
 static const size_t kPersistWords = 8 + 3 * 8 * 8 + 16;
+static const size_t kPersistCtrWords = 4; // the words that are reset together: counters, gave-up flag, stop word
 
 namespace {
 
@@ -673,7 +676,7 @@ int check_status(mci_problem *p) {
     HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int), p->ctx->stream));
     if (st & mci::ST_PERSIST_STALL) { // a grid-wide wait of the persistent :vegas launch ran out of time: its counters are void
         // (mci_integrate recovers by itself and never gets here with this bit; this is the message of a stall somebody else finds)
-        HIPCHK(hipMemsetAsync(p->d_persist, 0, 3 * sizeof(unsigned long long), p->ctx->stream));
+        HIPCHK(hipMemsetAsync(p->d_persist, 0, kPersistCtrWords * sizeof(unsigned long long), p->ctx->stream));
         HIPCHK(hipMemsetAsync(p->d_ghist, 0, 3 * (size_t)(p->shape.nbin ? p->shape.nbin : 1) * sizeof(double), p->ctx->stream));
         p->persist_arrive = p->persist_done = 0;
         p->persist_failed = true; // (later calls take the launch-per-iteration path)
@@ -691,7 +694,7 @@ int check_status(mci_problem *p) {
 int persist_recover(mci_problem *p) {
     hipStream_t st = p->ctx->stream;
     HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int), st));
-    HIPCHK(hipMemsetAsync(p->d_persist, 0, 3 * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(p->d_persist, 0, kPersistCtrWords * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(p->d_ghist, 0, 3 * (size_t)(p->shape.nbin ? p->shape.nbin : 1) * sizeof(double), st));
     p->persist_arrive = p->persist_done = 0;
     p->persist_failed = true; // (later calls take the launch-per-iteration path)

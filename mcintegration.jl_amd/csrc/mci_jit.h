@@ -39,6 +39,7 @@ extern const char *const kSweepLeavesHeader;  // mci_sweep_leaves.h (sweeps of p
 extern const char *const kSweepStratHeader;   // mci_sweep_strat.h (stratified points in sweeps)
 extern const char *const kSweepChainsHeader;  // mci_sweep_chains.h (batched :vegasmc and :mcmc parameter sweeps)
 extern const char *const kSweepStratLeavesHeader; // mci_sweep_strat_leaves.h (stratified points of problems with several Continuous leaves)
+extern const char *const kPersistUntilHeader; // mci_persist_until.h (the persistent :vegas kernel with a target error)
 
 struct ProblemShape {
     int ndraw = 0, nleaf = 0, ni = 0, npool = 0, nobs = 0, ncols = 0, table_mode = 0;
@@ -127,8 +128,10 @@ static std::string dbl_arr(const std::vector<double> &v) {
 // kUnitSweepChainsResume, kUnitSweepMcmcResume: the two carried units with a first iteration that continues the chains of the call before
 // (mci_sweep_chains.h chain_sweep<Cfg, MCMC, true, true>; mci_integrate_sweep_chains_resume | mci_integrate_sweep_mcmc_resume): kernels and
 // code objects of their own, compiled like them
+// kUnitVegasPersistUntil: kUnitVegasPersist with a target error (mci_persist_until.h vegas_persist_until; mci_integrate_until): a header, a
+// kernel and a code object of its own, compiled like it; it takes the stop rule from mci_sweep_common.h
 // The twelve sweep units share mci_sweep_common.h.  What a unit includes, is compiled against, defines and exports: its row of kUnits.
-enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitSweepStratLeaves = 13, kUnitSweepUntil = 14, kUnitSweepLeavesUntil = 15, kUnitSweepChainsResume = 16, kUnitSweepMcmcResume = 17, kUnitCount = 18 };
+enum { kUnitSolver = 0, kUnitVegasMf1 = 1, kUnitDump = 2, kUnitVegasPersist = 3, kUnitSpec = 4, kUnitStrat = 5, kUnitSweep = 6, kUnitSweepLeaves = 7, kUnitSweepStrat = 8, kUnitSweepChains = 9, kUnitSweepMcmc = 10, kUnitSweepChainsCarry = 11, kUnitSweepMcmcCarry = 12, kUnitSweepStratLeaves = 13, kUnitSweepUntil = 14, kUnitSweepLeavesUntil = 15, kUnitSweepChainsResume = 16, kUnitSweepMcmcResume = 17, kUnitVegasPersistUntil = 18, kUnitCount = 19 };
 // One row per unit, indexed by it: everything generate_source() and compile() need to know about a unit.
 struct UnitHeader {
     const char *name;
@@ -168,6 +171,7 @@ constexpr UnitRow kUnits[] = {
     /* kUnitSweepLeavesUntil */ {"mci_sweep_leaves.h", {MCI_HDR_SWEEP, {"mci_sweep_leaves.h", &kSweepLeavesHeader}}, "mci_vegas_sweep_leaves_until", "SweepUntilArgs", "f", "vegas_sweep_leaves_until", 1, false, 2, true, false, true},
     /* kUnitSweepChainsResume */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_vegasmc_sweep_resume", "SweepChainResumeArgs", "f", "vegasmc_sweep_resume", -1, false, 2, true, false, true},
     /* kUnitSweepMcmcResume   */ {"mci_sweep_chains.h", {MCI_HDR_SWEEP, {"mci_sweep_chains.h", &kSweepChainsHeader}}, "mci_mcmc_sweep_resume", "SweepChainResumeArgs", "f", "mcmc_sweep_resume", -1, false, 2, true, false, true},
+    /* kUnitVegasPersistUntil */ {"mci_persist_until.h", {MCI_HDR_SWEEP, {"mci_persist_until.h", &kPersistUntilHeader}}, "mci_vegas_persist_until", "PersistUntilArgs", "f", "vegas_persist_until", 1, true, 1, true, true, false},
 };
 #undef MCI_HDR_SWEEP
 #undef MCI_HDR_TRAIN

@@ -441,7 +441,8 @@ class Engine:
     def _kernel_code(solver):
         return {"vegas_persistent": 3, "vegasmc_lanes": 5, "mcmc_lanes": 6, "vegas_strat": 7, "vegas_sweep": 8, "vegas_sweep_leaves": 9, "vegas_sweep_strat": 10,
                 "vegasmc_sweep": 11, "mcmc_sweep": 12, "vegasmc_sweep_carry": 13, "mcmc_sweep_carry": 14, "vegas_big": 15,
-                "vegas_sweep_strat_leaves": 16, "vegas_sweep_until": 17, "vegas_sweep_leaves_until": 18, "vegasmc_sweep_resume": 19, "mcmc_sweep_resume": 20}.get(solver) or _lib.SOLVERS[solver]
+                "vegas_sweep_strat_leaves": 16, "vegas_sweep_until": 17, "vegas_sweep_leaves_until": 18, "vegasmc_sweep_resume": 19, "mcmc_sweep_resume": 20,
+                "vegas_persistent_until": 21}.get(solver) or _lib.SOLVERS[solver]
 
     def compile(self, solver="vegas"):
         """solver: "vegas" | "vegasmc" | "mcmc" | "vegas_persistent" (the persistent :vegas kernel, layouts with one Continuous leaf) |
@@ -457,7 +458,9 @@ class Engine:
         "vegas_sweep_strat_leaves" (the kernel of integrate_sweep_strat for a stratified problem with several Continuous leaves,
         csrc/mci_sweep_strat_leaves.h; after set_sweep_strat_leaves("all")) | "vegas_sweep_until" | "vegas_sweep_leaves_until" (the kernels
         of integrate_sweep_until: "vegas_sweep" and "vegas_sweep_leaves" with a target error per point) | "vegasmc_sweep_resume" |
-        "mcmc_sweep_resume" (the two carried kernels with a first iteration that continues the chains of the call before: state=)"""
+        "mcmc_sweep_resume" (the two carried kernels with a first iteration that continues the chains of the call before: state=) |
+        "vegas_persistent_until" (the persistent :vegas kernel with a target error, csrc/mci_persist_until.h: what integrate(..., rtol= |
+        atol=) launches where a fixed call launches "vegas_persistent")"""
         check(lib().mci_compile_solver(self.p, self._kernel_code(solver)))
 
     def code_object(self, solver="vegas"):
@@ -845,8 +848,12 @@ class Engine:
         return int(n.value), int(b.value)
 
     def integrate(self, solver, neval, niter=10, block=16, ignore=-1, adapt=True, gamma=1.0, measurefreq=1, seed=1234,
-                  nchain=0, first_iteration=0, thermal_ratio=0.1, reweight_goal=None):
-        """the whole loop inside the library (mci_integrate)"""
+                  nchain=0, first_iteration=0, thermal_ratio=0.1, reweight_goal=None, target=None):
+        """the whole loop inside the library (mci_integrate).  target = (rtol, atol, min_niter) (None entries: 0): the call stops at the
+        first iteration n >= max(ignore + 2, min_niter) after which every statistics column has E <= max(atol, rtol |M|) -- M, E what
+        the call would report with niter = n (mci_integrate_until); the dict then also carries `niter_run` (that n, or niter) and
+        `converged`, its iter_mean / iter_std hold niter_run rows, and everything else is that of the call with niter = niter_run.
+        Raises MCIError with the reason of integrate_until_supported()."""
         goal = None
         if reweight_goal is not None:
             self._goal = np.ascontiguousarray(reweight_goal, dtype=np.float64)
@@ -859,16 +866,43 @@ class Engine:
         m, s, c2 = np.zeros(n), np.zeros(n), np.zeros(n)
         vis = np.zeros(self.config.N + 1)
         r = _lib.ResultC(niter, n, _dp(im), _dp(ie), _dp(m), _dp(s), _dp(c2), 0, 0.0, _dp(vis), 0, 0)
-        check(lib().mci_integrate(self.p, C.byref(a), C.byref(r)))
+        nrun = None
+        if target is None:
+            check(lib().mci_integrate(self.p, C.byref(a), C.byref(r)))
+        else:
+            t, nrun = self._sweep_target(*target), C.c_int32(0)
+            check(lib().mci_integrate_until(self.p, C.byref(a), C.byref(t), C.byref(r), C.byref(nrun)))
         dn, dl = C.c_int64(), C.c_int32()
         check(lib().mci_last_integrate_discarded(self.p, C.byref(dn), C.byref(dl)))
         out = dict(mean=m, stdev=s, chi2=c2, iter_mean=im, iter_std=ie, neval=r.neval, seconds=r.seconds, visited=vis,
                    correlated=bool(r.correlated), block_mean=None, warmup=int(r.warmup), neval_discarded=int(dn.value))
+        if nrun is not None:
+            niter = int(nrun.value)
+            out["niter_run"] = niter
+            out["iter_mean"], out["iter_std"] = im[:niter], ie[:niter]
+            out["converged"] = self._integrate_until_met(out, ignore if ignore >= 0 else (1 if adapt else 0), t, len(im))
         if _lib.SOLVERS[solver] != _lib.VEGAS and out["correlated"]:
             # (only a run of carried chains needs them -- the block-lineage error of Result.with_ignore; a launch-bound default-size call is
             # spared the flush, the copy and the second synchronisation)
             out["block_mean"] = self.block_means(niter)[0]
         return out
+
+    @staticmethod
+    def _integrate_until_met(out, ignore, t, niter):
+        """whether a call with a target met it: one that stopped below niter did by definition (the library's verdict, never
+        second-guessed here); one that ran all niter iterations may have met it in the last -- the rule on what the call reports"""
+        n = out["niter_run"]
+        if n < niter:
+            return True
+        M, E = np.asarray(out["mean"]), np.asarray(out["stdev"])
+        ok = np.isfinite(M) & np.isfinite(E) & (E <= np.maximum(t.atol, t.rtol * np.abs(M)))
+        return bool(ok.all() and n >= max(ignore + 2, t.min_niter))
+
+    def integrate_until_supported(self, solver="vegas", neval=10000, niter=10, block=16, measurefreq=1, rtol=0.0, atol=0.0, min_niter=0, **kw):
+        """None when integrate(..., target=) takes this problem with these arguments and this target, else the reason
+        (mci_integrate_until_supported: a negative or non-finite rtol / atol, min_niter < 0, several ranks, whatever mci_integrate refuses)"""
+        t = _lib.SweepTarget(float(rtol), float(atol), int(min_niter))
+        return self._sweep_refusal(lambda p, a, why, n: lib().mci_integrate_until_supported(p, a, C.byref(t), why, n), solver, neval, niter, block, measurefreq)
 
     def _integrate_args(self, solver, neval, niter, block, ignore, adapt, gamma, measurefreq, seed, first_iteration, nchain=0, thermal_ratio=0.1):
         return _lib.IntegrateArgs(_lib.SOLVERS[solver], int(neval), int(niter), int(block), int(ignore), 1 if adapt else 0, float(gamma),

@@ -75,6 +75,31 @@ def _stratify_request(stratify, solver, config, integrand, measure, measurefreq,
     return st
 
 
+def _target_request(rtol, atol, min_niter):
+    """(rtol, atol, min_niter) of an integrate() call with a target error, None without one; what mci_integrate_until_supported refuses
+    of a target is refused here with its words, before any engine exists"""
+    if rtol is None and atol is None:
+        if min_niter is not None:
+            raise ValueError("min_niter = %r without a tolerance: give rtol and / or atol" % (min_niter,))
+        return None
+    tol = []
+    for name, v in (("rtol", rtol), ("atol", atol)):
+        try:
+            v = 0.0 if v is None else float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s = %r: %s is negative or not finite" % (name, v, name)) from None
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError("%s = %r: %s is negative or not finite" % (name, v, name))
+        tol.append(v)
+    if min_niter is None:
+        min_niter = 0
+    if isinstance(min_niter, (bool, np.bool_)) or not isinstance(min_niter, (int, np.integer)):
+        raise ValueError("min_niter = %r: an int >= 0" % (min_niter,))
+    if min_niter < 0:
+        raise ValueError("min_niter = %r: min_niter < 0" % (min_niter,))
+    return tol[0], tol[1], int(min_niter)
+
+
 def standardize_block(neval, nblock, nworker=1):
     """_standardize_block (main.jl:220-234)"""
     assert neval > nblock, "neval=%s should be larger than nblock = %s" % (neval, nblock)   # :222
@@ -226,7 +251,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
               adapt=True, debug=False, reweight_goal=None, ignore=None, measure=None, measurefreq=1,
               thermal_ratio=0.1, inplace=False, parallel="nothread", print=-1, printio=None, timer=None,
               comm=None, device=None, nchain=0, engine_factory=None, rng_bits=52, rng_rounds=10, deterministic=False, trace=None,
-              integrand_form=None, measure_form=None, stratify=None, **kwargs):
+              integrand_form=None, measure_form=None, stratify=None, rtol=None, atol=None, min_niter=None, **kwargs):
     """Same keywords as the reference (main.jl:71-90; unknown ones go to Configuration, :95-97).
     Extra, engine-specific keywords: `comm` (LocalComm | RcclComm | TorchDistComm), `device`, `nchain`
     (vegasmc chains per block; 0 = auto), `rng_bits` (52 | 32: opt-in cheaper uniform stream of solver="vegas", see
@@ -237,8 +262,14 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     cannot be written out takes the host batch-callback path, silently with None, with a RuntimeWarning naming the reason with True;
     False: always the host path), `integrand_form` / `measure_form` (callback_form: by default a closure is called in the form the
     reference's solver calls it in -- `inplace` included -- and one whose parameters do not fit raises TypeError), `stratify` (True or
-    Stratify(beta, nstrat, max_nhcube, carry): VEGAS+ adaptive stratified sampling under solver="vegas", see Stratify), `engine_factory`
-    (test seam)."""
+    Stratify(beta, nstrat, max_nhcube, carry): VEGAS+ adaptive stratified sampling under solver="vegas", see Stratify), `rtol` / `atol` /
+    `min_niter` (a target error, mci_integrate_until: `niter` becomes the most the call runs, and it stops at the first iteration
+    n >= max(ignore + 2, min_niter) after which every statistics column has E <= max(atol, rtol |M|), M and E being what the call would
+    report with niter = n -- the block-lineage error once chains are carried; the Result carries `niter_run` and `converged`, report()
+    says when the target was not reached, config.iterations_done advances by niter_run; one process and the library's own loop only:
+    several ranks, an `engine_factory` and the host-loop path raise ValueError, nothing runs un-stopped in the target's place),
+    `engine_factory` (test seam)."""
+    target = _target_request(rtol, atol, min_niter)
     if trace is None:
         trace = TRACE_DEFAULT
     if solver in (":vegas", ":vegasmc", ":mcmc"):
@@ -253,6 +284,10 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     if ignore is None:
         ignore = 1 if adapt else 0                                                    # main.jl:82
     comm = comm or LocalComm()
+    if target is not None and comm.size > 1:
+        raise ValueError("rtol / atol: refused for %d ranks: more than one rank (the block-lineage sums would need a collective per iteration)" % comm.size)
+    if target is not None and engine_factory is not None:
+        raise ValueError("rtol / atol: refused with an engine_factory (the target is applied inside the library's own loop, mci_integrate_until)")
     strat = _stratify_request(stratify, solver, config, integrand, measure, measurefreq, trace, comm)
     if device is None:   # an RcclComm is bound to one device: the engine has to live there (its all_reduce checks it)
         device = getattr(comm, "device", 0)
@@ -284,6 +319,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
     neval_done = 0
     warmup = 0                             # launches run again instead of being counted (automatic :mcmc chain lengths)
     neval_discarded = 0
+    niter_run = converged = None           # a call with a target (rtol / atol): the iterations it ran | whether it met the target
     block_mean, correlated = None, False   # chain solvers: every block's mean of every iteration | the iterations continued each other's chains
     if type(comm) is LocalComm and engine_factory is None and hasattr(eng, "integrate") and getattr(eng, "comm_ranks", lambda: 0)() == 1:
         # one process: the whole loop runs inside the library (mci_integrate: the iterations are queued back to back on the
@@ -291,13 +327,19 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
         # 82 us with a host round trip per iteration, tools/call_overhead.py).  Same iterations, same numbers as the loop below.
         r = eng.integrate(s, nevalperblock * block, niter=niter, block=block, ignore=ignore, adapt=adapt, gamma=gamma,
                           measurefreq=measurefreq, seed=config.seed, nchain=nchain, first_iteration=config.iterations_done,
-                          thermal_ratio=thermal_ratio, reweight_goal=reweight_goal)
+                          thermal_ratio=thermal_ratio, reweight_goal=reweight_goal, **({} if target is None else {"target": target}))
+        if target is not None:
+            niter = niter_run = r["niter_run"]   # (everything below is that of the call with niter = niter_run)
+            converged = r["converged"]
         means, stds = list(r["iter_mean"]), list(r["iter_std"])
         block_mean, correlated, warmup = r.get("block_mean"), r.get("correlated", False), r.get("warmup", 0)
         neval_discarded = r.get("neval_discarded", 0)
         neval_done = nevalperblock * block * niter
         niter_loop = 0
         config.visited = r["visited"]    # config.visited of the last iteration (configuration.jl:46), for report(config)
+    elif target is not None:
+        raise ValueError("rtol / atol: refused on the host-loop path (this call does not run inside the library's own loop, "
+                         "mci_integrate_until; nothing runs un-stopped in the target's place)")
     else:
         niter_loop = niter
         if s != VEGAS and hasattr(eng, "reset_block_log"):
@@ -363,6 +405,7 @@ def integrate(integrand, *, solver="vegasmc", config=None, neval=1e4, niter=10, 
             res.vegas_check = eng.vegas_check_status()
         except Exception:
             res.vegas_check = None
+    res.niter_run, res.converged = niter_run, converged
     res.warmup = warmup   # launches that were run again instead of being counted (automatic :mcmc chain lengths)
     res.neval_discarded = neval_discarded   # ... and their evaluations: spent (they trained the map), in neither res.neval nor the estimate
     if print >= 0:

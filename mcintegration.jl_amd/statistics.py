@@ -375,5 +375,5 @@ def report(result, ignore=None, pick=0, name=None, verbose=0, io=None):
         print("  " + result.vegas_check_note, file=io)
     if getattr(result, "hold_note", None):   # (not in the reference)
         print("  " + result.hold_note, file=io)
-    if getattr(result, "converged", None) is False:   # (not in the reference: integrate_sweep(..., rtol= | atol=))
-        print("  note: this sweep point ran all %d iterations it was given without reaching its target error" % result.niter_run, file=io)
+    if getattr(result, "converged", None) is False:   # (not in the reference: integrate(..., rtol= | atol=) and integrate_sweep(..., rtol= | atol=))
+        print("  note: this run ran all %d iterations it was given without reaching its target error" % result.niter_run, file=io)
